@@ -3,7 +3,12 @@
 bubbles (BASELINE.json configs[2]), DenseKmerFinder -> FlatKmers columns resident in HBM (what the reference's
 `graph_kmer_index index` command computes, command_line_interface.py:553-622).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, the roofline of the
+dominant kernel from the steps' own kernel times).  `--full` adds everything else below: the CPU baselines, the
+from_obgraph adapter timing, the measured store ceiling, and the secondary records.  `--dump-outputs DIR` writes what the
+last timed step computed (rank 0's columns: a fixed sample plus whole-output checksums) as DIR/<name>.npy.
 
 One process per GPU.  Under a launcher (torch.distributed.run exports RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR /
 MASTER_PORT) this process IS a rank.  Without one, `--gpus N` with N > 1 makes this process the launcher: before it
@@ -18,7 +23,7 @@ to rank 0); neither torch nor any other framework is imported -- the compute pat
 
 A step = gki_finder_count (boundary count kernel + prefix sums) + gki_finder_emit_flat (interior + boundary emit
 kernels) over the rank's shard, inputs (graph arrays) already in HBM; there is no collective inside it (the
-enumeration shards without a halo).  Rank 0 prints one JSON line.  Records measured after the timed region:
+enumeration shards without a halo).  Rank 0 prints one JSON line.  Records measured after the timed region (--full):
   N = 1: `index_build` (CollisionFreeKmerIndex.from_flat_kmers of the variant index, collision_free_kmer_index.py:423-467),
          `full_index` (ALL records of the step indexed: bucket-range slices, since one int32 directory stops at 2^31),
          `read_mapping` (BASELINE configs[4]: reads -> k-mers of both strands -> CollisionFreeKmerIndex.get -> node
@@ -768,6 +773,11 @@ def main():
     ap.add_argument("--sharded-build-budget", type=float, default=300.0, help="seconds the sharded_build record may take before "
                     "rank 0 prints the line without it")
     ap.add_argument("--modulo", type=int, default=452930477)
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the CPU baselines, the "
+                    "from_obgraph adapter timing, the store ceiling of the roofline, the secondary records (N=1: index_build, "
+                    "full_index, read_mapping, early_stop_search) and sharded_build (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (rank 0) as "
+                    "DIR/<name>.npy, float32 / float64, at most 64 MB: column checksums and a fixed sample of the records")
     args = ap.parse_args()
     global FULL_INDEX_GROUP_BITS, FULL_INDEX_ROWS
     FULL_INDEX_GROUP_BITS = 0 if args.full_index_columns else args.full_index_group_bits      # (the grouping exists for rows only)
@@ -785,7 +795,7 @@ def main():
         log("WORLD_SIZE=%d but --gpus=%d; using WORLD_SIZE" % (world, args.gpus))
     plain = not (args.linear or args.indels or args.nested or args.all_nodes or args.pretend_shard or args.general)
     cpu = cpu2 = None
-    if world == 1 and not args.no_cpu_baseline:       # N=1 only, and before anything touches the GPU
+    if args.full and world == 1 and not args.no_cpu_baseline:       # N=1 only, and before anything touches the GPU
         cores = args.cpu_cores or min(16, len(os.sched_getaffinity(0)))
         cpu = cpu_baseline(int(args.cpu_sample_bases), args.k, args.max_variant_nodes, cores)
         log("cpu baseline: %.3g k-mers/s on %d cores" % (cpu["value"], cpu["cores"]))
@@ -797,7 +807,7 @@ def main():
     plane = SocketControlPlane(rank, world)           # barrier + max / sum of two scalars; a no-op at world 1
 
     g, t_gen, t_map, cleanup_dir = node_graph(args, plane, rank, local_rank)
-    adapter = adapter_times(g, args) if rank == 0 and world == 1 else None
+    adapter = adapter_times(g, args) if args.full and rank == 0 and world == 1 else None
 
     from graph_kmer_index_amd import _lib, DenseKmerFinder, CriticalGraphPaths, DeviceGraph
     from graph_kmer_index_amd.sharding import shard_range
@@ -844,7 +854,7 @@ def main():
         finder.synchronize()
     # the box's own store ceiling for the four-column pattern, into the output columns the warm-up just sized
     ceiling = None
-    if out is not None and out.n >= (1 << 20):
+    if args.full and out is not None and out.n >= (1 << 20):
         import ctypes as C
         bw = C.c_double(0.0)
         _lib.check(lib.gki_measure_store_bw(out.hashes.ptr, out.nodes.ptr, out.ref_offsets.ptr, out.allele_frequencies.ptr,
@@ -867,11 +877,14 @@ def main():
     n_total = sum(n_per_rank)
     ceilings = plane.allgather_float(ceiling or 0.0)
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, n_interior, args.dump_outputs)
+
     checks = None
     if args.verify:
         checks = verify(out, g, k, n_interior)
     secondary = None
-    if world == 1 and args.reads > 0 and plain and out.n - n_interior > 0:
+    if args.full and world == 1 and args.reads > 0 and plain and out.n - n_interior > 0:
         secondary = secondary_records(lib, _lib, g, k, cp, finder, out, int(args.reads), cpu2, args.max_variant_nodes,
                                       not args.no_full_index, args.modulo)
     res = None
@@ -884,7 +897,7 @@ def main():
         res = {
             "metric": "k-mers hashed+indexed per second (k=31, 3 Gbp graph)", "value": value, "unit": "k-mers/s",
             "timed_region": "enumerate + hash + FlatKmers rows in HBM (gki_finder_count + gki_finder_emit_flat); the index "
-                            "build, the exchange with ranks and the read side are the separate records below",
+                            "build, the exchange with ranks and the read side are the separate records of --full",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
             "config": {"workload": "BASELINE configs[%d]: synthetic %.3g bp linear-ref obgraph + %.3g SNP bubbles, k=%d, "
@@ -920,7 +933,7 @@ def main():
         res["cpu_baselines_note"] = ("`cpu_baseline` (beside `value`) is the oracle on ALL host cores (`cores` in the object); the "
                                      "`cpu_baseline` objects inside index_build / read_mapping / early_stop_search are the oracle on "
                                      "ONE core: compare ratios across records only after scaling by `cores`")
-    if world > 1 and plain and not args.no_sharded_build:
+    if args.full and world > 1 and plain and not args.no_sharded_build:
         # The exchange has never run between real GPUs (one GPU per builder box): if a rank fails or a collective never
         # returns, the headline line must still come out.  A watchdog prints it (rank 0) and ends the rank.
         import threading
@@ -955,6 +968,49 @@ def main():
     plane.close()
     if cleanup_dir:
         shutil.rmtree(cleanup_dir, ignore_errors=True)
+
+
+DUMP_BLOCKS, DUMP_BLOCK = 256, 4096                 # 2^20 sampled records, 44 B each as written: 46 MB
+
+
+def dump_outputs(out, n_interior, d):
+    """What the timed path left in HBM after its last step, as float32 / float64 .npy files under d: whole-output
+    checksums of the four FlatKmers columns, and a fixed sample of the records (every record when there are at most
+    2^20; else one block of 4096 consecutive records at a seeded offset inside each of 256 equal strata).  The 62-bit
+    hashes and the checksums are split into 32-bit halves so that float64 holds them exactly."""
+    os.makedirs(d, exist_ok=True)
+    n = out.n
+    if n <= DUMP_BLOCKS * DUMP_BLOCK:
+        starts, width = np.zeros(1, dtype=np.int64), n
+    else:
+        stratum = n // DUMP_BLOCKS
+        rng = np.random.default_rng(1234)
+        starts = np.arange(DUMP_BLOCKS, dtype=np.int64) * stratum + rng.integers(0, stratum - DUMP_BLOCK + 1, size=DUMP_BLOCKS)
+        width = DUMP_BLOCK
+    cols = {}
+    for name in ("hashes", "nodes", "ref_offsets", "allele_frequencies"):
+        col = getattr(out, name)
+        cols[name] = np.concatenate([col.view(int(a), width).to_host(width) for a in starts]) if width else col.to_host(0)
+    lo32 = np.uint64(0xFFFFFFFF)
+    h = cols["hashes"]
+    assert int(cols["ref_offsets"].max(initial=0)) < 2 ** 53
+    sums = []
+    for name in ("hashes", "nodes", "ref_offsets", "allele_frequencies"):
+        s_, x_ = getattr(out, name).checksum(n)
+        sums.append([s_ >> 32, s_ & 0xFFFFFFFF, x_ >> 32, x_ & 0xFFFFFFFF])
+    arrays = {
+        "records": np.array([n, n_interior], dtype=np.float64),
+        "column_checksums": np.array(sums, dtype=np.float64),    # rows: hashes, nodes, ref_offsets, allele_frequencies
+        "sample_index": (starts[:, None] + np.arange(width, dtype=np.int64)[None, :]).ravel().astype(np.float64),
+        "hashes_hi": (h >> np.uint64(32)).astype(np.float64),
+        "hashes_lo": (h & lo32).astype(np.float64),
+        "nodes": cols["nodes"].astype(np.float64),
+        "ref_offsets": cols["ref_offsets"].astype(np.float64),
+        "allele_frequencies": cols["allele_frequencies"].astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    log("outputs of the last step: %d sampled records of %d written to %s" % (len(h), n, d))
 
 
 def verify(out, g, k, n_interior):

@@ -4,11 +4,13 @@ Run in the build container only (needs /root/reference; the test-only stand-ins 
 tests/standins/ replace the absent third-party packages obgraph / npstructures / Bio / pyfaidx):
 
     python tests/golden/make_golden.py
+    python tests/golden/make_golden.py cross      # reference_cross.json.gz only (tests/test_oracle_vs_reference.py)
 
 Fixtures are data only: graph literals / generator parameters and the reference's outputs.
 Nothing of the reference's source is stored.  The GPU box has no /root/reference; tests there
 read these files.
 """
+import gzip
 import hashlib
 import json
 import logging
@@ -34,7 +36,7 @@ from obgraph import Graph  # noqa: E402
 from graph_kmer_index_amd.graph import GraphArrays, synthetic_linear_graph, synthetic_snp_graph  # noqa: E402
 from graphgen import (random_bubble_graph, overlapping_bubble_graph, nested_bubble_graph, deep_nested_graph,  # noqa: E402
                       empty_chain_graph)
-from golden_cases import REFERENCE_TEST_GRAPHS, canonical_digest  # noqa: E402
+from golden_cases import REFERENCE_TEST_GRAPHS, canonical_digest, graph_digest  # noqa: E402
 
 
 def run_finder(graph, k, **kw):
@@ -422,7 +424,113 @@ def deep_window_cases():
     return cases
 
 
+def _flat(fl, cp=None):
+    out = dict(kmers=fl._hashes.tolist(), nodes=fl._nodes.tolist(), start_nodes=fl._start_nodes.tolist(),
+               start_offsets=fl._start_offsets.tolist(), allele_frequencies=fl._allele_frequencies.tolist())
+    if cp is not None:
+        out.update(crit_nodes=cp.nodes.tolist(), crit_offsets=cp.offsets.tolist())
+    return out
+
+
+def _cross_graph(mode, rng, k):
+    if mode == "bubble":
+        return random_bubble_graph(rng, p_indel=float(rng.choice([0.0, 0.5])), with_af=True)
+    if mode == "overlap":
+        return overlapping_bubble_graph(rng)
+    nv = int(rng.integers(1, 4))
+    return random_bubble_graph(rng, n_var=nv, min_ref=1, max_ref=3 * k + 8, p_indel=0.3,
+                               chain_after={int(rng.integers(-1, nv)): int(rng.integers(1, k + 2))})
+
+
+def reference_cross_cases():
+    """tests/test_oracle_vs_reference.py's graphs, drawn from the same seeded generators in the same order, and what the
+    reference returns on each: critical paths and find() + get_flat_kmers() in emission order, or where it raises."""
+    out = {}
+    for mode, n, seed in [("bubble", 150, 1), ("overlap", 100, 2), ("chain", 250, 3)]:
+        rng = np.random.default_rng(seed)
+        cases = []
+        for _ in range(n):
+            k = int(rng.integers(3, 8))
+            M = int(rng.choice([0, 1, 2, 3, 4, 100]))
+            one = bool(rng.integers(0, 2))
+            seqs, edges, lin, af = _cross_graph(mode, rng, k)
+            case = dict(k=k, M=M, one=one, graph=graph_digest(seqs, edges, lin, af))
+            rg = Graph.from_dicts(seqs, edges, lin, af)
+            try:
+                cp = CriticalGraphPaths.from_graph(rg, k)
+            except OverflowError:
+                cases.append(dict(case, raises="E2"))
+                continue
+            f = DenseKmerFinder(rg, k, critical_graph_paths=cp, max_variant_nodes=M, only_save_one_node_per_kmer=one)
+            f.find()
+            cases.append(dict(case, **_flat(f.get_flat_kmers(), cp)))
+        out["%s-%d-%d" % (mode, n, seed)] = cases
+    from graph_kmer_index_amd.graph import synthetic_indel_graph
+    letters = "ACGT"
+    cases = []
+    for seed, k, M, one in [(1, 5, 4, True), (2, 7, 5, True), (3, 6, 2, False), (4, 7, 5, False), (5, 4, 1, True)]:
+        g = synthetic_indel_graph(1500, 70, k=k, seed=seed, p_del=0.3, p_ins=0.3)
+        seqs = {n: "".join(letters[c] for c in g.seq[g.seq_start[n]:g.seq_start[n + 1]]) for n in range(g.n_nodes)}
+        edges = {n: g.edges[g.edge_start[n]:g.edge_start[n + 1]].tolist() for n in range(g.n_nodes)
+                 if g.edge_start[n + 1] > g.edge_start[n]}
+        lin = [n for n in range(g.n_nodes) if g.is_ref[n] and g.node_size[n] > 0]
+        af = {n: float(g.allele_freq[n]) for n in range(g.n_nodes)}
+        rg = Graph.from_dicts(seqs, edges, lin, af)
+        cp = CriticalGraphPaths.from_graph(rg, k)
+        f = DenseKmerFinder(rg, k, critical_graph_paths=cp, max_variant_nodes=M, only_save_one_node_per_kmer=one)
+        f.find()
+        cases.append(dict(seed=seed, k=k, M=M, one=one, graph=graph_digest(seqs, edges, lin, af), **_flat(f.get_flat_kmers(), cp)))
+    out["indel"] = cases
+    for mode, n, seed in [("nested", 80, 5), ("deep", 80, 6), ("follow", 60, 7), ("nested_chain", 120, 8)]:
+        rng = np.random.default_rng(seed)
+        cases = []
+        for it in range(n):
+            k = int(rng.integers(3, 8))
+            M = int(rng.choice([0, 1, 2, 3, 4, 100]))
+            one = bool(rng.integers(0, 2))
+            if mode == "nested_chain":
+                k = int(rng.integers(3, 16))
+                M = int(rng.choice([1, 2, 3, 4]))
+                seqs, edges, lin, af = nested_bubble_graph(rng, n_var=int(rng.integers(2, 6)), min_ref=1, max_ref=12, p_nest=0.6,
+                                                           p_chain=0.5)
+            elif mode == "deep":
+                seqs, edges, lin, af = deep_nested_graph(rng, n_var=int(rng.integers(1, 4)), max_depth=int(rng.integers(1, 4)))
+            elif mode == "nested" or it % 2:
+                seqs, edges, lin, af = nested_bubble_graph(rng, n_var=int(rng.integers(2, 5)), p_nest=0.7)
+            else:
+                seqs, edges, lin, af = random_bubble_graph(rng)
+            g = GraphArrays.from_dicts(seqs, edges, lin, af)
+            rg = Graph.from_dicts(seqs, edges, lin, af)
+            follow = None
+            if mode == "follow":
+                cand = [x for x in seqs if not g.is_ref[x]]
+                follow = set(int(x) for x in rng.choice(cand, size=max(1, len(cand) // 3), replace=False))
+            case = dict(k=k, M=M, one=one, follow=None if follow is None else sorted(follow),
+                        graph=graph_digest(seqs, edges, lin, af))
+            try:
+                cp = CriticalGraphPaths.from_graph(rg, k)
+            except (OverflowError, AssertionError):
+                cases.append(dict(case, raises="critical_paths"))
+                continue
+            f = DenseKmerFinder(rg, k, critical_graph_paths=cp, max_variant_nodes=M, only_save_one_node_per_kmer=one,
+                                only_follow_nodes=None if follow is None else set(follow))
+            try:
+                f.find()
+            except AssertionError:
+                cases.append(dict(case, raises="find", crit_nodes=cp.nodes.tolist(), crit_offsets=cp.offsets.tolist()))
+                continue
+            cases.append(dict(case, **_flat(f.get_flat_kmers(), cp)))
+        out["%s-%d-%d" % (mode, n, seed)] = cases
+    return out
+
+
 def main():
+    if sys.argv[1:] == ["cross"]:
+        cross = reference_cross_cases()
+        with gzip.open(os.path.join(HERE, "reference_cross.json.gz"), "wt") as f:
+            json.dump(cross, f, separators=(",", ":"))
+        print("reference cross-check cases:", {m: len(c) for m, c in cross.items()})
+        return
     if sys.argv[1:] == ["deep"]:
         deep = deep_window_cases()
         with open(os.path.join(HERE, "finder_deep.json"), "w") as f:

@@ -6,6 +6,7 @@ tests/test_critical_graph_paths.py -- cited per entry) and of SURVEY.md Appendix
 `find_only_kmers_starting_at_position(node, offset)` instead of `find()`.
 """
 import hashlib
+import json
 import numpy as np
 
 REFERENCE_TEST_GRAPHS = {
@@ -134,3 +135,11 @@ def canonical_digest(cols):
     h.update(np.asarray(cols["start_offsets"]).astype(np.int16)[o].tobytes())
     h.update(np.asarray(cols["allele_frequencies"]).astype(np.float64)[o].tobytes())
     return h.hexdigest()
+
+
+def graph_digest(seqs, edges, lin, af):
+    """sha256 of a generator's graph literals (node -> sequence, node -> successors, linear-ref nodes, node -> allele
+    frequency or None): a fixture recorded from a seeded generator names the graph it was recorded on."""
+    canon = [sorted((int(a), str(b)) for a, b in seqs.items()), sorted((int(a), [int(x) for x in b]) for a, b in edges.items()),
+             [int(x) for x in lin], None if af is None else sorted((int(a), float(b)) for a, b in af.items())]
+    return hashlib.sha256(json.dumps(canon, separators=(",", ":")).encode()).hexdigest()

@@ -326,15 +326,15 @@ def test_loopback_ranks_build_the_oracle_index(world):
 
 
 def test_bench_line_has_the_contract_fields(tmp_path):
-    """bench.py end to end at a small size: one JSON line with the driver's fields, the roofline and CPU-baseline objects
-    and the three secondary records; a second run as two ranks (on this one GPU) over the socket control plane."""
+    """bench.py --full end to end at a small size: one JSON line with the driver's fields, the roofline and CPU-baseline
+    objects and the three secondary records; a second run as two ranks (on this one GPU) over the socket control plane."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     small = ["--bases", "2e7", "--sites", "3e4", "--steps", "2", "--warmup", "1", "--cpu-sample-bases", "2e6", "--cpu-cores", "2"]
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--reads", "2e4"] + small, capture_output=True,
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--reads", "2e4"] + small, capture_output=True,
                          text=True, timeout=600, check=True).stdout.strip().splitlines()
     assert len(out) == 1
     d = json.loads(out[0])
@@ -361,7 +361,7 @@ def test_bench_line_has_the_contract_fields(tmp_path):
     # (1) the driver's form: `python bench.py --gpus 2` with NO launcher environment -- bench.py starts its own two rank
     # processes (fresh children, before any GPU call), generates the graph once, and times exchange + build with ranks
     clean = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--no-cpu-baseline"] + small, env=clean,
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--no-cpu-baseline"] + small, env=clean,
                          capture_output=True, text=True, timeout=900)
     assert run.returncode == 0, run.stderr[-3000:]
     lines = run.stdout.strip().splitlines()
@@ -392,3 +392,60 @@ def test_bench_line_has_the_contract_fields(tmp_path):
     assert lines[1] == "" and lines[0].count("\n") == 0                 # rank 0 alone prints the line
     d3 = json.loads(lines[0])
     assert d3["n_gpus"] == 2 and d3["config"]["records_per_step"] == d["config"]["records_per_step"]
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full): the headline line alone, --steps timed steps, and --dump-outputs writes the last
+    step's columns -- float32 / float64, under 64 MB, the same from run to run, and equal to a fresh find on the device."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from graph_kmer_index_amd import DenseKmerFinder
+    from graph_kmer_index_amd.graph import synthetic_snp_graph
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    small = ["--bases", "2e7", "--sites", "3e4", "--steps", "3", "--warmup", "1"]
+    lines = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--dump-outputs", str(d)] + small,
+                             capture_output=True, text=True, timeout=600)
+        assert run.returncode == 0, run.stderr[-3000:]
+        out = run.stdout.strip().splitlines()
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+    d = lines[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "roofline"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"]
+    for key in ("index_build", "read_mapping", "early_stop_search", "full_index", "sharded_build"):
+        assert key not in d, key                                  # measured under --full only
+    assert d["cpu_baseline"] is None and d["roofline"]["ceiling_measured"] is None
+    names = sorted(f for f in os.listdir(str(tmp_path / "run0")))
+    assert names == sorted(f for f in os.listdir(str(tmp_path / "run1"))) and "column_checksums.npy" in names
+    total = 0
+    got = {}
+    for f in names:
+        a, b = np.load(str(tmp_path / "run0" / f)), np.load(str(tmp_path / "run1" / f))
+        assert a.dtype in (np.float32, np.float64), f
+        assert np.array_equal(a, b), f
+        total += a.nbytes
+        got[f[:-4]] = a
+    assert total <= 64 << 20
+    # the dump is the step's output: the sampled records and the checksums against a fresh find on the device
+    g = synthetic_snp_graph(20_000_000, 30_000, k=31, seed=1234)
+    finder = DenseKmerFinder(g, 31, only_save_one_node_per_kmer=True, max_variant_nodes=5)
+    fl = finder.find_flat_on_device()
+    finder.synchronize()
+    n = fl.n
+    assert got["records"].tolist() == [n, finder.interior_records()] and n == d["config"]["records_per_step"]
+    idx = got["sample_index"].astype(np.int64)
+    assert len(idx) == min(n, 1 << 20) and np.all(np.diff(idx) > 0) and idx[-1] < n
+    h = fl.hashes.to_host(n)[idx]
+    assert np.array_equal((got["hashes_hi"].astype(np.uint64) << np.uint64(32)) | got["hashes_lo"].astype(np.uint64), h)
+    assert np.array_equal(got["nodes"], fl.nodes.to_host(n)[idx].astype(np.float64))
+    assert np.array_equal(got["ref_offsets"], fl.ref_offsets.to_host(n)[idx].astype(np.float64))
+    assert np.array_equal(got["allele_frequencies"], fl.allele_frequencies.to_host(n)[idx])
+    for row, name in zip(got["column_checksums"].tolist(), ("hashes", "nodes", "ref_offsets", "allele_frequencies")):
+        s_, x_ = getattr(fl, name).checksum(n)
+        assert row == [s_ >> 32, s_ & 0xFFFFFFFF, x_ >> 32, x_ & 0xFFFFFFFF], name

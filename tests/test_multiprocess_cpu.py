@@ -110,10 +110,12 @@ def test_shards_partition_small_graphs_with_few_or_offset0_critical_points():
     assert seen_no_crit > 0 and seen_offset0 > 0
 
 
-def _socket_worker(rank, world, port, tmpdir):
+def _socket_worker(rank, world, port, tmpdir, joined=None):
     """Twin of _worker over parallel.SocketControlPlane (the product's control plane: plain TCP, no torch)."""
     from graph_kmer_index_amd.parallel import SocketControlPlane
     plane = SocketControlPlane(rank, world, "127.0.0.1", port)
+    if joined is not None:
+        joined.set()                           # rank 0 has adopted this rank
     g = synthetic_snp_graph(60000, 700, k=31, seed=21)
     cp = CriticalGraphPaths.from_graph(g, 31)
     a, b = shard_range(g, cp, rank, world)
@@ -133,9 +135,10 @@ def _socket_worker(rank, world, port, tmpdir):
     plane.close()
 
 
-def _intruders(port, world, stop):
+def _intruders(port, world, stop, rank1_joined):
     """What a shared host throws at rank 0's port while the real ranks join: a connection that says nothing, one that
-    sends junk, a worker of another job (wrong token), a rank outside the world, and a second 'rank 1'."""
+    sends junk, a worker of another job (wrong token), a rank outside the world, and a second 'rank 1' -- the last one
+    only once the real rank 1 has been adopted (before that, a 'rank 1' with the job's token IS rank 1 to rank 0)."""
     import socket
     import struct
     import time
@@ -144,7 +147,9 @@ def _intruders(port, world, stop):
     hellos = [b"GET / HTTP/1.0\r\n\r\n" + b"x" * 40, P.MAGIC + b"\0" * 16 + struct.pack("<qq", world, 1),
               P.MAGIC + good + struct.pack("<qq", world, world + 3), None, P.MAGIC + good + struct.pack("<qq", world, 1)]
     verdicts = []
-    for h in hellos:
+    for i, h in enumerate(hellos):
+        if i == len(hellos) - 1 and not rank1_joined.wait(60):
+            break
         deadline = time.time() + 20
         while time.time() < deadline and not stop.is_set():
             try:
@@ -175,21 +180,31 @@ def test_socket_control_plane_ranks(tmp_path, world):
     import threading
     port = 31000 + os.getpid() % 2000 + 20 * world
     ctx = multiprocessing.get_context("spawn")
-    procs = [ctx.Process(target=_socket_worker, args=(r, world, port, str(tmp_path))) for r in range(world)]
+    rank1_joined = ctx.Event()
+    procs = [ctx.Process(target=_socket_worker, args=(r, world, port, str(tmp_path), rank1_joined if r == 1 else None))
+             for r in range(world)]
     stop, seen = threading.Event(), []
-    intruder = threading.Thread(target=lambda: seen.extend(_intruders(port, world, stop)))
+    intruder = threading.Thread(target=lambda: seen.extend(_intruders(port, world, stop, rank1_joined)))
     procs[0].start()
     intruder.start()
     import time
     time.sleep(1.0)                          # the intruders get there first
-    for p in procs[1:]:
+    procs[1].start()
+    # ranks 2.. join after the second 'rank 1' has had its answer: at world > 2 rank 0 is still accepting then, and must
+    # turn the duplicate away
+    intruder.join(150)
+    for p in procs[2:]:
         p.start()
     for p in procs:
         p.join(120)
         assert p.exitcode == 0
     stop.set()
     intruder.join(30)
-    assert len(seen) >= 3 and b"OK" not in seen[:4]       # junk, foreign token, rank out of range, silence: never adopted
+    assert not intruder.is_alive()
+    # junk, foreign token, rank out of range, silence, a second rank 1: never adopted
+    assert len(seen) >= 3 and b"OK" not in seen
+    if world > 2:
+        assert len(seen) == 5 and seen[4] == b"NO"
     parts = [np.load(str(tmp_path / ("r%d.npz" % r))) for r in range(world)]
     g = synthetic_snp_graph(60000, 700, k=31, seed=21)
     n_full = len(oracle.find(g, 31, None, True, 5)["kmers"])

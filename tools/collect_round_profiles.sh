@@ -8,7 +8,7 @@
 set -u
 tag="$1"; R="$(pwd)"; O="$R/gpurun_out/${tag}_final"; mkdir -p "$O"; export TMPDIR=/tmp
 cd /tmp
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -- python3 "$R/bench.py" > "$O/bench.json" 2> "$O/bench.err" || { echo "bench under rocprofv3 failed"; tail -5 "$O/bench.err"; exit 1; }
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -- python3 "$R/bench.py" --full > "$O/bench.json" 2> "$O/bench.err" || { echo "bench under rocprofv3 failed"; tail -5 "$O/bench.err"; exit 1; }
 cd "$R"
 cp "$O"/trace/*/*kernel_stats.csv "$O/kernel_stats.csv"
 python3 - "$O" <<'PY'

@@ -7,12 +7,12 @@ R="$(pwd)"; L="$R/graph_kmer_index_amd/libgki_hip.so"; export TMPDIR=/tmp
 cp "$L" /tmp/gki_new_keep.so
 one() {  # $1 tag, $2 lib
   cp "$2" "$L"
-  timeout -k 10 300 python3 "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null \
+  timeout -k 10 300 python3 "$R/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null \
    | python3 -c "import json,sys; d=json.loads(sys.stdin.readline()); print('$1  index_build %.2f ms   reverse_index %.2f ms' % (d['index_build']['ms'], d['index_build']['reverse_index']['ms']))"
 }
 trace() {  # $1 tag, $2 lib
   cp "$2" "$L"; local d="$R/gpurun_out/idx_trace_$1"
-  (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$d" -- python3 "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline > "$d.json" 2> "$d.err") || { echo "trace $1 failed"; return; }
+  (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$d" -- python3 "$R/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline > "$d.json" 2> "$d.err") || { echo "trace $1 failed"; return; }
   python3 - "$d" "$1" <<'PY'
 import csv, glob, sys
 for f in glob.glob(sys.argv[1] + "/*/*kernel_stats.csv"):
