@@ -5,6 +5,9 @@ collision_free_kmer_index.py:393-402).
 
     python -m graph_kmer_index_amd.command_line_interface index -g graph.npz -k 31 -o flat
     python -m graph_kmer_index_amd.command_line_interface make_from_flat -f flat -o index
+    python -m graph_kmer_index_amd.command_line_interface make_unique_variant_kmers -g graph.npz -V variant_to_nodes.npz \
+        -k 31 -i index.npz -p position_id -D True -v variants.vcf -o variant_kmers
+    python -m graph_kmer_index_amd.command_line_interface make_reverse -f variant_kmers.npz -o reverse
 
 `-g` takes an obgraph file when obgraph is installed, else a GraphArrays .npz (GraphArrays.to_file).  `index -t N` runs
 one process per GPU (at most N, at most the visible devices), each on its own range of critical-path numbers, and
@@ -144,6 +147,63 @@ def add_reverse_complements(args):
         .to_file(args.out_file_name)
 
 
+def make_reverse(args):
+    """command_line_interface.py:177-181."""
+    from .reverse_kmer_index import ReverseKmerIndex
+    flat = FlatKmers.from_file(args.flat_index)
+    ReverseKmerIndex.from_flat_kmers(flat).to_file(args.out_file_name)
+    logging.info("Done. Wrote reverse index to file: %s" % args.out_file_name)
+
+
+def load_position_id(file_name, graph):
+    """-p: the reference's PositionId file (through shared_memory_wrapper when installed); None = the default position
+    ids of the graph (exclusive cumulative node size)."""
+    if file_name is None:
+        return _DefaultPositionId(graph)
+    from shared_memory_wrapper import from_file
+    return from_file(file_name)
+
+
+class _DefaultPositionId:
+    def __init__(self, graph):
+        self._base = GraphArrays.from_obgraph(graph).position_id_base()
+
+    def get(self, nodes, offsets):
+        return self._base[np.asarray(nodes, dtype=np.int64)] + np.asarray(offsets, dtype=np.int64)
+
+
+def make_unique_variant_kmers(args):
+    """command_line_interface.py:299-389, dense path: one finder per `-c` chunk of VCF data lines (`_nodes_found` starts
+    empty at every chunk), run here as one device batch.  `-t` is accepted; the chunks' outputs do not depend on it."""
+    from .unique_variant_kmers import UniqueVariantKmersFinder, VariantArrays, load_variant_to_nodes
+    if not _bool(args.use_dense_kmer_finder):
+        raise NotImplementedError("make_unique_variant_kmers: only the dense path is supported; pass -D True "
+                                  "(the SnpKmerFinder path is not ported)")
+    if _bool(args.simple):
+        raise NotImplementedError("make_unique_variant_kmers: -S (simple selection) is not supported; the supported "
+                                  "mode is -D True without -S")
+    for flag, value in (("-N", args.node_to_variants), ("-H", args.haplotype_matrix), ("-I", args.kmer_counter)):
+        if value is not None:
+            raise NotImplementedError("make_unique_variant_kmers: %s is not supported (dense path with a "
+                                      "CollisionFreeKmerIndex from -i only)" % flag)
+    if args.kmer_index is None:
+        raise ValueError("make_unique_variant_kmers: -i (a CollisionFreeKmerIndex with frequencies) is required")
+    if args.vcf is None:
+        raise ValueError("make_unique_variant_kmers: -v (the VCF) is required")
+    graph = load_graph(args.graph)
+    finder = UniqueVariantKmersFinder(graph, load_variant_to_nodes(args.variant_to_nodes), VariantArrays.from_vcf(args.vcf),
+                                      args.kmer_size, args.max_variant_nodes,
+                                      kmer_index_with_frequencies=CollisionFreeKmerIndex.from_file(args.kmer_index),
+                                      do_not_choose_lowest_frequency_kmers=_bool(args.do_not_choose_lowest_frequency_kmers),
+                                      use_dense_kmer_finder=True,
+                                      position_id_index=load_position_id(args.position_id_index, graph),
+                                      chunk_size=args.chunk_size)
+    flat = finder.find_unique_kmers()
+    flat.to_file(args.out_file_name)
+    logging.info("Wrote %d k-mers of %d variants to %s" % (len(flat._hashes), finder.last_counts.get("active", 0),
+                                                          args.out_file_name))
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description="graph_kmer_index on MI355X (in-scope sub-commands)")
     sub = parser.add_subparsers()
@@ -182,6 +242,28 @@ def build_parser():
     p.add_argument("-o", "--out-file-name", required=True)
     p.add_argument("-k", "--kmer-size", type=int, required=True)
     p.set_defaults(func=add_reverse_complements)
+    p = sub.add_parser("make_reverse")
+    p.add_argument("-f", "--flat-index", required=True)
+    p.add_argument("-o", "--out-file-name", required=True)
+    p.set_defaults(func=make_reverse)
+    p = sub.add_parser("make_unique_variant_kmers")
+    p.add_argument("-g", "--graph", required=True)
+    p.add_argument("-V", "--variant_to_nodes", required=True)
+    p.add_argument("-N", "--node-to-variants", required=False)
+    p.add_argument("-H", "--haplotype-matrix", required=False)
+    p.add_argument("-k", "--kmer-size", required=True, type=int)
+    p.add_argument("-i", "--kmer-index", required=False)
+    p.add_argument("-I", "--kmer-counter", required=False)
+    p.add_argument("-p", "--position-id-index", required=False)
+    p.add_argument("-D", "--use-dense-kmer-finder", required=False, type=_bool, default=False)
+    p.add_argument("-o", "--out-file-name", required=True)
+    p.add_argument("-v", "--vcf", required=False)
+    p.add_argument("-t", "--n-threads", required=False, default=1, type=int)
+    p.add_argument("-c", "--chunk-size", required=False, default=10000, type=int)
+    p.add_argument("-m", "--max-variant-nodes", required=False, default=6, type=int)
+    p.add_argument("-d", "--do-not-choose-lowest-frequency-kmers", required=False, type=_bool, default=False)
+    p.add_argument("-S", "--simple", type=_bool, default=False)
+    p.set_defaults(func=make_unique_variant_kmers)
     return parser
 
 

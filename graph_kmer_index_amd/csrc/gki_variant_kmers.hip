@@ -1,0 +1,281 @@
+// UniqueVariantKmersFinder on the device (unique_variant_kmers.py:114-270 of the reference, dense path): for every variant
+// the k-mers that stand for its ref and alt allele, chosen among its P = len(range(2, k-2)[::4]) start positions.
+//
+//   gki_uvk_starts     one lane per (variant, start): linear-ref offset -> (node, offset) by binary search
+//   (gki_forward_count / gki_forward_emit over all starts at once, no store filter)
+//   gki_uvk_summarize  one lane per start: its records of the variant's ref and alt node, their maximum frequency in the
+//                      index (first hit of h plus first hit of its 31-mer reverse complement, get_frequency's defaults),
+//                      and whether a hash is shared by a ref window and an alt window among the first 500 windows
+//   gki_uvk_select     one lane per variant: rules 5-6 over its summaries for a given store set, record counts, scan
+//   gki_uvk_emit       one lane per variant: the chosen start's records of the stored nodes, in emission order
+//
+// Every per-lane quantity is a scalar in registers: no arrays, no scratch.
+#include "gki_common.h"
+
+namespace {
+
+constexpr int UVK_WINDOW_CAP = 500;          // kmer_finder.py:137-160: kmers_found keeps the first 500 windows
+
+// rc(x) at k = 31: digit-reverse(~x) (gki_hash.hip, kmer_hashing.py:24-28)
+__device__ __forceinline__ uint64_t uvk_revcomp31(uint64_t x) {
+    uint64_t y = __brevll(~(x & ((1ull << 62) - 1ull)));
+    y = ((y & 0xAAAAAAAAAAAAAAAAull) >> 1) | ((y & 0x5555555555555555ull) << 1);
+    return y >> 2;
+}
+
+// frequency of the first record of `q` in its bucket, 0 for a miss (collision_free_kmer_index.py:336-344)
+__device__ __forceinline__ uint32_t uvk_first_hit_frequency(const int32_t *__restrict__ hashes_to_index,
+                                                            const uint32_t *__restrict__ n_kmers,
+                                                            const uint64_t *__restrict__ kmers,
+                                                            const uint16_t *__restrict__ frequencies, int64_t n,
+                                                            GkiMod mod, uint64_t bucket_begin, uint64_t n_buckets,
+                                                            uint64_t q) {
+    const uint64_t b = gki_mod(mod, q);
+    if (b < bucket_begin || b - bucket_begin >= n_buckets) return 0;
+    const int64_t first = hashes_to_index[b - bucket_begin];
+    const int64_t cnt = n_kmers[b - bucket_begin];
+    for (int64_t j = 0; j < cnt; ++j) {
+        const int64_t p = first + j;
+        if (p < 0 || p >= n) break;
+        if (kmers[p] == q) return frequencies[p];
+    }
+    return 0;
+}
+
+__global__ __launch_bounds__(256) void k_uvk_starts(const int64_t *__restrict__ lin_start, const int32_t *__restrict__ lin_node,
+                                                    const int32_t *__restrict__ node_size, int64_t n_lin,
+                                                    const int64_t *__restrict__ var_ref_offset, int64_t n_var, int P,
+                                                    int32_t *__restrict__ out_nodes, int32_t *__restrict__ out_offsets,
+                                                    int32_t *__restrict__ out_variant, unsigned long long *__restrict__ first_bad) {
+    const int64_t n = n_var * P;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const int64_t v = i / P;
+        const int j = (int)(i - v * P);
+        const int64_t x = var_ref_offset[v] - (2 + 4 * (P - 1 - j));     // [POS - i for i in range(2, k-2)][::4][::-1]
+        // the last linear node whose first base is at or before x
+        int64_t lo = 0, hi = n_lin;                      // answer in [lo, hi): lin_start[lo] <= x < lin_start[hi]
+        int32_t node = 0, off = 0;
+        bool ok = n_lin > 0 && x >= lin_start[0];
+        if (ok) {
+            while (hi - lo > 1) {
+                const int64_t mid = lo + ((hi - lo) >> 1);
+                if (lin_start[mid] <= x) lo = mid; else hi = mid;
+            }
+            node = lin_node[lo];
+            const int64_t d = x - lin_start[lo];
+            ok = d < (int64_t)node_size[node];
+            off = (int32_t)d;
+        }
+        if (!ok) { atomicMin(first_bad, (unsigned long long)v); node = 0; off = 0; }
+        out_nodes[i] = node;
+        out_offsets[i] = off;
+        out_variant[i] = (int32_t)v;
+    }
+}
+
+// A new window begins at record r unless r continues the previous record's window: same hash, same end position, a
+// larger node (a window's records are its distinct nodes in ascending order, and two windows that end at the same
+// position both hold the node they end in, so the next window's first node is never above the previous one's last).
+__device__ __forceinline__ bool uvk_new_window(const int64_t *__restrict__ hashes, const int32_t *__restrict__ start_nodes,
+                                               const int16_t *__restrict__ start_offsets, const int32_t *__restrict__ nodes,
+                                               int64_t r, int64_t rs) {
+    return r == rs || hashes[r] != hashes[r - 1] || start_nodes[r] != start_nodes[r - 1] ||
+           start_offsets[r] != start_offsets[r - 1] || nodes[r] <= nodes[r - 1];
+}
+
+__global__ __launch_bounds__(256) void k_uvk_summarize(
+    const int64_t *__restrict__ rec_start, int64_t n_pos, int P, const int64_t *__restrict__ hashes,
+    const int32_t *__restrict__ start_nodes, const int16_t *__restrict__ start_offsets, const int32_t *__restrict__ nodes,
+    const int32_t *__restrict__ ref_nodes, const int32_t *__restrict__ alt_nodes,
+    const int32_t *__restrict__ hashes_to_index, const uint32_t *__restrict__ n_kmers, const uint64_t *__restrict__ kmers,
+    const uint16_t *__restrict__ frequencies, int64_t n_index, GkiMod mod, uint64_t bucket_begin, uint64_t n_buckets,
+    gki_uvk_summary *__restrict__ out) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_pos; i += stride) {
+        const int64_t v = i / P;
+        const int32_t ref = ref_nodes[v], alt = alt_nodes[v];
+        const bool same = ref == alt;
+        const int64_t rs = rec_start[i], re = rec_start[i + 1];
+        // records inside the first 500 windows: [rs, lim); at most 500 records hold at most 500 windows
+        int64_t lim = re;
+        if (re - rs > UVK_WINDOW_CAP) {
+            int w = 0;
+            for (int64_t r = rs; r < re; ++r) {
+                if (uvk_new_window(hashes, start_nodes, start_offsets, nodes, r, rs)) {
+                    if (w == UVK_WINDOW_CAP) { lim = r; break; }
+                    ++w;
+                }
+            }
+        }
+        uint32_t n_ref = 0, n_alt = 0, f_ref = 0, f_alt = 0, flags = same ? 2u : 0u;
+        for (int64_t r = rs; r < re; ++r) {
+            const int32_t nd = nodes[r];
+            const bool is_ref = nd == ref, is_alt = !same && nd == alt;
+            if (!is_ref && !is_alt) continue;
+            const uint64_t h = (uint64_t)hashes[r];
+            const uint32_t f = uvk_first_hit_frequency(hashes_to_index, n_kmers, kmers, frequencies, n_index, mod,
+                                                       bucket_begin, n_buckets, h) +
+                               uvk_first_hit_frequency(hashes_to_index, n_kmers, kmers, frequencies, n_index, mod,
+                                                       bucket_begin, n_buckets, uvk_revcomp31(h));
+            if (is_ref) { ++n_ref; f_ref = f > f_ref ? f : f_ref; }
+            else { ++n_alt; f_alt = f > f_alt ? f : f_alt; }
+            if (r < lim && !(flags & 1u)) {
+                if (same) flags |= 1u;                  // kmers_ref and kmers_variant are the same non-empty set
+                else if (is_alt) {                      // an earlier-or-later ref record of the first 500 windows with h
+                    for (int64_t q = rs; q < lim; ++q)
+                        if (nodes[q] == ref && hashes[q] == (int64_t)h) { flags |= 1u; break; }
+                }
+            }
+        }
+        gki_uvk_summary s;
+        s.n_ref = n_ref; s.n_alt = n_alt; s.f_ref = f_ref; s.f_alt = f_alt; s.flags = flags;
+        out[i] = s;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_uvk_select(const gki_uvk_summary *__restrict__ summ, int64_t n_var, int P, int lowest,
+                                                    const uint8_t *__restrict__ store_mask, int32_t *__restrict__ choice,
+                                                    uint32_t *__restrict__ count) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n_var; v += stride) {
+        const uint32_t m = store_mask ? store_mask[v] : 3u;
+        int best = P - 1, first = -1;
+        uint32_t best_score = 0xFFFFFFFFu;
+        for (int j = 0; j < P; ++j) {
+            const gki_uvk_summary s = summ[v * P + j];
+            const bool shared = (s.flags & 1u) && (m & 1u) && ((m & 2u) || (s.flags & 2u));
+            if (shared && j != P - 1) continue;                       // rule 5; the last position is always valid
+            uint32_t score = 0;
+            if (m & 1u) score = s.f_ref;
+            if ((m & 2u) && s.f_alt > score) score = s.f_alt;
+            if (first < 0) first = j;
+            if (score < best_score) { best_score = score; best = j; }  // stable sort: the first of the lowest
+            if (score <= 1) break;                                    // rule 6: no later position is looked at
+        }
+        const int c = lowest ? best : first;
+        const gki_uvk_summary s = summ[v * P + c];
+        choice[v] = c;
+        count[v] = ((m & 1u) ? s.n_ref : 0u) + ((m & 2u) ? s.n_alt : 0u);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_uvk_emit(
+    const int64_t *__restrict__ rec_start, int64_t n_var, int P, const int32_t *__restrict__ choice,
+    const uint8_t *__restrict__ store_mask, const int32_t *__restrict__ ref_nodes, const int32_t *__restrict__ alt_nodes,
+    const int64_t *__restrict__ out_start, const int64_t *__restrict__ hashes, const int32_t *__restrict__ start_nodes,
+    const int16_t *__restrict__ start_offsets, const int32_t *__restrict__ nodes, const double *__restrict__ af64,
+    const int64_t *__restrict__ pos_base, uint64_t *__restrict__ o_hashes, uint32_t *__restrict__ o_nodes,
+    uint64_t *__restrict__ o_ref_offsets, float *__restrict__ o_af) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n_var; v += stride) {
+        const uint32_t m = store_mask ? store_mask[v] : 3u;
+        const int32_t ref = ref_nodes[v], alt = alt_nodes[v];
+        const int64_t i = v * P + choice[v];
+        const int64_t re = rec_start[i + 1];
+        int64_t o = out_start[v];
+        const int64_t o_end = out_start[v + 1];
+        for (int64_t r = rec_start[i]; r < re && o < o_end; ++r) {
+            const int32_t nd = nodes[r];
+            if (!(((m & 1u) && nd == ref) || ((m & 2u) && nd == alt && alt != ref))) continue;
+            o_hashes[o] = (uint64_t)hashes[r];
+            o_nodes[o] = (uint32_t)nd;
+            o_ref_offsets[o] = (uint64_t)(pos_base[start_nodes[r]] + (int64_t)start_offsets[r]);   // PositionId.get
+            o_af[o] = (float)af64[r];
+            ++o;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int gki_uvk_starts(gki_graph *g, const void *d_lin_start, const void *d_lin_node, int64_t n_lin,
+                   const void *d_var_ref_offset, int64_t n_var, int n_starts_per_variant, void *d_nodes, void *d_offsets,
+                   void *d_variant, int64_t *first_bad_variant) {
+    *first_bad_variant = -1;
+    if (n_starts_per_variant < 1) return gki_set_error(GKI_ERR_BAD_ARG, "gki_uvk_starts: no start position per variant");
+    GKI_TRY(gki_check_graph_device(g, "gki_uvk_starts"));
+    if (n_var <= 0) return GKI_OK;
+    unsigned long long *bad = nullptr;
+    HIP_TRY(gki_dev_malloc((void **)&bad, 8));
+    hipError_t e = hipMemset(bad, 0xFF, 8);
+    if (e == hipSuccess) {
+        const int64_t n = n_var * n_starts_per_variant;
+        hipLaunchKernelGGL(k_uvk_starts, dim3(stream_grid(n, 256)), dim3(256), 0, 0, (const int64_t *)d_lin_start,
+                           (const int32_t *)d_lin_node, g->d.node_size, n_lin, (const int64_t *)d_var_ref_offset, n_var,
+                           n_starts_per_variant, (int32_t *)d_nodes, (int32_t *)d_offsets, (int32_t *)d_variant, bad);
+        e = hipGetLastError();
+    }
+    unsigned long long h = ~0ull;
+    if (e == hipSuccess) e = hipMemcpy(&h, bad, 8, hipMemcpyDeviceToHost);
+    (void)gki_dev_free(bad);
+    HIP_TRY(e);
+    if (h != ~0ull) *first_bad_variant = (int64_t)h;
+    return GKI_OK;
+}
+
+int gki_uvk_summarize(gki_graph *g, const gki_index_view *ix, const void *d_rec_start, int64_t n_var,
+                      int n_starts_per_variant, const void *d_hashes, const void *d_start_nodes, const void *d_start_offsets,
+                      const void *d_nodes, const void *d_ref_nodes, const void *d_alt_nodes, void *d_summary) {
+    if (n_starts_per_variant < 1) return gki_set_error(GKI_ERR_BAD_ARG, "gki_uvk_summarize: no start position per variant");
+    if (ix == nullptr || ix->modulo == 0) return gki_set_error(GKI_ERR_BAD_ARG, "gki_uvk_summarize: no frequency index");
+    GKI_TRY(gki_check_graph_device(g, "gki_uvk_summarize"));
+    const int64_t n_pos = n_var * n_starts_per_variant;
+    if (n_pos <= 0) return GKI_OK;
+    const uint64_t n_buckets = ix->n_buckets ? ix->n_buckets : ix->modulo;
+    hipLaunchKernelGGL(k_uvk_summarize, dim3(stream_grid(n_pos, 256)), dim3(256), 0, 0, (const int64_t *)d_rec_start, n_pos,
+                       n_starts_per_variant, (const int64_t *)d_hashes, (const int32_t *)d_start_nodes,
+                       (const int16_t *)d_start_offsets, (const int32_t *)d_nodes, (const int32_t *)d_ref_nodes,
+                       (const int32_t *)d_alt_nodes, (const int32_t *)ix->d_hashes_to_index, (const uint32_t *)ix->d_n_kmers,
+                       (const uint64_t *)ix->d_kmers, (const uint16_t *)ix->d_frequencies, ix->n, gki_mod_of(ix->modulo),
+                       ix->bucket_begin, n_buckets, (gki_uvk_summary *)d_summary);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(0));
+    return GKI_OK;
+}
+
+int gki_uvk_select(const void *d_summary, int64_t n_var, int n_starts_per_variant, int choose_lowest,
+                   const void *d_store_mask, void *d_choice, void *d_out_start, int64_t *n_records) {
+    *n_records = 0;
+    if (n_starts_per_variant < 1) return gki_set_error(GKI_ERR_BAD_ARG, "gki_uvk_select: no start position per variant");
+    if (n_var <= 0) { HIP_TRY(hipMemset(d_out_start, 0, 8)); return GKI_OK; }
+    uint32_t *cnt = nullptr; void *tmp = nullptr;
+    const int64_t tmp_bytes = gki_scan_tmp_bytes(n_var);
+    HIP_TRY(gki_dev_malloc((void **)&cnt, (size_t)n_var * 4));
+    const hipError_t et = gki_dev_malloc(&tmp, (size_t)tmp_bytes);
+    if (et != hipSuccess) { (void)gki_dev_free(cnt); HIP_TRY(et); }
+    hipLaunchKernelGGL(k_uvk_select, dim3(stream_grid(n_var, 256)), dim3(256), 0, 0, (const gki_uvk_summary *)d_summary,
+                       n_var, n_starts_per_variant, choose_lowest, (const uint8_t *)d_store_mask, (int32_t *)d_choice, cnt);
+    hipError_t e = hipGetLastError();
+    int rc = e == hipSuccess ? gki_scan_u32_to_i64(cnt, n_var, (int64_t *)d_out_start, tmp, tmp_bytes, 0) : GKI_OK;
+    int64_t total = 0;
+    if (e == hipSuccess && rc == GKI_OK) e = hipMemcpy(&total, (const int64_t *)d_out_start + n_var, 8, hipMemcpyDeviceToHost);
+    (void)gki_dev_free(cnt);
+    (void)gki_dev_free(tmp);
+    HIP_TRY(e);
+    if (rc != GKI_OK) return rc;
+    *n_records = total;
+    return GKI_OK;
+}
+
+int gki_uvk_emit(gki_graph *g, const void *d_rec_start, int64_t n_var, int n_starts_per_variant, const void *d_choice,
+                 const void *d_store_mask, const void *d_ref_nodes, const void *d_alt_nodes, const void *d_out_start,
+                 const void *d_hashes, const void *d_start_nodes, const void *d_start_offsets, const void *d_nodes,
+                 const void *d_af64, void *d_out_hashes, void *d_out_nodes, void *d_out_ref_offsets, void *d_out_af32) {
+    if (n_starts_per_variant < 1) return gki_set_error(GKI_ERR_BAD_ARG, "gki_uvk_emit: no start position per variant");
+    GKI_TRY(gki_check_graph_device(g, "gki_uvk_emit"));
+    if (n_var <= 0) return GKI_OK;
+    hipLaunchKernelGGL(k_uvk_emit, dim3(stream_grid(n_var, 256)), dim3(256), 0, 0, (const int64_t *)d_rec_start, n_var,
+                       n_starts_per_variant, (const int32_t *)d_choice, (const uint8_t *)d_store_mask,
+                       (const int32_t *)d_ref_nodes, (const int32_t *)d_alt_nodes, (const int64_t *)d_out_start,
+                       (const int64_t *)d_hashes, (const int32_t *)d_start_nodes, (const int16_t *)d_start_offsets,
+                       (const int32_t *)d_nodes, (const double *)d_af64, g->d.pos_base, (uint64_t *)d_out_hashes,
+                       (uint32_t *)d_out_nodes, (uint64_t *)d_out_ref_offsets, (float *)d_out_af32);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(0));
+    return GKI_OK;
+}
+
+}  // extern "C"

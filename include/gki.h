@@ -412,6 +412,42 @@ int gki_index_lookup_emit(const gki_index_view *ix, const void *d_queries, int64
 int gki_index_get_small(const gki_index_view *ix, const uint64_t *h_queries, int q, int64_t max_hits,
                         int64_t *h_n_hits, int64_t *h_positions, int64_t capacity_per_query);
 
+/* ---------------------------------------------------------------- UniqueVariantKmersFinder (dense path)
+ * unique_variant_kmers.py:114-270: per variant, the k-mers that stand for its ref and alt node, chosen among its
+ * P = len(range(2, k-2)[::4]) start positions.  Steps (graph_kmer_index_amd/unique_variant_kmers.py drives them):
+ * gki_uvk_starts -> gki_forward_count / gki_forward_emit over all starts (no store filter, both nodes per window) ->
+ * gki_uvk_summarize -> gki_uvk_select -> gki_uvk_emit.  Start i of variant v is v * P + i, farthest from POS first.
+ *
+ * gki_uvk_starts: d_lin_start int64[n_lin] ascending linear-ref offsets of the first base of the linear-ref nodes of
+ *   nonzero size d_lin_node int32[n_lin]; d_var_ref_offset int64[n_var] = graph ref offset of POS (chromosome's start
+ *   offset + POS).  Writes (node, offset) int32 of every start and its variant int32.  *first_bad_variant = the lowest
+ *   variant with a start before 0 or past the linear path (-1: none); such starts get (0, 0).
+ * gki_uvk_summarize: one gki_uvk_summary per start from the forward search's v2 columns (records of start i are
+ *   [rec_start[i], rec_start[i+1])) and the frequency index: n_ref / n_alt records of the ref / alt node (n_alt stays 0
+ *   when alt == ref), f_ref / f_alt their maximum CollisionFreeKmerIndex.get_frequency (first hit of h plus first hit of
+ *   its 31-mer reverse complement), flags bit 0: a hash lies on a ref window and on an alt window among the first 500
+ *   windows (for alt == ref: a ref window among them), bit 1: alt == ref.
+ * gki_uvk_select: rules 5-6 per variant for store set d_store_mask uint8[n_var] (bit 0 ref stored, bit 1 alt stored;
+ *   NULL = both): d_choice int32[n_var] the chosen start (0..P-1), d_out_start int64[n_var+1] the exclusive scan of
+ *   the chosen records, *n_records the total.
+ * gki_uvk_emit: the chosen records of the stored nodes in emission order, as FlatKmers columns (uint64, uint32,
+ *   uint64 = position id of the record's end position, float32). */
+typedef struct {
+    uint32_t n_ref, n_alt, f_ref, f_alt, flags;
+} gki_uvk_summary;
+int gki_uvk_starts(gki_graph *g, const void *d_lin_start, const void *d_lin_node, int64_t n_lin,
+                   const void *d_var_ref_offset, int64_t n_var, int n_starts_per_variant, void *d_nodes, void *d_offsets,
+                   void *d_variant, int64_t *first_bad_variant);
+int gki_uvk_summarize(gki_graph *g, const gki_index_view *ix, const void *d_rec_start, int64_t n_var,
+                      int n_starts_per_variant, const void *d_hashes, const void *d_start_nodes, const void *d_start_offsets,
+                      const void *d_nodes, const void *d_ref_nodes, const void *d_alt_nodes, void *d_summary);
+int gki_uvk_select(const void *d_summary, int64_t n_var, int n_starts_per_variant, int choose_lowest,
+                   const void *d_store_mask, void *d_choice, void *d_out_start, int64_t *n_records);
+int gki_uvk_emit(gki_graph *g, const void *d_rec_start, int64_t n_var, int n_starts_per_variant, const void *d_choice,
+                 const void *d_store_mask, const void *d_ref_nodes, const void *d_alt_nodes, const void *d_out_start,
+                 const void *d_hashes, const void *d_start_nodes, const void *d_start_offsets, const void *d_nodes,
+                 const void *d_af64, void *d_out_hashes, void *d_out_nodes, void *d_out_ref_offsets, void *d_out_af32);
+
 /* ---------------------------------------------------------------- probe table (read-side hot loop)
  * A device-only re-layout of an index for counting: dir uint2[modulo] = {first record, count (16 bit, saturating)
  * | 16-bit fingerprint set << 16}, rows uint4[n] = {kmer, node, frequency}: one random 64-byte sector per query,
