@@ -1159,9 +1159,20 @@ __global__ __launch_bounds__(64 * BND_WPB, (EMIT_SLIM && !GEN && !ALL && !HAS_LO
 }
 
 // ------------------------------------------------------------------------------------ per-node constants
+// Split layout: the interior section is one dense stream of records ordered by position.  Its output blocks of IB records
+// are what k_emit_interior_dense hands to a wave; blk[b] names the node (rank among non-empty nodes) that holds record
+// min(b * IB, n_int - 1) and that record's position, for b = 0 .. ceil(n_int / IB).  Written by k_node_emit.
+constexpr int IB = 4096;
+struct BlkFirst {
+    int64_t p;          // position of the record
+    int32_t j;          // its node's index into the NodeEmit table
+    int32_t pad;
+};
+
 __global__ __launch_bounds__(256) void k_node_emit(DevGraph g, FindArgs a, const uint16_t *__restrict__ lossy,
                                                    const uint32_t *__restrict__ bcount,
-                                                   const int64_t *__restrict__ rec_base, NodeEmit *__restrict__ ne) {
+                                                   const int64_t *__restrict__ rec_base, NodeEmit *__restrict__ ne,
+                                                   BlkFirst *__restrict__ blk) {
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     // Only the run's nodes are refreshed; records of other nodes may be stale from an earlier run, which is why the
     // interior kernels also bound p by the run's base range [p_begin, p_end).
@@ -1181,6 +1192,14 @@ __global__ __launch_bounds__(256) void k_node_emit(DevGraph g, FindArgs a, const
         e.cnt = (inside && hi > lo) ? (int32_t)(hi - lo) : 0;
         e.pad0 = 0; e.pad1 = 0;
         ne[g.node_rank[n]] = e;         // indexed by rank among non-empty nodes: what the bitmap popcount yields
+        if (blk && e.cnt > 0) {
+            // split layout: this node's interior records are [s, s + cnt); it owns every block start inside them, and the
+            // node of the last interior record also owns the end entry blk[ceil(n_int / IB)]
+            const int64_t s = e.glo + e.D, t = s + e.cnt, n_int = rec_base[a.n1];
+            const int32_t j = (int32_t)g.node_rank[n];
+            for (int64_t b = (s + IB - 1) / IB; b * IB < t; b++) blk[b] = BlkFirst{b * IB - e.D, j, 0};
+            if (t == n_int) blk[(n_int + IB - 1) / IB] = BlkFirst{n_int - 1 - e.D, j, 0};
+        }
     }
 }
 
@@ -1277,6 +1296,171 @@ __global__ __launch_bounds__(256) void k_emit_interior_runs(DevGraph g, FindArgs
     }
 }
 
+// Split layout, all four columns: lanes mapped to OUTPUT blocks.  A wave owns output block b, the interior records
+// [b * IB, (b + 1) * IB), and writes them as 64 full, line-aligned 64-record groups (k_store_columns' pattern); the node
+// of each record comes from a per-lane walk over the block's node runs staged in LDS (ends ascending), usually zero or
+// one step.  Before it writes block b the wave issues the loads of its next block into registers (the NodeEmit slice
+// and the 2-bit words, fixed-size with clamped addresses: no branch around a load), so they are in flight under the
+// 256 stores of block b and never wait behind them: with more than 63 vector-memory instructions issued after a load
+// the in-order vmcnt has retired it and no wait is needed at all (v4 above issued each window's loads after the previous
+// window's stores: every window waited for the wave's stores to drain).  Blocks whose runs or bases do not fit the
+// stage, and the last, partial block, are left to k_emit_interior_dense_rest.
+#define GKI_CONST __attribute__((address_space(4)))
+constexpr int DCAP = 64;                // node runs staged per block
+constexpr int DSW = 192;                // 2-bit words staged per block (6144 bases: 4096 records + 2048 other bases)
+
+__device__ __forceinline__ BlkFirst blk_at(const GKI_CONST BlkFirst *t, int64_t b) { return BlkFirst{t[b].p, t[b].j, 0}; }
+
+__device__ __forceinline__ bool dense_fits(const BlkFirst &t0, const BlkFirst &t1, int k) {
+    const int64_t w0 = (t0.p - (k - 1)) >> 5, w1 = ((t1.p - (k - 1)) >> 5) + 1;
+    return (int64_t)t1.j - t0.j < DCAP && w1 - w0 < DSW;
+}
+
+struct DenseStage {
+    uint32_t ne[12 * DCAP / 64];
+    uint64_t seq[DSW / 64];
+};
+
+// (lanes past what the block needs read its last word again: same cache line, no extra traffic)
+__device__ __forceinline__ void dense_load(DenseStage &r, const uint32_t *__restrict__ ne32, const uint64_t *__restrict__ seq2,
+                                           const BlkFirst &t0, const BlkFirst &t1, int k, int lane) {
+    const int64_t e0 = 12 * (int64_t)t0.j, e_last = 12 * (int64_t)t1.j + 11;
+    const int64_t w0 = (t0.p - (k - 1)) >> 5, w_last = ((t1.p - (k - 1)) >> 5) + 1;
+#pragma unroll
+    for (int u = 0; u < 12 * DCAP / 64; u++) {
+        const int64_t i = e0 + u * 64 + lane;
+        r.ne[u] = ne32[i < e_last ? i : e_last];
+    }
+#pragma unroll
+    for (int u = 0; u < DSW / 64; u++) {
+        const int64_t i = w0 + u * 64 + lane;
+        r.seq[u] = seq2[i < w_last ? i : w_last];
+    }
+}
+
+// registers -> LDS, and the record end of every staged run (INT64_MIN for a node without interior records: never a match)
+__device__ __forceinline__ void dense_stage(const DenseStage &r, uint32_t *my_ne, int64_t *my_end, uint64_t *my_seq, int lane) {
+#pragma unroll
+    for (int u = 0; u < 12 * DCAP / 64; u++) my_ne[u * 64 + lane] = r.ne[u];
+#pragma unroll
+    for (int u = 0; u < DSW / 64; u++) my_seq[u * 64 + lane] = r.seq[u];
+    const uint32_t *e = my_ne + 12 * lane;
+    const int64_t glo = (int64_t)(((uint64_t)e[1] << 32) | e[0]), D = (int64_t)(((uint64_t)e[3] << 32) | e[2]);
+    const int32_t cnt = (int32_t)e[8];
+    my_end[lane] = cnt > 0 ? glo + D + cnt : (int64_t)(-0x7FFFFFFFFFFFFFFFll - 1);
+}
+
+__global__ __launch_bounds__(256) void k_emit_interior_dense(DevGraph g, FindArgs a, const NodeEmit *__restrict__ ne,
+                                                             const BlkFirst *__restrict__ blk,
+                                                             const int64_t *__restrict__ n_int_p, OutFlat out) {
+    __shared__ uint32_t s_ne[4][12 * DCAP];
+    __shared__ int64_t s_end[4][DCAP];
+    __shared__ uint64_t s_seq[4][DSW];
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t wave = (int64_t)blockIdx.x * 4 + wib;
+    const int64_t n_waves = (int64_t)gridDim.x * 4;
+    const int k = a.k;
+    const uint64_t kmask = (1ull << (2 * k)) - 1ull;
+    const uint32_t *ne32 = reinterpret_cast<const uint32_t *>(ne);
+    const int64_t n_full = *n_int_p / IB;
+    // the block table through the constant address space: scalar loads, which never queue behind the stores on vmcnt the
+    // way a vector load of it would
+    const GKI_CONST BlkFirst *cblk = (const GKI_CONST BlkFirst *)blk;
+    uint32_t *my_ne = s_ne[wib];
+    int64_t *my_end = s_end[wib];
+    uint64_t *my_seq = s_seq[wib];
+    int64_t b = wave;
+    BlkFirst t0, t1;
+    for (; b < n_full; b += n_waves) {
+        t0 = blk_at(cblk, b); t1 = blk_at(cblk, b + 1);
+        if (dense_fits(t0, t1, k)) break;
+    }
+    if (b >= n_full) return;
+    DenseStage r;
+    dense_load(r, ne32, g.seq2, t0, t1, k, lane);
+    dense_stage(r, my_ne, my_end, my_seq, lane);
+    for (;;) {
+        const int64_t rec0 = b * IB;
+        const int nrun = t1.j - t0.j + 1;
+        const int64_t w0 = (t0.p - (k - 1)) >> 5;
+        // the next block of this wave: its loads go out now, ahead of this block's stores
+        int64_t bn = b + n_waves;
+        BlkFirst u0, u1;
+        for (; bn < n_full; bn += n_waves) {
+            u0 = blk_at(cblk, bn); u1 = blk_at(cblk, bn + 1);
+            if (dense_fits(u0, u1, k)) break;
+        }
+        if (bn < n_full) dense_load(r, ne32, g.seq2, u0, u1, k, lane);
+        // Fully unrolled: the 256 stores are one straight line, so the loads above are behind more than 63 vector-memory
+        // instructions when their registers are read below and the compiler emits no wait for them (a loop here made it
+        // wait vmcnt(0) in front of the loop instead: a loop of stores that reads a register loaded before it).
+        int rc = 0;                                         // run of the previous group's last record (wave-uniform)
+#pragma unroll
+        for (int gq = 0; gq < IB / 64; gq++) {
+            const int64_t idx = rec0 + gq * 64 + lane;
+            int rr = rc;
+            while (rr < nrun - 1 && idx >= my_end[rr]) rr++;
+            rc = __builtin_amdgcn_readlane(rr, 63);
+            const uint32_t *e = my_ne + 12 * rr;
+            const int64_t D = (int64_t)(((uint64_t)e[3] << 32) | e[2]);
+            const int64_t E = (int64_t)(((uint64_t)e[5] << 32) | e[4]);
+            const int64_t p = idx - D;
+            const int64_t P = p - (k - 1);
+            const int si = (int)((P >> 5) - w0);
+            const int sh = (int)(P & 31) * 2;
+            const uint64_t lo = my_seq[si], hi = my_seq[si + 1];
+            out.hash[idx] = ((lo >> sh) | ((hi << 1) << (63 - sh))) & kmask;
+            out.node[idx] = e[6];
+            out.ref_offset[idx] = (uint64_t)(p + E);
+            out.af[idx] = __uint_as_float(e[7]);
+        }
+        if (bn >= n_full) break;
+        dense_stage(r, my_ne, my_end, my_seq, lane);
+        b = bn; t0 = u0; t1 = u1;
+    }
+}
+
+// What k_emit_interior_dense leaves: the last, partial block and the blocks whose node runs or bases do not fit its stage
+// (long stretches of nodes shorter than k: dense variant clusters, indels).  Rare, so plain global reads.  64 blocks per
+// wave are checked at once (one lane each); the wave then writes the ones that are its, one at a time.
+__global__ __launch_bounds__(256) void k_emit_interior_dense_rest(DevGraph g, FindArgs a, const NodeEmit *__restrict__ ne,
+                                                                  const BlkFirst *__restrict__ blk,
+                                                                  const int64_t *__restrict__ n_int_p, OutFlat out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int k = a.k;
+    const int64_t n_int = *n_int_p, n_full = n_int / IB, n_blk = (n_int + IB - 1) / IB;
+    for (int64_t base = wave * 64; base < n_blk; base += n_waves * 64) {
+        const int64_t bl = base + lane;
+        bool mine = false;
+        if (bl < n_blk) mine = bl >= n_full || !dense_fits(blk[bl], blk[bl + 1], k);
+        uint64_t todo = __ballot(mine);
+        while (todo) {
+            const int64_t b = base + __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const int64_t rec0 = b * IB, rec1 = rec0 + IB < n_int ? rec0 + IB : n_int;
+            const int32_t j_last = blk[b + 1].j;
+            int32_t jc = blk[b].j;
+            for (int64_t g0 = rec0; g0 < rec1; g0 += 64) {
+                const int64_t idx = g0 + lane;
+                int32_t j = jc;
+                if (idx < rec1) {
+                    NodeEmit e = ne[j];
+                    while (j < j_last && (e.cnt <= 0 || idx >= e.glo + e.D + e.cnt)) e = ne[++j];
+                    const int64_t p = idx - e.D;
+                    out.hash[idx] = gki_extract(g.seq2, p - (k - 1), k);
+                    out.node[idx] = (uint32_t)e.node;
+                    out.ref_offset[idx] = (uint64_t)(p + e.E);
+                    out.af[idx] = e.af;
+                }
+                jc = __builtin_amdgcn_readfirstlane(j);       // lane 0 (idx = g0 < rec1): no later record is before its run
+            }
+        }
+    }
+}
+
 // General variant (any subset of columns, v2 layout): same mapping, branchy.
 template <int FMT>
 __global__ __launch_bounds__(256) void k_emit_interior(DevGraph g, FindArgs a, const NodeEmit *__restrict__ ne,
@@ -1330,6 +1514,7 @@ struct gki_finder {
     uint32_t *bcount, *total;
     int64_t *rec_base, *bnd_base;     // by-node layout: rec_base only; split layout: interior bases / boundary bases
     NodeEmit *ne;
+    BlkFirst *blk;                    // split layout: the output-block table of k_emit_interior_dense (n_bases / IB + 2 entries)
     uint16_t *lossy;
     const uint16_t *lossy_cur;        // the table of the run in progress: `lossy` (uploaded by the count) or the caller's device table
     uint16_t *nflags; uint8_t *store; // general graphs / only_store_nodes (gki_find_params), allocated on first use
@@ -1433,7 +1618,26 @@ static int launch_boundary(gki_finder *f, const DevGraph &d, const FindArgs &a, 
 
 static int launch_interior(gki_finder *f, const DevGraph &d, const FindArgs &a, OutFlat out, unsigned blocks) {
     hipStream_t s = f->stream;
-    if (out.hash && out.node && out.ref_offset && out.af) {
+    const bool all = out.hash && out.node && out.ref_offset && out.af;
+    if (all && a.split && GKI_KNOB("GKI_DENSE", 1)) {
+        // split layout: output blocks (k_emit_interior_dense), then whatever did not fit its stage.  8 workgroups of 4 waves
+        // per CU are resident (20 KB of LDS each).  Tuning builds: GKI_DENSE=0 runs k_emit_interior_runs instead.
+        const int64_t n_blk = ceil_div(f->n_interior_records, IB);
+        int64_t gb = ceil_div(n_blk, 4);
+        const int db = GKI_KNOB("GKI_DENSE_BLOCKS", 2048);
+        if (gb > db) gb = db;
+        if (gb < 1) gb = 1;
+        const int64_t *n_int = f->rec_base + a.n1;
+        hipLaunchKernelGGL(k_emit_interior_dense, dim3((unsigned)gb), dim3(256), 0, s, d, a, f->ne, f->blk, n_int, out);
+        HIP_TRY(hipGetLastError());
+        int64_t rb = ceil_div(ceil_div(n_blk, 64), 4);
+        if (rb > 1024) rb = 1024;
+        if (rb < 1) rb = 1;
+        hipLaunchKernelGGL(k_emit_interior_dense_rest, dim3((unsigned)rb), dim3(256), 0, s, d, a, f->ne, f->blk, n_int, out);
+        HIP_TRY(hipGetLastError());
+        return GKI_OK;
+    }
+    if (all) {
         const int swt = GKI_KNOB("GKI_SW", 64);                 // bases per wave trip / 64
         const int rb = GKI_KNOB("GKI_RUN_BLOCKS", 256 * 5);
         const int cap = GKI_KNOB("GKI_NE_CAP", 128);
@@ -1544,6 +1748,7 @@ static int finder_init(gki_finder *f, gki_graph *g) {
     HIP_TRY(gki_dev_malloc((void **)&f->bnd_base, (size_t)(n + 1) * 8));
     HIP_TRY(gki_dev_malloc((void **)&f->ne, (size_t)(g->d.n_nonempty + 1) * sizeof(NodeEmit)));
     HIP_TRY(hipMemset(f->ne, 0, (size_t)(g->d.n_nonempty + 1) * sizeof(NodeEmit)));   // cnt = 0: a record never refreshed emits nothing
+    HIP_TRY(gki_dev_malloc((void **)&f->blk, (size_t)(g->d.n_bases / IB + 2) * sizeof(BlkFirst)));
     HIP_TRY(gki_dev_malloc((void **)&f->lossy, (size_t)n * 2));
     HIP_TRY(gki_dev_malloc((void **)&f->d_err, 4));
     HIP_TRY(gki_dev_malloc((void **)&f->d_totals, 4 * 8));
@@ -1572,7 +1777,7 @@ int gki_finder_destroy(gki_finder *f) {
     if (!f) return GKI_OK;
     if (f->stream) (void)hipStreamSynchronize(f->stream);
     if (f->stream2) (void)hipStreamSynchronize(f->stream2);
-    void *ptrs[] = {f->bcount, f->total, f->rec_base, f->bnd_base, f->ne, f->lossy, f->scan_tmp, f->d_err, f->d_totals, f->d_bsum,
+    void *ptrs[] = {f->bcount, f->total, f->rec_base, f->bnd_base, f->ne, f->blk, f->lossy, f->scan_tmp, f->d_err, f->d_totals, f->d_bsum,
                     f->d_rank, f->nflags, f->store, f->deep.base};
     for (void *p : ptrs) if (p) (void)gki_dev_free(p);
     if (f->h_totals) (void)hipHostFree(f->h_totals);
@@ -1697,7 +1902,7 @@ int gki_finder_count(gki_finder *f, const gki_find_params *p, int64_t *n_records
             // one node per thread, no grid-stride loop: a thread's loads and its 48-byte store form one dependent chain, so the
             // kernel lives on the number of chains in flight
             hipLaunchKernelGGL(k_node_emit, dim3((unsigned)ceil_div(n_run, 256)), dim3(256), 0, s, d, a, f->lossy_cur, f->bcount,
-                               f->rec_base, f->ne);
+                               f->rec_base, f->ne, a.split ? f->blk : nullptr);
             HIP_TRY(hipGetLastError());
         }
         if (n_run > 0 && !a.split) {
