@@ -301,15 +301,17 @@ class PartitionedDeviceIndex:
         except _lib.GkiError as e:
             # a slice outside the row-carrying build's domain (a handful of buckets holding millions of records): the build
             # from columns can hand such a slice to the pair-sorting form, the build from rows cannot -- start over that way
-            for sl in parts:
-                sl.free()
-            if out is None:
-                part.free()
             if not grouped or e.code != 8:                # GKI_ERR_OUT_OF_DOMAIN
                 raise
+        finally:
+            # whatever stopped the loop, the slices built so far and the partition go back before anything else runs
+            if len(parts) < n_parts:
+                for sl in parts:
+                    sl.free()
+            if out is None:
+                part.free()
+        if len(parts) < n_parts:
             return cls.build(dflat, modulo, n_parts, skip_frequencies, grouped=False)
-        if out is None:
-            part.free()
         return cls(modulo, parts)
 
     @staticmethod

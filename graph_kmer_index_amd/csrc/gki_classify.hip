@@ -220,79 +220,73 @@ extern "C" int gki_graph_classify_nodes(gki_graph *gr, const uint8_t *h_follow, 
     if (n <= 0) return GKI_OK;
     HIP_TRY(hipSetDevice(gr->device));
     hipStream_t s = gr->stream;
-    char *arena = nullptr;
-    int rc = GKI_OK;
-#define HIP_G(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = gki_set_error(GKI_ERR_HIP, "%s:%d %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); goto done; } } while (0)
-    {
-        size_t off = 0;
-        auto carve = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
-        const size_t o_state = carve((size_t)n * sizeof(NodeState)), o_local = carve((size_t)n), o_root = carve((size_t)n),
-                     o_follow = carve(h_follow ? (size_t)n : 0), o_roots = carve((size_t)(n_roots > 0 ? n_roots : 1) * 4),
-                     o_out = carve((size_t)n * 2), o_small = carve(256), o_dead = carve((size_t)n);
-        HIP_G(gki_dev_malloc((void **)&arena, off));
-        NodeState *st = (NodeState *)(arena + o_state);
-        uint8_t *local = (uint8_t *)(arena + o_local), *is_root = (uint8_t *)(arena + o_root);
-        uint8_t *follow = h_follow ? (uint8_t *)(arena + o_follow) : nullptr;
-        int32_t *roots = (int32_t *)(arena + o_roots);
-        uint16_t *out16 = (uint16_t *)(arena + o_out);
-        unsigned int *small = (unsigned int *)(arena + o_small);          // [0] changed, [1] general, [2] candidates / gave up
-        uint8_t *dead_hist = (uint8_t *)(arena + o_dead);                // nodes found without an admissible history so far
-        HIP_G(hipMemsetAsync(is_root, 0, (size_t)n, s));
-        HIP_G(hipMemsetAsync(dead_hist, 0, (size_t)n, s));
-        HIP_G(hipMemsetAsync(small, 0, 16, s));
-        if (h_follow) HIP_G(hipMemcpyAsync(follow, h_follow, (size_t)n, hipMemcpyHostToDevice, s));
-        if (n_roots > 0) HIP_G(hipMemcpyAsync(roots, h_roots, (size_t)n_roots * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_cls_local, dim3(stream_grid(n, 256)), dim3(256), 0, s, g, (const uint8_t *)follow, local);
-        HIP_G(hipGetLastError());
-        for (int round = 0;; round++) {
-            if (round >= MAX_ROUNDS) { *needs_host = 1; goto done; }
-            // ---- least fixed point with the nodes found dead so far held dead
-            HIP_G(hipMemsetAsync(st, 0, (size_t)n * sizeof(NodeState), s));
-            if (n_roots > 0) {
-                hipLaunchKernelGGL(k_cls_roots, dim3(stream_grid(n_roots, 256)), dim3(256), 0, s, (const int32_t *)roots, n_roots, n, k, is_root, st);
-                HIP_G(hipGetLastError());
-            }
-            bool converged = false;
-            for (int sweep = 0; sweep < MAX_SWEEPS && !converged; sweep += 4) {
-                HIP_G(hipMemsetAsync(small, 0, 4, s));
-                for (int i = 0; i < 4; i++) {                           // four sweeps per look at the flag
-                    if (i == 3) HIP_G(hipMemsetAsync(small, 0, 4, s));  // the last sweep of a batch alone decides
-                    hipLaunchKernelGGL(k_cls_relax, dim3(stream_grid(n, 256)), dim3(256), 0, s, g, (const uint8_t *)local,
-                                       (const uint8_t *)is_root, k, max_variant_nodes, st, small, (const uint8_t *)dead_hist);
-                    HIP_G(hipGetLastError());
-                }
-                unsigned int changed = 0;
-                HIP_G(hipMemcpyAsync(&changed, small, 4, hipMemcpyDeviceToHost, s));
-                HIP_G(hipStreamSynchronize(s));
-                converged = changed == 0;
-            }
-            if (!converged) { *needs_host = 1; goto done; }             // a dependency chain longer than the sweep budget
-            HIP_G(hipMemsetAsync(small, 0, 16, s));
-            hipLaunchKernelGGL(k_cls_final, dim3(stream_grid(n, 256)), dim3(256), 0, s, g, (const uint8_t *)local, (const uint8_t *)is_root,
-                               (const NodeState *)st, max_variant_nodes, out16, small + 1);
-            HIP_G(hipGetLastError());
-            unsigned int verdict[2] = {0, 0};
-            HIP_G(hipMemcpyAsync(verdict, small + 1, 8, hipMemcpyDeviceToHost, s));
-            HIP_G(hipStreamSynchronize(s));
-            *general = verdict[0] ? 1 : 0;
-            if (!verdict[1]) break;                                     // no nested non-free node: the fixed point is the answer
-            // ---- which of the candidates have no admissible history?  (every candidate, every round: a node found dead takes
-            // histories away from the nodes after it)
-            HIP_G(hipMemsetAsync(small, 0, 16, s));
-            hipLaunchKernelGGL(k_cls_history, dim3(stream_grid(n, 64)), dim3(64), 0, s, g, (const uint8_t *)local, (const uint8_t *)is_root,
-                               (const NodeState *)st, (const uint16_t *)out16, k, max_variant_nodes, dead_hist, small);
-            HIP_G(hipGetLastError());
-            unsigned int res[3] = {0, 0, 0};
-            HIP_G(hipMemcpyAsync(res, small, 12, hipMemcpyDeviceToHost, s));
-            HIP_G(hipStreamSynchronize(s));
-            if (res[2]) { *needs_host = 1; goto done; }                 // a history deeper than the kernel's stack or budget
-            if (!res[0]) break;                                         // every candidate is entered: the flags stand
+    size_t off = 0;
+    auto carve = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
+    const size_t o_state = carve((size_t)n * sizeof(NodeState)), o_local = carve((size_t)n), o_root = carve((size_t)n),
+                 o_follow = carve(h_follow ? (size_t)n : 0), o_roots = carve((size_t)(n_roots > 0 ? n_roots : 1) * 4),
+                 o_out = carve((size_t)n * 2), o_small = carve(256), o_dead = carve((size_t)n);
+    DevBuf arena_b;
+    HIP_TRY(arena_b.alloc(off));
+    char *arena = arena_b.get<char>();
+    NodeState *st = (NodeState *)(arena + o_state);
+    uint8_t *local = (uint8_t *)(arena + o_local), *is_root = (uint8_t *)(arena + o_root);
+    uint8_t *follow = h_follow ? (uint8_t *)(arena + o_follow) : nullptr;
+    int32_t *roots = (int32_t *)(arena + o_roots);
+    uint16_t *out16 = (uint16_t *)(arena + o_out);
+    unsigned int *small = (unsigned int *)(arena + o_small);          // [0] changed, [1] general, [2] candidates / gave up
+    uint8_t *dead_hist = (uint8_t *)(arena + o_dead);                // nodes found without an admissible history so far
+    HIP_TRY(hipMemsetAsync(is_root, 0, (size_t)n, s));
+    HIP_TRY(hipMemsetAsync(dead_hist, 0, (size_t)n, s));
+    HIP_TRY(hipMemsetAsync(small, 0, 16, s));
+    if (h_follow) HIP_TRY(hipMemcpyAsync(follow, h_follow, (size_t)n, hipMemcpyHostToDevice, s));
+    if (n_roots > 0) HIP_TRY(hipMemcpyAsync(roots, h_roots, (size_t)n_roots * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_cls_local, dim3(stream_grid(n, 256)), dim3(256), 0, s, g, (const uint8_t *)follow, local);
+    HIP_TRY(hipGetLastError());
+    for (int round = 0;; round++) {
+        if (round >= MAX_ROUNDS) { *needs_host = 1; return GKI_OK; }
+        // ---- least fixed point with the nodes found dead so far held dead
+        HIP_TRY(hipMemsetAsync(st, 0, (size_t)n * sizeof(NodeState), s));
+        if (n_roots > 0) {
+            hipLaunchKernelGGL(k_cls_roots, dim3(stream_grid(n_roots, 256)), dim3(256), 0, s, (const int32_t *)roots, n_roots, n, k, is_root, st);
+            HIP_TRY(hipGetLastError());
         }
-        if (h_out_flags && (*general || always_copy_flags))             // the flags are read only by the general kernels
-            HIP_G(hipMemcpy(h_out_flags, out16, (size_t)n * 2, hipMemcpyDeviceToHost));
+        bool converged = false;
+        for (int sweep = 0; sweep < MAX_SWEEPS && !converged; sweep += 4) {
+            HIP_TRY(hipMemsetAsync(small, 0, 4, s));
+            for (int i = 0; i < 4; i++) {                           // four sweeps per look at the flag
+                if (i == 3) HIP_TRY(hipMemsetAsync(small, 0, 4, s));  // the last sweep of a batch alone decides
+                hipLaunchKernelGGL(k_cls_relax, dim3(stream_grid(n, 256)), dim3(256), 0, s, g, (const uint8_t *)local,
+                                   (const uint8_t *)is_root, k, max_variant_nodes, st, small, (const uint8_t *)dead_hist);
+                HIP_TRY(hipGetLastError());
+            }
+            unsigned int changed = 0;
+            HIP_TRY(hipMemcpyAsync(&changed, small, 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            converged = changed == 0;
+        }
+        if (!converged) { *needs_host = 1; return GKI_OK; }             // a dependency chain longer than the sweep budget
+        HIP_TRY(hipMemsetAsync(small, 0, 16, s));
+        hipLaunchKernelGGL(k_cls_final, dim3(stream_grid(n, 256)), dim3(256), 0, s, g, (const uint8_t *)local, (const uint8_t *)is_root,
+                           (const NodeState *)st, max_variant_nodes, out16, small + 1);
+        HIP_TRY(hipGetLastError());
+        unsigned int verdict[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(verdict, small + 1, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        *general = verdict[0] ? 1 : 0;
+        if (!verdict[1]) break;                                     // no nested non-free node: the fixed point is the answer
+        // ---- which of the candidates have no admissible history?  (every candidate, every round: a node found dead takes
+        // histories away from the nodes after it)
+        HIP_TRY(hipMemsetAsync(small, 0, 16, s));
+        hipLaunchKernelGGL(k_cls_history, dim3(stream_grid(n, 64)), dim3(64), 0, s, g, (const uint8_t *)local, (const uint8_t *)is_root,
+                           (const NodeState *)st, (const uint16_t *)out16, k, max_variant_nodes, dead_hist, small);
+        HIP_TRY(hipGetLastError());
+        unsigned int res[3] = {0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(res, small, 12, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (res[2]) { *needs_host = 1; return GKI_OK; }                 // a history deeper than the kernel's stack or budget
+        if (!res[0]) break;                                         // every candidate is entered: the flags stand
     }
-done:
-    (void)gki_dev_free(arena);
-#undef HIP_G
-    return rc;
+    if (h_out_flags && (*general || always_copy_flags))             // the flags are read only by the general kernels
+        HIP_TRY(hipMemcpy(h_out_flags, out16, (size_t)n * 2, hipMemcpyDeviceToHost));
+    return GKI_OK;
 }

@@ -31,6 +31,33 @@ hipError_t gki_dev_malloc(void **ptr, size_t bytes);
 hipError_t gki_dev_free(void *ptr);
 template <typename T> static inline hipError_t gki_dev_malloc(T **ptr, size_t bytes) { return gki_dev_malloc((void **)ptr, bytes); }
 
+// Owner of one pooled device buffer (host only): freed by reset() or when it goes out of scope, so that an entry point
+// returns straight through HIP_TRY / GKI_TRY without leaking its scratch.  gki_dev_free synchronises the device, so where
+// a DevBuf dies is a free point: declare host buffers that an asynchronous copy reads BEFORE the DevBufs, so that the
+// DevBufs' destructors (which wait for the device) run first.
+class DevBuf {
+  public:
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { reset(); }
+    hipError_t alloc(size_t bytes) { reset(); return gki_dev_malloc(&p_, bytes); }
+    void reset() { if (p_) { (void)gki_dev_free(p_); p_ = nullptr; } }
+    template <class T = void> T *get() const { return static_cast<T *>(p_); }
+
+  private:
+    void *p_ = nullptr;
+};
+
+// The two events of a timed launch (host only), destroyed when it goes out of scope
+struct TimerEvents {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    TimerEvents() = default;
+    TimerEvents(const TimerEvents &) = delete;
+    TimerEvents &operator=(const TimerEvents &) = delete;
+    ~TimerEvents() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+};
+
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // Grid for a grid-stride streaming kernel: enough blocks to fill 256 CUs x 8 blocks, no more.
@@ -157,6 +184,15 @@ struct gki_graph {
     FwdScript fwd_script;                    // early-stop search: what the count call left for the emit call (csrc/gki_forward.hip)
     NodeFwd *fwd_nodes;                      // early-stop search: its per-node records, built by the first search after a prepare
 };
+
+// the early-stop search's script goes back to the pool (a new count call, the emit call, a prepare, the graph's destroy)
+static inline void script_drop(gki_graph *gr) {
+    FwdScript &sc = gr->fwd_script;
+    if (sc.entries) (void)gki_dev_free(sc.entries);
+    if (sc.ncomp) (void)gki_dev_free(sc.ncomp);
+    if (sc.over_list) (void)gki_dev_free(sc.over_list);
+    sc = FwdScript{};
+}
 
 // GKI_ERR_BAD_ARG unless the device that is current is the one the graph was uploaded to (gki_finder.hip)
 int gki_check_graph_device(const gki_graph *g, const char *who);

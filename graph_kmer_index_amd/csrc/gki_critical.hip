@@ -191,193 +191,178 @@ extern "C" int gki_graph_critical_paths(gki_graph *gr, const int32_t *h_chrom_st
     int rounds = 1;
     while (((int64_t)1 << rounds) < n + 1) rounds++;
     rounds++;                                               // 2^rounds > n + 1 steps: only a cycle is still walking then
-    int32_t **jump = (int32_t **)calloc((size_t)rounds + 1, sizeof(int32_t *));
-    uint32_t *cnt[2] = {nullptr, nullptr};
-    char *arena = nullptr, *arena2 = nullptr;
-    uint32_t *d_out_nodes = nullptr;
-    uint16_t *d_out_off = nullptr;
-    int rc = GKI_OK;
-    if (!jump) return gki_set_error(GKI_ERR_BAD_ARG, "out of host memory");
-#define HIP_G(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = gki_set_error(GKI_ERR_HIP, "%s:%d %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); goto done; } } while (0)
+    // one allocation for everything sized by the node count (the allocator, not the kernels, was the cost of a cold call)
+    size_t off = 0;
+    auto carve = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
+    const size_t o_next = carve((size_t)n * 4), o_bad = carve((size_t)n), o_flag = carve((size_t)n * 4),
+                 o_at = carve((size_t)(n + 1) * 4), o_list = carve((size_t)n * 4), o_tmp = carve((size_t)gki_scan_tmp_bytes(n + 1)),
+                 o_small = carve(256);
+    DevBuf arena_b, cnt_b[2], arena2_b, jump_b[65], work_b, out_nodes_b, out_off_b;      // rounds <= 64
+    HIP_TRY(arena_b.alloc(off));
+    char *arena = arena_b.get<char>();
+    int32_t *next = (int32_t *)(arena + o_next), *list = (int32_t *)(arena + o_list);
+    uint8_t *bad = (uint8_t *)(arena + o_bad);
+    uint32_t *flag = (uint32_t *)(arena + o_flag), *at = (uint32_t *)(arena + o_at);
+    void *tmp = arena + o_tmp;
+    const int64_t tmp_bytes = gki_scan_tmp_bytes(n + 1);
+    unsigned int *small = (unsigned int *)(arena + o_small);     // [0] not-one-ref position, [1] offset -1 position, [2] mismatch
+    HIP_TRY(hipMemsetAsync(small, 0xFF, 8, s));
+    HIP_TRY(hipMemsetAsync(small + 2, 0, 4, s));
+    HIP_TRY(cnt_b[0].alloc((size_t)n * 4));
+    uint32_t *cnt[2] = {cnt_b[0].get<uint32_t>(), nullptr};
+    hipLaunchKernelGGL(k_walk_next, dim3(stream_grid(n, 256)), dim3(256), 0, s, g, next, cnt[0], bad);
+    HIP_TRY(hipGetLastError());
+    // ---- the guess: linear-ref(-dummy) nodes in id order
+    hipLaunchKernelGGL(k_walk_ref_flags, dim3(stream_grid(n, 256)), dim3(256), 0, s, g, flag);
+    HIP_TRY(hipGetLastError());
+    GKI_TRY(gki_scan_u32_to_u32(flag, n, at, tmp, tmp_bytes, s));
+    hipLaunchKernelGGL(k_walk_ref_list, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const uint32_t *)flag, (const uint32_t *)at, n, list);
+    HIP_TRY(hipGetLastError());
+    Chroms c;
+    c.n = n_chrom;
+    c.begin[0] = 0;
+    bool guessed = true;
     {
-        // one allocation for everything sized by the node count (the allocator, not the kernels, was the cost of a cold call)
-        size_t off = 0;
-        auto carve = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
-        const size_t o_next = carve((size_t)n * 4), o_bad = carve((size_t)n), o_flag = carve((size_t)n * 4),
-                     o_at = carve((size_t)(n + 1) * 4), o_list = carve((size_t)n * 4), o_tmp = carve((size_t)gki_scan_tmp_bytes(n + 1)),
-                     o_small = carve(256);
-        HIP_G(gki_dev_malloc((void **)&arena, off));
-        int32_t *next = (int32_t *)(arena + o_next), *list = (int32_t *)(arena + o_list);
-        uint8_t *bad = (uint8_t *)(arena + o_bad);
-        uint32_t *flag = (uint32_t *)(arena + o_flag), *at = (uint32_t *)(arena + o_at);
-        void *tmp = arena + o_tmp;
-        const int64_t tmp_bytes = gki_scan_tmp_bytes(n + 1);
-        unsigned int *small = (unsigned int *)(arena + o_small);     // [0] not-one-ref position, [1] offset -1 position, [2] mismatch
-        HIP_G(hipMemsetAsync(small, 0xFF, 8, s));
-        HIP_G(hipMemsetAsync(small + 2, 0, 4, s));
-        HIP_G(gki_dev_malloc((void **)&cnt[0], (size_t)n * 4));
-        hipLaunchKernelGGL(k_walk_next, dim3(stream_grid(n, 256)), dim3(256), 0, s, g, next, cnt[0], bad);
-        HIP_G(hipGetLastError());
-        // ---- the guess: linear-ref(-dummy) nodes in id order
-        hipLaunchKernelGGL(k_walk_ref_flags, dim3(stream_grid(n, 256)), dim3(256), 0, s, g, flag);
-        HIP_G(hipGetLastError());
-        rc = gki_scan_u32_to_u32(flag, n, at, tmp, tmp_bytes, s);
-        if (rc != GKI_OK) goto done;
-        hipLaunchKernelGGL(k_walk_ref_list, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const uint32_t *)flag, (const uint32_t *)at, n, list);
-        HIP_G(hipGetLastError());
-        Chroms c;
-        c.n = n_chrom;
-        c.begin[0] = 0;
-        bool guessed = true;
-        {
-            // slice of every chromosome in the list: from its start node to the next chromosome start (by id) or the end
-            uint32_t h_at[64], h_flag[64], n_ref = 0;
-            for (int q = 0; q < n_chrom; q++) {
-                HIP_G(hipMemcpyAsync(&h_at[q], at + h_chrom_start[q], 4, hipMemcpyDeviceToHost, s));
-                HIP_G(hipMemcpyAsync(&h_flag[q], flag + h_chrom_start[q], 4, hipMemcpyDeviceToHost, s));
-            }
-            HIP_G(hipMemcpyAsync(&n_ref, at + n, 4, hipMemcpyDeviceToHost, s));
-            HIP_G(hipStreamSynchronize(s));
-            RefSlices r;
-            r.n = n_chrom;
-            r.begin[0] = 0;
-            for (int q = 0; q < n_chrom && guessed; q++) {
-                if (!h_flag[q]) { guessed = false; break; }
-                int64_t to = n_ref;
-                for (int o = 0; o < n_chrom; o++)
-                    if (h_chrom_start[o] > h_chrom_start[q] && (int64_t)h_at[o] < to) to = h_at[o];
-                r.from[q] = h_at[q]; r.to[q] = to;
-                r.begin[q + 1] = r.begin[q] + (to - (int64_t)h_at[q]);
-                c.start[q] = h_chrom_start[q];
-                c.begin[q + 1] = r.begin[q + 1];
-            }
-            if (guessed) {
-                const int64_t total = r.begin[n_chrom];
-                HIP_G(gki_dev_malloc((void **)&arena2, (size_t)total * 4 + 256));
-                hipLaunchKernelGGL(k_walk_ref_path, dim3(stream_grid(total, 256)), dim3(256), 0, s, r, (const int32_t *)list,
-                                   (const int32_t *)next, total, (int32_t *)arena2, small + 2);
-                HIP_G(hipGetLastError());
-                unsigned int mismatch = 0;
-                HIP_G(hipMemcpyAsync(&mismatch, small + 2, 4, hipMemcpyDeviceToHost, s));
-                HIP_G(hipStreamSynchronize(s));
-                if (mismatch) { guessed = false; (void)gki_dev_free(arena2); arena2 = nullptr; }
-            }
+        // slice of every chromosome in the list: from its start node to the next chromosome start (by id) or the end
+        uint32_t h_at[64], h_flag[64], n_ref = 0;
+        for (int q = 0; q < n_chrom; q++) {
+            HIP_TRY(hipMemcpyAsync(&h_at[q], at + h_chrom_start[q], 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(&h_flag[q], flag + h_chrom_start[q], 4, hipMemcpyDeviceToHost, s));
         }
-        int32_t *path = (int32_t *)arena2;
-        if (!guessed) {
-            // ---- any DAG: jump tables by pointer doubling, then the path level by level
-            jump[0] = nullptr;
-            for (int i = 1; i <= rounds; i++) HIP_G(gki_dev_malloc((void **)&jump[i], (size_t)n * 4));
-            HIP_G(gki_dev_malloc((void **)&cnt[1], (size_t)n * 4));
-            for (int i = 0; i < rounds; i++) {
-                hipLaunchKernelGGL(k_walk_double, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const int32_t *)(i ? jump[i] : next),
-                                   (const uint32_t *)cnt[i & 1], n, jump[i + 1], cnt[(i + 1) & 1]);
-                HIP_G(hipGetLastError());
-            }
-            for (int q = 0; q < n_chrom; q++) {
-                uint32_t steps = 0;
-                int32_t last = 0, after = 0;
-                HIP_G(hipMemcpyAsync(&steps, cnt[rounds & 1] + h_chrom_start[q], 4, hipMemcpyDeviceToHost, s));
-                HIP_G(hipMemcpyAsync(&last, jump[rounds] + h_chrom_start[q], 4, hipMemcpyDeviceToHost, s));
-                HIP_G(hipStreamSynchronize(s));
-                HIP_G(hipMemcpyAsync(&after, next + last, 4, hipMemcpyDeviceToHost, s));
-                HIP_G(hipStreamSynchronize(s));
-                if (after != last || (int64_t)steps > n) { rc = gki_set_error(GKI_ERR_BAD_ARG, "critical paths: walk left the graph or found a cycle"); goto done; }
-                c.start[q] = h_chrom_start[q];
-                c.begin[q + 1] = c.begin[q] + (int64_t)steps + 1;
-            }
-            const int64_t total = c.begin[n_chrom];
-            HIP_G(gki_dev_malloc((void **)&arena2, (size_t)total * 4 + 256));
-            path = (int32_t *)arena2;
-            for (int q = 0; q < n_chrom; q++)
-                HIP_G(hipMemcpyAsync(path + c.begin[q], &c.start[q], 4, hipMemcpyHostToDevice, s));
-            HIP_G(hipStreamSynchronize(s));                      // c.start lives on this stack frame
-            int top = 0;
-            int64_t longest = 1;
-            for (int q = 0; q < n_chrom; q++) if (c.begin[q + 1] - c.begin[q] > longest) longest = c.begin[q + 1] - c.begin[q];
-            while (((int64_t)1 << (top + 1)) < longest) top++;
-            for (int level = top; level >= 0; level--) {
-                const int64_t work = total / ((int64_t)2 << level) + n_chrom;
-                hipLaunchKernelGGL(k_walk_fill, dim3(stream_grid(work, 256)), dim3(256), 0, s, c, (const int32_t *)(level ? jump[level] : next),
-                                   level, total, path);
-                HIP_G(hipGetLastError());
-            }
+        HIP_TRY(hipMemcpyAsync(&n_ref, at + n, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        RefSlices r;
+        r.n = n_chrom;
+        r.begin[0] = 0;
+        for (int q = 0; q < n_chrom && guessed; q++) {
+            if (!h_flag[q]) { guessed = false; break; }
+            int64_t to = n_ref;
+            for (int o = 0; o < n_chrom; o++)
+                if (h_chrom_start[o] > h_chrom_start[q] && (int64_t)h_at[o] < to) to = h_at[o];
+            r.from[q] = h_at[q]; r.to[q] = to;
+            r.begin[q + 1] = r.begin[q] + (to - (int64_t)h_at[q]);
+            c.start[q] = h_chrom_start[q];
+            c.begin[q + 1] = r.begin[q + 1];
         }
-        // ---- the walk's state over the path, as scans
-        const int64_t total = c.begin[n_chrom];
-        {
-            size_t off2 = 0;
-            auto carve2 = [&off2](size_t bytes) { const size_t at2 = off2; off2 += (bytes + 255) / 256 * 256; return at2; };
-            const size_t p_delta = carve2((size_t)total * 4), p_weight = carve2((size_t)total * 4), p_head = carve2((size_t)total * 4),
-                         p_seg = carve2((size_t)(total + 1) * 4), p_crit = carve2((size_t)total * 4), p_pos = carve2((size_t)(total + 1) * 4),
-                         p_off = carve2((size_t)total * 2), p_depth = carve2((size_t)(total + 1) * 8), p_bp = carve2((size_t)(total + 1) * 8),
-                         p_hbp = carve2((size_t)(total + 1) * 8), p_tmp = carve2((size_t)gki_scan_tmp_bytes(total + 1)), p_err = carve2(256);
-            char *work = nullptr;
-            HIP_G(gki_dev_malloc((void **)&work, off2));
-            (void)gki_dev_free(cnt[0]); cnt[0] = (uint32_t *)work;          // freed with the rest below
-            int32_t *delta = (int32_t *)(work + p_delta);
-            uint32_t *weight = (uint32_t *)(work + p_weight), *head = (uint32_t *)(work + p_head), *seg = (uint32_t *)(work + p_seg),
-                     *crit = (uint32_t *)(work + p_crit), *pos = (uint32_t *)(work + p_pos);
-            uint16_t *offp = (uint16_t *)(work + p_off);
-            int64_t *depth_sum = (int64_t *)(work + p_depth), *bp_sum = (int64_t *)(work + p_bp), *head_bp = (int64_t *)(work + p_hbp);
-            void *tmp2 = work + p_tmp;
-            const int64_t tmp2_bytes = gki_scan_tmp_bytes(total + 1);
-            unsigned int *first_err = (unsigned int *)(work + p_err);
-            HIP_G(hipMemsetAsync(first_err, 0xFF, 16, s));
-            hipLaunchKernelGGL(k_walk_deltas, dim3(stream_grid(total, 256)), dim3(256), 0, s, g, (const int32_t *)path, total, delta, weight);
-            HIP_G(hipGetLastError());
-            rc = gki_scan_i32_to_i64(delta, total, depth_sum, tmp2, tmp2_bytes, s);
-            if (rc == GKI_OK) rc = gki_scan_u32_to_i64(weight, total, bp_sum, tmp2, tmp2_bytes, s);
-            if (rc != GKI_OK) goto done;
-            hipLaunchKernelGGL(k_walk_heads, dim3(stream_grid(total, 256)), dim3(256), 0, s, g, c, (const int32_t *)path, total,
-                               (const int64_t *)depth_sum, head);
-            HIP_G(hipGetLastError());
-            rc = gki_scan_u32_to_u32(head, total, seg, tmp2, tmp2_bytes, s);
-            if (rc != GKI_OK) goto done;
-            hipLaunchKernelGGL(k_walk_head_values, dim3(stream_grid(total, 256)), dim3(256), 0, s, (const uint32_t *)head,
-                               (const uint32_t *)seg, (const int64_t *)bp_sum, total, head_bp);
-            HIP_G(hipGetLastError());
-            hipLaunchKernelGGL(k_walk_test, dim3(stream_grid(total, 256)), dim3(256), 0, s, g, c, (const int32_t *)path, total,
-                               (const int64_t *)depth_sum, (const int64_t *)bp_sum, (const uint32_t *)head, (const uint32_t *)seg,
-                               (const int64_t *)head_bp, (const uint8_t *)bad, k, crit, offp, first_err);
-            HIP_G(hipGetLastError());
-            rc = gki_scan_u32_to_u32(crit, total, pos, tmp2, tmp2_bytes, s);
-            if (rc != GKI_OK) goto done;
-            unsigned int h_err[2] = {ERR_NONE, ERR_NONE};
-            uint32_t found = 0;
-            HIP_G(hipMemcpyAsync(h_err, first_err, 8, hipMemcpyDeviceToHost, s));
-            HIP_G(hipMemcpyAsync(&found, pos + total, 4, hipMemcpyDeviceToHost, s));
-            HIP_G(hipStreamSynchronize(s));
-            if (h_err[0] != ERR_NONE || h_err[1] != ERR_NONE) {
-                // the reference raises inside the walk for a branching node without exactly one linear-ref successor (:96-100);
-                // the offset -1 only surfaces when the offsets become uint16 after all walks (:104) -- so the former wins
-                int32_t node = 0;
-                const bool off_err = h_err[0] == ERR_NONE;
-                HIP_G(hipMemcpy(&node, path + (off_err ? h_err[1] : h_err[0]), 4, hipMemcpyDeviceToHost));
-                rc = off_err ? gki_set_error(GKI_ERR_BAD_ARG, "critical paths: node %d is reached after exactly k bases of single-edge "
-                                             "chain; the reference raises here (uint16 offset -1)", node)
-                             : gki_set_error(GKI_ERR_BAD_ARG, "critical paths: node %d does not have exactly one linear-ref successor "
-                                             "(the reference requires exactly one)", node);
-                goto done;
-            }
-            if (found > 0) {
-                HIP_G(gki_dev_malloc((void **)&d_out_nodes, (size_t)found * 4));
-                HIP_G(gki_dev_malloc((void **)&d_out_off, (size_t)found * 2));
-                hipLaunchKernelGGL(k_walk_emit, dim3(stream_grid(total, 256)), dim3(256), 0, s, (const int32_t *)path, (const uint32_t *)crit,
-                                   (const uint32_t *)pos, (const uint16_t *)offp, total, d_out_nodes, d_out_off);
-                HIP_G(hipGetLastError());
-                HIP_G(hipMemcpyAsync(h_out_nodes, d_out_nodes, (size_t)found * 4, hipMemcpyDeviceToHost, s));
-                HIP_G(hipMemcpyAsync(h_out_offsets, d_out_off, (size_t)found * 2, hipMemcpyDeviceToHost, s));
-                HIP_G(hipStreamSynchronize(s));
-            }
-            *n_out = found;
+        if (guessed) {
+            const int64_t total = r.begin[n_chrom];
+            HIP_TRY(arena2_b.alloc((size_t)total * 4 + 256));
+            hipLaunchKernelGGL(k_walk_ref_path, dim3(stream_grid(total, 256)), dim3(256), 0, s, r, (const int32_t *)list,
+                               (const int32_t *)next, total, arena2_b.get<int32_t>(), small + 2);
+            HIP_TRY(hipGetLastError());
+            unsigned int mismatch = 0;
+            HIP_TRY(hipMemcpyAsync(&mismatch, small + 2, 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if (mismatch) { guessed = false; arena2_b.reset(); }
         }
     }
-done:
-    for (int i = 1; i <= rounds; i++) (void)gki_dev_free(jump[i]);
-    free(jump);
-    (void)gki_dev_free(cnt[0]); (void)gki_dev_free(cnt[1]); (void)gki_dev_free(arena); (void)gki_dev_free(arena2);
-    (void)gki_dev_free(d_out_nodes); (void)gki_dev_free(d_out_off);
-#undef HIP_G
-    return rc;
+    int32_t *path = arena2_b.get<int32_t>();
+    if (!guessed) {
+        // ---- any DAG: jump tables by pointer doubling, then the path level by level
+        int32_t *jump[65] = {nullptr};
+        for (int i = 1; i <= rounds; i++) { HIP_TRY(jump_b[i].alloc((size_t)n * 4)); jump[i] = jump_b[i].get<int32_t>(); }
+        HIP_TRY(cnt_b[1].alloc((size_t)n * 4));
+        cnt[1] = cnt_b[1].get<uint32_t>();
+        for (int i = 0; i < rounds; i++) {
+            hipLaunchKernelGGL(k_walk_double, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const int32_t *)(i ? jump[i] : next),
+                               (const uint32_t *)cnt[i & 1], n, jump[i + 1], cnt[(i + 1) & 1]);
+            HIP_TRY(hipGetLastError());
+        }
+        for (int q = 0; q < n_chrom; q++) {
+            uint32_t steps = 0;
+            int32_t last = 0, after = 0;
+            HIP_TRY(hipMemcpyAsync(&steps, cnt[rounds & 1] + h_chrom_start[q], 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(&last, jump[rounds] + h_chrom_start[q], 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            HIP_TRY(hipMemcpyAsync(&after, next + last, 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if (after != last || (int64_t)steps > n) return gki_set_error(GKI_ERR_BAD_ARG, "critical paths: walk left the graph or found a cycle");
+            c.start[q] = h_chrom_start[q];
+            c.begin[q + 1] = c.begin[q] + (int64_t)steps + 1;
+        }
+        const int64_t total = c.begin[n_chrom];
+        HIP_TRY(arena2_b.alloc((size_t)total * 4 + 256));
+        path = arena2_b.get<int32_t>();
+        for (int q = 0; q < n_chrom; q++)
+            HIP_TRY(hipMemcpyAsync(path + c.begin[q], &c.start[q], 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));                      // c.start lives on this stack frame
+        int top = 0;
+        int64_t longest = 1;
+        for (int q = 0; q < n_chrom; q++) if (c.begin[q + 1] - c.begin[q] > longest) longest = c.begin[q + 1] - c.begin[q];
+        while (((int64_t)1 << (top + 1)) < longest) top++;
+        for (int level = top; level >= 0; level--) {
+            const int64_t work = total / ((int64_t)2 << level) + n_chrom;
+            hipLaunchKernelGGL(k_walk_fill, dim3(stream_grid(work, 256)), dim3(256), 0, s, c, (const int32_t *)(level ? jump[level] : next),
+                               level, total, path);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    // ---- the walk's state over the path, as scans
+    const int64_t total = c.begin[n_chrom];
+    {
+        size_t off2 = 0;
+        auto carve2 = [&off2](size_t bytes) { const size_t at2 = off2; off2 += (bytes + 255) / 256 * 256; return at2; };
+        const size_t p_delta = carve2((size_t)total * 4), p_weight = carve2((size_t)total * 4), p_head = carve2((size_t)total * 4),
+                     p_seg = carve2((size_t)(total + 1) * 4), p_crit = carve2((size_t)total * 4), p_pos = carve2((size_t)(total + 1) * 4),
+                     p_off = carve2((size_t)total * 2), p_depth = carve2((size_t)(total + 1) * 8), p_bp = carve2((size_t)(total + 1) * 8),
+                     p_hbp = carve2((size_t)(total + 1) * 8), p_tmp = carve2((size_t)gki_scan_tmp_bytes(total + 1)), p_err = carve2(256);
+        HIP_TRY(work_b.alloc(off2));
+        cnt_b[0].reset();
+        char *work = work_b.get<char>();
+        int32_t *delta = (int32_t *)(work + p_delta);
+        uint32_t *weight = (uint32_t *)(work + p_weight), *head = (uint32_t *)(work + p_head), *seg = (uint32_t *)(work + p_seg),
+                 *crit = (uint32_t *)(work + p_crit), *pos = (uint32_t *)(work + p_pos);
+        uint16_t *offp = (uint16_t *)(work + p_off);
+        int64_t *depth_sum = (int64_t *)(work + p_depth), *bp_sum = (int64_t *)(work + p_bp), *head_bp = (int64_t *)(work + p_hbp);
+        void *tmp2 = work + p_tmp;
+        const int64_t tmp2_bytes = gki_scan_tmp_bytes(total + 1);
+        unsigned int *first_err = (unsigned int *)(work + p_err);
+        HIP_TRY(hipMemsetAsync(first_err, 0xFF, 16, s));
+        hipLaunchKernelGGL(k_walk_deltas, dim3(stream_grid(total, 256)), dim3(256), 0, s, g, (const int32_t *)path, total, delta, weight);
+        HIP_TRY(hipGetLastError());
+        GKI_TRY(gki_scan_i32_to_i64(delta, total, depth_sum, tmp2, tmp2_bytes, s));
+        GKI_TRY(gki_scan_u32_to_i64(weight, total, bp_sum, tmp2, tmp2_bytes, s));
+        hipLaunchKernelGGL(k_walk_heads, dim3(stream_grid(total, 256)), dim3(256), 0, s, g, c, (const int32_t *)path, total,
+                           (const int64_t *)depth_sum, head);
+        HIP_TRY(hipGetLastError());
+        GKI_TRY(gki_scan_u32_to_u32(head, total, seg, tmp2, tmp2_bytes, s));
+        hipLaunchKernelGGL(k_walk_head_values, dim3(stream_grid(total, 256)), dim3(256), 0, s, (const uint32_t *)head,
+                           (const uint32_t *)seg, (const int64_t *)bp_sum, total, head_bp);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_walk_test, dim3(stream_grid(total, 256)), dim3(256), 0, s, g, c, (const int32_t *)path, total,
+                           (const int64_t *)depth_sum, (const int64_t *)bp_sum, (const uint32_t *)head, (const uint32_t *)seg,
+                           (const int64_t *)head_bp, (const uint8_t *)bad, k, crit, offp, first_err);
+        HIP_TRY(hipGetLastError());
+        GKI_TRY(gki_scan_u32_to_u32(crit, total, pos, tmp2, tmp2_bytes, s));
+        unsigned int h_err[2] = {ERR_NONE, ERR_NONE};
+        uint32_t found = 0;
+        HIP_TRY(hipMemcpyAsync(h_err, first_err, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&found, pos + total, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (h_err[0] != ERR_NONE || h_err[1] != ERR_NONE) {
+            // the reference raises inside the walk for a branching node without exactly one linear-ref successor (:96-100);
+            // the offset -1 only surfaces when the offsets become uint16 after all walks (:104) -- so the former wins
+            int32_t node = 0;
+            const bool off_err = h_err[0] == ERR_NONE;
+            HIP_TRY(hipMemcpy(&node, path + (off_err ? h_err[1] : h_err[0]), 4, hipMemcpyDeviceToHost));
+            return off_err ? gki_set_error(GKI_ERR_BAD_ARG, "critical paths: node %d is reached after exactly k bases of single-edge "
+                                         "chain; the reference raises here (uint16 offset -1)", node)
+                         : gki_set_error(GKI_ERR_BAD_ARG, "critical paths: node %d does not have exactly one linear-ref successor "
+                                         "(the reference requires exactly one)", node);
+        }
+        if (found > 0) {
+            HIP_TRY(out_nodes_b.alloc((size_t)found * 4));
+            HIP_TRY(out_off_b.alloc((size_t)found * 2));
+            uint32_t *d_out_nodes = out_nodes_b.get<uint32_t>();
+            uint16_t *d_out_off = out_off_b.get<uint16_t>();
+            hipLaunchKernelGGL(k_walk_emit, dim3(stream_grid(total, 256)), dim3(256), 0, s, (const int32_t *)path, (const uint32_t *)crit,
+                               (const uint32_t *)pos, (const uint16_t *)offp, total, d_out_nodes, d_out_off);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(h_out_nodes, d_out_nodes, (size_t)found * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(h_out_offsets, d_out_off, (size_t)found * 2, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        *n_out = found;
+    }
+    return GKI_OK;
 }

@@ -492,15 +492,16 @@ namespace {
 // the search's per-node records: built by the first search on a graph (and again after gki_graph_prepare), 32 B per node
 int fwd_nodes_ready(gki_graph *gr) {
     if (gr->fwd_nodes) return GKI_OK;
-    void *p = nullptr;
-    if (hipMalloc(&p, (size_t)gr->d.n_nodes * sizeof(NodeFwd)) != hipSuccess) {
+    NodeFwd *p = nullptr;
+    if (gki_dev_malloc(&p, (size_t)gr->d.n_nodes * sizeof(NodeFwd)) != hipSuccess) {
         (void)hipGetLastError();
         return gki_set_error(GKI_ERR_HIP, "forward search: no memory for %lld node records", (long long)gr->d.n_nodes);
     }
-    hipLaunchKernelGGL(k_build_fwd, dim3(stream_grid(gr->d.n_nodes, 256)), dim3(256), 0, 0, gr->d, (NodeFwd *)p);
-    const hipError_t e = hipGetLastError(), e2 = hipStreamSynchronize(0);
-    if (e != hipSuccess || e2 != hipSuccess) { (void)hipFree(p); HIP_TRY(e); HIP_TRY(e2); }
-    gr->fwd_nodes = (NodeFwd *)p;
+    hipLaunchKernelGGL(k_build_fwd, dim3(stream_grid(gr->d.n_nodes, 256)), dim3(256), 0, 0, gr->d, p);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(0);
+    if (e != hipSuccess) { (void)gki_dev_free(p); HIP_TRY(e); }
+    gr->fwd_nodes = p;
     return GKI_OK;
 }
 
@@ -523,13 +524,6 @@ int deep_grow(gki_graph *gr, int next_cap) {
     return GKI_OK;
 }
 
-void script_drop(gki_graph *gr) {
-    FwdScript &sc = gr->fwd_script;
-    if (sc.entries) (void)gki_dev_free(sc.entries);
-    if (sc.ncomp) (void)gki_dev_free(sc.ncomp);
-    if (sc.over_list) (void)gki_dev_free(sc.over_list);
-    sc = FwdScript{};
-}
 }  // namespace
 
 extern "C" {
@@ -542,12 +536,13 @@ int gki_forward_count(gki_graph *gr, int k, int max_variant_nodes, int one_node,
     if (n_pos <= 0) { HIP_TRY(hipMemset(d_rec_start, 0, 8)); return GKI_OK; }
     GKI_TRY(fwd_nodes_ready(gr));
     deep_release(gr);                     // a slow-path arena of an earlier search goes back to the pool (up to 5.6 GB)
-    uint32_t *cnt = nullptr; void *tmp = nullptr; int *d_err = nullptr;
     int64_t tmp_bytes = gki_scan_tmp_bytes(n_pos);
-    HIP_TRY(gki_dev_malloc((void **)&cnt, (size_t)n_pos * 4));
-    HIP_TRY(gki_dev_malloc(&tmp, (size_t)tmp_bytes));
-    HIP_TRY(gki_dev_malloc((void **)&d_err, 8));        // [0] the error word, [1] start positions that did not fit the script
-    HIP_TRY(hipMemset(d_err, 0, 8));
+    DevBuf cnt_b, tmp, d_err_b;
+    HIP_TRY(cnt_b.alloc((size_t)n_pos * 4));
+    HIP_TRY(tmp.alloc((size_t)tmp_bytes));
+    HIP_TRY(d_err_b.alloc(8));                          // [0] the error word, [1] start positions that did not fit the script
+    uint32_t *cnt = cnt_b.get<uint32_t>();
+    int *d_err = d_err_b.get<int>();
     FwdOut none{nullptr, nullptr, nullptr, nullptr, nullptr};
     const int M = max_variant_nodes > 250 ? 250 : max_variant_nodes;
     gr->fwd_deep.cap = 0;                 // the product kernel first; the emit call that follows uses what this call settles on
@@ -563,44 +558,41 @@ int gki_forward_count(gki_graph *gr, int k, int max_variant_nodes, int one_node,
         }
     }
     int64_t total = 0; int word[2] = {0, 0};
-    int rc = GKI_OK;
-    hipError_t e1 = hipSuccess, e2 = hipSuccess, e3 = hipSuccess;
-    for (;;) {
-        const DeepArena da = gr->fwd_deep;
-        e3 = hipMemset(d_err, 0, 8);
-        if (da.cap > 0) {
-            script_drop(gr);                // the slow path writes no script
-            hipLaunchKernelGGL((k_forward<false, true>), dim3((unsigned)(da.lanes / 64)), dim3(64), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
-                               (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, cnt, (const int64_t *)nullptr, none, d_err, da,
-                               (uint4 *)nullptr, (uint8_t *)nullptr, (int64_t *)nullptr, (int64_t)0);
-        } else if (sc.entries)
-            hipLaunchKernelGGL((k_forward<false, false, true>), dim3((unsigned)ceil_div(n_pos, GKI_FWD_BLOCK)), dim3(GKI_FWD_BLOCK), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
-                               (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, cnt, (const int64_t *)nullptr, none, d_err, da,
-                               (uint4 *)sc.entries, sc.ncomp, sc.over_list, sc.over_cap);
-        else
-            hipLaunchKernelGGL((k_forward<false, false>), dim3((unsigned)ceil_div(n_pos, GKI_FWD_BLOCK)), dim3(GKI_FWD_BLOCK), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
-                               (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, cnt, (const int64_t *)nullptr, none, d_err, da,
-                               (uint4 *)nullptr, (uint8_t *)nullptr, (int64_t *)nullptr, (int64_t)0);
-        rc = hipGetLastError() == hipSuccess ? GKI_OK : gki_set_error(GKI_ERR_HIP, "k_forward launch failed");
-        if (rc == GKI_OK) rc = gki_scan_u32_to_i64(cnt, n_pos, (int64_t *)d_rec_start, tmp, tmp_bytes, 0);
-        e1 = hipMemcpy(&total, (const int64_t *)d_rec_start + n_pos, 8, hipMemcpyDeviceToHost);
-        e2 = hipMemcpy(word, d_err, 8, hipMemcpyDeviceToHost);
-        if (rc != GKI_OK || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) break;
-        // bit 1: a stack of the walk was too short -- again with the deep variant, twice the levels each time round
-        const int next_cap = da.cap == 0 ? 4 * FMAX : 2 * da.cap;
-        if (!(word[0] & 2) || (word[0] & 4) || next_cap > GKI_MAX_DEEP_WINDOW_NODES) break;
-        rc = deep_grow(gr, next_cap);
-        if (rc != GKI_OK) break;
-    }
-    (void)gki_dev_free(cnt); (void)gki_dev_free(tmp); (void)gki_dev_free(d_err);
-    const int herr = rc == GKI_OK && e1 == hipSuccess && e2 == hipSuccess && e3 == hipSuccess ? gki_error_of_word(word[0]) : -1;
+    auto passes = [&]() -> int {
+        for (;;) {
+            const DeepArena da = gr->fwd_deep;
+            HIP_TRY(hipMemset(d_err, 0, 8));
+            if (da.cap > 0) {
+                script_drop(gr);                // the slow path writes no script
+                hipLaunchKernelGGL((k_forward<false, true>), dim3((unsigned)(da.lanes / 64)), dim3(64), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
+                                   (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, cnt, (const int64_t *)nullptr, none, d_err, da,
+                                   (uint4 *)nullptr, (uint8_t *)nullptr, (int64_t *)nullptr, (int64_t)0);
+            } else if (sc.entries)
+                hipLaunchKernelGGL((k_forward<false, false, true>), dim3((unsigned)ceil_div(n_pos, GKI_FWD_BLOCK)), dim3(GKI_FWD_BLOCK), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
+                                   (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, cnt, (const int64_t *)nullptr, none, d_err, da,
+                                   (uint4 *)sc.entries, sc.ncomp, sc.over_list, sc.over_cap);
+            else
+                hipLaunchKernelGGL((k_forward<false, false>), dim3((unsigned)ceil_div(n_pos, GKI_FWD_BLOCK)), dim3(GKI_FWD_BLOCK), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
+                                   (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, cnt, (const int64_t *)nullptr, none, d_err, da,
+                                   (uint4 *)nullptr, (uint8_t *)nullptr, (int64_t *)nullptr, (int64_t)0);
+            if (hipGetLastError() != hipSuccess) return gki_set_error(GKI_ERR_HIP, "k_forward launch failed");
+            GKI_TRY(gki_scan_u32_to_i64(cnt, n_pos, (int64_t *)d_rec_start, tmp.get(), tmp_bytes, 0));
+            HIP_TRY(hipMemcpy(&total, (const int64_t *)d_rec_start + n_pos, 8, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(word, d_err, 8, hipMemcpyDeviceToHost));
+            // bit 1: a stack of the walk was too short -- again with the deep variant, twice the levels each time round
+            const int next_cap = da.cap == 0 ? 4 * FMAX : 2 * da.cap;
+            if (!(word[0] & 2) || (word[0] & 4) || next_cap > GKI_MAX_DEEP_WINDOW_NODES) return GKI_OK;
+            GKI_TRY(deep_grow(gr, next_cap));
+        }
+    };
+    const int rc = passes();
+    const int herr = rc == GKI_OK ? gki_error_of_word(word[0]) : -1;
     if (herr != GKI_OK || !sc.entries) script_drop(gr);
     else {                                  // the emit call with these very arguments may expand the script
         sc.n_pos = n_pos; sc.overflow = word[1]; sc.nodes = d_nodes; sc.offsets = d_offsets; sc.follow = d_follow; sc.rec_start = d_rec_start;
         sc.k = k; sc.M = M; sc.one_node = one_node ? 1 : 0; sc.valid = 1;
     }
     if (rc != GKI_OK) return rc;
-    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
     if (herr == GKI_ERR_NOT_ONE_REF_SUCC)
         return gki_set_error(herr, "a path at the variant limit ends a node that does not have exactly one linear-ref "
                              "successor: the reference asserts here (kmer_finder.py:402)");
@@ -616,57 +608,56 @@ int gki_forward_emit(gki_graph *gr, int k, int max_variant_nodes, int one_node, 
     if (n_pos <= 0) return GKI_OK;
     GKI_TRY(gki_check_graph_device(gr, "gki_forward_emit"));
     GKI_TRY(fwd_nodes_ready(gr));
-    int *d_err = nullptr;
-    HIP_TRY(gki_dev_malloc((void **)&d_err, 4));
+    DevBuf d_err_b;
+    HIP_TRY(d_err_b.alloc(4));
+    int *d_err = d_err_b.get<int>();
     FwdOut out{(int64_t *)d_hashes, (int32_t *)d_start_nodes, (int16_t *)d_start_offsets, (int32_t *)d_nodes_out, (double *)d_af64};
     const int M = max_variant_nodes > 250 ? 250 : max_variant_nodes;
     FwdScript &sc = gr->fwd_script;
-    int word = 0, rc = GKI_OK;
-    hipError_t e = hipSuccess, e2 = hipSuccess, e3 = hipSuccess;
+    int word = 0;
     // The arena state on the graph handle is whatever the LAST count call left (cap > 0: it needed the slow path), which
     // need not be this search's count call (count(A), count(B), emit(A); two finders on one graph).  The emit pass
     // therefore settles the depth itself: it reads its own error word and goes round again with the deep variant like the
     // count pass does (the word was never read and a too-short stack lost records silently).  Records already
     // written are written again with the same values.
-    for (;;) {
-        const DeepArena da = gr->fwd_deep;
-        e3 = hipMemset(d_err, 0, 4);
-        const bool scripted = sc.valid && da.cap == 0 && sc.n_pos == n_pos && sc.nodes == d_nodes && sc.offsets == d_offsets && sc.follow == d_follow &&
-                              sc.rec_start == d_rec_start && sc.k == k && sc.M == M && sc.one_node == (one_node ? 1 : 0);
-        if (da.cap > 0)
-            hipLaunchKernelGGL((k_forward<true, true>), dim3((unsigned)(da.lanes / 64)), dim3(64), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
-                               (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, (uint32_t *)nullptr, (const int64_t *)d_rec_start, out, d_err, da,
-                               (uint4 *)nullptr, (uint8_t *)nullptr, (int64_t *)nullptr, (int64_t)0);
-        else if (scripted) {
-            hipLaunchKernelGGL(k_forward_expand, dim3((unsigned)ceil_div(n_pos * FW_SLOTS, 256)), dim3(256), 0, 0, (const uint4 *)sc.entries, sc.ncomp,
-                               (const int64_t *)d_rec_start, n_pos, out);
-            // the start positions the script could not hold are walked as before: those on the count pass's list, or -- when
-            // there were more than the list holds -- whichever the script marks, one lane per start position of the call
-            if (sc.overflow > 0 && sc.overflow <= sc.over_cap)
-                hipLaunchKernelGGL((k_forward<true, false>), dim3((unsigned)ceil_div(sc.overflow, GKI_FWD_BLOCK)), dim3(GKI_FWD_BLOCK), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
+    auto passes = [&]() -> int {
+        for (;;) {
+            const DeepArena da = gr->fwd_deep;
+            HIP_TRY(hipMemset(d_err, 0, 4));
+            const bool scripted = sc.valid && da.cap == 0 && sc.n_pos == n_pos && sc.nodes == d_nodes && sc.offsets == d_offsets && sc.follow == d_follow &&
+                                  sc.rec_start == d_rec_start && sc.k == k && sc.M == M && sc.one_node == (one_node ? 1 : 0);
+            if (da.cap > 0)
+                hipLaunchKernelGGL((k_forward<true, true>), dim3((unsigned)(da.lanes / 64)), dim3(64), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
                                    (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, (uint32_t *)nullptr, (const int64_t *)d_rec_start, out, d_err, da,
-                                   (uint4 *)nullptr, sc.ncomp, sc.over_list, sc.overflow);
-            else if (sc.overflow > 0)
+                                   (uint4 *)nullptr, (uint8_t *)nullptr, (int64_t *)nullptr, (int64_t)0);
+            else if (scripted) {
+                hipLaunchKernelGGL(k_forward_expand, dim3((unsigned)ceil_div(n_pos * FW_SLOTS, 256)), dim3(256), 0, 0, (const uint4 *)sc.entries, sc.ncomp,
+                                   (const int64_t *)d_rec_start, n_pos, out);
+                // the start positions the script could not hold are walked as before: those on the count pass's list, or -- when
+                // there were more than the list holds -- whichever the script marks, one lane per start position of the call
+                if (sc.overflow > 0 && sc.overflow <= sc.over_cap)
+                    hipLaunchKernelGGL((k_forward<true, false>), dim3((unsigned)ceil_div(sc.overflow, GKI_FWD_BLOCK)), dim3(GKI_FWD_BLOCK), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
+                                       (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, (uint32_t *)nullptr, (const int64_t *)d_rec_start, out, d_err, da,
+                                       (uint4 *)nullptr, sc.ncomp, sc.over_list, sc.overflow);
+                else if (sc.overflow > 0)
+                    hipLaunchKernelGGL((k_forward<true, false>), dim3((unsigned)ceil_div(n_pos, GKI_FWD_BLOCK)), dim3(GKI_FWD_BLOCK), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
+                                       (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, (uint32_t *)nullptr, (const int64_t *)d_rec_start, out, d_err, da,
+                                       (uint4 *)nullptr, sc.ncomp, (int64_t *)nullptr, (int64_t)0);
+            } else
                 hipLaunchKernelGGL((k_forward<true, false>), dim3((unsigned)ceil_div(n_pos, GKI_FWD_BLOCK)), dim3(GKI_FWD_BLOCK), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
                                    (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, (uint32_t *)nullptr, (const int64_t *)d_rec_start, out, d_err, da,
-                                   (uint4 *)nullptr, sc.ncomp, (int64_t *)nullptr, (int64_t)0);
-        } else
-            hipLaunchKernelGGL((k_forward<true, false>), dim3((unsigned)ceil_div(n_pos, GKI_FWD_BLOCK)), dim3(GKI_FWD_BLOCK), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
-                               (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, (uint32_t *)nullptr, (const int64_t *)d_rec_start, out, d_err, da,
-                               (uint4 *)nullptr, (uint8_t *)nullptr, (int64_t *)nullptr, (int64_t)0);
-        e = hipGetLastError();
-        e2 = hipMemcpy(&word, d_err, 4, hipMemcpyDeviceToHost);          // (synchronises)
-        if (e != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) break;
-        const int next_cap = da.cap == 0 ? 4 * FMAX : 2 * da.cap;
-        if (!(word & 2) || (word & 4) || next_cap > GKI_MAX_DEEP_WINDOW_NODES) break;
-        rc = deep_grow(gr, next_cap);
-        if (rc != GKI_OK) break;
-    }
-    (void)gki_dev_free(d_err);
+                                   (uint4 *)nullptr, (uint8_t *)nullptr, (int64_t *)nullptr, (int64_t)0);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpy(&word, d_err, 4, hipMemcpyDeviceToHost));          // (synchronises)
+            const int next_cap = da.cap == 0 ? 4 * FMAX : 2 * da.cap;
+            if (!(word & 2) || (word & 4) || next_cap > GKI_MAX_DEEP_WINDOW_NODES) return GKI_OK;
+            GKI_TRY(deep_grow(gr, next_cap));
+        }
+    };
+    const int rc = passes();
     script_drop(gr);                        // one emit per count: a second emit call walks
     deep_release(gr);                       // and the arena goes back to the pool
     if (rc != GKI_OK) return rc;
-    HIP_TRY(e); HIP_TRY(e2); HIP_TRY(e3);
     const int herr = gki_error_of_word(word);
     if (herr) return gki_set_error(herr, "the emit pass of the early-stop search left records unwritten (error word %d)", word);
     return GKI_OK;

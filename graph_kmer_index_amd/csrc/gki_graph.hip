@@ -77,6 +77,8 @@ int gki_launch_pack(const uint8_t *d_seq, int64_t n_bases, uint32_t *d_out, hipS
 }
 
 namespace {
+// The graph's own arrays live as long as the graph and stay on hipMalloc / hipFree, outside the pool: through it,
+// destroying a 3 Gbp graph would park gigabytes there.
 template <typename T>
 int upload(gki_graph *g, const T *h, int64_t n, const T **d_out) {
     void *d = nullptr;
@@ -88,15 +90,10 @@ int upload(gki_graph *g, const T *h, int64_t n, const T **d_out) {
     return GKI_OK;
 }
 
-int graph_create_common(gki_graph **out, int64_t n_nodes, const int32_t *h_node_size, const uint8_t *h_seq,
-                        const void *d_seq, bool seq_on_device, int64_t n_bases, const int64_t *h_edge_start, const int32_t *h_edges,
-                        const int64_t *h_rev_start, const int32_t *h_rev_edges, int64_t n_edges,
-                        const uint8_t *h_is_ref, const double *h_allele_freq, const int64_t *h_position_base) {
-    *out = nullptr;
-    if (n_nodes <= 0 || n_bases < 0 || n_edges < 0) return gki_set_error(GKI_ERR_BAD_ARG, "graph_create: bad sizes");
-    if (n_edges >= INT32_MAX) return gki_set_error(GKI_ERR_BAD_ARG, "graph_create: more than 2^31-1 edges");
-    gki_graph *g = new gki_graph();
-    memset(g, 0, sizeof(*g));
+int graph_init(gki_graph *g, int64_t n_nodes, const int32_t *h_node_size, const uint8_t *h_seq,
+               const void *d_seq, bool seq_on_device, int64_t n_bases, const int64_t *h_edge_start, const int32_t *h_edges,
+               const int64_t *h_rev_start, const int32_t *h_rev_edges, int64_t n_edges,
+               const uint8_t *h_is_ref, const double *h_allele_freq, const int64_t *h_position_base) {
     HIP_TRY(hipGetDevice(&g->device));
     HIP_TRY(hipStreamCreate(&g->stream));
     HIP_TRY(hipEventCreate(&g->ev_prep0));
@@ -109,15 +106,15 @@ int graph_create_common(gki_graph **out, int64_t n_nodes, const int32_t *h_node_
     nonempty.reserve((size_t)n_nodes);
     seq_start[0] = 0;
     for (int64_t n = 0; n < n_nodes; n++) {
-        if (h_node_size[n] < 0) { delete g; return gki_set_error(GKI_ERR_BAD_ARG, "negative node size"); }
+        if (h_node_size[n] < 0) return gki_set_error(GKI_ERR_BAD_ARG, "negative node size");
         seq_start[n + 1] = seq_start[n] + h_node_size[n];
         if (h_node_size[n] > 0) { node_rank[(size_t)n] = (int32_t)nonempty.size(); nonempty.push_back((int32_t)n); }
     }
-    if (seq_start[n_nodes] != n_bases) { delete g; return gki_set_error(GKI_ERR_BAD_ARG, "sum(node_size) != n_bases"); }
+    if (seq_start[n_nodes] != n_bases) return gki_set_error(GKI_ERR_BAD_ARG, "sum(node_size) != n_bases");
     d.n_nonempty = (int64_t)nonempty.size();
 
     g->h_seq_start = (int64_t *)malloc((size_t)(n_nodes + 1) * 8);
-    if (!g->h_seq_start) { delete g; return gki_set_error(GKI_ERR_HIP, "graph_create: out of host memory"); }
+    if (!g->h_seq_start) return gki_set_error(GKI_ERR_HIP, "graph_create: out of host memory");
     memcpy(g->h_seq_start, seq_start.data(), (size_t)(n_nodes + 1) * 8);
     GKI_TRY(upload(g, h_node_size, n_nodes, &d.node_size));
     GKI_TRY(upload(g, seq_start.data(), n_nodes + 1, &d.seq_start));
@@ -144,8 +141,23 @@ int graph_create_common(gki_graph **out, int64_t n_nodes, const int32_t *h_node_
     HIP_TRY(hipMalloc(&p, (size_t)(d.n_words64 + 1) * 8)); g->owned[g->n_owned++] = p; d.start_mask = (const uint64_t *)p;
     HIP_TRY(hipMalloc(&p, (size_t)(d.n_words64 + 2) * 4)); g->owned[g->n_owned++] = p; d.start_rank = (const uint32_t *)p;
     HIP_TRY(hipMalloc(&p, (size_t)n_nodes * sizeof(NodeWalk))); g->owned[g->n_owned++] = p; d.walk = (const NodeWalk *)p;
-    *out = g;
     return gki_graph_prepare(g);
+}
+
+int graph_create_common(gki_graph **out, int64_t n_nodes, const int32_t *h_node_size, const uint8_t *h_seq,
+                        const void *d_seq, bool seq_on_device, int64_t n_bases, const int64_t *h_edge_start, const int32_t *h_edges,
+                        const int64_t *h_rev_start, const int32_t *h_rev_edges, int64_t n_edges,
+                        const uint8_t *h_is_ref, const double *h_allele_freq, const int64_t *h_position_base) {
+    *out = nullptr;
+    if (n_nodes <= 0 || n_bases < 0 || n_edges < 0) return gki_set_error(GKI_ERR_BAD_ARG, "graph_create: bad sizes");
+    if (n_edges >= INT32_MAX) return gki_set_error(GKI_ERR_BAD_ARG, "graph_create: more than 2^31-1 edges");
+    gki_graph *g = new gki_graph();
+    memset(g, 0, sizeof(*g));
+    const int rc = graph_init(g, n_nodes, h_node_size, h_seq, d_seq, seq_on_device, n_bases, h_edge_start, h_edges, h_rev_start,
+                              h_rev_edges, n_edges, h_is_ref, h_allele_freq, h_position_base);
+    if (rc != GKI_OK) { (void)gki_graph_destroy(g); return rc; }      // nothing of a half-built graph stays behind
+    *out = g;
+    return GKI_OK;
 }
 }  // namespace
 
@@ -155,7 +167,9 @@ int gki_graph_prepare(gki_graph *g) {
     DevGraph &d = g->d;
     hipStream_t s = g->stream;
     int64_t n_u64 = ceil_div(d.n_bases, 32) + 2;
-    if (g->fwd_nodes) { (void)hipFree(g->fwd_nodes); g->fwd_nodes = nullptr; }     // of the sequence before: the next search builds them
+    // the early-stop search's node records and script are of the sequence before: the next search builds them again
+    if (g->fwd_nodes) { (void)gki_dev_free(g->fwd_nodes); g->fwd_nodes = nullptr; }
+    script_drop(g);
     HIP_TRY(hipEventRecord(g->ev_prep0, s));
     HIP_TRY(hipMemsetAsync((void *)d.seq2, 0, (size_t)n_u64 * 8, s));
     GKI_TRY(gki_launch_pack(d.seq, d.n_bases, (uint32_t *)d.seq2, s));
@@ -169,19 +183,16 @@ int gki_graph_prepare(gki_graph *g) {
     }
     if (d.n_words64 > 0) {
         // rank = exclusive scan of per-word popcounts (counts staged in a scratch buffer)
-        void *cnt = nullptr, *tmp = nullptr;
+        DevBuf cnt, tmp;
         int64_t tmp_bytes = gki_scan_tmp_bytes(d.n_words64);
-        HIP_TRY(hipMalloc(&cnt, (size_t)d.n_words64 * 4));
-        HIP_TRY(hipMalloc(&tmp, (size_t)tmp_bytes));
+        HIP_TRY(cnt.alloc((size_t)d.n_words64 * 4));
+        HIP_TRY(tmp.alloc((size_t)tmp_bytes));
         hipLaunchKernelGGL(k_popcount, dim3(stream_grid(d.n_words64, 256)), dim3(256), 0, s, d.start_mask,
-                           d.n_words64, (uint32_t *)cnt);
+                           d.n_words64, cnt.get<uint32_t>());
         HIP_TRY(hipGetLastError());
-        int r = gki_scan_u32_to_u32((const uint32_t *)cnt, d.n_words64, (uint32_t *)d.start_rank, tmp, tmp_bytes, s);
+        GKI_TRY(gki_scan_u32_to_u32(cnt.get<const uint32_t>(), d.n_words64, (uint32_t *)d.start_rank, tmp.get(), tmp_bytes, s));
         HIP_TRY(hipEventRecord(g->ev_prep1, s));
         HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(hipFree(cnt));
-        HIP_TRY(hipFree(tmp));
-        if (r != GKI_OK) return r;
     } else {
         HIP_TRY(hipEventRecord(g->ev_prep1, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -211,13 +222,11 @@ int gki_graph_destroy(gki_graph *g) {
     if (!g) return GKI_OK;
     for (int i = 0; i < g->n_owned; i++) (void)hipFree(g->owned[i]);
     if (g->fwd_deep.base) (void)gki_dev_free(g->fwd_deep.base);
-    if (g->fwd_script.entries) (void)gki_dev_free(g->fwd_script.entries);
-    if (g->fwd_script.ncomp) (void)gki_dev_free(g->fwd_script.ncomp);
-    if (g->fwd_script.over_list) (void)gki_dev_free(g->fwd_script.over_list);
-    if (g->fwd_nodes) (void)hipFree(g->fwd_nodes);
-    (void)hipEventDestroy(g->ev_prep0);
-    (void)hipEventDestroy(g->ev_prep1);
-    (void)hipStreamDestroy(g->stream);
+    script_drop(g);
+    if (g->fwd_nodes) (void)gki_dev_free(g->fwd_nodes);
+    if (g->ev_prep0) (void)hipEventDestroy(g->ev_prep0);
+    if (g->ev_prep1) (void)hipEventDestroy(g->ev_prep1);
+    if (g->stream) (void)hipStreamDestroy(g->stream);
     free(g->h_seq_start);
     delete g;
     return GKI_OK;

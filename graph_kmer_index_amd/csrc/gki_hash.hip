@@ -102,21 +102,16 @@ extern "C" {
 int gki_hash_sequence(const void *d_codes, int64_t n, int k, void *d_out) {
     if (k < 1 || k > GKI_MAX_K) return gki_set_error(GKI_ERR_BAD_ARG, "k must be in 1..31");
     if (n < k) return GKI_OK;
-    void *seq2 = nullptr;
     int64_t n_u64 = ceil_div(n, 32) + 2;
-    HIP_TRY(gki_dev_malloc(&seq2, (size_t)n_u64 * 8));
-    HIP_TRY(hipMemsetAsync(seq2, 0, (size_t)n_u64 * 8, 0));
-    int rc = gki_launch_pack((const uint8_t *)d_codes, n, (uint32_t *)seq2, 0);
-    if (rc == GKI_OK) {
-        int64_t n_out = n - k + 1;
-        hipLaunchKernelGGL(k_hash_windows, dim3(stream_grid(n_out, 256)), dim3(256), 0, 0, (const uint64_t *)seq2, n_out, k,
-                           (uint64_t *)d_out);
-        if (hipGetLastError() != hipSuccess) rc = gki_set_error(GKI_ERR_HIP, "k_hash_windows launch failed");
-    }
-    hipError_t e = hipStreamSynchronize(0);
-    (void)gki_dev_free(seq2);
-    if (rc != GKI_OK) return rc;
-    HIP_TRY(e);
+    DevBuf seq2;
+    HIP_TRY(seq2.alloc((size_t)n_u64 * 8));
+    HIP_TRY(hipMemsetAsync(seq2.get(), 0, (size_t)n_u64 * 8, 0));
+    GKI_TRY(gki_launch_pack((const uint8_t *)d_codes, n, seq2.get<uint32_t>(), 0));
+    int64_t n_out = n - k + 1;
+    hipLaunchKernelGGL(k_hash_windows, dim3(stream_grid(n_out, 256)), dim3(256), 0, 0, seq2.get<const uint64_t>(), n_out, k,
+                       (uint64_t *)d_out);
+    if (hipGetLastError() != hipSuccess) return gki_set_error(GKI_ERR_HIP, "k_hash_windows launch failed");
+    HIP_TRY(hipStreamSynchronize(0));
     return GKI_OK;
 }
 
@@ -126,19 +121,17 @@ int gki_hash_reads(const void *d_reads, const void *d_read_start, int64_t n_read
     if (k < 1 || k > GKI_MAX_K) return gki_set_error(GKI_ERR_BAD_ARG, "k must be in 1..31");
     if (strand != 0 && strand != 1) return gki_set_error(GKI_ERR_BAD_ARG, "strand must be 0 or 1");
     if (n_reads <= 0) { HIP_TRY(hipMemset(d_out_start, 0, 8)); return GKI_OK; }
-    void *cnt = nullptr, *tmp = nullptr;
-    int64_t tmp_bytes = gki_scan_tmp_bytes(n_reads);
-    HIP_TRY(gki_dev_malloc(&cnt, (size_t)n_reads * 4));
-    HIP_TRY(gki_dev_malloc(&tmp, (size_t)tmp_bytes));
-    hipLaunchKernelGGL(k_read_counts, dim3(stream_grid(n_reads, 256)), dim3(256), 0, 0, (const int64_t *)d_read_start,
-                       n_reads, k, (uint32_t *)cnt);
-    int rc = gki_scan_u32_to_i64((const uint32_t *)cnt, n_reads, (int64_t *)d_out_start, tmp, tmp_bytes, 0);
     int64_t total = 0;
-    hipError_t e = hipMemcpy(&total, (const int64_t *)d_out_start + n_reads, 8, hipMemcpyDeviceToHost);
-    (void)gki_dev_free(cnt);
-    (void)gki_dev_free(tmp);
-    if (rc != GKI_OK) return rc;
-    HIP_TRY(e);
+    {
+        DevBuf cnt, tmp;                               // freed before the hashing pass
+        int64_t tmp_bytes = gki_scan_tmp_bytes(n_reads);
+        HIP_TRY(cnt.alloc((size_t)n_reads * 4));
+        HIP_TRY(tmp.alloc((size_t)tmp_bytes));
+        hipLaunchKernelGGL(k_read_counts, dim3(stream_grid(n_reads, 256)), dim3(256), 0, 0, (const int64_t *)d_read_start,
+                           n_reads, k, cnt.get<uint32_t>());
+        GKI_TRY(gki_scan_u32_to_i64(cnt.get<const uint32_t>(), n_reads, (int64_t *)d_out_start, tmp.get(), tmp_bytes, 0));
+        HIP_TRY(hipMemcpy(&total, (const int64_t *)d_out_start + n_reads, 8, hipMemcpyDeviceToHost));
+    }
     *n_out = total;
     if (d_out == nullptr) return GKI_OK;               // count only
     if (total > out_capacity) return gki_set_error(GKI_ERR_BAD_ARG, "hash_reads: output needs %lld entries, capacity %lld",

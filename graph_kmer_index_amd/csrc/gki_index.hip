@@ -397,6 +397,26 @@ static int radix_sort_pairs(uint32_t *keys[2], uint32_t *vals[2], int64_t n, int
     return GKI_OK;
 }
 
+// The scratch of radix_sort_pairs over n pairs, allocated in this order: keys[0], vals[0], keys[1], vals[1], the tiles'
+// histograms, their offsets, the scan's temporary.
+struct SortScratch {
+    DevBuf kv[4], hist_b, offs_b, tmp_b;
+    uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr}, *hist = nullptr, *offs = nullptr;
+    int64_t tmp_bytes = 0;
+    int alloc(int64_t n) {
+        for (DevBuf &b : kv) HIP_TRY(b.alloc((size_t)n * 4));
+        const int64_t hist_n = (int64_t)RBINS * ceil_div(n, RTILE);
+        tmp_bytes = gki_scan_tmp_bytes(hist_n);
+        HIP_TRY(hist_b.alloc((size_t)hist_n * 4));
+        HIP_TRY(offs_b.alloc((size_t)(hist_n + 1) * 4));
+        HIP_TRY(tmp_b.alloc((size_t)tmp_bytes));
+        keys[0] = kv[0].get<uint32_t>(); vals[0] = kv[1].get<uint32_t>(); keys[1] = kv[2].get<uint32_t>(); vals[1] = kv[3].get<uint32_t>();
+        hist = hist_b.get<uint32_t>(); offs = offs_b.get<uint32_t>();
+        return GKI_OK;
+    }
+    int sort(int64_t n, int bits, hipStream_t s, int *cur) { return radix_sort_pairs(keys, vals, n, bits, hist, offs, tmp_b.get(), tmp_bytes, s, cur); }
+};
+
 // FlatKmers.get_new_without_singletons (flat_kmers.py:98-125): a record is kept iff an EARLIER record carries the same
 // hash.  After the stable sort by bucket the records of a bucket are in input order, so "earlier" = an earlier position
 // of the bucket's run; the flag goes back to the record's original position.
@@ -476,29 +496,23 @@ __global__ __launch_bounds__(256) void k_gather_pairs(const uint32_t *__restrict
 // per bucket.  `sizes` is scratch for n_large uint32.
 static int frequencies_large_pass(const uint32_t *large_list, unsigned int n_large, uint32_t *sizes, const void *d_hashes_to_index,
                                   const void *d_n_kmers, const void *d_kmers, const void *d_refs, void *d_freq, hipStream_t s) {
-    int64_t *starts = nullptr;
-    Pair *scratch = nullptr;
-    void *tmp2 = nullptr;
     hipLaunchKernelGGL(k_large_sizes, dim3(stream_grid(n_large, 256)), dim3(256), 0, s, large_list, n_large,
                        (const uint32_t *)d_n_kmers, sizes);
     HIP_TRY(hipGetLastError());
     const int64_t tmp2_bytes = gki_scan_tmp_bytes(n_large);
-    int r = GKI_OK;
-    if (gki_dev_malloc((void **)&starts, ((size_t)n_large + 1) * 8) != hipSuccess) r = GKI_ERR_HIP;
-    if (r == GKI_OK && gki_dev_malloc(&tmp2, (size_t)tmp2_bytes) != hipSuccess) r = GKI_ERR_HIP;
-    if (r == GKI_OK) r = gki_scan_u32_to_i64(sizes, n_large, starts, tmp2, tmp2_bytes, s);
+    DevBuf starts, tmp2, scratch;
+    HIP_TRY(starts.alloc(((size_t)n_large + 1) * 8));
+    HIP_TRY(tmp2.alloc((size_t)tmp2_bytes));
+    GKI_TRY(gki_scan_u32_to_i64(sizes, n_large, starts.get<int64_t>(), tmp2.get(), tmp2_bytes, s));
     int64_t total = 0;
-    if (r == GKI_OK && hipMemcpy(&total, starts + n_large, 8, hipMemcpyDeviceToHost) != hipSuccess) r = GKI_ERR_HIP;
-    if (r == GKI_OK && gki_dev_malloc((void **)&scratch, (size_t)total * sizeof(Pair)) != hipSuccess) r = GKI_ERR_HIP;
-    if (r == GKI_OK) {
-        const unsigned grid = n_large < 2048 ? n_large : 2048;
-        hipLaunchKernelGGL(k_frequencies_large, dim3(grid), dim3(256), 0, s, large_list, n_large, (const int32_t *)d_hashes_to_index,
-                           (const uint32_t *)d_n_kmers, (const uint64_t *)d_kmers, (const uint64_t *)d_refs, starts, scratch,
-                           (uint16_t *)d_freq);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) r = GKI_ERR_HIP;
-    }
-    (void)gki_dev_free(starts); (void)gki_dev_free(tmp2); (void)gki_dev_free(scratch);
-    if (r != GKI_OK) return gki_set_error(r, "large-bucket frequency pass failed");
+    HIP_TRY(hipMemcpy(&total, starts.get<int64_t>() + n_large, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(scratch.alloc((size_t)total * sizeof(Pair)));
+    const unsigned grid = n_large < 2048 ? n_large : 2048;
+    hipLaunchKernelGGL(k_frequencies_large, dim3(grid), dim3(256), 0, s, large_list, n_large, (const int32_t *)d_hashes_to_index,
+                       (const uint32_t *)d_n_kmers, (const uint64_t *)d_kmers, (const uint64_t *)d_refs, starts.get<const int64_t>(),
+                       scratch.get<Pair>(), (uint16_t *)d_freq);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
     return GKI_OK;
 }
 
@@ -538,26 +552,24 @@ int gki_frequencies_for_rows(const int64_t *d_row_begin, const int64_t *d_row_en
                              uint64_t bucket_begin, const void *d_hashes_to_index, const void *d_n_kmers, const void *d_kmers,
                              const void *d_refs, void *d_freq, int64_t n, hipStream_t s) {
     if (n_ranges <= 0) return GKI_OK;
-    uint32_t *large_list = nullptr, *sizes = nullptr;
-    unsigned int *n_large_d = nullptr;
     const size_t cap = (size_t)(n / SMALL_BUCKET + 1);
-    int rc = GKI_OK;
-    if (gki_dev_malloc((void **)&large_list, cap * 4) != hipSuccess || gki_dev_malloc((void **)&sizes, cap * 4) != hipSuccess ||
-        gki_dev_malloc((void **)&n_large_d, 16) != hipSuccess || hipMemsetAsync(n_large_d, 0, 4, s) != hipSuccess)
-        rc = gki_set_error(GKI_ERR_HIP, "frequency pass: allocation failed");
+    DevBuf large_list, sizes, n_large_d;
+    HIP_TRY(large_list.alloc(cap * 4));
+    HIP_TRY(sizes.alloc(cap * 4));
+    HIP_TRY(n_large_d.alloc(16));
+    HIP_TRY(hipMemsetAsync(n_large_d.get(), 0, 4, s));
+    hipLaunchKernelGGL(k_frequencies_ranges, dim3(n_ranges < 4096 ? n_ranges : 4096), dim3(256), 0, s, d_row_begin, d_row_end,
+                       n_ranges, modulo, bucket_begin, (const int32_t *)d_hashes_to_index, (const uint32_t *)d_n_kmers,
+                       (const uint64_t *)d_kmers, (const uint64_t *)d_refs, (uint16_t *)d_freq, large_list.get<uint32_t>(),
+                       n_large_d.get<unsigned int>());
+    HIP_TRY(hipGetLastError());
     unsigned int n_large = 0;
-    if (rc == GKI_OK) {
-        hipLaunchKernelGGL(k_frequencies_ranges, dim3(n_ranges < 4096 ? n_ranges : 4096), dim3(256), 0, s, d_row_begin, d_row_end,
-                           n_ranges, modulo, bucket_begin, (const int32_t *)d_hashes_to_index, (const uint32_t *)d_n_kmers,
-                           (const uint64_t *)d_kmers, (const uint64_t *)d_refs, (uint16_t *)d_freq, large_list, n_large_d);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&n_large, n_large_d, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            rc = gki_set_error(GKI_ERR_HIP, "frequency pass over open rows failed");
-    }
-    if (rc == GKI_OK && n_large > 0)
-        rc = frequencies_large_pass(large_list, n_large, sizes, d_hashes_to_index, d_n_kmers, d_kmers, d_refs, d_freq, s);
-    (void)gki_dev_free(large_list); (void)gki_dev_free(sizes); (void)gki_dev_free(n_large_d);
-    return rc;
+    HIP_TRY(hipMemcpyAsync(&n_large, n_large_d.get(), 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (n_large > 0)
+        GKI_TRY(frequencies_large_pass(large_list.get<uint32_t>(), n_large, sizes.get<uint32_t>(), d_hashes_to_index, d_n_kmers,
+                                       d_kmers, d_refs, d_freq, s));
+    return GKI_OK;
 }
 
 extern "C" {
@@ -578,77 +590,54 @@ int gki_index_build_pairs(const void *d_kmers, const void *d_nodes, const void *
     HIP_TRY(hipMemsetAsync(d_n_kmers, 0, (size_t)n_buckets * 4, s));               // :456
     if (n <= 0) { HIP_TRY(hipStreamSynchronize(s)); return GKI_OK; }
     HIP_TRY(hipMemsetAsync(d_out_frequencies, 0, (size_t)n * 2, s));               // :270
-    const int64_t n_tiles = ceil_div(n, RTILE);
-    uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr}, *hist = nullptr, *offs = nullptr;
-    uint4 *rows = nullptr;
-    void *tmp = nullptr;
-    const int64_t hist_n = (int64_t)RBINS * n_tiles;
-    const int64_t tmp_bytes = gki_scan_tmp_bytes(hist_n);
-    int rc = GKI_OK;
-#define CLEANUP_RETURN(code) do { rc = (code); goto done; } while (0)
-#define HIP_G(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = gki_set_error(GKI_ERR_HIP, "%s:%d %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); goto done; } } while (0)
-    {
-        for (int i = 0; i < 2; i++) {
-            HIP_G(gki_dev_malloc((void **)&keys[i], (size_t)n * 4));
-            HIP_G(gki_dev_malloc((void **)&vals[i], (size_t)n * 4));
-        }
-        HIP_G(gki_dev_malloc((void **)&hist, (size_t)hist_n * 4));
-        HIP_G(gki_dev_malloc((void **)&offs, (size_t)(hist_n + 1) * 4));
-        HIP_G(gki_dev_malloc(&tmp, (size_t)tmp_bytes));
-        int *bad = (int *)hist;                       // hist is not in use yet
-        HIP_G(hipMemsetAsync(bad, 0, 4, s));
-        hipLaunchKernelGGL(k_bucket_keys, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const uint64_t *)d_kmers, n, modulo,
-                           bucket_begin, n_buckets, keys[0], vals[0], bad);
-        HIP_G(hipGetLastError());
-        if (n_buckets != modulo) {
-            int h_bad = 0;
-            HIP_G(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, s));
-            HIP_G(hipStreamSynchronize(s));
-            if (h_bad) CLEANUP_RETURN(gki_set_error(GKI_ERR_BAD_ARG, "a record's bucket lies outside [%llu, +%llu)",
-                                                    (unsigned long long)bucket_begin, (unsigned long long)n_buckets));
-        }
-        int cur = 0;
-        {
-            int r = radix_sort_pairs(keys, vals, n, key_bits(n_buckets - 1), hist, offs, tmp, tmp_bytes, s, &cur);
-            if (r != GKI_OK) CLEANUP_RETURN(r);
-        }
-        HIP_G(gki_dev_malloc((void **)&rows, (size_t)n * 32));
-        hipLaunchKernelGGL(k_pack_rows, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const uint64_t *)d_kmers,
-                           (const uint32_t *)d_nodes, (const uint64_t *)d_ref_offsets, (const float *)d_af32, n, rows);
-        HIP_G(hipGetLastError());
-        hipLaunchKernelGGL(k_gather_rows, dim3(stream_grid(n, 256)), dim3(256), 0, s, vals[cur], n, (const uint4 *)rows,
-                           (uint64_t *)d_out_kmers, (uint32_t *)d_out_nodes, (uint64_t *)d_out_ref_offsets, (float *)d_out_af32);
-        HIP_G(hipGetLastError());
-        if (d_out_permutation) HIP_G(hipMemcpyAsync(d_out_permutation, vals[cur], (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(k_directory, dim3(stream_grid(n, 256)), dim3(256), 0, s, keys[cur], n, (int32_t *)d_hashes_to_index,
-                           (uint32_t *)d_n_kmers);
-        HIP_G(hipGetLastError());
-        if (!skip_frequencies) {
-            // large-bucket work list: at most n / SMALL_BUCKET entries; reuse the spare key/val buffers
-            uint32_t *large_list = keys[1 - cur];
-            unsigned int *n_large_d = (unsigned int *)hist;
-            HIP_G(hipMemsetAsync(n_large_d, 0, 4, s));
-            hipLaunchKernelGGL(k_frequencies_small, dim3(stream_grid(n, 256)), dim3(256), 0, s, keys[cur], n,
-                               (const int32_t *)d_hashes_to_index, (const uint32_t *)d_n_kmers, (const uint64_t *)d_out_kmers,
-                               (const uint64_t *)d_out_ref_offsets, (uint16_t *)d_out_frequencies, large_list, n_large_d);
-            HIP_G(hipGetLastError());
-            unsigned int n_large = 0;
-            HIP_G(hipMemcpyAsync(&n_large, n_large_d, 4, hipMemcpyDeviceToHost, s));
-            HIP_G(hipStreamSynchronize(s));
-            if (n_large > 0) {
-                int r = frequencies_large_pass(large_list, n_large, vals[1 - cur], d_hashes_to_index, d_n_kmers, d_out_kmers,
-                                               d_out_ref_offsets, d_out_frequencies, s);
-                if (r != GKI_OK) CLEANUP_RETURN(r);
-            }
-        }
-        HIP_G(hipStreamSynchronize(s));
+    SortScratch ss;
+    DevBuf rows_b;
+    GKI_TRY(ss.alloc(n));
+    uint32_t **keys = ss.keys, **vals = ss.vals, *hist = ss.hist;
+    int *bad = (int *)hist;                       // hist is not in use yet
+    HIP_TRY(hipMemsetAsync(bad, 0, 4, s));
+    hipLaunchKernelGGL(k_bucket_keys, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const uint64_t *)d_kmers, n, modulo,
+                       bucket_begin, n_buckets, keys[0], vals[0], bad);
+    HIP_TRY(hipGetLastError());
+    if (n_buckets != modulo) {
+        int h_bad = 0;
+        HIP_TRY(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (h_bad) return gki_set_error(GKI_ERR_BAD_ARG, "a record's bucket lies outside [%llu, +%llu)",
+                                        (unsigned long long)bucket_begin, (unsigned long long)n_buckets);
     }
-done:
-    for (int i = 0; i < 2; i++) { (void)gki_dev_free(keys[i]); (void)gki_dev_free(vals[i]); }
-    (void)gki_dev_free(hist); (void)gki_dev_free(offs); (void)gki_dev_free(tmp); (void)gki_dev_free(rows);
-#undef HIP_G
-#undef CLEANUP_RETURN
-    return rc;
+    int cur = 0;
+    GKI_TRY(ss.sort(n, key_bits(n_buckets - 1), s, &cur));
+    HIP_TRY(rows_b.alloc((size_t)n * 32));
+    uint4 *rows = rows_b.get<uint4>();
+    hipLaunchKernelGGL(k_pack_rows, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const uint64_t *)d_kmers,
+                       (const uint32_t *)d_nodes, (const uint64_t *)d_ref_offsets, (const float *)d_af32, n, rows);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_gather_rows, dim3(stream_grid(n, 256)), dim3(256), 0, s, vals[cur], n, (const uint4 *)rows,
+                       (uint64_t *)d_out_kmers, (uint32_t *)d_out_nodes, (uint64_t *)d_out_ref_offsets, (float *)d_out_af32);
+    HIP_TRY(hipGetLastError());
+    if (d_out_permutation) HIP_TRY(hipMemcpyAsync(d_out_permutation, vals[cur], (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(k_directory, dim3(stream_grid(n, 256)), dim3(256), 0, s, keys[cur], n, (int32_t *)d_hashes_to_index,
+                       (uint32_t *)d_n_kmers);
+    HIP_TRY(hipGetLastError());
+    if (!skip_frequencies) {
+        // large-bucket work list: at most n / SMALL_BUCKET entries; reuse the spare key/val buffers
+        uint32_t *large_list = keys[1 - cur];
+        unsigned int *n_large_d = (unsigned int *)hist;
+        HIP_TRY(hipMemsetAsync(n_large_d, 0, 4, s));
+        hipLaunchKernelGGL(k_frequencies_small, dim3(stream_grid(n, 256)), dim3(256), 0, s, keys[cur], n,
+                           (const int32_t *)d_hashes_to_index, (const uint32_t *)d_n_kmers, (const uint64_t *)d_out_kmers,
+                           (const uint64_t *)d_out_ref_offsets, (uint16_t *)d_out_frequencies, large_list, n_large_d);
+        HIP_TRY(hipGetLastError());
+        unsigned int n_large = 0;
+        HIP_TRY(hipMemcpyAsync(&n_large, n_large_d, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (n_large > 0)
+            GKI_TRY(frequencies_large_pass(large_list, n_large, vals[1 - cur], d_hashes_to_index, d_n_kmers, d_out_kmers,
+                                           d_out_ref_offsets, d_out_frequencies, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return GKI_OK;
 }
 
 int gki_index_build_range_grouped(const void *d_kmers, const void *d_nodes, const void *d_ref_offsets, const void *d_af32, int64_t n,
@@ -776,42 +765,23 @@ int gki_flag_repeated_kmers(const void *d_kmers, int64_t n, void *d_flags) {
     uint64_t modulo = (uint64_t)n * 2 + 1;
     if (modulo > 0xFFFFFFFBull) modulo = 0xFFFFFFFBull;
     hipStream_t s = 0;
-    const int64_t hist_n = (int64_t)RBINS * ceil_div(n, RTILE);
-    const int64_t tmp_bytes = gki_scan_tmp_bytes(hist_n);
-    uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr}, *hist = nullptr, *offs = nullptr, *cnt = nullptr;
-    int32_t *first = nullptr;
-    void *tmp = nullptr;
-    int rc = GKI_OK;
-#define HIP_G(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = gki_set_error(GKI_ERR_HIP, "%s:%d %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); goto done; } } while (0)
-    {
-        for (int i = 0; i < 2; i++) {
-            HIP_G(gki_dev_malloc((void **)&keys[i], (size_t)n * 4));
-            HIP_G(gki_dev_malloc((void **)&vals[i], (size_t)n * 4));
-        }
-        HIP_G(gki_dev_malloc((void **)&hist, (size_t)hist_n * 4));
-        HIP_G(gki_dev_malloc((void **)&offs, (size_t)(hist_n + 1) * 4));
-        HIP_G(gki_dev_malloc(&tmp, (size_t)tmp_bytes));
-        HIP_G(gki_dev_malloc((void **)&first, (size_t)modulo * 4));
-        HIP_G(gki_dev_malloc((void **)&cnt, (size_t)modulo * 4));
-        int *bad = (int *)hist;
-        hipLaunchKernelGGL(k_bucket_keys, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const uint64_t *)d_kmers, n, modulo,
-                           (uint64_t)0, modulo, keys[0], vals[0], bad);
-        HIP_G(hipGetLastError());
-        int cur = 0;
-        rc = radix_sort_pairs(keys, vals, n, key_bits(modulo - 1), hist, offs, tmp, tmp_bytes, s, &cur);
-        if (rc != GKI_OK) goto done;
-        hipLaunchKernelGGL(k_directory, dim3(stream_grid(n, 256)), dim3(256), 0, s, keys[cur], n, first, cnt);
-        HIP_G(hipGetLastError());
-        hipLaunchKernelGGL(k_flag_repeats, dim3(stream_grid(n, 256)), dim3(256), 0, s, keys[cur], vals[cur],
-                           (const uint64_t *)d_kmers, n, first, (uint8_t *)d_flags);
-        HIP_G(hipGetLastError());
-        HIP_G(hipStreamSynchronize(s));
-    }
-done:
-    for (int i = 0; i < 2; i++) { (void)gki_dev_free(keys[i]); (void)gki_dev_free(vals[i]); }
-    (void)gki_dev_free(hist); (void)gki_dev_free(offs); (void)gki_dev_free(tmp); (void)gki_dev_free(first); (void)gki_dev_free(cnt);
-#undef HIP_G
-    return rc;
+    SortScratch ss;
+    DevBuf first, cnt;
+    GKI_TRY(ss.alloc(n));
+    HIP_TRY(first.alloc((size_t)modulo * 4));
+    HIP_TRY(cnt.alloc((size_t)modulo * 4));
+    hipLaunchKernelGGL(k_bucket_keys, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const uint64_t *)d_kmers, n, modulo,
+                       (uint64_t)0, modulo, ss.keys[0], ss.vals[0], (int *)ss.hist);
+    HIP_TRY(hipGetLastError());
+    int cur = 0;
+    GKI_TRY(ss.sort(n, key_bits(modulo - 1), s, &cur));
+    hipLaunchKernelGGL(k_directory, dim3(stream_grid(n, 256)), dim3(256), 0, s, ss.keys[cur], n, first.get<int32_t>(), cnt.get<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_flag_repeats, dim3(stream_grid(n, 256)), dim3(256), 0, s, ss.keys[cur], ss.vals[cur],
+                       (const uint64_t *)d_kmers, n, first.get<const int32_t>(), (uint8_t *)d_flags);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    return GKI_OK;
 }
 
 int gki_reverse_index_build(const void *d_nodes, const void *d_kmers, const void *d_ref_offsets, int64_t n, int64_t n_nodes,
@@ -826,71 +796,51 @@ int gki_reverse_index_build(const void *d_nodes, const void *d_kmers, const void
         // the row-carrying form (gki_index_rows.hip) with the node id as the key: the payload travels with its key through the
         // staged partition passes and the in-LDS finish leaves the node directory as it goes -- no gather, no separate
         // directory passes (round 4; the pair-sorting form below stays for what lies outside its domain)
-        uint32_t *nk32 = nullptr;
-        HIP_TRY(gki_dev_malloc((void **)&nk32, (size_t)n_nodes * 4));
+        DevBuf nk32;
+        HIP_TRY(nk32.alloc((size_t)n_nodes * 4));
         int done = 0;
-        int rc = gki_index_build_rows(d_kmers, d_nodes, d_ref_offsets, nullptr, n, 1, 0, (uint64_t)n_nodes, 1, 0, nullptr, nullptr, nullptr,
-                                      d_index_positions, nk32, d_out_kmers, nullptr, d_out_ref_offsets, nullptr, nullptr, nullptr, &done, 1);
-        if (rc == GKI_OK && done) {
-            hipLaunchKernelGGL(k_narrow_counts, dim3(stream_grid(n_nodes, 256)), dim3(256), 0, s, nk32, n_nodes, (uint16_t *)d_n_hashes);
-            hipError_t e = hipGetLastError();
-            hipError_t e2 = hipStreamSynchronize(s);
-            (void)gki_dev_free(nk32);
-            HIP_TRY(e); HIP_TRY(e2);
+        GKI_TRY(gki_index_build_rows(d_kmers, d_nodes, d_ref_offsets, nullptr, n, 1, 0, (uint64_t)n_nodes, 1, 0, nullptr, nullptr, nullptr,
+                                     d_index_positions, nk32.get(), d_out_kmers, nullptr, d_out_ref_offsets, nullptr, nullptr, nullptr, &done, 1));
+        if (done) {
+            hipLaunchKernelGGL(k_narrow_counts, dim3(stream_grid(n_nodes, 256)), dim3(256), 0, s, nk32.get<const uint32_t>(), n_nodes,
+                               (uint16_t *)d_n_hashes);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(s));
             return GKI_OK;
         }
-        (void)gki_dev_free(nk32);
-        if (rc != GKI_OK) return rc;
-    }
+    }                                                 // (nk32 is freed before the pair-sorting form allocates)
     HIP_TRY(hipMemsetAsync(d_index_positions, 0, (size_t)n_nodes * 4, s));      // reverse_kmer_index.py:53
     HIP_TRY(hipMemsetAsync(d_n_hashes, 0, (size_t)n_nodes * 2, s));             // :54
     if (n <= 0) { HIP_TRY(hipStreamSynchronize(s)); return GKI_OK; }
-    const int64_t hist_n = (int64_t)RBINS * ceil_div(n, RTILE);
-    const int64_t tmp_bytes = gki_scan_tmp_bytes(hist_n);
-    uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr}, *hist = nullptr, *offs = nullptr;
-    uint4 *rows = nullptr;
-    void *tmp = nullptr;
-    int *bad = nullptr;
-    int rc = GKI_OK;
-#define HIP_G(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = gki_set_error(GKI_ERR_HIP, "%s:%d %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); goto done; } } while (0)
-    {
-        for (int i = 0; i < 2; i++) {
-            HIP_G(gki_dev_malloc((void **)&keys[i], (size_t)n * 4));
-            HIP_G(gki_dev_malloc((void **)&vals[i], (size_t)n * 4));
-        }
-        HIP_G(gki_dev_malloc((void **)&hist, (size_t)hist_n * 4));
-        HIP_G(gki_dev_malloc((void **)&offs, (size_t)(hist_n + 1) * 4));
-        HIP_G(gki_dev_malloc(&tmp, (size_t)tmp_bytes));
-        HIP_G(gki_dev_malloc((void **)&rows, (size_t)n * 16));
-        HIP_G(gki_dev_malloc((void **)&bad, 4));
-        HIP_G(hipMemsetAsync(bad, 0, 4, s));
-        hipLaunchKernelGGL(k_node_keys, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const uint32_t *)d_nodes, n, (uint64_t)n_nodes, keys[0], vals[0], bad);
-        HIP_G(hipGetLastError());
-        int cur = 0;
-        rc = radix_sort_pairs(keys, vals, n, key_bits((uint64_t)n_nodes - 1), hist, offs, tmp, tmp_bytes, s, &cur);
-        if (rc != GKI_OK) goto done;
-        hipLaunchKernelGGL(k_pack_pairs, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const uint64_t *)d_kmers,
-                           (const uint64_t *)d_ref_offsets, n, rows);
-        HIP_G(hipGetLastError());
-        hipLaunchKernelGGL(k_gather_pairs, dim3(stream_grid(n, 256)), dim3(256), 0, s, vals[cur], n, (const uint4 *)rows,
-                           (uint64_t *)d_out_kmers, (uint64_t *)d_out_ref_offsets);
-        HIP_G(hipGetLastError());
-        hipLaunchKernelGGL(k_node_directory<0>, dim3(stream_grid(n, 256)), dim3(256), 0, s, keys[cur], n,
-                           (uint32_t *)d_index_positions, (uint16_t *)d_n_hashes);
-        HIP_G(hipGetLastError());
-        hipLaunchKernelGGL(k_node_directory<1>, dim3(stream_grid(n, 256)), dim3(256), 0, s, keys[cur], n,
-                           (uint32_t *)d_index_positions, (uint16_t *)d_n_hashes);
-        HIP_G(hipGetLastError());
-        int h_bad = 0;
-        HIP_G(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, s));
-        HIP_G(hipStreamSynchronize(s));
-        if (h_bad) rc = gki_set_error(GKI_ERR_BAD_ARG, "a record's node id is not below n_nodes = %lld", (long long)n_nodes);
-    }
-done:
-    for (int i = 0; i < 2; i++) { (void)gki_dev_free(keys[i]); (void)gki_dev_free(vals[i]); }
-    (void)gki_dev_free(hist); (void)gki_dev_free(offs); (void)gki_dev_free(tmp); (void)gki_dev_free(rows); (void)gki_dev_free(bad);
-#undef HIP_G
-    return rc;
+    SortScratch ss;
+    DevBuf rows, bad;
+    GKI_TRY(ss.alloc(n));
+    HIP_TRY(rows.alloc((size_t)n * 16));
+    HIP_TRY(bad.alloc(4));
+    HIP_TRY(hipMemsetAsync(bad.get(), 0, 4, s));
+    uint32_t **keys = ss.keys, **vals = ss.vals;
+    hipLaunchKernelGGL(k_node_keys, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const uint32_t *)d_nodes, n, (uint64_t)n_nodes, keys[0], vals[0],
+                       bad.get<int>());
+    HIP_TRY(hipGetLastError());
+    int cur = 0;
+    GKI_TRY(ss.sort(n, key_bits((uint64_t)n_nodes - 1), s, &cur));
+    hipLaunchKernelGGL(k_pack_pairs, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const uint64_t *)d_kmers,
+                       (const uint64_t *)d_ref_offsets, n, rows.get<uint4>());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_gather_pairs, dim3(stream_grid(n, 256)), dim3(256), 0, s, vals[cur], n, rows.get<const uint4>(),
+                       (uint64_t *)d_out_kmers, (uint64_t *)d_out_ref_offsets);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_node_directory<0>, dim3(stream_grid(n, 256)), dim3(256), 0, s, keys[cur], n,
+                       (uint32_t *)d_index_positions, (uint16_t *)d_n_hashes);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_node_directory<1>, dim3(stream_grid(n, 256)), dim3(256), 0, s, keys[cur], n,
+                       (uint32_t *)d_index_positions, (uint16_t *)d_n_hashes);
+    HIP_TRY(hipGetLastError());
+    int h_bad = 0;
+    HIP_TRY(hipMemcpyAsync(&h_bad, bad.get(), 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h_bad) return gki_set_error(GKI_ERR_BAD_ARG, "a record's node id is not below n_nodes = %lld", (long long)n_nodes);
+    return GKI_OK;
 }
 
 static IndexDev view_of(const gki_index_view *ix) {
@@ -919,21 +869,17 @@ int gki_index_lookup_count(const gki_index_view *ix, const void *d_queries, int6
     *n_hits = 0;
     if (ix->modulo == 0) return gki_set_error(GKI_ERR_BAD_ARG, "modulo is 0");
     if (q <= 0) { HIP_TRY(hipMemset(d_hit_start, 0, 8)); return GKI_OK; }
-    uint32_t *cnt = nullptr;
-    void *tmp = nullptr;
     int64_t tmp_bytes = gki_scan_tmp_bytes(q);
-    HIP_TRY(gki_dev_malloc((void **)&cnt, (size_t)q * 4));
-    HIP_TRY(gki_dev_malloc(&tmp, (size_t)tmp_bytes));
+    DevBuf cnt, tmp;
+    HIP_TRY(cnt.alloc((size_t)q * 4));
+    HIP_TRY(tmp.alloc((size_t)tmp_bytes));
     hipLaunchKernelGGL(k_lookup<false>, dim3(stream_grid(q, 256)), dim3(256), 0, 0, view_of(ix), (const uint64_t *)d_queries, q,
-                       max_hits, cnt, (const int64_t *)nullptr, (uint32_t *)nullptr, (uint64_t *)nullptr, (int64_t *)nullptr,
+                       max_hits, cnt.get<uint32_t>(), (const int64_t *)nullptr, (uint32_t *)nullptr, (uint64_t *)nullptr, (int64_t *)nullptr,
                        (uint16_t *)nullptr, (float *)nullptr, (int64_t *)nullptr);
-    int rc = hipGetLastError() == hipSuccess ? GKI_OK : gki_set_error(GKI_ERR_HIP, "k_lookup launch failed");
-    if (rc == GKI_OK) rc = gki_scan_u32_to_i64(cnt, q, (int64_t *)d_hit_start, tmp, tmp_bytes, 0);
+    if (hipGetLastError() != hipSuccess) return gki_set_error(GKI_ERR_HIP, "k_lookup launch failed");
+    GKI_TRY(gki_scan_u32_to_i64(cnt.get<const uint32_t>(), q, (int64_t *)d_hit_start, tmp.get(), tmp_bytes, 0));
     int64_t total = 0;
-    hipError_t e = hipMemcpy(&total, (const int64_t *)d_hit_start + q, 8, hipMemcpyDeviceToHost);
-    (void)gki_dev_free(cnt); (void)gki_dev_free(tmp);
-    if (rc != GKI_OK) return rc;
-    HIP_TRY(e);
+    HIP_TRY(hipMemcpy(&total, (const int64_t *)d_hit_start + q, 8, hipMemcpyDeviceToHost));
     *n_hits = total;
     return GKI_OK;
 }

@@ -1114,142 +1114,132 @@ int gki_index_build_rows(const void *d_kmers, const void *d_nodes, const void *d
     }
     const int64_t hist_n = (int64_t)MAXB * n_tiles;
     const int64_t tmp_bytes = gki_scan_tmp_bytes(hist_n);
-    uint64_t *rows[2] = {nullptr, nullptr};
-    uint32_t *keys[2] = {nullptr, nullptr}, *hist = nullptr, *offs = nullptr, *gbegin = nullptr, *gend = nullptr;
-    uint32_t *large = nullptr, *big = nullptr;
-    unsigned int *stats = nullptr;                            // [0] max group, [1] large groups, [2] big buckets, [3] out of range
-    int64_t *rng = nullptr;
-    void *tmp = nullptr;
     const uint32_t large_cap = 1u << 16;
     const uint32_t big_cap = (uint32_t)(n / SMALL_BUCKET + 1);
-    TileDesc *d_tiles = nullptr;
-    int64_t *d_seg = nullptr;
     KeyRule rule;
     rule.mod = gki_mod_of(modulo); rule.bucket_begin = bucket_begin; rule.n_buckets = n_buckets; rule.n_parts = 0; rule.sub_bits = 0;
     rule.part_begin = nullptr; rule.sub_shift = nullptr; rule.parts_per_bucket = 0.f; rule.parts_log2 = -1; rule.by_node = by_node;
-    int rc = GKI_OK;
-#define HIP_G(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = gki_set_error(GKI_ERR_HIP, "%s:%d %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); goto done; } } while (0)
-    {
-        HIP_G(gki_dev_malloc((void **)&stats, 64));
-        HIP_G(hipMemsetAsync(stats, 0, 64, s));
-        if (grouped) {
-            HIP_G(gki_dev_malloc((void **)&d_tiles, (size_t)n_tiles * sizeof(TileDesc) + 32));
-            HIP_G(gki_dev_malloc((void **)&d_seg, h_seg.size() * 8));
-            HIP_G(hipMemcpyAsync(d_seg, h_seg.data(), h_seg.size() * 8, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_tile_descs, dim3((unsigned)n_seg), dim3(256), 0, s, d_seg, TILE, d_tiles);
-            HIP_G(hipGetLastError());
-        }
-        for (int i = 0; i < (n_pass > 1 ? 2 : n_pass); i++) {
-            HIP_G(gki_dev_malloc((void **)&rows[i], (size_t)n * 24));
-            HIP_G(gki_dev_malloc((void **)&keys[i], (size_t)n * 4));
-        }
-        HIP_G(gki_dev_malloc((void **)&hist, (size_t)hist_n * 4));
-        HIP_G(gki_dev_malloc((void **)&offs, (size_t)(hist_n + 1) * 4));
-        HIP_G(gki_dev_malloc(&tmp, (size_t)tmp_bytes));
-        HIP_G(gki_dev_malloc((void **)&gbegin, (size_t)n_groups * 4));
-        HIP_G(gki_dev_malloc((void **)&gend, (size_t)n_groups * 4));
-        HIP_G(gki_dev_malloc((void **)&large, (size_t)large_cap * 4));
-        HIP_G(gki_dev_malloc((void **)&big, (size_t)big_cap * 4));
-        HIP_G(hipMemsetAsync(gbegin, 0, (size_t)n_groups * 4, s));
-        HIP_G(hipMemsetAsync(gend, 0, (size_t)n_groups * 4, s));
-        // partition passes on the top bits, least significant digit first, each stable
-        const uint64_t *cur_rows = (const uint64_t *)d_rows_in;
-        const uint32_t *cur_keys = (const uint32_t *)d_keys_in;
-        int shift = L;
-        for (int p = 0; p < n_pass; p++) {
-            const int bits = (top - (shift - L) + (n_pass - p) - 1) / (n_pass - p);       // remaining bits spread evenly (an odd bit
-                                                                                           // first or last: no difference measured)
-            const int64_t bins_n = ((int64_t)1 << bits) * n_tiles;
-            const int xcd_tiles = (int)ceil_div(n_tiles, 8);
-            const unsigned xgrid = (unsigned)(xcd_tiles * 8);
-            if (p == 0 && by_node)
-                hipLaunchKernelGGL((k_digit_hist<THREADS, RI>), dim3(xgrid), dim3(THREADS), 0, s, (const uint32_t *)d_nodes, n, shift, bits,
-                                   hist, n_tiles, xcd_tiles, d_tiles);
-            else if (p == 0 && !from_rows)
-                hipLaunchKernelGGL((k_kmer_digit_hist<THREADS, RI>), dim3(xgrid), dim3(THREADS), 0, s, (const uint64_t *)d_kmers,
-                                   n, rule, shift, bits, hist, n_tiles, xcd_tiles, d_tiles, (int *)(stats + 3));
-            else
-                hipLaunchKernelGGL((k_digit_hist<THREADS, RI>), dim3(xgrid), dim3(THREADS), 0, s, cur_keys, n, shift, bits,
-                                   hist, n_tiles, xcd_tiles, d_tiles);
-            HIP_G(hipGetLastError());
-            rc = gki_scan_u32_to_u32(hist, bins_n, offs, tmp, tmp_bytes, s);
-            if (rc != GKI_OK) goto done;
-            PartArgs a;
-            a.tiles = d_tiles;
-            a.keys_in = cur_keys; a.c_kmers = (const uint64_t *)d_kmers; a.c_nodes = (const uint32_t *)d_nodes;
-            a.c_refs = (const uint64_t *)d_ref_offsets; a.c_af = (const uint32_t *)d_af32; a.rule = rule; a.rows_in = cur_rows;
-            a.n = n; a.n_tiles = n_tiles; a.shift = shift; a.bits = bits; a.offs = offs; a.carry_index = d_out_permutation != nullptr;
-            a.rows_out = rows[p & 1]; a.keys_out = keys[p & 1];
-            a.o_kmers = nullptr; a.o_nodes = nullptr; a.o_refs = nullptr; a.o_af = nullptr; a.dbase = nullptr;
-            a.xcd_tiles = xcd_tiles;
-#if GKI_PT_NCH > 1
-            if (p == 0 && !from_rows) hipLaunchKernelGGL((k_partition_rows_staged<THREADS, RI, true, GKI_PT_NCH>), dim3(xgrid), dim3(THREADS), 0, s, a);
-            else hipLaunchKernelGGL((k_partition_rows_staged<THREADS, RI, false, GKI_PT_NCH>), dim3(xgrid), dim3(THREADS), 0, s, a);
-#else
-            if (p == 0 && !from_rows) hipLaunchKernelGGL((k_partition_rows<THREADS, RI, true>), dim3(xgrid), dim3(THREADS), 0, s, a);
-            else hipLaunchKernelGGL((k_partition_rows<THREADS, RI, false>), dim3(xgrid), dim3(THREADS), 0, s, a);
-#endif
-            HIP_G(hipGetLastError());
-            cur_rows = a.rows_out; cur_keys = a.keys_out;
-            shift += bits;
-        }
-        hipLaunchKernelGGL(k_group_bounds, dim3((unsigned)ceil_div(n, 1024)), dim3(256), 0, s, cur_keys, n, L, (uint32_t)n_buckets, gbegin, gend,
-                           (int *)(stats + 3));
-        HIP_G(hipGetLastError());
-        hipLaunchKernelGGL(k_group_scan, dim3(stream_grid(n_groups, 256)), dim3(256), 0, s, gbegin, gend, n_groups,
-                           (uint32_t)cap, stats, large, large_cap);
-        HIP_G(hipGetLastError());
-        unsigned int h_stats[4] = {0, 0, 0, 0};
-        HIP_G(hipMemcpyAsync(h_stats, stats, 16, hipMemcpyDeviceToHost, s));
-        HIP_G(hipStreamSynchronize(s));
-        if (h_stats[3]) { rc = gki_set_error(GKI_ERR_BAD_ARG, "a record's bucket lies outside [%llu, +%llu)", (unsigned long long)bucket_begin, (unsigned long long)n_buckets); goto done; }
-        // one workgroup streams a large group: fine for the repeats of a genome, not for an index that IS one bucket
-        if (h_stats[1] > large_cap || h_stats[0] > (1u << 22)) goto done;           // *done stays 0
-        FinishArgs f;
-        f.rows = cur_rows; f.keys = cur_keys; f.gbegin = gbegin; f.gend = gend; f.n_groups = n_groups; f.L = L; f.lbits = L;
-        f.n_buckets = n_buckets; f.skip_frequencies = skip_frequencies; f.h2i = (int32_t *)d_hashes_to_index;
-        f.nk = (uint32_t *)d_n_kmers; f.o_kmers = (uint64_t *)d_out_kmers; f.o_nodes = (uint32_t *)d_out_nodes;
-        f.o_refs = (uint64_t *)d_out_ref_offsets; f.o_af = (uint32_t *)d_out_af32; f.o_freq = (uint16_t *)d_out_frequencies;
-        f.o_perm = (uint32_t *)d_out_permutation; f.af_in = (const uint32_t *)d_af32;
-        f.big_buckets = big; f.n_big = stats + 2; f.big_cap = big_cap;
-        f.xcd_groups = (int)ceil_div(n_groups, 8);
-        if (grouped && wrank) hipLaunchKernelGGL((k_group_finish<true, GROUP_CAP_BIG, GROUP_THREADS_BIG>), dim3((unsigned)(f.xcd_groups * 8)), dim3(GROUP_THREADS_BIG), 0, s, f);
-        else if (grouped) hipLaunchKernelGGL((k_group_finish<false, GROUP_CAP_BIG, GROUP_THREADS_BIG>), dim3((unsigned)(f.xcd_groups * 8)), dim3(GROUP_THREADS_BIG), 0, s, f);
-        else if (wrank) hipLaunchKernelGGL((k_group_finish<true>), dim3((unsigned)(f.xcd_groups * 8)), dim3(GROUP_THREADS), 0, s, f);
-        else hipLaunchKernelGGL((k_group_finish<false>), dim3((unsigned)(f.xcd_groups * 8)), dim3(GROUP_THREADS), 0, s, f);
-        HIP_G(hipGetLastError());
-        if (h_stats[1] > 0) {
-            const unsigned n_large = h_stats[1];
-            hipLaunchKernelGGL(k_group_large, dim3(n_large < 1024 ? n_large : 1024), dim3(256), 0, s, f, large, n_large);
-            HIP_G(hipGetLastError());
-        }
-        if (!skip_frequencies) {
-            // frequencies still open: the rows of large groups (all their buckets) and, from k_group_finish, buckets of
-            // more than SMALL_BUCKET rows.  Both go through the first form's kernels over the finished columns.
-            HIP_G(hipMemcpyAsync(h_stats, stats, 16, hipMemcpyDeviceToHost, s));
-            HIP_G(hipStreamSynchronize(s));
-            if (h_stats[1] > 0 || h_stats[2] > 0) {
-                const int n_ranges = (int)h_stats[1] + (int)h_stats[2];
-                HIP_G(gki_dev_malloc((void **)&rng, (size_t)n_ranges * 16));
-                hipLaunchKernelGGL(k_open_ranges, dim3(stream_grid(n_ranges, 256)), dim3(256), 0, s, large, h_stats[1], gbegin, gend,
-                                   big, h_stats[2], (const int32_t *)d_hashes_to_index, (const uint32_t *)d_n_kmers, rng,
-                                   rng + n_ranges);
-                HIP_G(hipGetLastError());
-                rc = gki_frequencies_for_rows(rng, rng + n_ranges, n_ranges, modulo, bucket_begin, d_hashes_to_index, d_n_kmers,
-                                              d_out_kmers, d_out_ref_offsets, d_out_frequencies, n, s);
-                if (rc != GKI_OK) goto done;
-            }
-        }
-        HIP_G(hipStreamSynchronize(s));
-        *done = 1;
+    // (declared after h_seg: their frees wait for the device, so the upload that reads h_seg has finished before it goes)
+    DevBuf stats_b, tiles_b, seg_b, rows_b[2], keys_b[2], hist_b, offs_b, tmp, gbegin_b, gend_b, large_b, big_b, rng_b;
+    HIP_TRY(stats_b.alloc(64));
+    unsigned int *stats = stats_b.get<unsigned int>();       // [0] max group, [1] large groups, [2] big buckets, [3] out of range
+    HIP_TRY(hipMemsetAsync(stats, 0, 64, s));
+    if (grouped) {
+        HIP_TRY(tiles_b.alloc((size_t)n_tiles * sizeof(TileDesc) + 32));
+        HIP_TRY(seg_b.alloc(h_seg.size() * 8));
+        HIP_TRY(hipMemcpyAsync(seg_b.get(), h_seg.data(), h_seg.size() * 8, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_tile_descs, dim3((unsigned)n_seg), dim3(256), 0, s, seg_b.get<const int64_t>(), TILE, tiles_b.get<TileDesc>());
+        HIP_TRY(hipGetLastError());
     }
-done:
-    for (int i = 0; i < 2; i++) { (void)gki_dev_free(rows[i]); (void)gki_dev_free(keys[i]); }
-    (void)gki_dev_free(hist); (void)gki_dev_free(offs); (void)gki_dev_free(tmp); (void)gki_dev_free(gbegin); (void)gki_dev_free(gend);
-    (void)gki_dev_free(large); (void)gki_dev_free(big); (void)gki_dev_free(stats); (void)gki_dev_free(rng);
-    if (d_tiles) { (void)hipStreamSynchronize(s); (void)gki_dev_free(d_tiles); (void)gki_dev_free(d_seg); }   // (the upload read h_seg asynchronously)
-#undef HIP_G
-    return rc;
+    const TileDesc *d_tiles = tiles_b.get<const TileDesc>();
+    uint64_t *rows[2] = {nullptr, nullptr};
+    uint32_t *keys[2] = {nullptr, nullptr};
+    for (int i = 0; i < (n_pass > 1 ? 2 : n_pass); i++) {
+        HIP_TRY(rows_b[i].alloc((size_t)n * 24));
+        HIP_TRY(keys_b[i].alloc((size_t)n * 4));
+        rows[i] = rows_b[i].get<uint64_t>(); keys[i] = keys_b[i].get<uint32_t>();
+    }
+    HIP_TRY(hist_b.alloc((size_t)hist_n * 4));
+    HIP_TRY(offs_b.alloc((size_t)(hist_n + 1) * 4));
+    HIP_TRY(tmp.alloc((size_t)tmp_bytes));
+    HIP_TRY(gbegin_b.alloc((size_t)n_groups * 4));
+    HIP_TRY(gend_b.alloc((size_t)n_groups * 4));
+    HIP_TRY(large_b.alloc((size_t)large_cap * 4));
+    HIP_TRY(big_b.alloc((size_t)big_cap * 4));
+    uint32_t *hist = hist_b.get<uint32_t>(), *offs = offs_b.get<uint32_t>(), *gbegin = gbegin_b.get<uint32_t>(), *gend = gend_b.get<uint32_t>();
+    uint32_t *large = large_b.get<uint32_t>(), *big = big_b.get<uint32_t>();
+    HIP_TRY(hipMemsetAsync(gbegin, 0, (size_t)n_groups * 4, s));
+    HIP_TRY(hipMemsetAsync(gend, 0, (size_t)n_groups * 4, s));
+    // partition passes on the top bits, least significant digit first, each stable
+    const uint64_t *cur_rows = (const uint64_t *)d_rows_in;
+    const uint32_t *cur_keys = (const uint32_t *)d_keys_in;
+    int shift = L;
+    for (int p = 0; p < n_pass; p++) {
+        const int bits = (top - (shift - L) + (n_pass - p) - 1) / (n_pass - p);       // remaining bits spread evenly (an odd bit
+                                                                                       // first or last: no difference measured)
+        const int64_t bins_n = ((int64_t)1 << bits) * n_tiles;
+        const int xcd_tiles = (int)ceil_div(n_tiles, 8);
+        const unsigned xgrid = (unsigned)(xcd_tiles * 8);
+        if (p == 0 && by_node)
+            hipLaunchKernelGGL((k_digit_hist<THREADS, RI>), dim3(xgrid), dim3(THREADS), 0, s, (const uint32_t *)d_nodes, n, shift, bits,
+                               hist, n_tiles, xcd_tiles, d_tiles);
+        else if (p == 0 && !from_rows)
+            hipLaunchKernelGGL((k_kmer_digit_hist<THREADS, RI>), dim3(xgrid), dim3(THREADS), 0, s, (const uint64_t *)d_kmers,
+                               n, rule, shift, bits, hist, n_tiles, xcd_tiles, d_tiles, (int *)(stats + 3));
+        else
+            hipLaunchKernelGGL((k_digit_hist<THREADS, RI>), dim3(xgrid), dim3(THREADS), 0, s, cur_keys, n, shift, bits,
+                               hist, n_tiles, xcd_tiles, d_tiles);
+        HIP_TRY(hipGetLastError());
+        GKI_TRY(gki_scan_u32_to_u32(hist, bins_n, offs, tmp.get(), tmp_bytes, s));
+        PartArgs a;
+        a.tiles = d_tiles;
+        a.keys_in = cur_keys; a.c_kmers = (const uint64_t *)d_kmers; a.c_nodes = (const uint32_t *)d_nodes;
+        a.c_refs = (const uint64_t *)d_ref_offsets; a.c_af = (const uint32_t *)d_af32; a.rule = rule; a.rows_in = cur_rows;
+        a.n = n; a.n_tiles = n_tiles; a.shift = shift; a.bits = bits; a.offs = offs; a.carry_index = d_out_permutation != nullptr;
+        a.rows_out = rows[p & 1]; a.keys_out = keys[p & 1];
+        a.o_kmers = nullptr; a.o_nodes = nullptr; a.o_refs = nullptr; a.o_af = nullptr; a.dbase = nullptr;
+        a.xcd_tiles = xcd_tiles;
+#if GKI_PT_NCH > 1
+        if (p == 0 && !from_rows) hipLaunchKernelGGL((k_partition_rows_staged<THREADS, RI, true, GKI_PT_NCH>), dim3(xgrid), dim3(THREADS), 0, s, a);
+        else hipLaunchKernelGGL((k_partition_rows_staged<THREADS, RI, false, GKI_PT_NCH>), dim3(xgrid), dim3(THREADS), 0, s, a);
+#else
+        if (p == 0 && !from_rows) hipLaunchKernelGGL((k_partition_rows<THREADS, RI, true>), dim3(xgrid), dim3(THREADS), 0, s, a);
+        else hipLaunchKernelGGL((k_partition_rows<THREADS, RI, false>), dim3(xgrid), dim3(THREADS), 0, s, a);
+#endif
+        HIP_TRY(hipGetLastError());
+        cur_rows = a.rows_out; cur_keys = a.keys_out;
+        shift += bits;
+    }
+    hipLaunchKernelGGL(k_group_bounds, dim3((unsigned)ceil_div(n, 1024)), dim3(256), 0, s, cur_keys, n, L, (uint32_t)n_buckets, gbegin, gend,
+                       (int *)(stats + 3));
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_group_scan, dim3(stream_grid(n_groups, 256)), dim3(256), 0, s, gbegin, gend, n_groups,
+                       (uint32_t)cap, stats, large, large_cap);
+    HIP_TRY(hipGetLastError());
+    unsigned int h_stats[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h_stats, stats, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h_stats[3]) return gki_set_error(GKI_ERR_BAD_ARG, "a record's bucket lies outside [%llu, +%llu)", (unsigned long long)bucket_begin, (unsigned long long)n_buckets);
+    // one workgroup streams a large group: fine for the repeats of a genome, not for an index that IS one bucket
+    if (h_stats[1] > large_cap || h_stats[0] > (1u << 22)) return GKI_OK;          // *done stays 0
+    FinishArgs f;
+    f.rows = cur_rows; f.keys = cur_keys; f.gbegin = gbegin; f.gend = gend; f.n_groups = n_groups; f.L = L; f.lbits = L;
+    f.n_buckets = n_buckets; f.skip_frequencies = skip_frequencies; f.h2i = (int32_t *)d_hashes_to_index;
+    f.nk = (uint32_t *)d_n_kmers; f.o_kmers = (uint64_t *)d_out_kmers; f.o_nodes = (uint32_t *)d_out_nodes;
+    f.o_refs = (uint64_t *)d_out_ref_offsets; f.o_af = (uint32_t *)d_out_af32; f.o_freq = (uint16_t *)d_out_frequencies;
+    f.o_perm = (uint32_t *)d_out_permutation; f.af_in = (const uint32_t *)d_af32;
+    f.big_buckets = big; f.n_big = stats + 2; f.big_cap = big_cap;
+    f.xcd_groups = (int)ceil_div(n_groups, 8);
+    if (grouped && wrank) hipLaunchKernelGGL((k_group_finish<true, GROUP_CAP_BIG, GROUP_THREADS_BIG>), dim3((unsigned)(f.xcd_groups * 8)), dim3(GROUP_THREADS_BIG), 0, s, f);
+    else if (grouped) hipLaunchKernelGGL((k_group_finish<false, GROUP_CAP_BIG, GROUP_THREADS_BIG>), dim3((unsigned)(f.xcd_groups * 8)), dim3(GROUP_THREADS_BIG), 0, s, f);
+    else if (wrank) hipLaunchKernelGGL((k_group_finish<true>), dim3((unsigned)(f.xcd_groups * 8)), dim3(GROUP_THREADS), 0, s, f);
+    else hipLaunchKernelGGL((k_group_finish<false>), dim3((unsigned)(f.xcd_groups * 8)), dim3(GROUP_THREADS), 0, s, f);
+    HIP_TRY(hipGetLastError());
+    if (h_stats[1] > 0) {
+        const unsigned n_large = h_stats[1];
+        hipLaunchKernelGGL(k_group_large, dim3(n_large < 1024 ? n_large : 1024), dim3(256), 0, s, f, large, n_large);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!skip_frequencies) {
+        // frequencies still open: the rows of large groups (all their buckets) and, from k_group_finish, buckets of
+        // more than SMALL_BUCKET rows.  Both go through the first form's kernels over the finished columns.
+        HIP_TRY(hipMemcpyAsync(h_stats, stats, 16, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (h_stats[1] > 0 || h_stats[2] > 0) {
+            const int n_ranges = (int)h_stats[1] + (int)h_stats[2];
+            HIP_TRY(rng_b.alloc((size_t)n_ranges * 16));
+            int64_t *rng = rng_b.get<int64_t>();
+            hipLaunchKernelGGL(k_open_ranges, dim3(stream_grid(n_ranges, 256)), dim3(256), 0, s, large, h_stats[1], gbegin, gend,
+                               big, h_stats[2], (const int32_t *)d_hashes_to_index, (const uint32_t *)d_n_kmers, rng,
+                               rng + n_ranges);
+            HIP_TRY(hipGetLastError());
+            GKI_TRY(gki_frequencies_for_rows(rng, rng + n_ranges, n_ranges, modulo, bucket_begin, d_hashes_to_index, d_n_kmers,
+                                             d_out_kmers, d_out_ref_offsets, d_out_frequencies, n, s));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    *done = 1;
+    return GKI_OK;
 }
 
 // ------------------------------------------------------------------------------------ bucket-range partition
@@ -1316,10 +1306,6 @@ static int partition_columns_by_part(const void *d_kmers, const void *d_nodes, c
         const int kbp = h_pb[p + 1] > h_pb[p] ? key_bits((uint64_t)(h_pb[p + 1] - h_pb[p]) - 1) : 0;
         h_pb[MAX_PARTS + 1 + p] = (uint32_t)(kbp > sub_bits ? kbp - sub_bits : 0);
     }
-    uint32_t *hist = nullptr, *offs[MAX_CHUNKS] = {nullptr}, *pb = nullptr;
-    int64_t *pstart = nullptr, *dbase = nullptr;
-    int *bad = nullptr;
-    void *tmp = nullptr;
     ChunkOffs co;
     co.n_chunks = n_chunks;
     KeyRule rule;
@@ -1327,68 +1313,67 @@ static int partition_columns_by_part(const void *d_kmers, const void *d_nodes, c
     rule.parts_per_bucket = (float)((double)n_parts / (double)modulo);
     rule.parts_log2 = -1; rule.by_node = 0;
     for (int l = 0; l <= 8; l++) if ((1 << l) == n_parts) rule.parts_log2 = l;
-    int rc = GKI_OK;
-#define HIP_G(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = gki_set_error(GKI_ERR_HIP, "%s:%d %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); goto done; } } while (0)
-    {
-        const int64_t max_tiles = ceil_div(n < chunk_rows ? n : chunk_rows, TILE);
-        const int64_t tmp_bytes = gki_scan_tmp_bytes((int64_t)bins * max_tiles);
-        HIP_G(gki_dev_malloc((void **)&hist, (size_t)bins * max_tiles * 4));
-        HIP_G(gki_dev_malloc(&tmp, (size_t)tmp_bytes));
-        HIP_G(gki_dev_malloc((void **)&pb, PB_WORDS * 4));
-        HIP_G(gki_dev_malloc((void **)&pstart, (size_t)(1024 + 1) * 8));
-        HIP_G(gki_dev_malloc((void **)&dbase, (size_t)n_chunks * bins * 8));
-        HIP_G(gki_dev_malloc((void **)&bad, 16));
-        HIP_G(hipMemcpyAsync(pb, h_pb, PB_WORDS * 4, hipMemcpyHostToDevice, s));
-        rule.part_begin = pb; rule.sub_shift = pb + MAX_PARTS + 1;
-        for (int c = 0; c < n_chunks; c++) {
-            const int64_t c0 = (int64_t)c * chunk_rows, nc = (n - c0) < chunk_rows ? (n - c0) : chunk_rows;
-            const int64_t n_tiles = ceil_div(nc, TILE), hist_n = (int64_t)bins * n_tiles;
-            co.n_tiles[c] = n_tiles; co.hist_n[c] = hist_n;
-            HIP_G(gki_dev_malloc((void **)&offs[c], (size_t)(hist_n + 1) * 4));
-            co.offs[c] = offs[c];
-            const int xcd_tiles = (int)ceil_div(n_tiles, 8);
-            hipLaunchKernelGGL((k_kmer_digit_hist<THREADS, RI>), dim3((unsigned)(xcd_tiles * 8)), dim3(THREADS), 0, s, (const uint64_t *)d_kmers + c0,
-                               nc, rule, 0, bits, hist, n_tiles, xcd_tiles, (const TileDesc *)nullptr, bad);
-            HIP_G(hipGetLastError());
-            rc = gki_scan_u32_to_u32(hist, hist_n, offs[c], tmp, tmp_bytes, s);
-            if (rc != GKI_OK) goto done;
-        }
-        hipLaunchKernelGGL(k_part_bases, dim3(1), dim3(1024), 0, s, co, n_digits, bins, pstart, dbase);
-        HIP_G(hipGetLastError());
-        for (int c = 0; c < n_chunks; c++) {
-            const int64_t c0 = (int64_t)c * chunk_rows, nc = (n - c0) < chunk_rows ? (n - c0) : chunk_rows;
-            PartArgs a;
-            a.tiles = nullptr;
-            a.keys_in = nullptr; a.c_kmers = (const uint64_t *)d_kmers + c0; a.c_nodes = (const uint32_t *)d_nodes + c0;
-            a.c_refs = (const uint64_t *)d_ref_offsets + c0; a.c_af = (const uint32_t *)d_af32 + c0; a.rule = rule; a.rows_in = nullptr;
-            a.n = nc; a.n_tiles = co.n_tiles[c]; a.shift = 0; a.bits = bits; a.offs = offs[c]; a.rows_out = nullptr; a.keys_out = nullptr;
-            a.o_kmers = (uint64_t *)d_out_kmers; a.o_nodes = (uint32_t *)d_out_nodes; a.o_refs = (uint64_t *)d_out_ref_offsets;
-            a.o_af = (uint32_t *)d_out_af32; a.dbase = dbase + (int64_t)c * bins; a.carry_index = 0;
-            a.xcd_tiles = (int)ceil_div(a.n_tiles, 8);
-            if (d_out_rows) {               // rows + keys out (the key: the bucket's offset in its part)
-                a.rows_out = (uint64_t *)d_out_rows; a.keys_out = (uint32_t *)d_out_keys;
-                bool launched = false;
-                if constexpr (GKI_PT_NCH > 1 && THREADS == GKI_PT_THREADS) {
-                    if (n < ((int64_t)1 << 32)) {
-                        hipLaunchKernelGGL((k_partition_rows_staged<THREADS, RI, true, GKI_PT_NCH>), dim3((unsigned)(a.xcd_tiles * 8)), dim3(THREADS), 0, s, a);
-                        launched = true;
-                    }
-                }
-                if (!launched)
-                    hipLaunchKernelGGL((k_partition_rows<THREADS, RI, true, false>), dim3((unsigned)(a.xcd_tiles * 8)), dim3(THREADS), 0, s, a);
-            } else
-                hipLaunchKernelGGL((k_partition_rows<THREADS, RI, true, true>), dim3((unsigned)(a.xcd_tiles * 8)), dim3(THREADS), 0, s, a);
-            HIP_G(hipGetLastError());
-        }
-        HIP_G(hipMemcpyAsync(h_part_start, pstart, (size_t)(n_digits + 1) * 8, hipMemcpyDeviceToHost, s));
-        HIP_G(hipStreamSynchronize(s));
+    const int64_t max_tiles = ceil_div(n < chunk_rows ? n : chunk_rows, TILE);
+    const int64_t tmp_bytes = gki_scan_tmp_bytes((int64_t)bins * max_tiles);
+    // (declared after h_pb: their frees wait for the device, so the upload that reads h_pb has finished before it goes)
+    DevBuf hist_b, tmp, pb_b, pstart_b, dbase_b, bad_b, offs_b[MAX_CHUNKS];
+    HIP_TRY(hist_b.alloc((size_t)bins * max_tiles * 4));
+    HIP_TRY(tmp.alloc((size_t)tmp_bytes));
+    HIP_TRY(pb_b.alloc(PB_WORDS * 4));
+    HIP_TRY(pstart_b.alloc((size_t)(1024 + 1) * 8));
+    HIP_TRY(dbase_b.alloc((size_t)n_chunks * bins * 8));
+    HIP_TRY(bad_b.alloc(16));
+    uint32_t *hist = hist_b.get<uint32_t>(), *pb = pb_b.get<uint32_t>();
+    int64_t *pstart = pstart_b.get<int64_t>(), *dbase = dbase_b.get<int64_t>();
+    int *bad = bad_b.get<int>();
+    HIP_TRY(hipMemcpyAsync(pb, h_pb, PB_WORDS * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(bad, 0, 4, s));
+    rule.part_begin = pb; rule.sub_shift = pb + MAX_PARTS + 1;
+    for (int c = 0; c < n_chunks; c++) {
+        const int64_t c0 = (int64_t)c * chunk_rows, nc = (n - c0) < chunk_rows ? (n - c0) : chunk_rows;
+        const int64_t n_tiles = ceil_div(nc, TILE), hist_n = (int64_t)bins * n_tiles;
+        co.n_tiles[c] = n_tiles; co.hist_n[c] = hist_n;
+        HIP_TRY(offs_b[c].alloc((size_t)(hist_n + 1) * 4));
+        co.offs[c] = offs_b[c].get<const uint32_t>();
+        const int xcd_tiles = (int)ceil_div(n_tiles, 8);
+        hipLaunchKernelGGL((k_kmer_digit_hist<THREADS, RI>), dim3((unsigned)(xcd_tiles * 8)), dim3(THREADS), 0, s, (const uint64_t *)d_kmers + c0,
+                           nc, rule, 0, bits, hist, n_tiles, xcd_tiles, (const TileDesc *)nullptr, bad);
+        HIP_TRY(hipGetLastError());
+        GKI_TRY(gki_scan_u32_to_u32(hist, hist_n, offs_b[c].get<uint32_t>(), tmp.get(), tmp_bytes, s));
     }
-done:
-    (void)gki_dev_free(hist); (void)gki_dev_free(tmp); (void)gki_dev_free(pb); (void)gki_dev_free(pstart); (void)gki_dev_free(dbase);
-    (void)gki_dev_free(bad);
-    for (int c = 0; c < n_chunks; c++) (void)gki_dev_free(offs[c]);
-#undef HIP_G
-    return rc;
+    hipLaunchKernelGGL(k_part_bases, dim3(1), dim3(1024), 0, s, co, n_digits, bins, pstart, dbase);
+    HIP_TRY(hipGetLastError());
+    for (int c = 0; c < n_chunks; c++) {
+        const int64_t c0 = (int64_t)c * chunk_rows, nc = (n - c0) < chunk_rows ? (n - c0) : chunk_rows;
+        PartArgs a;
+        a.tiles = nullptr;
+        a.keys_in = nullptr; a.c_kmers = (const uint64_t *)d_kmers + c0; a.c_nodes = (const uint32_t *)d_nodes + c0;
+        a.c_refs = (const uint64_t *)d_ref_offsets + c0; a.c_af = (const uint32_t *)d_af32 + c0; a.rule = rule; a.rows_in = nullptr;
+        a.n = nc; a.n_tiles = co.n_tiles[c]; a.shift = 0; a.bits = bits; a.offs = co.offs[c]; a.rows_out = nullptr; a.keys_out = nullptr;
+        a.o_kmers = (uint64_t *)d_out_kmers; a.o_nodes = (uint32_t *)d_out_nodes; a.o_refs = (uint64_t *)d_out_ref_offsets;
+        a.o_af = (uint32_t *)d_out_af32; a.dbase = dbase + (int64_t)c * bins; a.carry_index = 0;
+        a.xcd_tiles = (int)ceil_div(a.n_tiles, 8);
+        if (d_out_rows) {               // rows + keys out (the key: the bucket's offset in its part)
+            a.rows_out = (uint64_t *)d_out_rows; a.keys_out = (uint32_t *)d_out_keys;
+            bool launched = false;
+            if constexpr (GKI_PT_NCH > 1 && THREADS == GKI_PT_THREADS) {
+                if (n < ((int64_t)1 << 32)) {
+                    hipLaunchKernelGGL((k_partition_rows_staged<THREADS, RI, true, GKI_PT_NCH>), dim3((unsigned)(a.xcd_tiles * 8)), dim3(THREADS), 0, s, a);
+                    launched = true;
+                }
+            }
+            if (!launched)
+                hipLaunchKernelGGL((k_partition_rows<THREADS, RI, true, false>), dim3((unsigned)(a.xcd_tiles * 8)), dim3(THREADS), 0, s, a);
+        } else
+            hipLaunchKernelGGL((k_partition_rows<THREADS, RI, true, true>), dim3((unsigned)(a.xcd_tiles * 8)), dim3(THREADS), 0, s, a);
+        HIP_TRY(hipGetLastError());
+    }
+    int h_bad = 0;
+    HIP_TRY(hipMemcpyAsync(h_part_start, pstart, (size_t)(n_digits + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h_bad) return gki_set_error(GKI_ERR_BAD_ARG, "a record's bucket lies outside [0, %llu)", (unsigned long long)modulo);
+    return GKI_OK;
 }
 
 // sub_bits > 0: grouped -- part p's records leave grouped by the top sub_bits bits of (bucket - part_begin[p]); h_part_start has

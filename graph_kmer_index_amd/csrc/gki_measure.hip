@@ -82,43 +82,35 @@ extern "C" {
 int gki_measure_store_bw(void *d_hashes, void *d_nodes, void *d_ref_offsets, void *d_af32, int64_t n, double *bytes_per_s) {
     *bytes_per_s = 0.0;
     if (n < (1 << 20)) return gki_set_error(GKI_ERR_BAD_ARG, "measure_store_bw: at least 2^20 records");
-    hipEvent_t e0 = nullptr, e1 = nullptr;
     float best = 0.f;
-    int rc = GKI_OK;
-#define HIP_G(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = gki_set_error(GKI_ERR_HIP, "%s:%d %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); goto done; } } while (0)
-    HIP_G(hipEventCreate(&e0));
-    HIP_G(hipEventCreate(&e1));
+    TimerEvents ev;
+    HIP_TRY(hipEventCreate(&ev.e0));
+    HIP_TRY(hipEventCreate(&ev.e1));
     for (int rep = 0; rep < 3; rep++) {              // best of the last two launches
         float ms = 0.f;
-        HIP_G(hipEventRecord(e0, 0));
+        HIP_TRY(hipEventRecord(ev.e0, 0));
         hipLaunchKernelGGL(k_store_columns, dim3(2048), dim3(256), 0, 0, (uint64_t *)d_hashes, (uint32_t *)d_nodes,
                            (uint64_t *)d_ref_offsets, (float *)d_af32, n);
-        HIP_G(hipGetLastError());
-        HIP_G(hipEventRecord(e1, 0));
-        HIP_G(hipEventSynchronize(e1));
-        HIP_G(hipEventElapsedTime(&ms, e0, e1));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev.e1, 0));
+        HIP_TRY(hipEventSynchronize(ev.e1));
+        HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
         if (rep > 0 && (best == 0.f || ms < best)) best = ms;
     }
     if (best > 0.f) *bytes_per_s = 24.0 * (double)n / ((double)best * 1e-3);
-done:
-#undef HIP_G
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
+    return GKI_OK;
 }
 
 int gki_selftest_wave_scan(int64_t *n_bad) {
-    int *d_bad = nullptr;
+    DevBuf d_bad;
     int h_bad = -1;
-    HIP_TRY(hipMalloc(&d_bad, sizeof(int)));
-    hipError_t e = hipMemset(d_bad, 0, sizeof(int));
-    for (int rep = 0; rep < 4 && e == hipSuccess; rep++) {
-        hipLaunchKernelGGL(k_selftest_wave_scan, dim3(1024), dim3(256), 0, 0, (uint64_t)(0x1234567ull * (rep + 1) + rep * 17), d_bad);
-        e = hipGetLastError();
+    HIP_TRY(d_bad.alloc(sizeof(int)));
+    HIP_TRY(hipMemset(d_bad.get(), 0, sizeof(int)));
+    for (int rep = 0; rep < 4; rep++) {
+        hipLaunchKernelGGL(k_selftest_wave_scan, dim3(1024), dim3(256), 0, 0, (uint64_t)(0x1234567ull * (rep + 1) + rep * 17), d_bad.get<int>());
+        HIP_TRY(hipGetLastError());
     }
-    if (e == hipSuccess) e = hipMemcpy(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost);
-    (void)hipFree(d_bad);
-    if (e != hipSuccess) return gki_set_error(GKI_ERR_HIP, "selftest_wave_scan: %s", hipGetErrorString(e));
+    HIP_TRY(hipMemcpy(&h_bad, d_bad.get(), sizeof(int), hipMemcpyDeviceToHost));
     *n_bad = h_bad;
     return GKI_OK;
 }

@@ -363,31 +363,30 @@ static int read_counters(gki_probe *p, int64_t *n_hits, int64_t *n_kmers) {
 
 extern "C" {
 
+static int probe_init(gki_probe *p, const gki_index_view *ix) {
+    p->modulo = ix->modulo; p->n = ix->n; p->n_kmers = (const uint32_t *)ix->d_n_kmers;
+    p->bucket_begin = ix->n_buckets ? ix->bucket_begin : 0; p->n_buckets = ix->n_buckets ? ix->n_buckets : ix->modulo;
+    HIP_TRY(gki_dev_malloc(&p->dir, (size_t)p->n_buckets * sizeof(uint2)));
+    HIP_TRY(gki_dev_malloc(&p->rows, (size_t)(ix->n > 0 ? ix->n : 1) * sizeof(uint4)));
+    HIP_TRY(gki_dev_malloc(&p->counters, 2 * sizeof(unsigned long long)));
+    if (ix->n > 0)
+        hipLaunchKernelGGL(k_probe_rows, dim3(stream_grid(ix->n, 256)), dim3(256), 0, 0, (const uint64_t *)ix->d_kmers,
+                           (const uint32_t *)ix->d_nodes, (const uint16_t *)ix->d_frequencies, ix->n, p->rows);
+    hipLaunchKernelGGL(k_probe_dir, dim3(stream_grid((int64_t)p->n_buckets, 256)), dim3(256), 0, 0,
+                       (const int32_t *)ix->d_hashes_to_index, (const uint32_t *)ix->d_n_kmers,
+                       (const uint64_t *)ix->d_kmers, p->n_buckets, p->dir);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(0));
+    return GKI_OK;
+}
+
 int gki_probe_create(const gki_index_view *ix, gki_probe **out) {
     *out = nullptr;
     if (ix->modulo == 0 || ix->modulo > 0xFFFFFFFFull) return gki_set_error(GKI_ERR_BAD_ARG, "modulo must be in 1..2^32-1");
     if (ix->n < 0 || ix->n >= (1ll << 32)) return gki_set_error(GKI_ERR_BAD_ARG, "record count must be below 2^32");
     gki_probe *p = new gki_probe();
-    p->modulo = ix->modulo; p->n = ix->n; p->n_kmers = (const uint32_t *)ix->d_n_kmers;
-    p->bucket_begin = ix->n_buckets ? ix->bucket_begin : 0; p->n_buckets = ix->n_buckets ? ix->n_buckets : ix->modulo;
-    hipError_t e = gki_dev_malloc((void **)&p->dir, (size_t)p->n_buckets * sizeof(uint2));
-    if (e == hipSuccess) e = gki_dev_malloc((void **)&p->rows, (size_t)(ix->n > 0 ? ix->n : 1) * sizeof(uint4));
-    if (e == hipSuccess) e = gki_dev_malloc((void **)&p->counters, 2 * sizeof(unsigned long long));
-    if (e == hipSuccess) {
-        if (ix->n > 0)
-            hipLaunchKernelGGL(k_probe_rows, dim3(stream_grid(ix->n, 256)), dim3(256), 0, 0, (const uint64_t *)ix->d_kmers,
-                               (const uint32_t *)ix->d_nodes, (const uint16_t *)ix->d_frequencies, ix->n, p->rows);
-        hipLaunchKernelGGL(k_probe_dir, dim3(stream_grid((int64_t)p->n_buckets, 256)), dim3(256), 0, 0,
-                           (const int32_t *)ix->d_hashes_to_index, (const uint32_t *)ix->d_n_kmers,
-                           (const uint64_t *)ix->d_kmers, p->n_buckets, p->dir);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(0);
-    }
-    if (e != hipSuccess) {
-        (void)gki_dev_free(p->dir); (void)gki_dev_free(p->rows); (void)gki_dev_free(p->counters);
-        delete p;
-        return gki_set_error(GKI_ERR_HIP, "gki_probe_create: %s", hipGetErrorString(e));
-    }
+    const int rc = probe_init(p, ix);
+    if (rc != GKI_OK) { (void)gki_probe_destroy(p); return rc; }      // nothing of a half-built probe table stays behind
     *out = p;
     return GKI_OK;
 }
@@ -440,21 +439,16 @@ int gki_probe_contains(gki_probe *p, const void *d_queries, int64_t q, void *d_f
 int gki_probe_lookup_count(gki_probe *p, const void *d_queries, int64_t q, int64_t max_hits, void *d_hit_start, int64_t *n_hits) {
     *n_hits = 0;
     if (q <= 0) { HIP_TRY(hipMemset(d_hit_start, 0, 8)); return GKI_OK; }
-    uint32_t *cnt = nullptr;
-    void *tmp = nullptr;
     const int64_t tmp_bytes = gki_scan_tmp_bytes(q);
-    HIP_TRY(gki_dev_malloc((void **)&cnt, (size_t)q * 4));
-    hipError_t e = gki_dev_malloc(&tmp, (size_t)tmp_bytes);
-    if (e != hipSuccess) { (void)gki_dev_free(cnt); HIP_TRY(e); }
+    DevBuf cnt, tmp;
+    HIP_TRY(cnt.alloc((size_t)q * 4));
+    HIP_TRY(tmp.alloc((size_t)tmp_bytes));
     hipLaunchKernelGGL(k_probe_lookup<false>, dim3(stream_grid(q, 256)), dim3(256), 0, 0, dev_of(p), (const uint64_t *)d_queries, q,
-                       max_hits, cnt, (const int64_t *)nullptr, (int64_t *)nullptr, (int64_t *)nullptr);
-    int rc = hipGetLastError() == hipSuccess ? GKI_OK : gki_set_error(GKI_ERR_HIP, "k_probe_lookup launch failed");
-    if (rc == GKI_OK) rc = gki_scan_u32_to_i64(cnt, q, (int64_t *)d_hit_start, tmp, tmp_bytes, 0);
+                       max_hits, cnt.get<uint32_t>(), (const int64_t *)nullptr, (int64_t *)nullptr, (int64_t *)nullptr);
+    if (hipGetLastError() != hipSuccess) return gki_set_error(GKI_ERR_HIP, "k_probe_lookup launch failed");
+    GKI_TRY(gki_scan_u32_to_i64(cnt.get<const uint32_t>(), q, (int64_t *)d_hit_start, tmp.get(), tmp_bytes, 0));
     int64_t total = 0;
-    e = hipMemcpy(&total, (const int64_t *)d_hit_start + q, 8, hipMemcpyDeviceToHost);
-    (void)gki_dev_free(cnt); (void)gki_dev_free(tmp);
-    if (rc != GKI_OK) return rc;
-    HIP_TRY(e);
+    HIP_TRY(hipMemcpy(&total, (const int64_t *)d_hit_start + q, 8, hipMemcpyDeviceToHost));
     *n_hits = total;
     return GKI_OK;
 }
@@ -497,31 +491,24 @@ __global__ __launch_bounds__(256) void k_random_loads(const uint64_t *__restrict
 extern "C" int gki_measure_random_loads(int64_t table_bytes, int64_t n_loads, double *loads_per_s) {
     *loads_per_s = 0.0;
     if (table_bytes < 4096 || n_loads < 1) return gki_set_error(GKI_ERR_BAD_ARG, "measure_random_loads: bad sizes");
-    uint64_t *table = nullptr, *sink = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
     float ms = 0.f;
-    int rc = GKI_OK;
-    // every early exit passes through `done`: the 2 GB table must not outlive a failed call (bench.py measures with
-    // the whole 3 Gbp output resident)
-#define HIP_G(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = gki_set_error(GKI_ERR_HIP, "%s:%d %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); goto done; } } while (0)
-    HIP_G(gki_dev_malloc((void **)&table, (size_t)table_bytes));
-    HIP_G(gki_dev_malloc((void **)&sink, 8));
-    HIP_G(hipMemset(table, 1, (size_t)table_bytes));
-    HIP_G(hipEventCreate(&e0));
-    HIP_G(hipEventCreate(&e1));
+    // the 2 GB table is freed on every early exit too (bench.py measures with the whole 3 Gbp output resident)
+    DevBuf table, sink;
+    HIP_TRY(table.alloc((size_t)table_bytes));
+    HIP_TRY(sink.alloc(8));
+    HIP_TRY(hipMemset(table.get(), 1, (size_t)table_bytes));
+    TimerEvents ev;
+    HIP_TRY(hipEventCreate(&ev.e0));
+    HIP_TRY(hipEventCreate(&ev.e1));
     for (int rep = 0; rep < 2; rep++) {              // the second launch is the measurement
-        HIP_G(hipEventRecord(e0, 0));
-        hipLaunchKernelGGL(k_random_loads, dim3(2048), dim3(256), 0, 0, table, (uint64_t)(table_bytes / 8), n_loads, sink);
-        HIP_G(hipGetLastError());
-        HIP_G(hipEventRecord(e1, 0));
-        HIP_G(hipEventSynchronize(e1));
-        HIP_G(hipEventElapsedTime(&ms, e0, e1));
+        HIP_TRY(hipEventRecord(ev.e0, 0));
+        hipLaunchKernelGGL(k_random_loads, dim3(2048), dim3(256), 0, 0, table.get<const uint64_t>(), (uint64_t)(table_bytes / 8), n_loads,
+                           sink.get<uint64_t>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev.e1, 0));
+        HIP_TRY(hipEventSynchronize(ev.e1));
+        HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
     }
     if (ms > 0.f) *loads_per_s = (double)n_loads / ((double)ms * 1e-3);
-done:
-#undef HIP_G
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)gki_dev_free(table); (void)gki_dev_free(sink);
-    return rc;
+    return GKI_OK;
 }

@@ -215,35 +215,35 @@ int gki_compact_flat(const void *d_flags, int64_t n, const void *d_hashes, const
     if (n <= 0) return GKI_OK;
     const int64_t CH = 1ll << 27;                     // records per scan: bounds the temporaries at 1.6 GB
     const int64_t m = n < CH ? n : CH;
-    uint32_t *wide = nullptr; int64_t *pos = nullptr; void *tmp = nullptr;
     const int64_t tmp_bytes = gki_scan_tmp_bytes(m);
-    hipError_t e = gki_dev_malloc((void **)&wide, (size_t)m * 4);
-    if (e == hipSuccess) e = gki_dev_malloc((void **)&pos, (size_t)(m + 1) * 8);
-    if (e == hipSuccess) e = gki_dev_malloc(&tmp, (size_t)tmp_bytes);
-    int rc = e == hipSuccess ? GKI_OK : gki_set_error(GKI_ERR_HIP, "gki_compact_flat: %s", hipGetErrorString(e));
+    DevBuf wide_b, pos_b, tmp;
+    HIP_TRY(wide_b.alloc((size_t)m * 4));
+    HIP_TRY(pos_b.alloc((size_t)(m + 1) * 8));
+    HIP_TRY(tmp.alloc((size_t)tmp_bytes));
+    uint32_t *wide = wide_b.get<uint32_t>();
+    int64_t *pos = pos_b.get<int64_t>();
     int64_t base = 0;
-    for (int64_t a = 0; a < n && rc == GKI_OK; a += CH) {
+    for (int64_t a = 0; a < n; a += CH) {
         const int64_t c = n - a < CH ? n - a : CH;
         const uint8_t *f = (const uint8_t *)d_flags + a;
         hipLaunchKernelGGL(k_widen_flags, dim3(stream_grid(c, 256)), dim3(256), 0, 0, f, c, wide);
-        rc = gki_scan_u32_to_i64(wide, c, pos, tmp, tmp_bytes, 0);
+        GKI_TRY(gki_scan_u32_to_i64(wide, c, pos, tmp.get(), tmp_bytes, 0));
         int64_t kept = 0;
-        if (rc == GKI_OK && hipMemcpy(&kept, pos + c, 8, hipMemcpyDeviceToHost) != hipSuccess) rc = gki_set_error(GKI_ERR_HIP, "copy of the chunk total failed");
-        if (rc == GKI_OK && base + kept > out_capacity)
-            rc = gki_set_error(GKI_ERR_BAD_ARG, "gki_compact_flat: output needs more than %lld records", (long long)out_capacity);
-        if (rc == GKI_OK && kept > 0) {
+        HIP_TRY(hipMemcpy(&kept, pos + c, 8, hipMemcpyDeviceToHost));
+        if (base + kept > out_capacity)
+            return gki_set_error(GKI_ERR_BAD_ARG, "gki_compact_flat: output needs more than %lld records", (long long)out_capacity);
+        if (kept > 0) {
             hipLaunchKernelGGL(k_compact_flat, dim3(stream_grid(c, 256)), dim3(256), 0, 0, f, pos, c, base,
                                (const uint64_t *)d_hashes + a, (const uint32_t *)d_nodes + a, (const uint64_t *)d_ref_offsets + a,
                                (const float *)d_af32 + a, (uint64_t *)d_out_hashes, (uint32_t *)d_out_nodes,
                                (uint64_t *)d_out_ref_offsets, (float *)d_out_af32);
-            if (hipGetLastError() != hipSuccess) rc = gki_set_error(GKI_ERR_HIP, "k_compact_flat launch failed");
+            HIP_TRY(hipGetLastError());
         }
         base += kept;
     }
-    if (hipDeviceSynchronize() != hipSuccess && rc == GKI_OK) rc = gki_set_error(GKI_ERR_HIP, "gki_compact_flat failed");
-    (void)gki_dev_free(wide); (void)gki_dev_free(pos); (void)gki_dev_free(tmp);
-    if (rc == GKI_OK) *n_out = base;
-    return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    *n_out = base;
+    return GKI_OK;
 }
 
 int gki_column_checksum(const void *d_column, int64_t n, int elem_bytes, uint64_t *sum, uint64_t *xor_fold) {
@@ -251,21 +251,18 @@ int gki_column_checksum(const void *d_column, int64_t n, int elem_bytes, uint64_
     if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8)
         return gki_set_error(GKI_ERR_BAD_ARG, "elem_bytes must be 1, 2, 4 or 8");
     if (n <= 0) return GKI_OK;
-    unsigned long long *d = nullptr;
-    HIP_TRY(gki_dev_malloc((void **)&d, 16));
-    hipError_t e = hipMemsetAsync(d, 0, 16, 0);
-    if (e == hipSuccess) {
-        const dim3 grid(stream_grid(n, 256)), block(256);
-        if (elem_bytes == 8) hipLaunchKernelGGL(k_checksum<uint64_t>, grid, block, 0, 0, (const uint64_t *)d_column, n, d);
-        else if (elem_bytes == 4) hipLaunchKernelGGL(k_checksum<uint32_t>, grid, block, 0, 0, (const uint32_t *)d_column, n, d);
-        else if (elem_bytes == 2) hipLaunchKernelGGL(k_checksum<uint16_t>, grid, block, 0, 0, (const uint16_t *)d_column, n, d);
-        else hipLaunchKernelGGL(k_checksum<uint8_t>, grid, block, 0, 0, (const uint8_t *)d_column, n, d);
-        e = hipGetLastError();
-    }
+    DevBuf d_b;
+    HIP_TRY(d_b.alloc(16));
+    unsigned long long *d = d_b.get<unsigned long long>();
+    HIP_TRY(hipMemsetAsync(d, 0, 16, 0));
+    const dim3 grid(stream_grid(n, 256)), block(256);
+    if (elem_bytes == 8) hipLaunchKernelGGL(k_checksum<uint64_t>, grid, block, 0, 0, (const uint64_t *)d_column, n, d);
+    else if (elem_bytes == 4) hipLaunchKernelGGL(k_checksum<uint32_t>, grid, block, 0, 0, (const uint32_t *)d_column, n, d);
+    else if (elem_bytes == 2) hipLaunchKernelGGL(k_checksum<uint16_t>, grid, block, 0, 0, (const uint16_t *)d_column, n, d);
+    else hipLaunchKernelGGL(k_checksum<uint8_t>, grid, block, 0, 0, (const uint8_t *)d_column, n, d);
+    HIP_TRY(hipGetLastError());
     unsigned long long h[2] = {0, 0};
-    if (e == hipSuccess) e = hipMemcpy(h, d, 16, hipMemcpyDeviceToHost);
-    (void)gki_dev_free(d);
-    HIP_TRY(e);
+    HIP_TRY(hipMemcpy(h, d, 16, hipMemcpyDeviceToHost));
     *sum = h[0]; *xor_fold = h[1];
     return GKI_OK;
 }

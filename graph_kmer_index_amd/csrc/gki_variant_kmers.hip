@@ -198,20 +198,16 @@ int gki_uvk_starts(gki_graph *g, const void *d_lin_start, const void *d_lin_node
     if (n_starts_per_variant < 1) return gki_set_error(GKI_ERR_BAD_ARG, "gki_uvk_starts: no start position per variant");
     GKI_TRY(gki_check_graph_device(g, "gki_uvk_starts"));
     if (n_var <= 0) return GKI_OK;
-    unsigned long long *bad = nullptr;
-    HIP_TRY(gki_dev_malloc((void **)&bad, 8));
-    hipError_t e = hipMemset(bad, 0xFF, 8);
-    if (e == hipSuccess) {
-        const int64_t n = n_var * n_starts_per_variant;
-        hipLaunchKernelGGL(k_uvk_starts, dim3(stream_grid(n, 256)), dim3(256), 0, 0, (const int64_t *)d_lin_start,
-                           (const int32_t *)d_lin_node, g->d.node_size, n_lin, (const int64_t *)d_var_ref_offset, n_var,
-                           n_starts_per_variant, (int32_t *)d_nodes, (int32_t *)d_offsets, (int32_t *)d_variant, bad);
-        e = hipGetLastError();
-    }
+    DevBuf bad;
+    HIP_TRY(bad.alloc(8));
+    HIP_TRY(hipMemset(bad.get(), 0xFF, 8));
+    const int64_t n = n_var * n_starts_per_variant;
+    hipLaunchKernelGGL(k_uvk_starts, dim3(stream_grid(n, 256)), dim3(256), 0, 0, (const int64_t *)d_lin_start,
+                       (const int32_t *)d_lin_node, g->d.node_size, n_lin, (const int64_t *)d_var_ref_offset, n_var,
+                       n_starts_per_variant, (int32_t *)d_nodes, (int32_t *)d_offsets, (int32_t *)d_variant, bad.get<unsigned long long>());
+    HIP_TRY(hipGetLastError());
     unsigned long long h = ~0ull;
-    if (e == hipSuccess) e = hipMemcpy(&h, bad, 8, hipMemcpyDeviceToHost);
-    (void)gki_dev_free(bad);
-    HIP_TRY(e);
+    HIP_TRY(hipMemcpy(&h, bad.get(), 8, hipMemcpyDeviceToHost));
     if (h != ~0ull) *first_bad_variant = (int64_t)h;
     return GKI_OK;
 }
@@ -241,21 +237,16 @@ int gki_uvk_select(const void *d_summary, int64_t n_var, int n_starts_per_varian
     *n_records = 0;
     if (n_starts_per_variant < 1) return gki_set_error(GKI_ERR_BAD_ARG, "gki_uvk_select: no start position per variant");
     if (n_var <= 0) { HIP_TRY(hipMemset(d_out_start, 0, 8)); return GKI_OK; }
-    uint32_t *cnt = nullptr; void *tmp = nullptr;
     const int64_t tmp_bytes = gki_scan_tmp_bytes(n_var);
-    HIP_TRY(gki_dev_malloc((void **)&cnt, (size_t)n_var * 4));
-    const hipError_t et = gki_dev_malloc(&tmp, (size_t)tmp_bytes);
-    if (et != hipSuccess) { (void)gki_dev_free(cnt); HIP_TRY(et); }
+    DevBuf cnt, tmp;
+    HIP_TRY(cnt.alloc((size_t)n_var * 4));
+    HIP_TRY(tmp.alloc((size_t)tmp_bytes));
     hipLaunchKernelGGL(k_uvk_select, dim3(stream_grid(n_var, 256)), dim3(256), 0, 0, (const gki_uvk_summary *)d_summary,
-                       n_var, n_starts_per_variant, choose_lowest, (const uint8_t *)d_store_mask, (int32_t *)d_choice, cnt);
-    hipError_t e = hipGetLastError();
-    int rc = e == hipSuccess ? gki_scan_u32_to_i64(cnt, n_var, (int64_t *)d_out_start, tmp, tmp_bytes, 0) : GKI_OK;
+                       n_var, n_starts_per_variant, choose_lowest, (const uint8_t *)d_store_mask, (int32_t *)d_choice, cnt.get<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    GKI_TRY(gki_scan_u32_to_i64(cnt.get<const uint32_t>(), n_var, (int64_t *)d_out_start, tmp.get(), tmp_bytes, 0));
     int64_t total = 0;
-    if (e == hipSuccess && rc == GKI_OK) e = hipMemcpy(&total, (const int64_t *)d_out_start + n_var, 8, hipMemcpyDeviceToHost);
-    (void)gki_dev_free(cnt);
-    (void)gki_dev_free(tmp);
-    HIP_TRY(e);
-    if (rc != GKI_OK) return rc;
+    HIP_TRY(hipMemcpy(&total, (const int64_t *)d_out_start + n_var, 8, hipMemcpyDeviceToHost));
     *n_records = total;
     return GKI_OK;
 }

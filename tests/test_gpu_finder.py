@@ -429,10 +429,16 @@ def test_kmers_from_positions_when_node_ids_do_not_grow_along_the_path():
 def test_early_stop_search_after_the_sequence_on_the_device_was_replaced():
     # gki_graph_prepare (include/gki.h) after the caller rewrote its device sequence: the search's per-node records (first
     # bases of every node, built by the first search on the graph) belong to the old sequence and have to be built again --
-    # and so do the finder's walk records, whose tails the search reads for its start nodes
+    # and so do the finder's walk records, whose tails the search reads for its start nodes.  The script an all-nodes
+    # count call left for its emit call holds k-mers of the old sequence too: count, replace the bases, prepare, emit
+    # with the count's arguments -- the emit call must not expand it.
+    import ctypes as C
     from graph_kmer_index_amd import _lib
     from graph_kmer_index_amd.device_graph import DeviceGraph
+    lib = _lib.load()
+    dt = [np.int64, np.int32, np.int16, np.int32, np.float64]
     rng = np.random.default_rng(77)
+    emitted = 0
     for it in range(6):
         k = int(rng.integers(4, 14))
         seqs, edges, lin, af = overlapping_bubble_graph(rng, n_var=int(rng.integers(3, 10)), min_ref=1, max_ref=k)
@@ -450,12 +456,31 @@ def test_early_stop_search_after_the_sequence_on_the_device_was_replaced():
             f.find_kmers_starting_at_positions(nodes, offs)
             assert_same_records(finder_cols(f), {key: np.concatenate([e[key] for e in exp]) for key in exp[0]}, exact_order=True)
             f.close()
+            d_nodes = _lib.DeviceArray.from_host(np.asarray(nodes, dtype=np.int32))
+            d_offs = _lib.DeviceArray.from_host(np.asarray(offs, dtype=np.int32))
+            d_start = _lib.DeviceArray(len(nodes) + 1, np.int64)
+            n = C.c_int64(0)
+            args = (g._device.handle, k, 4, 0, None, d_nodes.ptr, d_offs.ptr, len(nodes))
+            _lib.check(lib.gki_forward_count(*args, d_start.ptr, C.byref(n)))
             # other bases in the same nodes, written over the caller's device buffer
             g.seq[:] = rng.integers(0, 4, size=len(g.seq)).astype(g.seq.dtype)
             _lib.check(_lib.load().gki_memcpy_h2d(d_seq.ptr, _lib.hptr(np.ascontiguousarray(g.seq, dtype=np.uint8)), len(g.seq)))
             g._device.prepare()
+            # the paths, and so the record counts, depend on the graph alone: the count's offsets still hold
+            exp = [oracle.find_from_position(g, k, int(p), int(o), False, 4) for p, o in zip(nodes, offs)]
+            exp = {key: np.concatenate([e[key] for e in exp]) for key in exp[0]}
+            assert n.value == len(exp["kmers"])
+            cols = [_lib.DeviceArray(max(n.value, 1), d) for d in dt]
+            _lib.check(lib.gki_forward_emit(*args, d_start.ptr, *[c.ptr for c in cols]))
+            got = [c.to_host()[:n.value] for c in cols]
+            assert_same_records(dict(kmers=got[0], start_nodes=got[1], start_offsets=got[2], nodes=got[3], allele_frequencies=got[4]),
+                                exp, exact_order=True)
+            emitted += n.value
+            for x in cols + [d_nodes, d_offs, d_start]:
+                x.free()
         g._device.close()
         g._device = None
+    assert emitted > 0
 
 
 def test_early_stop_emit_from_the_script_equals_the_walking_emit():

@@ -261,3 +261,74 @@ def test_partitioned_index_with_a_giant_bucket_falls_back_to_columns():
     assert np.array_equal(got.astype(np.int64), want)
     idx.free()
     d.free()
+
+
+def test_failed_calls_return_their_scratch_to_the_pool():
+    """Guard for the error paths that inputs reach after an entry point allocated its scratch: the first failing call after
+    gki_trim() takes its buffers from hipMalloc and returns them to the pool, so the same call again finds them parked --
+    no new device allocation, the same bytes parked.  A buffer leaked by the first call would cost a hipMalloc."""
+    import ctypes as C
+    lib = _lib.load()
+    n, modulo, world = 20000, 999983, 3
+    kmers, nodes, refs, af = _records(4 * n, 3 * n, seed=13)
+    lo, hi = bucket_range(modulo, world, 1)
+    buckets = kmers % np.uint64(modulo)
+    sel = np.nonzero((buckets >= lo) & (buckets < hi))[0][:n - 1]
+    sel = np.append(sel, np.nonzero(buckets >= hi)[0][0])             # one record outside [lo, hi)
+    d = DeviceFlatKmers.from_flat_kmers(FlatKmers(kmers[sel], nodes[sel], refs[sel], af[sel]))
+    nb = hi - lo
+    outs = [_lib.DeviceArray(nb, np.int32), _lib.DeviceArray(nb, np.uint32), _lib.DeviceArray(n, np.uint64),
+            _lib.DeviceArray(n, np.uint32), _lib.DeviceArray(n, np.uint64), _lib.DeviceArray(n, np.float32),
+            _lib.DeviceArray(n, np.uint16)]
+    head = (d.hashes.ptr, d.nodes.ptr, d.ref_offsets.ptr, d.allele_frequencies.ptr, n, modulo, lo, nb, 0)
+    tail = tuple(o.ptr for o in outs) + (None,)
+    reads = np.random.default_rng(14).integers(0, 4, size=200 * 150).astype(np.uint8)
+    d_reads = _lib.DeviceArray.from_host(reads)
+    d_read_start = _lib.DeviceArray.from_host(np.arange(0, len(reads) + 1, 150, dtype=np.int64))
+    d_hash_start = _lib.DeviceArray(201, np.int64)
+    d_hashes = _lib.DeviceArray(200 * 120, np.uint64)
+    calls = {
+        "gki_index_build_pairs": lambda: lib.gki_index_build_pairs(*head, *tail),
+        "gki_index_build_range": lambda: lib.gki_index_build_range(*head, *tail),
+        # 200 reads of 150 bases hash to 200 * 120 31-mers: one slot short
+        "gki_hash_reads": lambda: lib.gki_hash_reads(d_reads.ptr, d_read_start.ptr, 200, 31, 0, d_hash_start.ptr, d_hashes.ptr,
+                                                     200 * 120 - 1, C.byref(C.c_int64(0))),
+    }
+    for name, call in calls.items():
+        _lib.check(lib.gki_trim())
+        assert call() == 2, name                                       # GKI_ERR_BAD_ARG
+        before = _lib.pool_stats()
+        assert call() == 2, name
+        after = _lib.pool_stats()
+        assert after[0] == before[0], "%s: %d new device allocations" % (name, after[0] - before[0])
+        assert after[4] == before[4], "%s: parked bytes %d -> %d" % (name, before[4], after[4])
+    for x in outs + [d_reads, d_read_start, d_hash_start, d_hashes]:
+        x.free()
+    d.free()
+
+
+def test_partitioned_build_frees_the_slices_and_the_partition_on_any_error(monkeypatch):
+    """PartitionedDeviceIndex.build releases what it built when a slice build fails with an exception other than the
+    library's: the slices already built and the partition it allocated."""
+    from graph_kmer_index_amd.collision_free_kmer_index import PartitionedDeviceIndex
+    kmers, nodes, refs, af = _records(200000, 100000, seed=15)
+    d = DeviceFlatKmers.from_flat_kmers(FlatKmers(kmers, nodes, refs, af))
+    build_slice = PartitionedDeviceIndex.build_slice
+    built, parts = [], []
+
+    def failing_build_slice(part, *args, **kw):
+        parts.append(part)
+        if len(built) == 2:
+            raise AssertionError("third slice")
+        built.append(build_slice(part, *args, **kw))
+        return built[-1]
+
+    monkeypatch.setattr(PartitionedDeviceIndex, "build_slice", staticmethod(failing_build_slice))
+    with pytest.raises(AssertionError, match="third slice"):
+        PartitionedDeviceIndex.build(d, 200003, n_parts=4)
+    assert len(built) == 2 and len(parts) == 3
+    for sl in built:
+        assert all(a.ptr is None for a in (sl.hashes_to_index, sl.n_kmers, sl.kmers, sl.nodes, sl.ref_offsets,
+                                           sl.allele_frequencies, sl.frequencies))
+    assert parts[0].rows.ptr is None and parts[0].keys.ptr is None
+    d.free()
