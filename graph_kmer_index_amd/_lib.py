@@ -78,6 +78,8 @@ SYMBOLS = {
     "gki_hash_reads": (_I32, [_P, _P, _I64, _I32, _I32, _P, _P, _I64, C.POINTER(_I64)]),
     "gki_reverse_complement": (_I32, [_P, _I64, _I32, _P]),
     "gki_complement": (_I32, [_P, _I64, _I32, _P]),
+    "gki_linear_kmers": (_I32, [_P, _I64, _I32, _I64, _P, _P, _I64, _I32, _P, _P, _P, _P, _I64, C.POINTER(_I64),
+                                C.POINTER(C.c_float)]),
     "gki_graph_create": (_I32, [C.POINTER(_P), _I64, _P, _P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P]),
     "gki_graph_create_dseq": (_I32, [C.POINTER(_P), _I64, _P, _P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P]),
     "gki_graph_prepare": (_I32, [_P]),

@@ -8,6 +8,7 @@ collision_free_kmer_index.py:393-402).
     python -m graph_kmer_index_amd.command_line_interface make_unique_variant_kmers -g graph.npz -V variant_to_nodes.npz \
         -k 31 -i index.npz -p position_id -D True -v variants.vcf -o variant_kmers
     python -m graph_kmer_index_amd.command_line_interface make_reverse -f variant_kmers.npz -o reverse
+    python -m graph_kmer_index_amd.command_line_interface make -t 16 -s 1 -k 31 -r True -R ref.fa -n chr1 -G <size> -o linear_kmers
 
 `-g` takes an obgraph file when obgraph is installed, else a GraphArrays .npz (GraphArrays.to_file).  `index -t N` runs
 one process per GPU (at most N, at most the visible devices), each on its own range of critical-path numbers, and
@@ -204,6 +205,46 @@ def make_unique_variant_kmers(args):
                                                           args.out_file_name))
 
 
+def create_index(args):
+    """`make` (command_line_interface.py:105-153) from a linear reference: the reference's chunked output -- 10 * t
+    intervals, each ending on the position the next one starts with, each followed by its own reverse complements with
+    -r -- as one device call.  The reference's `-t 1` path fails on a linear reference (it adds k to None), so the
+    chunked form is used for every -t."""
+    from .snp_kmer_finder import make_linear_reference_flat_on_device, read_fasta_record
+    if args.graph_file_name is not None:
+        raise NotImplementedError("make -g: SnpKmerFinder over a graph is not ported (use `index`); "
+                                  "make builds from a linear reference, -R and -n")
+    assert args.reference_fasta is not None
+    assert args.reference_name is not None, "Reference name must be specified"
+    letters = read_fasta_record(args.reference_fasta, args.reference_name)
+    assert len(letters) > 0, "Length of ref sequennce is 0. Seomthing is wrong"
+    dflat = make_linear_reference_flat_on_device(letters, args.kmer_size, args.spacing, args.genome_size, args.threads,
+                                                 _bool(args.include_reverse_complement))
+    flat = dflat.to_flat_kmers()
+    dflat.free()
+    logging.info("N kmers in flat kmers: %d" % len(flat._hashes))
+    flat.to_file(args.out_file_name)
+
+
+def make_reference_kmer_index(args):
+    """command_line_interface.py:184-193."""
+    from .reference_kmer_index import ReferenceKmerIndex
+    if args.reference_fasta is not None:
+        index = ReferenceKmerIndex.from_linear_reference(args.reference_fasta, args.reference_name, args.kmer_size,
+                                                         _bool(args.only_store_kmers))
+    else:
+        index = ReferenceKmerIndex.from_flat_kmers(FlatKmers.from_file(args.flat_index))
+    index.to_file(args.out_file_name)
+    logging.info("Saved reference kmer index to file %s" % args.out_file_name)
+
+
+def merge_flat_kmers(args):
+    """command_line_interface.py:489-492."""
+    new = FlatKmers.from_multiple_flat_kmers([FlatKmers.from_file(f) for f in args.flat_kmers.split(",")])
+    new.to_file(args.out_file_name)
+    logging.info("Wrote merged index to %s" % args.out_file_name)
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description="graph_kmer_index on MI355X (in-scope sub-commands)")
     sub = parser.add_subparsers()
@@ -222,6 +263,38 @@ def build_parser():
                    "than devices share them round-robin)")
     p.add_argument("--shard", default=None, help=argparse.SUPPRESS)       # R/W: this process is rank R of `index -t`
     p.set_defaults(func=index)
+    p = sub.add_parser("make")
+    p.add_argument("-g", "--graph_file_name", required=False)
+    p.add_argument("-o", "--out_file_name", required=True)
+    p.add_argument("-k", "--kmer_size", required=False, type=int, default=31)
+    p.add_argument("-r", "--include-reverse-complement", required=False, type=_bool, default=False)
+    p.add_argument("-s", "--spacing", required=False, type=int, default=31)
+    p.add_argument("-p", "--pruning", required=False, type=_bool, default=False)
+    p.add_argument("-m", "--max-kmers-same-position", required=False, type=int, default=100000)
+    p.add_argument("-M", "--max-frequency", required=False, type=int, default=10000000)
+    p.add_argument("-v", "--max-variant-nodes", required=False, type=int, default=100000)
+    p.add_argument("-V", "--only-add-variant-kmers", required=False, type=_bool, default=False)
+    p.add_argument("-N", "--only-save-variant-nodes", required=False, type=_bool, default=False)
+    p.add_argument("-O", "--only-save-one-node-per-kmer", required=False, type=_bool, default=False)
+    p.add_argument("-S", "--skip-kmers-with-nodes", required=False)
+    p.add_argument("-w", "--whitelist", required=False)
+    p.add_argument("-t", "--threads", required=False, default=1, type=int)
+    p.add_argument("-G", "--genome-size", required=False, default=3000000000, type=int)
+    p.add_argument("-R", "--reference-fasta", required=False)
+    p.add_argument("-n", "--reference-name", required=False)
+    p.set_defaults(func=create_index)
+    p = sub.add_parser("make_reference_kmer_index")
+    p.add_argument("-f", "--flat-index", required=False)
+    p.add_argument("-r", "--reference-fasta", required=False)
+    p.add_argument("-n", "--reference-name", required=False)
+    p.add_argument("-k", "--kmer-size", required=False, type=int, default=16)
+    p.add_argument("-o", "--out-file-name", required=True)
+    p.add_argument("-O", "--only-store-kmers", required=False, default=False, type=_bool)
+    p.set_defaults(func=make_reference_kmer_index)
+    p = sub.add_parser("merge_flat_kmers")
+    p.add_argument("-f", "--flat-kmers", required=True)
+    p.add_argument("-o", "--out-file-name", required=True)
+    p.set_defaults(func=merge_flat_kmers)
     p = sub.add_parser("make_from_flat")
     p.add_argument("-o", "--out_file_name", required=True)
     p.add_argument("-f", "--flat-index", required=True)

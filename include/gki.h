@@ -100,6 +100,23 @@ int gki_hash_reads(const void *d_reads, const void *d_read_start, int64_t n_read
 int gki_reverse_complement(const void *d_in, int64_t n, int k, void *d_out);
 int gki_complement(const void *d_in, int64_t n, int k, void *d_out);
 
+/* K-mers of a linear reference as FlatKmers columns: replaces SnpKmerFinder.find_kmers_on_linear_reference
+ * (snp_kmer_finder.py:298-312) for every chunk of `make -R` (command_line_interface.py:105-153) in one call.
+ * d_letters uint8[n_letters]: ASCII, either case; c/g/t are 1/2/3 and every other byte is 0 (flat_kmers.py:134-145).
+ * The output is described by n_segments segments (host arrays h_seg_first, h_seg_count, int64): record j of a segment is
+ * the k-mer at position h_seg_first[s] + j * spacing.  Segments follow each other in the output in table order and may
+ * overlap or repeat.  with_reverse_complement: the h_seg_count[s] records of a segment are followed by as many records
+ * whose hash is the reverse complement of theirs (kmer_hashing.py:24-28), the other columns repeated.
+ * Columns (device, out_capacity records each): hashes uint64, nodes uint32 (all 1), ref_offsets uint64 (the position),
+ * allele_frequencies float32 (all 1.0).  d_hashes NULL: count only (*n_out is set, nothing is written); d_nodes NULL:
+ * hashes only.  kernel_ms NULL or float[2]: HIP-event times of the 2-bit pack and of the emit kernel.
+ * GKI_ERR_BAD_ARG: k outside 1..31, spacing < 1, a segment whose last k-mer ends past the sequence (nothing is clipped
+ * here), or *n_out > out_capacity. */
+int gki_linear_kmers(const void *d_letters, int64_t n_letters, int k, int64_t spacing, const int64_t *h_seg_first,
+                     const int64_t *h_seg_count, int64_t n_segments, int with_reverse_complement, void *d_hashes,
+                     void *d_nodes, void *d_ref_offsets, void *d_af32, int64_t out_capacity, int64_t *n_out,
+                     float *kernel_ms);
+
 /* ---------------------------------------------------------------- graph (the obgraph arrays in HBM)
  * Replaces the per-node obgraph accessor calls of kmer_finder.py:50,62,259,279,350,384,138,143,374.
  * Host arrays in (copied to HBM, 2-bit packed on device):
