@@ -7,6 +7,9 @@ collision_free_kmer_index.py:393-402).
     python -m graph_kmer_index_amd.command_line_interface make_from_flat -f flat -o index
     python -m graph_kmer_index_amd.command_line_interface make_unique_variant_kmers -g graph.npz -V variant_to_nodes.npz \
         -k 31 -i index.npz -p position_id -D True -v variants.vcf -o variant_kmers
+    python -m graph_kmer_index_amd.command_line_interface sample_kmers_from_structural_variants -g graph.npz \
+        -V variant_to_nodes.npz -k 31 -i index.npz -o sv_kmers
+    python -m graph_kmer_index_amd.command_line_interface merge_flat_kmers -f variant_kmers.npz,sv_kmers.npz -o all_variant_kmers
     python -m graph_kmer_index_amd.command_line_interface make_reverse -f variant_kmers.npz -o reverse
     python -m graph_kmer_index_amd.command_line_interface make -t 16 -s 1 -k 31 -r True -R ref.fa -n chr1 -G <size> -o linear_kmers
 
@@ -205,6 +208,22 @@ def make_unique_variant_kmers(args):
                                                           args.out_file_name))
 
 
+def sample_kmers_from_structural_variants_command(args):
+    """command_line_interface.py:461-481: extra k-mers of big variant nodes, to be merged with the variant k-mers
+    (merge_flat_kmers).  `-t` is accepted; all nodes run as one device batch."""
+    from .structural_variants import sample_kmers_from_structural_variants
+    from .unique_variant_kmers import load_variant_to_nodes
+    if args.kmer_counter is not None:
+        raise NotImplementedError("sample_kmers_from_structural_variants: -I is not supported (a "
+                                  "CollisionFreeKmerIndex from -i only)")
+    if args.kmer_index is None:
+        raise ValueError("sample_kmers_from_structural_variants: -i (a CollisionFreeKmerIndex with frequencies) is required")
+    flat = sample_kmers_from_structural_variants(load_graph(args.graph), load_variant_to_nodes(args.variant_to_nodes),
+                                                 CollisionFreeKmerIndex.from_file(args.kmer_index), args.kmer_size)
+    flat.to_file(args.out_file_name)
+    logging.info("Wrote %d k-mers of structural variant nodes to %s" % (len(flat._hashes), args.out_file_name))
+
+
 def create_index(args):
     """`make` (command_line_interface.py:105-153) from a linear reference: the reference's chunked output -- 10 * t
     intervals, each ending on the position the next one starts with, each followed by its own reverse complements with
@@ -337,6 +356,15 @@ def build_parser():
     p.add_argument("-d", "--do-not-choose-lowest-frequency-kmers", required=False, type=_bool, default=False)
     p.add_argument("-S", "--simple", type=_bool, default=False)
     p.set_defaults(func=make_unique_variant_kmers)
+    p = sub.add_parser("sample_kmers_from_structural_variants")
+    p.add_argument("-g", "--graph", required=True)
+    p.add_argument("-V", "--variant_to_nodes", required=True)
+    p.add_argument("-k", "--kmer-size", required=True, type=int)
+    p.add_argument("-i", "--kmer-index", required=False)
+    p.add_argument("-I", "--kmer-counter", required=False)
+    p.add_argument("-o", "--out-file-name", required=True)
+    p.add_argument("-t", "--n-threads", required=False, default=1, type=int)
+    p.set_defaults(func=sample_kmers_from_structural_variants_command)
     return parser
 
 

@@ -92,6 +92,36 @@ __device__ __forceinline__ uint64_t gki_mod(const GkiMod &d, uint64_t x) {
     return r;
 }
 
+// ---------------------------------------------------------------------------------- get_frequency on the device
+// CollisionFreeKmerIndex.get_frequency with its defaults (collision_free_kmer_index.py:336-352): the first hit's frequency
+// of a k-mer plus that of its reverse complement, which the reference takes at k = 31 whatever the caller's k is.
+// Shared by gki_variant_kmers.hip and gki_sv_kmers.hip.
+// rc(x) at k = 31: digit-reverse(~x) (gki_hash.hip, kmer_hashing.py:24-28)
+__device__ __forceinline__ uint64_t gki_revcomp31(uint64_t x) {
+    uint64_t y = __brevll(~(x & ((1ull << 62) - 1ull)));
+    y = ((y & 0xAAAAAAAAAAAAAAAAull) >> 1) | ((y & 0x5555555555555555ull) << 1);
+    return y >> 2;
+}
+
+// frequency of the first record of `q` in its bucket, 0 for a miss (collision_free_kmer_index.py:336-344)
+__device__ __forceinline__ uint32_t gki_first_hit_frequency(const int32_t *__restrict__ hashes_to_index,
+                                                            const uint32_t *__restrict__ n_kmers,
+                                                            const uint64_t *__restrict__ kmers,
+                                                            const uint16_t *__restrict__ frequencies, int64_t n,
+                                                            GkiMod mod, uint64_t bucket_begin, uint64_t n_buckets,
+                                                            uint64_t q) {
+    const uint64_t b = gki_mod(mod, q);
+    if (b < bucket_begin || b - bucket_begin >= n_buckets) return 0;
+    const int64_t first = hashes_to_index[b - bucket_begin];
+    const int64_t cnt = n_kmers[b - bucket_begin];
+    for (int64_t j = 0; j < cnt; ++j) {
+        const int64_t p = first + j;
+        if (p < 0 || p >= n) break;
+        if (kmers[p] == q) return frequencies[p];
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------- device graph view
 struct alignas(32) NodeWalk { // everything the boundary walk needs about a node, one aligned 32-B record
     int64_t seq_start;

@@ -16,32 +16,6 @@ namespace {
 
 constexpr int UVK_WINDOW_CAP = 500;          // kmer_finder.py:137-160: kmers_found keeps the first 500 windows
 
-// rc(x) at k = 31: digit-reverse(~x) (gki_hash.hip, kmer_hashing.py:24-28)
-__device__ __forceinline__ uint64_t uvk_revcomp31(uint64_t x) {
-    uint64_t y = __brevll(~(x & ((1ull << 62) - 1ull)));
-    y = ((y & 0xAAAAAAAAAAAAAAAAull) >> 1) | ((y & 0x5555555555555555ull) << 1);
-    return y >> 2;
-}
-
-// frequency of the first record of `q` in its bucket, 0 for a miss (collision_free_kmer_index.py:336-344)
-__device__ __forceinline__ uint32_t uvk_first_hit_frequency(const int32_t *__restrict__ hashes_to_index,
-                                                            const uint32_t *__restrict__ n_kmers,
-                                                            const uint64_t *__restrict__ kmers,
-                                                            const uint16_t *__restrict__ frequencies, int64_t n,
-                                                            GkiMod mod, uint64_t bucket_begin, uint64_t n_buckets,
-                                                            uint64_t q) {
-    const uint64_t b = gki_mod(mod, q);
-    if (b < bucket_begin || b - bucket_begin >= n_buckets) return 0;
-    const int64_t first = hashes_to_index[b - bucket_begin];
-    const int64_t cnt = n_kmers[b - bucket_begin];
-    for (int64_t j = 0; j < cnt; ++j) {
-        const int64_t p = first + j;
-        if (p < 0 || p >= n) break;
-        if (kmers[p] == q) return frequencies[p];
-    }
-    return 0;
-}
-
 __global__ __launch_bounds__(256) void k_uvk_starts(const int64_t *__restrict__ lin_start, const int32_t *__restrict__ lin_node,
                                                     const int32_t *__restrict__ node_size, int64_t n_lin,
                                                     const int64_t *__restrict__ var_ref_offset, int64_t n_var, int P,
@@ -114,10 +88,10 @@ __global__ __launch_bounds__(256) void k_uvk_summarize(
             const bool is_ref = nd == ref, is_alt = !same && nd == alt;
             if (!is_ref && !is_alt) continue;
             const uint64_t h = (uint64_t)hashes[r];
-            const uint32_t f = uvk_first_hit_frequency(hashes_to_index, n_kmers, kmers, frequencies, n_index, mod,
+            const uint32_t f = gki_first_hit_frequency(hashes_to_index, n_kmers, kmers, frequencies, n_index, mod,
                                                        bucket_begin, n_buckets, h) +
-                               uvk_first_hit_frequency(hashes_to_index, n_kmers, kmers, frequencies, n_index, mod,
-                                                       bucket_begin, n_buckets, uvk_revcomp31(h));
+                               gki_first_hit_frequency(hashes_to_index, n_kmers, kmers, frequencies, n_index, mod,
+                                                       bucket_begin, n_buckets, gki_revcomp31(h));
             if (is_ref) { ++n_ref; f_ref = f > f_ref ? f : f_ref; }
             else { ++n_alt; f_alt = f > f_alt ? f : f_alt; }
             if (r < lim && !(flags & 1u)) {

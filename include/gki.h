@@ -465,6 +465,29 @@ int gki_uvk_emit(gki_graph *g, const void *d_rec_start, int64_t n_var, int n_sta
                  const void *d_hashes, const void *d_start_nodes, const void *d_start_offsets, const void *d_nodes,
                  const void *d_af64, void *d_out_hashes, void *d_out_nodes, void *d_out_ref_offsets, void *d_out_af32);
 
+/* ---------------------------------------------------------------- sample_kmers_from_structural_variants
+ * structural_variants.py:6-43: extra signature k-mers of big variant nodes.  d_cand_nodes int32[n_cand] are the nodes in
+ * visiting order (every (ref, var) pair flattened, ref first; duplicates stay and give their records again).  A candidate
+ * is looked at when its size exceeds k + 5; its windows j = 0 .. size - k are hashed from the packed sequence, window j is
+ * valid when CollisionFreeKmerIndex.get_frequency (first hit of h plus first hit of its 31-mer reverse complement, as in
+ * gki_uvk_summarize) is below max_frequency, and valid windows are chosen in ascending order iff they lie k or more after
+ * the previous chosen one.
+ * gki_sv_sample_count: probes every window once into a bitmap the plan keeps, counts the chosen windows per candidate;
+ *   d_rec_start (nullable) int64[n_cand + 1] = their exclusive scan, *n_records the total, *plan what the emit call
+ *   needs (release it with gki_sv_sample_destroy; the graph must outlive it).  kernel_ms (nullable) float[2]: probe pass,
+ *   greedy count pass with its scan.  GKI_ERR_BAD_ARG: k outside 1..31, max_frequency < 0, no index, a candidate that is
+ *   not a node of the graph (nothing is read through it).
+ * gki_sv_sample_emit: the records of candidate i at [rec_start[i], rec_start[i+1]) in window order: hashes uint64, nodes
+ *   uint32, and when given ref_offsets uint64 (all 0) and allele frequencies float32 (all 1), each sized n_records.
+ *   kernel_ms (nullable) float[1]: greedy emit pass and record pass. */
+typedef struct gki_sv_plan gki_sv_plan;
+int gki_sv_sample_count(gki_graph *g, const gki_index_view *ix, const void *d_cand_nodes, int64_t n_cand, int k,
+                        int64_t max_frequency, void *d_rec_start, int64_t *n_records, gki_sv_plan **plan,
+                        float *kernel_ms);
+int gki_sv_sample_emit(gki_sv_plan *plan, void *d_hashes, void *d_nodes, void *d_ref_offsets, void *d_af32,
+                       float *kernel_ms);
+int gki_sv_sample_destroy(gki_sv_plan *plan);
+
 /* ---------------------------------------------------------------- probe table (read-side hot loop)
  * A device-only re-layout of an index for counting: dir uint2[modulo] = {first record, count (16 bit, saturating)
  * | 16-bit fingerprint set << 16}, rows uint4[n] = {kmer, node, frequency}: one random 64-byte sector per query,
