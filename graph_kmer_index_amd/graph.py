@@ -420,7 +420,6 @@ def random_codes(n, seed, chunk=1 << 26):
 
 def synthetic_linear_graph(n_bases, node_len=25000, seed=1234):
     """BASELINE config 2: single-edge chain of linear-ref nodes."""
-    assert node_len <= 32767
     n_nodes = (n_bases + node_len - 1) // node_len
     node_size = np.full(n_nodes, node_len, dtype=np.int32)
     node_size[-1] = n_bases - node_len * (n_nodes - 1)

@@ -165,10 +165,12 @@ class DenseKmerFinder:
             pid = self._position_id
             if pid is None:
                 self._device = DeviceGraph.of(self._arrays)
+                self._position_base = self._arrays.position_id_base()
             else:
                 g = self._arrays
                 base = np.asarray(pid.get(np.arange(g.n_nodes), np.zeros(g.n_nodes, dtype=np.int64))).astype(np.int64)
                 self._device = DeviceGraph(g, position_base=base)
+                self._position_base = base
         return self._device
 
     def _finder_handle(self):
@@ -327,12 +329,24 @@ class DenseKmerFinder:
             for b in bufs:
                 b.free()
         kmers, start_nodes, start_offsets, nodes, af = cols
+        # The int16 column holds the end offset modulo 2^16 (the reference's dtype).  The positions
+        # get_flat_kmers(v="0"/"1") hands out need the true offset: the same run's 64-bit position column (by-node layout,
+        # the v2 order) minus the end node's base.
+        offsets = start_offsets.astype(np.int64)
+        if n and int(self._arrays.node_size.max()) > 32768:
+            pos = _lib.DeviceArray(n, np.uint64)
+            _lib.check(lib.gki_finder_emit_flat(self._finder_handle(), None, None, pos.ptr, None))
+            _lib.check(lib.gki_finder_synchronize(self._finder_handle()))
+            offsets = pos.to_host().view(np.int64) - self._position_base[start_nodes]
+            pos.free()
         keep = None
         if self._whitelist is not None:                                # kmer_finder.py:130-132, 362-365
             keep = self._in_whitelist(kmers)
         if keep is not None:
-            kmers, start_nodes, start_offsets, nodes, af = (c[keep] for c in (kmers, start_nodes, start_offsets, nodes, af))
-        self._cols = dict(kmers=kmers, start_nodes=start_nodes, start_offsets=start_offsets, nodes=nodes, af=af)
+            kmers, start_nodes, start_offsets, nodes, af, offsets = (
+                c[keep] for c in (kmers, start_nodes, start_offsets, nodes, af, offsets))
+        self._cols = dict(kmers=kmers, start_nodes=start_nodes, start_offsets=start_offsets, nodes=nodes, af=af,
+                          offsets=offsets)
 
     def find_flat_on_device(self, out=None, split_layout=True):
         """find() + get_flat_kmers(v="1") + FlatKmers.from_multiple_flat_kmers dtypes, columns left in
@@ -406,6 +420,7 @@ class DenseKmerFinder:
 
     def find_kmers_starting_at_positions(self, nodes, offsets):
         """Batched form of the above (one kernel launch for many start positions)."""
+        offsets_in = offsets
         lib = _lib.load()
         g = self._arrays
         graph = self._device_graph()
@@ -431,9 +446,17 @@ class DenseKmerFinder:
                 b.free()
         else:
             cols = [np.zeros(0, dtype=d) for d in dt]
+        per_start = np.diff(d_start.to_host())
         for b in (d_nodes, d_offs, d_start) + (() if d_follow is None else (d_follow,)):
             b.free()
         kmers, start_nodes, start_offsets, out_nodes, af = cols
+        # True end offsets beside the int16 column.  The search stops at the first k-mer of every
+        # path, k bases from its start: a window that ends in the node it started in ends at start offset + k - 1, every
+        # other one ends fewer than k bases into a later node, where the narrow column is exact.
+        search = np.repeat(np.arange(n_pos), per_start)
+        offsets = start_offsets.astype(np.int64)
+        same = start_nodes == np.asarray(nodes, dtype=np.int64)[search]
+        offsets[same] = np.asarray(offsets_in, dtype=np.int64)[search][same] + self._k - 1
         keep = None
         if self._whitelist is not None:
             keep = self._in_whitelist(kmers)
@@ -441,8 +464,9 @@ class DenseKmerFinder:
             sel = np.isin(out_nodes, np.fromiter((int(x) for x in self._only_store_nodes), dtype=np.int64))
             keep = sel if keep is None else keep & sel
         if keep is not None:
-            kmers, start_nodes, start_offsets, out_nodes, af = (c[keep] for c in (kmers, start_nodes, start_offsets, out_nodes, af))
-        new = dict(kmers=kmers, start_nodes=start_nodes, start_offsets=start_offsets, nodes=out_nodes, af=af)
+            kmers, start_nodes, start_offsets, out_nodes, af, offsets = (
+                c[keep] for c in (kmers, start_nodes, start_offsets, out_nodes, af, offsets))
+        new = dict(kmers=kmers, start_nodes=start_nodes, start_offsets=start_offsets, nodes=out_nodes, af=af, offsets=offsets)
         if self._cols is None:
             self._cols = new
         else:
@@ -458,15 +482,18 @@ class DenseKmerFinder:
         return c["kmers"], c["nodes"]
 
     def get_flat_kmers(self, v="2"):
+        """v="2": the reference's columns, `start_offsets` int16 (the end offset modulo 2^16).  v="0" / "1": 64-bit
+        positions from the TRUE end offset -- on nodes longer than 32 767 bases the reference adds the wrapped int16
+        column here (or raises, depending on the NumPy version); this port does not."""
         c = self._require_found()
         if v == "0" or v == "1":
             if v == "1":
                 if self._position_id is not None:
-                    ref_offsets = self._position_id.get(c["start_nodes"], c["start_offsets"])       # :117
+                    ref_offsets = self._position_id.get(c["start_nodes"], c["offsets"])             # :117
                 else:
-                    ref_offsets = self._arrays.position_id_base()[c["start_nodes"]] + c["start_offsets"]
+                    ref_offsets = self._arrays.position_id_base()[c["start_nodes"]] + c["offsets"]
             else:
-                ref_offsets = np.asarray(self._graph.node_to_ref_offset)[c["start_nodes"]] + c["start_offsets"]  # :119
+                ref_offsets = np.asarray(self._graph.node_to_ref_offset)[c["start_nodes"]] + c["offsets"]        # :119
             return FlatKmers(c["kmers"], c["nodes"], ref_offsets, c["af"])
         return FlatKmers2(c["kmers"], c["start_nodes"], c["start_offsets"], c["nodes"], c["af"])
 

@@ -43,7 +43,7 @@ class _Graph(C.Structure):
 class _Records(C.Structure):
     _fields_ = [("n", C.c_int64), ("cap", C.c_int64), ("kmers", C.c_void_p), ("nodes", C.c_void_p),
                 ("start_nodes", C.c_void_p), ("start_offsets", C.c_void_p), ("af", C.c_void_p),
-                ("window_id", C.c_void_p)]
+                ("window_id", C.c_void_p), ("start_offsets_wide", C.c_void_p)]      # orc_records_wide
 
 
 _lib = None
@@ -55,6 +55,11 @@ def lib():
         if not os.path.exists(_LIB_PATH):
             build()
         _lib = C.CDLL(_LIB_PATH)
+        if not hasattr(_lib, "orc_find_wide"):       # a library built from an older gki_oracle.c: build this one
+            import _ctypes
+            _ctypes.dlclose(_lib._handle)
+            build(force=True)
+            _lib = C.CDLL(_LIB_PATH)
         _lib.orc_kmer_to_hash.restype = C.c_uint64
         _lib.orc_update_hash.restype = C.c_uint64
         _lib.orc_update_hash.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int]
@@ -153,10 +158,12 @@ def _take(rec, with_window_id=False):
 
     out = dict(kmers=arr(rec.kmers, np.int64), nodes=arr(rec.nodes, np.int32),
                start_nodes=arr(rec.start_nodes, np.int32), start_offsets=arr(rec.start_offsets, np.int16),
-               allele_frequencies=arr(rec.af, np.float64))
+               allele_frequencies=arr(rec.af, np.float64),
+               # the end offset at full width: `start_offsets` is this column narrowed to the reference's int16
+               start_offsets_wide=arr(rec.start_offsets_wide, np.int32))
     if with_window_id:
         out["window_id"] = arr(rec.window_id, np.int64)
-    lib().orc_free_records(C.byref(rec))
+    lib().orc_free_records_wide(C.byref(rec))
     return out
 
 
@@ -180,7 +187,7 @@ def find(g, k, critical=None, only_save_one_node_per_kmer=False, max_variant_nod
     osn, ofn = _node_mask(g, only_store_nodes), _node_mask(g, only_follow_nodes)
     gs = _graph_struct(g)
     rec, flags = _Records(), C.c_int32(0)
-    err = lib().orc_find(C.byref(gs), C.c_int(k), _p(cn), _p(co), C.c_int64(len(cn)),
+    err = lib().orc_find_wide(C.byref(gs), C.c_int(k), _p(cn), _p(co), C.c_int64(len(cn)),
                          C.c_int(bool(only_save_one_node_per_kmer)), C.c_int(max_variant_nodes),
                          C.c_int64(-1 if start_at_critical_path_number is None else start_at_critical_path_number),
                          C.c_int64(-1 if stop_at_critical_path_number is None else stop_at_critical_path_number),
@@ -199,7 +206,7 @@ def find_from_position(g, k, node, offset, only_save_one_node_per_kmer=False, ma
     osn, ofn = _node_mask(g, only_store_nodes), _node_mask(g, only_follow_nodes)
     gs = _graph_struct(g)
     rec, flags = _Records(), C.c_int32(0)
-    err = lib().orc_find_from_position(C.byref(gs), C.c_int(k), C.c_int32(node), C.c_int64(offset),
+    err = lib().orc_find_from_position_wide(C.byref(gs), C.c_int(k), C.c_int32(node), C.c_int64(offset),
                                        C.c_int(bool(only_save_one_node_per_kmer)), C.c_int(max_variant_nodes),
                                        _p(wl), C.c_int64(-1 if wl is None else len(wl)), _p(osn), _p(ofn),
                                        C.byref(rec), C.byref(flags))
@@ -286,8 +293,16 @@ def map_reads(index, letters, read_start, k, n_nodes, strands=3, max_hits=10):
     return counts, nk.value, nh.value
 
 
-def find_from_positions(g, k, nodes, offsets, only_save_one_node_per_kmer=False, max_variant_nodes=4):
-    """Number of records of a loop of find_only_kmers_starting_at_position over the start positions."""
+def find_from_positions(g, k, nodes, offsets, only_save_one_node_per_kmer=False, max_variant_nodes=4, only_follow_nodes=None,
+                        with_records=False):
+    """Number of records of a loop of find_only_kmers_starting_at_position over the start positions; with_records: the
+    records themselves instead (find_from_position's columns, `start_offsets_wide` among them, start after start)."""
+    if with_records:
+        parts = [find_from_position(g, k, int(n), int(o), only_save_one_node_per_kmer, max_variant_nodes,
+                                    only_follow_nodes=only_follow_nodes) for n, o in zip(nodes, offsets)]
+        if not parts:
+            parts = [_take(_Records())]
+        return {key: np.concatenate([p[key] for p in parts]) for key in parts[0]}
     nodes = np.ascontiguousarray(nodes, dtype=np.int32)
     offsets = np.ascontiguousarray(offsets, dtype=np.int32)
     gs = _graph_struct(g)

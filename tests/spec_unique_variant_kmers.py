@@ -57,7 +57,7 @@ def unique_variant_kmers(g, ref_nodes, var_nodes, positions, line_numbers, k, ma
                 continue
             keep = np.isin(nd, np.array(sorted(store), dtype=np.int64))
             flat = (h[keep].astype(np.uint64), nd[keep].astype(np.uint32),
-                    (pb[rec["start_nodes"][keep]] + rec["start_offsets"][keep]).astype(np.uint64),
+                    (pb[rec["start_nodes"][keep]] + rec["start_offsets_wide"][keep]).astype(np.uint64),
                     rec["allele_frequencies"][keep].astype(np.float32))
             score = max([0] + [frequency(int(x)) for x in flat[0]])
             valid.append((score, flat))

@@ -114,9 +114,12 @@ def _random_case(seed, generator, sizes, k, max_frequencies, **kw):
     total = 0
     for mf in max_frequencies:
         h, n, r = spec.sample_kmers(g, pairs, table, k, mf)
-        _same(sample_kmers_from_structural_variants(g, pairs, index, k, mf), (h, n, r, np.ones(len(h), np.float32)))
+        got = sample_kmers_from_structural_variants(g, pairs, index, k, mf)
+        _same(got, (h, n, r, np.ones(len(h), np.float32)))
+        assert got._ref_offsets.dtype == np.uint32 and not got._ref_offsets.any()       # the reference stores no position here
         total += len(h)
     assert total > 0
+    return g, got
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
@@ -131,7 +134,13 @@ def test_random_nested_graph_matches_spec(seed):
 
 
 def test_random_graph_with_a_200000_base_node_matches_spec():
-    _random_case(6, graphgen.random_bubble_graph, [200000, 60000, 40, 9000], 31, (1, 2), n_var=30, p_indel=0.6)
+    g, got = _random_case(6, graphgen.random_bubble_graph, [200000, 60000, 40, 9000], 31, (1, 2), n_var=30, p_indel=0.6)
+    # a sampled window that lies beyond offset 65 536 of the 200 000-base node: its hash read from the sequence there
+    node = int(np.argmax(g.node_size))
+    assert g.node_size[node] == 200000
+    s = g.seq[g.seq_start[node] + 65536:g.seq_start[node + 1]].astype(np.uint64)
+    far = sum(s[i:len(s) - 30 + i] << np.uint64(2 * i) for i in range(31))
+    assert np.count_nonzero(np.isin(got._hashes[got._nodes == node], far)) > 0
     _random_case(7, graphgen.random_bubble_graph, [150000, 50], 23, (2,), n_var=20, p_indel=0.6)
 
 
