@@ -5,6 +5,8 @@
 #include <cstddef>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
+#include <utility>
 #include "../../include/gki.h"
 
 #define GKI_WAVE 64
@@ -189,39 +191,70 @@ __device__ __forceinline__ uint64_t node_tail(const NodeWalk &w, int t) {
 // arena behind the slow path of a graph walk (see "stacks of the graph walks" below): cap levels for each of `lanes` lanes
 struct DeepArena { char *base; int64_t lanes; int32_t cap; int32_t pad; };
 
+// Host-side owner of such an arena (the finder has one, the early-stop search one per graph).  cap > 0: the run in progress
+// needs the deep kernel variants.  release() returns the buffer to the pool and keeps cap, so that grow(cap, ..) brings
+// the same arena back; 64 workgroups walk a run grid-stride, hence 16 384 lanes whatever the run.
+struct DeepArenaOwner {
+    DevBuf buf;
+    int64_t bytes = 0;
+    int32_t cap = 0;
+    static constexpr int64_t LANES = 64 * 256;
+    // the arena for next_cap levels of cell_bytes each; reallocates only when the buffer must get larger
+    hipError_t grow(int next_cap, int cell_bytes) {
+        const int64_t need = LANES * (int64_t)next_cap * cell_bytes;
+        if (need > bytes) {
+            release();
+            const hipError_t e = buf.alloc((size_t)need);
+            if (e != hipSuccess) return e;
+            bytes = need;
+        }
+        cap = next_cap;
+        return hipSuccess;
+    }
+    void release() { buf.reset(); bytes = 0; }
+    DeepArena view() const { return DeepArena{buf.get<char>(), LANES, cap, 0}; }
+};
+
 // early-stop search: the finished k-mers the count pass wrote down for the emit pass (csrc/gki_forward.hip, "script"), and
 // the call they belong to -- the emit call uses them only when it is given the same arguments
 struct FwdScript {
-    void *entries;                           // FW_SLOTS entries of up to three 16-byte pieces per start position, piece-major
-    uint8_t *ncomp;                          // [n_pos] entries in use, 0xFF: the start position did not fit, walk it again
-    int64_t n_pos, overflow;
-    int64_t *over_list; int64_t over_cap;    // the start positions that did not fit (the first over_cap of them), for the emit pass
-    const void *nodes, *offsets, *follow, *rec_start;
-    int k, M, one_node, valid;
+    DevBuf entries;                          // FW_SLOTS entries of up to three 16-byte pieces per start position, piece-major
+    DevBuf ncomp;                            // uint8 [n_pos] entries in use, 0xFF: the start position did not fit, walk it again
+    int64_t n_pos = 0, overflow = 0;
+    DevBuf over_list; int64_t over_cap = 0;  // int64: the start positions that did not fit (the first over_cap of them), for the emit pass
+    const void *nodes = nullptr, *offsets = nullptr, *follow = nullptr, *rec_start = nullptr;
+    int k = 0, M = 0, one_node = 0, valid = 0;
 };
 
 struct gki_graph {
-    DevGraph d;
-    int64_t *h_seq_start;                    // host copy of d.seq_start [n_nodes+1] (chunk bounds without a device read)
-    hipStream_t stream;
-    int device;
-    void *owned[24];
-    int n_owned;
-    bool owns_seq;
-    hipEvent_t ev_prep0, ev_prep1;
-    DeepArena fwd_deep;                      // early-stop search: arena of its slow path, cap > 0 after a count call that needed it
-    int64_t fwd_deep_bytes;
+    DevGraph d = {};
+    int64_t *h_seq_start = nullptr;          // host copy of d.seq_start [n_nodes+1] (chunk bounds without a device read)
+    hipStream_t stream = nullptr;
+    int device = 0;
+    void *owned[24] = {};
+    int n_owned = 0;
+    bool owns_seq = false;
+    hipEvent_t ev_prep0 = nullptr, ev_prep1 = nullptr;
+    DeepArenaOwner fwd_deep;                 // early-stop search: arena of its slow path, cap > 0 after a count call that needed it
     FwdScript fwd_script;                    // early-stop search: what the count call left for the emit call (csrc/gki_forward.hip)
-    NodeFwd *fwd_nodes;                      // early-stop search: its per-node records, built by the first search after a prepare
+    DevBuf fwd_nodes;                        // early-stop search: its NodeFwd records, built by the first search after a prepare
 };
 
 // the early-stop search's script goes back to the pool (a new count call, the emit call, a prepare, the graph's destroy)
 static inline void script_drop(gki_graph *gr) {
     FwdScript &sc = gr->fwd_script;
-    if (sc.entries) (void)gki_dev_free(sc.entries);
-    if (sc.ncomp) (void)gki_dev_free(sc.ncomp);
-    if (sc.over_list) (void)gki_dev_free(sc.over_list);
-    sc = FwdScript{};
+    sc.entries.reset(); sc.ncomp.reset(); sc.over_list.reset();
+    sc.n_pos = sc.overflow = sc.over_cap = 0;
+    sc.nodes = sc.offsets = sc.follow = sc.rec_start = nullptr;
+    sc.k = sc.M = sc.one_node = sc.valid = 0;
+}
+
+// Run-time booleans as template arguments: with_bools(f, b0, b1, ..) calls f(std::bool_constant<b0>{}, ..), so that a
+// kernel with boolean template parameters is launched from ONE statement (host only; no allocation, nothing type-erased).
+template <class F> static inline void with_bools(F &&f) { f(); }
+template <class F, class... Rest> static inline void with_bools(F &&f, bool b, Rest... rest) {
+    if (b) with_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+    else with_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
 }
 
 // GKI_ERR_BAD_ARG unless the device that is current is the one the graph was uploaded to (gki_finder.hip)
@@ -241,6 +274,13 @@ __device__ __forceinline__ void gki_raise(int *err, int code) {
 __device__ __forceinline__ void gki_raise_budget(int *err) { atomicOr((unsigned int *)err, 4u); }
 static inline int gki_error_of_word(int64_t word) {
     return (word & 6) ? GKI_ERR_WINDOW_TOO_DEEP : (word & 1) ? GKI_ERR_NOT_ONE_REF_SUCC : GKI_OK;
+}
+// The slow path's rule, after a pass that ran with `cap` levels (0: the product kernels) and left `word`: 0 = stop -- the
+// pass fitted, or failed for a reason no deeper stack cures (bit 2), or the arena is at its limit -- else the cap to go
+// round again with: first_cap, then twice the levels each time round.
+static inline int gki_deep_next_cap(int64_t word, int cap, int first_cap) {
+    const int next_cap = cap == 0 ? first_cap : 2 * cap;
+    return (!(word & 2) || (word & 4) || next_cap > GKI_MAX_DEEP_WINDOW_NODES) ? 0 : next_cap;
 }
 
 // ---------------------------------------------------------------------------------- stacks of the graph walks
@@ -286,12 +326,6 @@ template <> struct CountOf<true> { typedef uint16_t T; };
 // one per trip in all-nodes mode -- 40 % of that kernel's LDS instructions.  Every lane of the wave must be active.
 // gki_selftest_wave_scan (gki_measure.hip) checks it against the shuffle form on the device.
 __device__ __forceinline__ int gki_wave_incl_sum(int x) {
-#ifdef GKI_SCAN_SHUFFLE                                                 // A/B builds: the shuffle form
-    const int lane_ = (int)(threadIdx.x & 63);
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(x, d, 64); if (lane_ >= d) x += t; }
-    return x;
-#endif
     x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, true);     // row_shr:1
     x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, true);     // row_shr:2
     x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, true);     // row_shr:4

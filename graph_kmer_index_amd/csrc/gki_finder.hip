@@ -67,13 +67,8 @@ template <> struct OutSel<2> { typedef OutFlatAll T; };
 // (one-node) / 5.5 ms (all-nodes), and the real stores ADD their whole transfer time at the store ceiling instead of
 // hiding under it.  Same-box A/B (profiles/r03_boundary_nt_stores_ab.txt): one-node 2.69 -> 2.43 ms, all-nodes
 // 7.28 -> 6.61 ms, and the count pass that follows 0.587 -> 0.566 ms.  (The interior kernels, which re-read nothing,
-// were 7 % slower with the hint: DESIGN.md 4.1.)  put<false> = plain stores;
-// GKI_BND_PLAIN_STORES builds the plain-store form of everything for the A/B.
-#ifdef GKI_BND_PLAIN_STORES
-template <bool NT, class T> __device__ __forceinline__ void st(T *p, T v) { *p = v; }
-#else
+// were 7 % slower with the hint: DESIGN.md 4.1.)  put<false> = plain stores.
 template <bool NT, class T> __device__ __forceinline__ void st(T *p, T v) { if (NT) __builtin_nontemporal_store(v, p); else *p = v; }
-#endif
 template <bool NT = true>
 __device__ __forceinline__ void put(const OutFlat &o, int64_t idx, uint64_t h, int32_t node, int32_t end_node,
                                     int32_t end_off, int64_t pos_id, double af) {
@@ -418,10 +413,7 @@ __device__ __forceinline__ int stored_nodes(const uint8_t *__restrict__ store, P
 // needs 100 VGPRs unconstrained (4 waves per SIMD; the others 53-55 = 8) -- held to 64 it spills ~30 values around the
 // history_ok call and is still faster at every step: 1.27 / 1.11 / 0.99 / 0.95 / 0.94 ms at 4 / 5 / 6 / 7 / 8 waves on the
 // 3 Gbp SNP graph, 2.19 / 1.88 / 1.70 / 1.66 / 1.64 ms with 20 % nested sites (tools/exp/ab_libs.sh, same box).
-#ifndef GKI_CNT_WPB
-#define GKI_CNT_WPB 1
-#endif
-constexpr int CNT_WPB = GKI_CNT_WPB;      // waves per workgroup of the count kernel (independent waves: see BND_WPB)
+constexpr int CNT_WPB = 1;                // waves per workgroup of the count kernel (independent waves: see BND_WPB)
 template <bool HAS_LOSSY, bool GEN, bool DEEP = false>
 __global__ __launch_bounds__(64 * CNT_WPB, (GEN && !DEEP) ? 8 : 1) void k_count_boundary(DevGraph g, FindArgs a, const uint16_t *__restrict__ lossy,
                                                         uint32_t *__restrict__ bcount, uint32_t *__restrict__ total,
@@ -577,10 +569,7 @@ __global__ __launch_bounds__(64 * CNT_WPB, (GEN && !DEEP) ? 8 : 1) void k_count_
 // store inside the walk stalls the next dependent load.
 // EVQ: 128 steps per queue; 96 would save 4.5 KB of LDS per workgroup but is ~7 % slower at equal occupancy (fewer steps
 // per flush), which is why the LDS diet for a fifth workgroup per CU was dropped.
-#ifndef GKI_EVQ
-#define GKI_EVQ 128
-#endif
-constexpr int EVQ = GKI_EVQ;        // step descriptors per wave queue (a walk round adds at most 64)
+constexpr int EVQ = 128;            // step descriptors per wave queue (a walk round adds at most 64)
 constexpr int MW = EVQ * 32 / 64;   // words of the window bitmap (a step holds at most 31 windows)
 static_assert(EVQ > 64 && EVQ <= 128 && EVQ % 2 == 0 && MW <= 64, "two steps per lane, one bitmap word per lane");
 
@@ -592,11 +581,6 @@ template <> struct MafOf<1> { typedef double T; };           // get_flat_kmers(v
 
 template <bool ALL> struct IdxOf { typedef int64_t T; };
 template <> struct IdxOf<true> { typedef uint32_t T; };
-#ifdef GKI_EMIT_SLIM
-constexpr bool EMIT_SLIM = true;     // one-node mode too: per-lane facts shuffled, 32-bit slots, no flag words -> 32 KB, 5 workgroups per CU
-#else
-constexpr bool EMIT_SLIM = false;
-#endif
 
 // One-node mode packs what a record's lane reads about its step and about the step's node into three aligned structs --
 // one ds_read_b128 for {context, first slot}, one ds_read_b64 for {allele-frequency minimum, smallest node}, one
@@ -625,8 +609,8 @@ template <int FMT> struct EvPacked<FMT, true> {
 };
 
 template <int FMT, bool ALL>
-struct EvQueue : EvPacked<FMT, !ALL && !EMIT_SLIM> {
-    static constexpr bool PACKED = !ALL && !EMIT_SLIM;
+struct EvQueue : EvPacked<FMT, !ALL> {
+    static constexpr bool PACKED = !ALL;
     // the other modes: per queued step
     uint64_t ctx[PACKED ? 1 : EVQ];
     typename IdxOf<true>::T idx[PACKED ? 1 : EVQ];  // first record slot of the step, relative to the node group's first
@@ -732,28 +716,7 @@ __device__ __forceinline__ void expand_queue(EvQueue<FMT, ALL> &q, int n_ev, int
     if (lane < MW) q.wrank[lane] = (uint16_t)(ps - pc);
     __builtin_amdgcn_wave_barrier();
     const int shift = ALL ? 0 : (int)((mn_idx + idx_base) & 15);
-    if constexpr (!ALL && EMIT_SLIM) {
-        for (int r0 = -shift; r0 < T; r0 += 64) {
-            const int r = r0 + lane;
-            const bool valid = r >= 0 && r < T;
-            int e = 0, j = 0, o = 0, ln = 0;
-            if (valid) {
-                const int w = r >> 6;
-                const int sp = (int)q.wrank[w] + __popcll(q.marks[w] & ((2ull << (r & 63)) - 1ull)) - 1;
-                e = (int)q.order[sp];
-                j = r - (int)q.pre[sp];
-                const uint32_t sm = q.small[e];
-                o = sw_from(sm) + j; ln = sw_ln(sm);
-            }
-            const uint64_t own_v = (uint64_t)__shfl((unsigned long long)own_reg, ln, 64);
-            const int64_t pos0_v = (int64_t)__shfl((long long)pos0_reg, ln, 64);
-            const int32_t n_v = __shfl(n_reg, ln, 64);
-            if (valid) {
-                const uint64_t h = ((q.ctx[e] >> (2 * o)) | (own_v << (2 * (k - 1 - o)))) & kmask;
-                put(out, idx_base + (int64_t)q.idx[e] + j, h, q.mn[e], n_v, o, pos0_v + o, (double)q.maf[e]);
-            }
-        }
-    } else if constexpr (!ALL) {
+    if constexpr (!ALL) {
         for (int r0 = -shift; r0 < T; r0 += 64) {
             const int r = r0 + lane;
             if (r >= 0 && r < T) {
@@ -789,7 +752,6 @@ __device__ __forceinline__ void expand_queue(EvQueue<FMT, ALL> &q, int n_ev, int
             const uint64_t own_v = (uint64_t)__shfl((unsigned long long)own_reg, ln, 64);
             const int64_t pos0_v = (int64_t)__shfl((long long)pos0_reg, ln, 64);
             const int32_t n_v = __shfl(n_reg, ln, 64);
-#ifndef GKI_ALL_LANE_PER_WINDOW
             // One lane per RECORD: the trip's windows hold nl records each (1 .. NLQ); written by their window's lane in
             // turn, neighbouring lanes store nl records apart and every line is touched by up to five store instructions
             // (the expansion ran at 3.75 TB/s where one-node mode's, coalesced, reaches 5.7).  Here the trip's records are
@@ -834,15 +796,6 @@ __device__ __forceinline__ void expand_queue(EvQueue<FMT, ALL> &q, int n_ev, int
                 if (live) put(out, GKI_DBG_SLOT(first_o + t), h_o, q.nodes[e_o][t], n_o, o_o, pos0_o + o_o, maf_o);
             }
             __builtin_amdgcn_wave_barrier();
-#else
-            if (valid) {
-                const uint64_t h = ((q.ctx[e] >> (2 * o)) | (own_v << (2 * (k - 1 - o)))) & kmask;
-                const int nl = (int)q.nl[e];
-                const int64_t first = idx_base + (int64_t)q.idx[e] + (int64_t)j * nl;
-                for (int t = 0; t < nl; t++)
-                    put(out, first + t, h, q.nodes[e][t], n_v, o, pos0_v + o, (double)q.maf[e]);
-            }
-#endif
         }
     }
 }
@@ -862,19 +815,16 @@ static_assert(sizeof(LevelEmitT<false>) == 32 && sizeof(LevelEmitT<true>) <= DA_
 // the workgroup is only the unit the hardware schedules -- and the smaller that unit, the better the uneven node groups
 // balance over the CUs.  Same LDS per wave, same 16 waves per CU.  One-node 2.23 -> 2.13 ms same-box, one rank's shard
 // of eight 0.330 -> 0.311 ms, all-nodes unchanged within its noise (profiles/r03_boundary_grid_ab.txt); two waves per
-// workgroup: half of that.  (-DGKI_BND_WPB=4: the workgroups of rounds 1-3.)
-#ifndef GKI_BND_WPB
-#define GKI_BND_WPB 1
-#endif
-constexpr int BND_WPB = GKI_BND_WPB;      // waves (groups of 64 nodes) per workgroup of the emit kernel
+// workgroup: half of that.  (Four waves: the workgroups of rounds 1-3.)
+constexpr int BND_WPB = 1;                // waves (groups of 64 nodes) per workgroup of the emit kernel
 template <bool HAS_LOSSY, int FMT, bool ALL, bool GEN, bool DEEP = false>
 // (general one-node variants in the flat layouts: LDS allows 4 workgroups per CU; without the request they take 129 VGPRs)
-__global__ __launch_bounds__(64 * BND_WPB, (EMIT_SLIM && !GEN && !ALL && !HAS_LOSSY && FMT != 1) ? 5 : (GEN && !ALL && FMT != 1 && !DEEP) ? 4 : 1) void k_emit_boundary_one(DevGraph g, FindArgs a, const uint16_t *__restrict__ lossy,
+__global__ __launch_bounds__(64 * BND_WPB, (GEN && !ALL && FMT != 1 && !DEEP) ? 4 : 1) void k_emit_boundary_one(DevGraph g, FindArgs a, const uint16_t *__restrict__ lossy,
                                                            const uint32_t *__restrict__ bcount,
                                                            const int64_t *__restrict__ rec_base,
                                                            const int64_t *__restrict__ bnd_shift,
                                                            typename OutSel<FMT>::T out, int *__restrict__ err, DeepArena da) {
-    typedef WalkCacheT<(!ALL && !EMIT_SLIM) || GEN || HAS_LOSSY> WCache;      // the flag words only where they are read (or LDS is not the limit)
+    typedef WalkCacheT<!ALL || GEN || HAS_LOSSY> WCache;      // the flag words only where they are read (or LDS is not the limit)
     __shared__ EvQueue<FMT, ALL> s_q[BND_WPB];
     __shared__ WCache s_wc[BND_WPB];
     typedef LevelEmitT<DEEP> LevelEmit;
@@ -903,7 +853,7 @@ __global__ __launch_bounds__(64 * BND_WPB, (EMIT_SLIM && !GEN && !ALL && !HAS_LO
     int n_ev = 0, my_cnt = 0;              // steps in the queue; of them, queued by this lane
     for (int64_t base = a.n0 + (int64_t)blockIdx.x * blockDim.x + wib * 64; base < a.n1; base += n_threads) {
         int64_t idx_base = 0;              // all-nodes mode: queued record slots are 32-bit offsets from the group's first
-        if (ALL || EMIT_SLIM) {
+        if (ALL) {
             const int64_t last = base + 64 < a.n1 ? base + 64 : a.n1;
             idx_base = rec_base[base] + *bnd_shift;
             if (rec_base[last] - rec_base[base] > 0xFFFFFFFFll) { gki_raise(err, GKI_ERR_WINDOW_TOO_DEEP); continue; }
@@ -1509,30 +1459,29 @@ __global__ __launch_bounds__(256) void k_sum_u32(const uint32_t *__restrict__ x,
 }  // namespace
 
 struct gki_finder {
-    gki_graph *g;
-    hipStream_t stream, stream2;
-    uint32_t *bcount, *total;
-    int64_t *rec_base, *bnd_base;     // by-node layout: rec_base only; split layout: interior bases / boundary bases
-    NodeEmit *ne;
-    BlkFirst *blk;                    // split layout: the output-block table of k_emit_interior_dense (n_bases / IB + 2 entries)
-    uint16_t *lossy;
-    const uint16_t *lossy_cur;        // the table of the run in progress: `lossy` (uploaded by the count) or the caller's device table
-    uint16_t *nflags; uint8_t *store; // general graphs / only_store_nodes (gki_find_params), allocated on first use
-    void *scan_tmp; int64_t scan_tmp_bytes;
-    int *d_err; int64_t *d_totals; unsigned long long *d_bsum;
-    int64_t *h_totals;                // pinned: {total, error, boundary records, 0, boundary sum} read back by every count;
+    gki_graph *g = nullptr;
+    hipStream_t stream = nullptr, stream2 = nullptr;
+    DevBuf bcount, total;             // uint32 per node
+    DevBuf rec_base, bnd_base;        // int64 [n_nodes + 1].  by-node layout: rec_base only; split layout: interior bases / boundary bases
+    DevBuf ne;                        // NodeEmit per non-empty node
+    DevBuf blk;                       // BlkFirst.  split layout: the output-block table of k_emit_interior_dense (n_bases / IB + 2 entries)
+    DevBuf lossy;                     // uint16 per node
+    const uint16_t *lossy_cur = nullptr;  // the table of the run in progress: `lossy` (uploaded by the count) or the caller's device table
+    DevBuf nflags, store;             // general graphs / only_store_nodes (gki_find_params), allocated on first use
+    DevBuf scan_tmp; int64_t scan_tmp_bytes = 0;
+    DevBuf d_err, d_totals, d_bsum;   // int; int64 [4]; unsigned long long
+    int64_t *h_totals = nullptr;      // pinned: {total, error, boundary records, 0, boundary sum} read back by every count;
                                       // [5]: the error word after the emit kernels (read by gki_finder_synchronize)
-    bool emit_pending;                // an emit call's error word has not been looked at yet
-    int32_t *d_rank;                  // topological ranks of the run in progress (non-topological node ids only)
-    DeepArena deep;                   // cap > 0: the run in progress needed the deep kernel variants (their stacks live here)
-    int64_t deep_bytes;
-    FindArgs args;
-    int64_t n_records, n_boundary_records, n_interior_records;
-    int64_t word_begin, word_end, p_begin, p_end;
-    bool counted;
-    hipEvent_t ev[8];    // pairs: 0/1 count-boundary, 2/3 emit-interior, 4/5 emit-boundary, 6/7 scan + per-node constants
-    hipEvent_t ev_ready, ev_join;
-    bool ev_valid[4];
+    bool emit_pending = false;        // an emit call's error word has not been looked at yet
+    DevBuf d_rank;                    // topological ranks of the run in progress (non-topological node ids only)
+    DeepArenaOwner deep;              // cap > 0: the run in progress needed the deep kernel variants (their stacks live here)
+    FindArgs args = {};
+    int64_t n_records = 0, n_boundary_records = 0, n_interior_records = 0;
+    int64_t word_begin = 0, word_end = 0, p_begin = 0, p_end = 0;
+    bool counted = false;
+    hipEvent_t ev[8] = {};   // pairs: 0/1 count-boundary, 2/3 emit-interior, 4/5 emit-boundary, 6/7 scan + per-node constants
+    hipEvent_t ev_ready = nullptr, ev_join = nullptr;
+    bool ev_valid[4] = {};
 };
 
 // Launch parameters are fixed in the product; `make tuning` (-DGKI_TUNING, used by tools/exp) reads them from the
@@ -1549,31 +1498,16 @@ static int launch_boundary_mode(gki_finder *f, const DevGraph &d, const FindArgs
                                 const dim3 grid, const dim3 block, const int64_t *base, const int64_t *shift) {
     const int emit_pad = GKI_KNOB("GKI_EMIT_LDS_PAD", 0);  // tuning builds: unused dynamic LDS, to lower the occupancy
     // the lossy-restart logic costs 0.4-0.5 ms (emit) + 0.1-0.2 ms (count) per step on the 3 Gbp graphs even when the run has
-    // no such point (a lossy[q] load per predecessor step): every variant exists without it
-    const DeepArena da = f->deep;
-    if (da.cap > 0) {
-        // the count pass met a window deeper than the product kernels' stacks: the same kernels with their stacks in the
-        // arena, on the grid the arena was sized for
-        const dim3 dgrid((unsigned)(da.lanes / (64 * BND_WPB)));
-        if (a.nflags && a.has_lossy)
-            hipLaunchKernelGGL((k_emit_boundary_one<true, FMT, ALL, true, true>), dgrid, block, 0, s2, d, a, f->lossy_cur, f->bcount, base, shift, out, f->d_err, da);
-        else if (a.nflags)
-            hipLaunchKernelGGL((k_emit_boundary_one<false, FMT, ALL, true, true>), dgrid, block, 0, s2, d, a, f->lossy_cur, f->bcount, base, shift, out, f->d_err, da);
-        else if (a.has_lossy)
-            hipLaunchKernelGGL((k_emit_boundary_one<true, FMT, ALL, false, true>), dgrid, block, 0, s2, d, a, f->lossy_cur, f->bcount, base, shift, out, f->d_err, da);
-        else
-            hipLaunchKernelGGL((k_emit_boundary_one<false, FMT, ALL, false, true>), dgrid, block, 0, s2, d, a, f->lossy_cur, f->bcount, base, shift, out, f->d_err, da);
-        HIP_TRY(hipGetLastError());
-        return GKI_OK;
-    }
-    if (a.nflags && a.has_lossy)
-        hipLaunchKernelGGL((k_emit_boundary_one<true, FMT, ALL, true>), grid, block, emit_pad, s2, d, a, f->lossy_cur, f->bcount, base, shift, out, f->d_err, da);
-    else if (a.nflags)
-        hipLaunchKernelGGL((k_emit_boundary_one<false, FMT, ALL, true>), grid, block, emit_pad, s2, d, a, f->lossy_cur, f->bcount, base, shift, out, f->d_err, da);
-    else if (a.has_lossy)
-        hipLaunchKernelGGL((k_emit_boundary_one<true, FMT, ALL, false>), grid, block, emit_pad, s2, d, a, f->lossy_cur, f->bcount, base, shift, out, f->d_err, da);
-    else
-        hipLaunchKernelGGL((k_emit_boundary_one<false, FMT, ALL, false>), grid, block, emit_pad, s2, d, a, f->lossy_cur, f->bcount, base, shift, out, f->d_err, da);
+    // no such point (a lossy[q] load per predecessor step): every variant exists without it.
+    // da.cap > 0: the count pass met a window deeper than the product kernels' stacks -- the same kernels with their stacks
+    // in the arena, on the grid the arena was sized for
+    const DeepArena da = f->deep.view();
+    const bool deep = da.cap > 0;
+    const dim3 g = deep ? dim3((unsigned)(da.lanes / (64 * BND_WPB))) : grid;
+    with_bools([&](auto HAS_LOSSY, auto GEN, auto DEEP) {
+        hipLaunchKernelGGL((k_emit_boundary_one<decltype(HAS_LOSSY)::value, FMT, ALL, decltype(GEN)::value, decltype(DEEP)::value>), g, block,
+                           deep ? 0 : emit_pad, s2, d, a, f->lossy_cur, f->bcount.get<const uint32_t>(), base, shift, out, f->d_err.get<int>(), da);
+    }, a.has_lossy != 0, a.nflags != nullptr, deep);
     HIP_TRY(hipGetLastError());
     return GKI_OK;
 }
@@ -1600,8 +1534,8 @@ static int launch_boundary_fmt(gki_finder *f, const DevGraph &d, const FindArgs 
     if (gb < 1) gb = 1;
     const dim3 grid(gb), block(64 * BND_WPB);
     // split layout: boundary block of node n starts at (number of interior records) + bnd_base[n]
-    const int64_t *base = a.split ? f->bnd_base : f->rec_base;
-    const int64_t *shift = a.split ? f->rec_base + a.n1 : f->d_totals + 3;
+    const int64_t *base = a.split ? f->bnd_base.get<int64_t>() : f->rec_base.get<int64_t>();
+    const int64_t *shift = a.split ? f->rec_base.get<int64_t>() + a.n1 : f->d_totals.get<int64_t>() + 3;
     if (a.one_node) return launch_boundary_mode<FMT, false>(f, d, a, out, s2, grid, block, base, shift);
     return launch_boundary_mode<FMT, true>(f, d, a, out, s2, grid, block, base, shift);
 }
@@ -1618,6 +1552,7 @@ static int launch_boundary(gki_finder *f, const DevGraph &d, const FindArgs &a, 
 
 static int launch_interior(gki_finder *f, const DevGraph &d, const FindArgs &a, OutFlat out, unsigned blocks) {
     hipStream_t s = f->stream;
+    const NodeEmit *ne = f->ne.get<NodeEmit>();
     const bool all = out.hash && out.node && out.ref_offset && out.af;
     if (all && a.split && GKI_KNOB("GKI_DENSE", 1)) {
         // split layout: output blocks (k_emit_interior_dense), then whatever did not fit its stage.  8 workgroups of 4 waves
@@ -1627,13 +1562,14 @@ static int launch_interior(gki_finder *f, const DevGraph &d, const FindArgs &a, 
         const int db = GKI_KNOB("GKI_DENSE_BLOCKS", 2048);
         if (gb > db) gb = db;
         if (gb < 1) gb = 1;
-        const int64_t *n_int = f->rec_base + a.n1;
-        hipLaunchKernelGGL(k_emit_interior_dense, dim3((unsigned)gb), dim3(256), 0, s, d, a, f->ne, f->blk, n_int, out);
+        const int64_t *n_int = f->rec_base.get<int64_t>() + a.n1;
+        const BlkFirst *blk = f->blk.get<BlkFirst>();
+        hipLaunchKernelGGL(k_emit_interior_dense, dim3((unsigned)gb), dim3(256), 0, s, d, a, ne, blk, n_int, out);
         HIP_TRY(hipGetLastError());
         int64_t rb = ceil_div(ceil_div(n_blk, 64), 4);
         if (rb > 1024) rb = 1024;
         if (rb < 1) rb = 1;
-        hipLaunchKernelGGL(k_emit_interior_dense_rest, dim3((unsigned)rb), dim3(256), 0, s, d, a, f->ne, f->blk, n_int, out);
+        hipLaunchKernelGGL(k_emit_interior_dense_rest, dim3((unsigned)rb), dim3(256), 0, s, d, a, ne, blk, n_int, out);
         HIP_TRY(hipGetLastError());
         return GKI_OK;
     }
@@ -1646,26 +1582,26 @@ static int launch_interior(gki_finder *f, const DevGraph &d, const FindArgs &a, 
         if (gb > (unsigned)rb) gb = (unsigned)rb;
 #ifdef GKI_TUNING
         if (swt == 128)
-            hipLaunchKernelGGL((k_emit_interior_runs<128, 128>), dim3(gb), dim3(256), 0, s, d, a, f->ne, out, f->word_begin, f->word_end, f->p_begin, f->p_end);
+            hipLaunchKernelGGL((k_emit_interior_runs<128, 128>), dim3(gb), dim3(256), 0, s, d, a, ne, out, f->word_begin, f->word_end, f->p_begin, f->p_end);
         else if (cap == 64)      // 16.7 KB of LDS per block: 8 blocks per CU
-            hipLaunchKernelGGL((k_emit_interior_runs<64, 64>), dim3(gb), dim3(256), 0, s, d, a, f->ne, out, f->word_begin, f->word_end, f->p_begin, f->p_end);
+            hipLaunchKernelGGL((k_emit_interior_runs<64, 64>), dim3(gb), dim3(256), 0, s, d, a, ne, out, f->word_begin, f->word_end, f->p_begin, f->p_end);
         else if (cap == 32)
-            hipLaunchKernelGGL((k_emit_interior_runs<64, 32>), dim3(gb), dim3(256), 0, s, d, a, f->ne, out, f->word_begin, f->word_end, f->p_begin, f->p_end);
+            hipLaunchKernelGGL((k_emit_interior_runs<64, 32>), dim3(gb), dim3(256), 0, s, d, a, ne, out, f->word_begin, f->word_end, f->p_begin, f->p_end);
         else
 #else
         (void)cap;
 #endif
         // 29 KB of LDS per block: 5 blocks per CU are resident
-        hipLaunchKernelGGL((k_emit_interior_runs<64, 128>), dim3(gb), dim3(256), 0, s, d, a, f->ne, out, f->word_begin, f->word_end, f->p_begin, f->p_end);
+        hipLaunchKernelGGL((k_emit_interior_runs<64, 128>), dim3(gb), dim3(256), 0, s, d, a, ne, out, f->word_begin, f->word_end, f->p_begin, f->p_end);
     }
     else
-        hipLaunchKernelGGL(k_emit_interior<0>, dim3(blocks), dim3(256), 0, s, d, a, f->ne, out, f->word_begin, f->word_end,
+        hipLaunchKernelGGL(k_emit_interior<0>, dim3(blocks), dim3(256), 0, s, d, a, ne, out, f->word_begin, f->word_end,
                            f->p_begin, f->p_end);
     HIP_TRY(hipGetLastError());
     return GKI_OK;
 }
 static int launch_interior(gki_finder *f, const DevGraph &d, const FindArgs &a, OutV2 out, unsigned blocks) {
-    hipLaunchKernelGGL(k_emit_interior<1>, dim3(blocks), dim3(256), 0, f->stream, d, a, f->ne, out, f->word_begin, f->word_end,
+    hipLaunchKernelGGL(k_emit_interior<1>, dim3(blocks), dim3(256), 0, f->stream, d, a, f->ne.get<NodeEmit>(), out, f->word_begin, f->word_end,
                        f->p_begin, f->p_end);
     HIP_TRY(hipGetLastError());
     return GKI_OK;
@@ -1674,11 +1610,7 @@ static int launch_interior(gki_finder *f, const DevGraph &d, const FindArgs &a, 
 template <int FMT>
 static int emit_impl(gki_finder *f, typename OutSel<FMT>::T out) {
     if (!f->counted) return gki_set_error(GKI_ERR_STATE, "gki_finder_emit_* called before gki_finder_count");
-    if (f->deep.cap > 0 && !f->deep.base) {                       // a second emit after one count: the arena again
-        const int64_t bytes = f->deep.lanes * (int64_t)f->deep.cap * DA_CELL;
-        HIP_TRY(gki_dev_malloc((void **)&f->deep.base, (size_t)bytes));
-        f->deep_bytes = bytes;
-    }
+    if (f->deep.cap > 0) HIP_TRY(f->deep.grow(f->deep.cap, DA_CELL));       // a second emit after one count: the arena again
     const DevGraph &d = f->g->d;
     hipStream_t s = f->stream, s2 = f->stream2;
     const FindArgs a = f->args;
@@ -1713,7 +1645,7 @@ static int emit_impl(gki_finder *f, typename OutSel<FMT>::T out) {
     // records between them; a window deeper than the count pass met) raises the error word and leaves them unwritten:
     // gki_finder_synchronize returns it (nothing read the word after an emit launch)
     f->h_totals[5] = 0;
-    HIP_TRY(hipMemcpyAsync(&f->h_totals[5], f->d_err, 4, hipMemcpyDeviceToHost, s2));
+    HIP_TRY(hipMemcpyAsync(&f->h_totals[5], f->d_err.get(), 4, hipMemcpyDeviceToHost, s2));
     f->emit_pending = true;
     HIP_TRY(hipEventRecord(f->ev_join, s2));
     HIP_TRY(hipStreamWaitEvent(s, f->ev_join, 0));
@@ -1733,66 +1665,47 @@ int gki_check_graph_device(const gki_graph *g, const char *who) {
     return GKI_OK;
 }
 
-extern "C" {
+namespace {
 
-static int finder_init(gki_finder *f, gki_graph *g) {
+int finder_init(gki_finder *f, gki_graph *g) {
     const int64_t n = g->d.n_nodes;
     HIP_TRY(hipStreamCreate(&f->stream));
     HIP_TRY(hipStreamCreate(&f->stream2));
     for (int i = 0; i < 8; i++) HIP_TRY(hipEventCreate(&f->ev[i]));
     HIP_TRY(hipEventCreateWithFlags(&f->ev_ready, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&f->ev_join, hipEventDisableTiming));
-    HIP_TRY(gki_dev_malloc((void **)&f->bcount, (size_t)n * 4));
-    HIP_TRY(gki_dev_malloc((void **)&f->total, (size_t)n * 4));
-    HIP_TRY(gki_dev_malloc((void **)&f->rec_base, (size_t)(n + 1) * 8));
-    HIP_TRY(gki_dev_malloc((void **)&f->bnd_base, (size_t)(n + 1) * 8));
-    HIP_TRY(gki_dev_malloc((void **)&f->ne, (size_t)(g->d.n_nonempty + 1) * sizeof(NodeEmit)));
-    HIP_TRY(hipMemset(f->ne, 0, (size_t)(g->d.n_nonempty + 1) * sizeof(NodeEmit)));   // cnt = 0: a record never refreshed emits nothing
-    HIP_TRY(gki_dev_malloc((void **)&f->blk, (size_t)(g->d.n_bases / IB + 2) * sizeof(BlkFirst)));
-    HIP_TRY(gki_dev_malloc((void **)&f->lossy, (size_t)n * 2));
-    HIP_TRY(gki_dev_malloc((void **)&f->d_err, 4));
-    HIP_TRY(gki_dev_malloc((void **)&f->d_totals, 4 * 8));
-    HIP_TRY(hipMemset(f->d_totals, 0, 4 * 8));
-    HIP_TRY(gki_dev_malloc((void **)&f->d_bsum, 8));
+    HIP_TRY(f->bcount.alloc((size_t)n * 4));
+    HIP_TRY(f->total.alloc((size_t)n * 4));
+    HIP_TRY(f->rec_base.alloc((size_t)(n + 1) * 8));
+    HIP_TRY(f->bnd_base.alloc((size_t)(n + 1) * 8));
+    HIP_TRY(f->ne.alloc((size_t)(g->d.n_nonempty + 1) * sizeof(NodeEmit)));
+    HIP_TRY(hipMemset(f->ne.get(), 0, (size_t)(g->d.n_nonempty + 1) * sizeof(NodeEmit)));   // cnt = 0: a record never refreshed emits nothing
+    HIP_TRY(f->blk.alloc((size_t)(g->d.n_bases / IB + 2) * sizeof(BlkFirst)));
+    HIP_TRY(f->lossy.alloc((size_t)n * 2));
+    HIP_TRY(f->d_err.alloc(4));
+    HIP_TRY(f->d_totals.alloc(4 * 8));
+    HIP_TRY(hipMemset(f->d_totals.get(), 0, 4 * 8));
+    HIP_TRY(f->d_bsum.alloc(8));
     HIP_TRY(hipHostMalloc((void **)&f->h_totals, 6 * 8, hipHostMallocDefault));
     f->scan_tmp_bytes = gki_scan_tmp_bytes(n);
-    HIP_TRY(gki_dev_malloc(&f->scan_tmp, (size_t)f->scan_tmp_bytes));
+    HIP_TRY(f->scan_tmp.alloc((size_t)f->scan_tmp_bytes));
     return GKI_OK;
 }
 
-int gki_finder_create(gki_graph *g, gki_finder **out) {
-    *out = nullptr;
-    if (!g) return gki_set_error(GKI_ERR_BAD_ARG, "finder_create: graph is NULL");
-    GKI_TRY(gki_check_graph_device(g, "gki_finder_create"));
-    gki_finder *f = new gki_finder();
-    memset(f, 0, sizeof(*f));
-    f->g = g;
-    const int rc = finder_init(f, g);
-    if (rc != GKI_OK) { (void)gki_finder_destroy(f); return rc; }      // nothing of a half-built finder stays behind
-    *out = f;
+// A per-run table of gki_find_params: the caller's device table (nothing to upload), else the host array uploaded into a
+// buffer the finder owns, allocated on first use; NULL when the run has neither.
+template <class T>
+int run_table(DevBuf &own, const T *d_tab, const T *h_tab, int64_t n, hipStream_t s, const T **out) {
+    *out = d_tab;
+    if (d_tab || !h_tab) return GKI_OK;
+    if (!own.get()) HIP_TRY(own.alloc((size_t)n * sizeof(T)));
+    HIP_TRY(hipMemcpyAsync(own.get(), h_tab, (size_t)n * sizeof(T), hipMemcpyHostToDevice, s));
+    *out = own.get<T>();
     return GKI_OK;
 }
 
-int gki_finder_destroy(gki_finder *f) {
-    if (!f) return GKI_OK;
-    if (f->stream) (void)hipStreamSynchronize(f->stream);
-    if (f->stream2) (void)hipStreamSynchronize(f->stream2);
-    void *ptrs[] = {f->bcount, f->total, f->rec_base, f->bnd_base, f->ne, f->blk, f->lossy, f->scan_tmp, f->d_err, f->d_totals, f->d_bsum,
-                    f->d_rank, f->nflags, f->store, f->deep.base};
-    for (void *p : ptrs) if (p) (void)gki_dev_free(p);
-    if (f->h_totals) (void)hipHostFree(f->h_totals);
-    for (int i = 0; i < 8; i++) if (f->ev[i]) (void)hipEventDestroy(f->ev[i]);
-    if (f->ev_ready) (void)hipEventDestroy(f->ev_ready);
-    if (f->ev_join) (void)hipEventDestroy(f->ev_join);
-    if (f->stream) (void)hipStreamDestroy(f->stream);
-    if (f->stream2) (void)hipStreamDestroy(f->stream2);
-    delete f;
-    return GKI_OK;
-}
-
-int gki_finder_count(gki_finder *f, const gki_find_params *p, int64_t *n_records) {
-    *n_records = 0;
-    f->counted = false;
+// argument checks; the run's FindArgs (f->args) and its four tables on the device
+int count_setup(gki_finder *f, const gki_find_params *p) {
     const DevGraph &d = f->g->d;
     if (p->struct_size != sizeof(gki_find_params))
         return gki_set_error(GKI_ERR_BAD_ARG, "gki_find_params.struct_size is %u, this library expects %u: the binding was "
@@ -1808,144 +1721,97 @@ int gki_finder_count(gki_finder *f, const gki_find_params *p, int64_t *n_records
     a.has_lossy = (p->h_lossy_crit || p->d_lossy_crit) ? 1 : 0;
     // tuning builds: run the lossy-restart kernel variants on a graph without such points (what does the variant cost?)
     const bool force_lossy = !a.has_lossy && GKI_KNOB("GKI_FORCE_LOSSY", 0) != 0;
-    if (force_lossy) { HIP_TRY(hipMemsetAsync(f->lossy, 0xFF, (size_t)d.n_nodes * 2, s)); a.has_lossy = 1; }
+    if (force_lossy) { HIP_TRY(hipMemsetAsync(f->lossy.get(), 0xFF, (size_t)d.n_nodes * 2, s)); a.has_lossy = 1; }
     a.node_begin = p->node_begin; a.off_begin = p->off_begin; a.node_end = p->node_end; a.off_end = p->off_end;
     a.n0 = p->node_begin < d.n_nodes ? p->node_begin : d.n_nodes;
     a.n1 = p->node_end < d.n_nodes ? p->node_end + 1 : d.n_nodes;
     a.split = p->layout == GKI_LAYOUT_SPLIT ? 1 : 0; a.pad = 0;
-    a.rank = nullptr; a.rank_begin = 0; a.rank_end = 0;
-    a.nflags = nullptr; a.store = nullptr;
-    // the four per-run tables: already on the device (d_ forms: nothing to upload), or host arrays uploaded per count
-    if (p->d_store_nodes || p->h_store_nodes) {
-        if (!p->h_node_flags && !p->d_node_flags) return gki_set_error(GKI_ERR_BAD_ARG, "store_nodes needs node_flags (gki_classify_nodes)");
-        if (p->d_store_nodes) a.store = p->d_store_nodes;
-        else {
-            if (!f->store) HIP_TRY(gki_dev_malloc((void **)&f->store, (size_t)d.n_nodes));
-            HIP_TRY(hipMemcpyAsync(f->store, p->h_store_nodes, (size_t)d.n_nodes, hipMemcpyHostToDevice, s));
-            a.store = f->store;
-        }
-    }
-    if (p->d_node_flags) a.nflags = p->d_node_flags;
-    else if (p->h_node_flags) {
-        if (!f->nflags) HIP_TRY(gki_dev_malloc((void **)&f->nflags, (size_t)d.n_nodes * 2));
-        HIP_TRY(hipMemcpyAsync(f->nflags, p->h_node_flags, (size_t)d.n_nodes * 2, hipMemcpyHostToDevice, s));
-        a.nflags = f->nflags;
-    }
-    if (p->d_node_rank) {
-        a.rank = p->d_node_rank; a.rank_begin = p->rank_begin; a.rank_end = p->rank_end;
-        a.n0 = 0; a.n1 = d.n_nodes;
-    } else if (p->h_node_rank) {
+    a.rank_begin = 0; a.rank_end = 0;
+    if ((p->d_store_nodes || p->h_store_nodes) && !p->h_node_flags && !p->d_node_flags)
+        return gki_set_error(GKI_ERR_BAD_ARG, "store_nodes needs node_flags (gki_classify_nodes)");
+    GKI_TRY(run_table(f->store, p->d_store_nodes, p->h_store_nodes, d.n_nodes, s, &a.store));
+    GKI_TRY(run_table(f->nflags, p->d_node_flags, p->h_node_flags, d.n_nodes, s, &a.nflags));
+    GKI_TRY(run_table(f->d_rank, p->d_node_rank, p->h_node_rank, d.n_nodes, s, &a.rank));
+    if (a.rank) {
         // node ids are not topological: membership by rank, every node is looked at
-        if (!f->d_rank) HIP_TRY(gki_dev_malloc((void **)&f->d_rank, (size_t)d.n_nodes * 4));
-        HIP_TRY(hipMemcpyAsync(f->d_rank, p->h_node_rank, (size_t)d.n_nodes * 4, hipMemcpyHostToDevice, s));
-        a.rank = f->d_rank;
-        a.rank_begin = p->node_begin < d.n_nodes ? p->h_node_rank[p->node_begin] : INT_MAX;
-        a.rank_end = p->node_end < d.n_nodes ? p->h_node_rank[p->node_end] : INT_MAX;
+        if (p->d_node_rank) { a.rank_begin = p->rank_begin; a.rank_end = p->rank_end; }
+        else {
+            a.rank_begin = p->node_begin < d.n_nodes ? p->h_node_rank[p->node_begin] : INT_MAX;
+            a.rank_end = p->node_end < d.n_nodes ? p->h_node_rank[p->node_end] : INT_MAX;
+        }
         a.n0 = 0; a.n1 = d.n_nodes;
     }
+    f->lossy_cur = f->lossy.get<uint16_t>();
+    if (a.has_lossy && !force_lossy) GKI_TRY(run_table(f->lossy, p->d_lossy_crit, p->h_lossy_crit, d.n_nodes, s, &f->lossy_cur));
     f->args = a;
-    const int64_t n_run = a.n1 - a.n0;
-    f->lossy_cur = f->lossy;
-    if (a.has_lossy && !force_lossy) {
-        if (p->d_lossy_crit) f->lossy_cur = p->d_lossy_crit;
-        else HIP_TRY(hipMemcpyAsync(f->lossy, p->h_lossy_crit, (size_t)d.n_nodes * 2, hipMemcpyHostToDevice, s));
-    }
-    // the product kernels first; a window deeper than their stacks sends the pass round again.  The slow path's arena of an
-    // earlier run (up to 14 GB) went back to the pool when that run's emit completed (gki_finder_synchronize).
-    f->deep.cap = 0;
-    int64_t *tot = f->h_totals;       // pinned host memory: the two small copies are true async DMAs
-    unsigned long long bsum = 0;
-    for (;;) {
-        HIP_TRY(hipMemsetAsync(f->d_err, 0, 4, s));
-        HIP_TRY(hipMemsetAsync(f->d_bsum, 0, 8, s));
+    return GKI_OK;
+}
 
-        HIP_TRY(hipEventRecord(f->ev[0], s));
-        if (n_run > 0) {
-            // one group of 256 nodes per workgroup, no grid-stride loop: with 2048 workgroups of 29 groups each (7 fit a CU,
-            // an eighth waits) the pass took 0.70 ms, with one group each 0.59 (GKI_CNT_BLOCKS sweeps it in tuning builds)
-            const int64_t want = ceil_div(n_run, 64 * CNT_WPB), cap = GKI_KNOB("GKI_CNT_BLOCKS", 1 << 30);
-            const int count_grid = (int)(want < cap ? want : cap);
-            const int cnt_pad = GKI_KNOB("GKI_CNT_LDS_PAD", 0);   // tuning builds: unused dynamic LDS, to lower the occupancy
-            const DeepArena da = f->deep;
-            if (da.cap > 0) {
-                const dim3 dgrid((unsigned)(da.lanes / (64 * CNT_WPB)));
-                if (a.nflags && a.has_lossy)
-                    hipLaunchKernelGGL((k_count_boundary<true, true, true>), dgrid, dim3(64 * CNT_WPB), 0, s, d, a, f->lossy_cur, f->bcount, f->total, f->d_err, da);
-                else if (a.nflags)
-                    hipLaunchKernelGGL((k_count_boundary<false, true, true>), dgrid, dim3(64 * CNT_WPB), 0, s, d, a, f->lossy_cur, f->bcount, f->total, f->d_err, da);
-                else if (a.has_lossy)
-                    hipLaunchKernelGGL((k_count_boundary<true, false, true>), dgrid, dim3(64 * CNT_WPB), 0, s, d, a, f->lossy_cur, f->bcount, f->total, f->d_err, da);
-                else
-                    hipLaunchKernelGGL((k_count_boundary<false, false, true>), dgrid, dim3(64 * CNT_WPB), 0, s, d, a, f->lossy_cur, f->bcount, f->total, f->d_err, da);
-            }
-            else if (a.nflags && a.has_lossy)
-                hipLaunchKernelGGL((k_count_boundary<true, true>), dim3(count_grid), dim3(64 * CNT_WPB), cnt_pad, s, d, a, f->lossy_cur,
-                                   f->bcount, f->total, f->d_err, da);
-            else if (a.nflags)
-                hipLaunchKernelGGL((k_count_boundary<false, true>), dim3(count_grid), dim3(64 * CNT_WPB), cnt_pad, s, d, a, f->lossy_cur,
-                                   f->bcount, f->total, f->d_err, da);
-            else if (a.has_lossy)
-                hipLaunchKernelGGL((k_count_boundary<true, false>), dim3(count_grid), dim3(64 * CNT_WPB), cnt_pad, s, d, a, f->lossy_cur,
-                                   f->bcount, f->total, f->d_err, da);
-            else
-                hipLaunchKernelGGL((k_count_boundary<false, false>), dim3(count_grid), dim3(64 * CNT_WPB), cnt_pad, s, d, a, f->lossy_cur,
-                                   f->bcount, f->total, f->d_err, da);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipEventRecord(f->ev[1], s));
-        HIP_TRY(hipEventRecord(f->ev[6], s));
-        // records of nodes [n0, n1) only: rec_base[n0 + i] = exclusive prefix inside the run, rec_base[n1] = total
-        GKI_TRY(gki_scan_u32_to_i64(f->total + a.n0, n_run, f->rec_base + a.n0, f->scan_tmp, f->scan_tmp_bytes, s));
-        if (a.split)
-            GKI_TRY(gki_scan_u32_to_i64(f->bcount + a.n0, n_run, f->bnd_base + a.n0, f->scan_tmp, f->scan_tmp_bytes, s));
-        if (n_run > 0) {
-            // one node per thread, no grid-stride loop: a thread's loads and its 48-byte store form one dependent chain, so the
-            // kernel lives on the number of chains in flight
-            hipLaunchKernelGGL(k_node_emit, dim3((unsigned)ceil_div(n_run, 256)), dim3(256), 0, s, d, a, f->lossy_cur, f->bcount,
-                               f->rec_base, f->ne, a.split ? f->blk : nullptr);
-            HIP_TRY(hipGetLastError());
-        }
-        if (n_run > 0 && !a.split) {
-            hipLaunchKernelGGL(k_sum_u32, dim3(stream_grid(n_run, 256)), dim3(256), 0, s, f->bcount + a.n0, n_run, f->d_bsum);
-            HIP_TRY(hipGetLastError());
-        }
-        hipLaunchKernelGGL(k_totals, dim3(1), dim3(1), 0, s, f->rec_base, f->bnd_base, a.n1, a.split, f->d_err, f->d_totals);
+// One pass over the run with the product kernels, or (f->deep.cap > 0) their deep variants: boundary count, the scans,
+// the per-node constants, the totals; h_totals[0..4] hold what it found when it returns.
+int count_pass(gki_finder *f) {
+    const DevGraph &d = f->g->d;
+    const FindArgs &a = f->args;
+    hipStream_t s = f->stream;
+    const int64_t n_run = a.n1 - a.n0;
+    uint32_t *bcount = f->bcount.get<uint32_t>(), *total = f->total.get<uint32_t>();
+    int64_t *rec_base = f->rec_base.get<int64_t>(), *bnd_base = f->bnd_base.get<int64_t>();
+    int *d_err = f->d_err.get<int>();
+    unsigned long long *d_bsum = f->d_bsum.get<unsigned long long>();
+    int64_t *tot = f->h_totals;       // pinned host memory: the two small copies are true async DMAs
+    HIP_TRY(hipMemsetAsync(d_err, 0, 4, s));
+    HIP_TRY(hipMemsetAsync(d_bsum, 0, 8, s));
+
+    HIP_TRY(hipEventRecord(f->ev[0], s));
+    if (n_run > 0) {
+        // one group of 256 nodes per workgroup, no grid-stride loop: with 2048 workgroups of 29 groups each (7 fit a CU,
+        // an eighth waits) the pass took 0.70 ms, with one group each 0.59 (GKI_CNT_BLOCKS sweeps it in tuning builds)
+        const int64_t want = ceil_div(n_run, 64 * CNT_WPB), cap = GKI_KNOB("GKI_CNT_BLOCKS", 1 << 30);
+        const int cnt_pad = GKI_KNOB("GKI_CNT_LDS_PAD", 0);   // tuning builds: unused dynamic LDS, to lower the occupancy
+        const DeepArena da = f->deep.view();
+        const bool deep = da.cap > 0;                         // the arena's grid
+        const dim3 grid((unsigned)(deep ? da.lanes / (64 * CNT_WPB) : (want < cap ? want : cap)));
+        with_bools([&](auto HAS_LOSSY, auto GEN, auto DEEP) {
+            hipLaunchKernelGGL((k_count_boundary<decltype(HAS_LOSSY)::value, decltype(GEN)::value, decltype(DEEP)::value>), grid, dim3(64 * CNT_WPB),
+                               deep ? 0 : cnt_pad, s, d, a, f->lossy_cur, bcount, total, d_err, da);
+        }, a.has_lossy != 0, a.nflags != nullptr, deep);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(f->ev[7], s));
-        HIP_TRY(hipMemcpyAsync(tot, f->d_totals, 32, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(tot + 4, f->d_bsum, 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        bsum = (unsigned long long)tot[4];
-        const int run_err = gki_error_of_word(tot[1]);
-        if (run_err == GKI_ERR_NOT_ONE_REF_SUCC && !(tot[1] & 2))
-            return gki_set_error(GKI_ERR_NOT_ONE_REF_SUCC, "a window at the variant limit ends a node that does not have exactly one "
-                                 "linear-ref successor: the reference asserts here (kmer_finder.py:402); raise max_variant_nodes");
-        if (run_err == GKI_OK) break;
-        // GKI_ERR_WINDOW_TOO_DEEP.  Bit 1 of the word: a stack of the walk (or of a history) was too short -- the slow path:
-        // the pass again with the deep kernel variants, their stacks in an arena of twice the levels each time round.
-        // Bit 2: a history enumeration ran out of its step budget, which no depth cures.
-        const int next_cap = f->deep.cap == 0 ? 4 * MAXN : 2 * f->deep.cap;
-        if ((tot[1] & 4) || !(tot[1] & 2) || next_cap > GKI_MAX_DEEP_WINDOW_NODES)
-            return gki_set_error(GKI_ERR_WINDOW_TOO_DEEP, (tot[1] & 4) ? "the k-windows ending in one node (or the histories that decide one of them) take more "
-                                 "than %d descents to enumerate: too many paths" : "a k-window (or the history that decides it) crosses more than %d nodes",
-                                 (tot[1] & 4) ? STEP_BUDGET : GKI_MAX_DEEP_WINDOW_NODES - 2);
-        {
-            // 64 workgroups walk the run (grid-stride): 16 384 lanes x cap levels x 70 bytes = 0.3 GB at the first cap
-            const int64_t lanes = 64 * 256, bytes = lanes * (int64_t)next_cap * DA_CELL;
-            if (bytes > f->deep_bytes) {
-                if (f->deep.base) HIP_TRY(gki_dev_free(f->deep.base));
-                f->deep.base = nullptr; f->deep_bytes = 0;
-                HIP_TRY(gki_dev_malloc((void **)&f->deep.base, (size_t)bytes));
-                f->deep_bytes = bytes;
-            }
-            f->deep.lanes = lanes; f->deep.cap = next_cap; f->deep.pad = 0;
-        }
     }
-    if (a.split) bsum = (unsigned long long)tot[2];
+    HIP_TRY(hipEventRecord(f->ev[1], s));
+    HIP_TRY(hipEventRecord(f->ev[6], s));
+    // records of nodes [n0, n1) only: rec_base[n0 + i] = exclusive prefix inside the run, rec_base[n1] = total
+    GKI_TRY(gki_scan_u32_to_i64(total + a.n0, n_run, rec_base + a.n0, f->scan_tmp.get(), f->scan_tmp_bytes, s));
+    if (a.split)
+        GKI_TRY(gki_scan_u32_to_i64(bcount + a.n0, n_run, bnd_base + a.n0, f->scan_tmp.get(), f->scan_tmp_bytes, s));
+    if (n_run > 0) {
+        // one node per thread, no grid-stride loop: a thread's loads and its 48-byte store form one dependent chain, so the
+        // kernel lives on the number of chains in flight
+        hipLaunchKernelGGL(k_node_emit, dim3((unsigned)ceil_div(n_run, 256)), dim3(256), 0, s, d, a, f->lossy_cur, bcount,
+                           rec_base, f->ne.get<NodeEmit>(), a.split ? f->blk.get<BlkFirst>() : nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    if (n_run > 0 && !a.split) {
+        hipLaunchKernelGGL(k_sum_u32, dim3(stream_grid(n_run, 256)), dim3(256), 0, s, bcount + a.n0, n_run, d_bsum);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_totals, dim3(1), dim3(1), 0, s, rec_base, bnd_base, a.n1, a.split, d_err, f->d_totals.get<int64_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(f->ev[7], s));
+    HIP_TRY(hipMemcpyAsync(tot, f->d_totals.get(), 32, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(tot + 4, d_bsum, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return GKI_OK;
+}
+
+// what the emit calls need of a finished count: the record totals and the words of the sequence the node range covers
+void count_finish(gki_finder *f) {
+    const DevGraph &d = f->g->d;
+    const FindArgs &a = f->args;
+    const int64_t *tot = f->h_totals;
+    const int64_t bsum = a.split ? tot[2] : tot[4];
     f->n_records = tot[0];
-    f->n_boundary_records = (int64_t)bsum;
-    f->n_interior_records = tot[0] - (int64_t)bsum;
-    // words of the sequence covered by the node range
+    f->n_boundary_records = bsum;
+    f->n_interior_records = tot[0] - bsum;
     int64_t p0 = 0, p1 = d.n_bases;
     if (!a.rank && (a.node_begin > 0 || a.node_end < d.n_nodes)) {
         int64_t nb = a.node_begin < d.n_nodes ? a.node_begin : d.n_nodes;
@@ -1962,7 +1828,65 @@ int gki_finder_count(gki_finder *f, const gki_find_params *p, int64_t *n_records
     f->p_end = p1;
     f->ev_valid[0] = true; f->ev_valid[3] = true;
     f->counted = true;
-    *n_records = tot[0];
+}
+
+}  // namespace
+
+extern "C" {
+
+int gki_finder_create(gki_graph *g, gki_finder **out) {
+    *out = nullptr;
+    if (!g) return gki_set_error(GKI_ERR_BAD_ARG, "finder_create: graph is NULL");
+    GKI_TRY(gki_check_graph_device(g, "gki_finder_create"));
+    gki_finder *f = new gki_finder();
+    f->g = g;
+    const int rc = finder_init(f, g);
+    if (rc != GKI_OK) { (void)gki_finder_destroy(f); return rc; }      // nothing of a half-built finder stays behind
+    *out = f;
+    return GKI_OK;
+}
+
+int gki_finder_destroy(gki_finder *f) {
+    if (!f) return GKI_OK;
+    if (f->stream) (void)hipStreamSynchronize(f->stream);
+    if (f->stream2) (void)hipStreamSynchronize(f->stream2);
+    if (f->h_totals) (void)hipHostFree(f->h_totals);
+    for (int i = 0; i < 8; i++) if (f->ev[i]) (void)hipEventDestroy(f->ev[i]);
+    if (f->ev_ready) (void)hipEventDestroy(f->ev_ready);
+    if (f->ev_join) (void)hipEventDestroy(f->ev_join);
+    if (f->stream) (void)hipStreamDestroy(f->stream);
+    if (f->stream2) (void)hipStreamDestroy(f->stream2);
+    delete f;                                 // (its device buffers go back to the pool)
+    return GKI_OK;
+}
+
+int gki_finder_count(gki_finder *f, const gki_find_params *p, int64_t *n_records) {
+    *n_records = 0;
+    f->counted = false;
+    GKI_TRY(count_setup(f, p));
+    // the product kernels first; a window deeper than their stacks sends the pass round again with the deep kernel variants,
+    // their stacks in the arena (bit 1 of the error word; gki_deep_next_cap).  The slow path's arena of an earlier run (up to
+    // 14 GB) went back to the pool when that run's emit completed (gki_finder_synchronize).
+    f->deep.cap = 0;
+    for (;;) {
+        GKI_TRY(count_pass(f));
+        const int next_cap = gki_deep_next_cap(f->h_totals[1], f->deep.cap, 4 * MAXN);
+        if (!next_cap) break;
+        // 16 384 lanes x cap levels x 70 bytes = 0.3 GB at the first cap
+        HIP_TRY(f->deep.grow(next_cap, DA_CELL));
+    }
+    const int64_t word = f->h_totals[1];
+    const int run_err = gki_error_of_word(word);
+    if (run_err == GKI_ERR_NOT_ONE_REF_SUCC)
+        return gki_set_error(GKI_ERR_NOT_ONE_REF_SUCC, "a window at the variant limit ends a node that does not have exactly one "
+                             "linear-ref successor: the reference asserts here (kmer_finder.py:402); raise max_variant_nodes");
+    // GKI_ERR_WINDOW_TOO_DEEP.  Bit 2: a history enumeration ran out of its step budget, which no depth cures.
+    if (run_err != GKI_OK)
+        return gki_set_error(GKI_ERR_WINDOW_TOO_DEEP, (word & 4) ? "the k-windows ending in one node (or the histories that decide one of them) take more "
+                             "than %d descents to enumerate: too many paths" : "a k-window (or the history that decides it) crosses more than %d nodes",
+                             (word & 4) ? STEP_BUDGET : GKI_MAX_DEEP_WINDOW_NODES - 2);
+    count_finish(f);
+    *n_records = f->n_records;
     return GKI_OK;
 }
 
@@ -1980,10 +1904,7 @@ int gki_finder_emit_v2(gki_finder *f, void *d_hashes, void *d_start_nodes, void 
 int gki_finder_synchronize(gki_finder *f) {
     HIP_TRY(hipStreamSynchronize(f->stream));
     HIP_TRY(hipStreamSynchronize(f->stream2));
-    if (f->deep.base) {                                           // the emit kernels are done with the slow path's stacks
-        (void)gki_dev_free(f->deep.base);
-        f->deep.base = nullptr; f->deep_bytes = 0;                // (cap stays: a second emit of this run allocates them again)
-    }
+    f->deep.release();            // the emit kernels are done with the slow path's stacks (cap stays: a second emit of this run allocates them again)
     if (f->emit_pending) {
         f->emit_pending = false;
         const int64_t word = f->h_totals[5] & 0xFFFFFFFFll;

@@ -10,10 +10,7 @@
 #include <math.h>
 
 namespace {
-#ifndef GKI_FWD_LEVELS
-#define GKI_FWD_LEVELS GKI_MAX_WINDOW_NODES
-#endif
-constexpr int FMAX = GKI_FWD_LEVELS;
+constexpr int FMAX = GKI_MAX_WINDOW_NODES;
 
 struct FwdOut { int64_t *hash; int32_t *start_node; int16_t *start_offset; int32_t *node; double *af; };
 
@@ -22,19 +19,16 @@ struct FwdOut { int64_t *hash; int32_t *start_node; int16_t *start_offset; int32
 // reads stay in L2 -- 2.98 -> 2.79 ms per batch of 1.14e7 start positions, same box, alternating.  In all-nodes mode a
 // lane writes a k-mer's records (one per path node) into consecutive slots and the plain stores merge into whole lines
 // in L2; the hint sends every partial line to memory on its own: 3.96 -> 7.3 ms, so that mode keeps plain stores
-// (profiles/r03_forward_nt_stores_ab.txt; -DGKI_FWD_NT=0 / =2 rebuild the two partners: hint nowhere / everywhere).
-#ifndef GKI_FWD_NT
-#define GKI_FWD_NT 1
-#endif
+// (profiles/r03_forward_nt_stores_ab.txt).
 template <bool NT, class T> __device__ __forceinline__ void fst(T *p, T v) { if (NT) __builtin_nontemporal_store(v, p); else *p = v; }
 template <bool ONE>
 __device__ __forceinline__ void put_record(const FwdOut &out, int64_t idx, uint64_t h, int32_t end_node, int end_off, int32_t node, double af) {
-    constexpr bool NT = GKI_FWD_NT == 2 || (GKI_FWD_NT == 1 && ONE);
+    constexpr bool NT = ONE;
     fst<NT>(&out.hash[idx], (int64_t)h); fst<NT>(&out.start_node[idx], end_node); fst<NT>(&out.start_offset[idx], (int16_t)end_off);
     fst<NT>(&out.node[idx], node); fst<NT>(&out.af[idx], af);
 }
 
-// "Script" of a search (GKI_FWD_SCRIPT, round 3): the emit pass used to repeat the count pass's whole walk.  Instead the
+// "Script" of a search (round 3): the emit pass used to repeat the count pass's whole walk.  Instead the
 // count pass writes every finished k-mer down -- hash, end position, minimum allele frequency, the path's nodes, the
 // number of the k-mer's first record among its start position's -- in one of FW_SLOTS 48-byte entries per start position,
 // and the emit pass is a streaming expansion with one thread per entry.  A start position with more finished k-mers, a
@@ -46,26 +40,16 @@ __device__ __forceinline__ void put_record(const FwdOut &out, int64_t idx, uint6
 // all-nodes mode 4.16 -> 3.73 ms, and 3.75 -> 3.21 ms with short_path_facts below; one node per k-mer 2.98 -> 3.06 ms
 // with round 3's layout of the script.  With round 4's (below) both modes take it: 3 Gbp graph, 3.43e7 start positions,
 // all nodes 8.1 -> 6.2 ms, one node per k-mer 6.7 -> 5.1 ms (profiles/r04_forward_script_layout_ab.txt).
-#ifndef GKI_FWD_SCRIPT
-#define GKI_FWD_SCRIPT 1
-#endif
-// Layout (GKI_FWD_SCRIPT_SOA, round 4): the three 16-byte pieces of slot c of start position i lie at
+// Layout (round 4): the three 16-byte pieces of slot c of start position i lie at
 // [(c * 3 + piece) * n_pos + i] -- the lanes of a wave (neighbouring start positions, mostly in step) write a piece of
 // their c-th k-mer into consecutive 16-byte cells, whole lines per store instruction, and slots nobody uses are lines nobody
 // touches.  (Rounds 3-4 had the four 48-byte entries of a start position side by side, 192 B apart from lane to lane: 64
 // partly written lines per store instruction, and the script's 100 written bytes per start position cost the count pass
-// 1.9 ms on top of a 2.9 ms walk.)  =0 rebuilds that layout.
-#ifndef GKI_FWD_SCRIPT_ONE
-#define GKI_FWD_SCRIPT_ONE 1
-#endif
-#ifndef GKI_FWD_SCRIPT_SOA
-#define GKI_FWD_SCRIPT_SOA 1
-#endif
+// 1.9 ms on top of a 2.9 ms walk.)
 constexpr int FW_SLOTS = 4, FW_SN = 5, FW_ENTRY_U4 = 3;
 // cell of (start position i, slot c, piece p) in units of uint4
 __device__ __forceinline__ size_t script_cell(int64_t i, int c, int p, int64_t n_pos) {
-    return GKI_FWD_SCRIPT_SOA ? (size_t)(c * FW_ENTRY_U4 + p) * (size_t)n_pos + (size_t)i
-                              : ((size_t)i * FW_SLOTS + (size_t)c) * FW_ENTRY_U4 + (size_t)p;
+    return (size_t)(c * FW_ENTRY_U4 + p) * (size_t)n_pos + (size_t)i;
 }
 // An entry: piece 0 = (hash, minimum allele frequency); piece 1 = (end node q, end offset | records << 16 | flags << 24, first two
 // nodes of the list); piece 2 = (the list's third and fourth node), written and read only when the list is that long.  The
@@ -73,17 +57,11 @@ __device__ __forceinline__ size_t script_cell(int64_t i, int c, int p, int64_t n
 // that completes the k-mer -- is two pieces); in one-node mode (flag bit 0) the one node the record reports.  The number of
 // the entry's first record among its start position's is not stored: it is the sum of the records of the slots before it.
 // The script's cells leave with the non-temporal hint: they are read once, by another kernel, and the lines of the graph the
-// walk reads stay in L2 -- all nodes 4.27 -> 3.97 ms, same box, alternating (profiles/r04_forward_script_layout_ab.txt;
-// -DGKI_FWD_SCRIPT_NT=0 rebuilds the plain stores).
-#ifndef GKI_FWD_SCRIPT_NT
-#define GKI_FWD_SCRIPT_NT 1
-#endif
+// walk reads stay in L2 -- all nodes 4.27 -> 3.97 ms, same box, alternating (profiles/r04_forward_script_layout_ab.txt).
 __device__ __forceinline__ void script_store(uint4 *p, const uint4 &v) {
-    if (GKI_FWD_SCRIPT_NT) {
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        u32x4 t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
-        __builtin_nontemporal_store(t, reinterpret_cast<u32x4 *>(p));
-    } else *p = v;
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    u32x4 t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
+    __builtin_nontemporal_store(t, reinterpret_cast<u32x4 *>(p));
 }
 __device__ __forceinline__ void script_write(uint4 *script, int64_t i, int c, int64_t n_pos, uint64_t h, double maf, int32_t q, int off, int lw,
                                              bool one_node, const int32_t *nodes) {
@@ -122,20 +100,14 @@ enum { FW_NM = 0, FW_CE = 8, FW_HS = 16, FW_MF = 24, FW_LAST = 32, FW_CELL = 36 
 // up and the call refused, as in the finder (csrc/gki_finder.hip, STEP_BUDGET).
 constexpr int FW_BUDGET = 1 << 22, FW_BUDGET_FROM = 8;     // (every step of this walk reads global memory: ~1 us each)
 
-// The walk's levels: the first GKI_FWD_REG_LEVELS of them in registers (a read is a select over R values, a write R
+// The walk's levels: the first FWD_REG_LEVELS of them in registers (a read is a select over R values, a write R
 // predicated moves), the rest in the stack behind (scratch; the slow path's arena).  A forward path of the usual search --
 // the start node, an allele, the node that completes the k-mer, which is never stored -- lives in two levels, so the
 // product kernel touches no scratch at all for it (rounds 2-4 kept every level in scratch: three stores per descent and
 // two loads per turn of the loop, each a trip to L2 -- a wave's levels do not fit L1 beside its neighbours').
-#ifndef GKI_FWD_BLOCK
-#define GKI_FWD_BLOCK 64                  // threads per workgroup of the product kernels (one start position per lane)
-#endif
-#ifndef GKI_FWD_WAVES
-#define GKI_FWD_WAVES 8                   // waves per SIMD the product kernels are held to
-#endif
-#ifndef GKI_FWD_REG_LEVELS
-#define GKI_FWD_REG_LEVELS 2
-#endif
+constexpr int FWD_BLOCK = 64;             // threads per workgroup of the product kernels (one start position per lane)
+constexpr int FWD_WAVES = 8;              // waves per SIMD the product kernels are held to
+constexpr int FWD_REG_LEVELS = 2;
 // (the register levels are a variable of their own, apart from the stack behind them: one aggregate holding both is one
 // stack object to the compiler, and the dynamically indexed part keeps the whole of it in scratch)
 template <class T, int R> struct RegLevels { T r[R > 0 ? R : 1]; };
@@ -187,7 +159,7 @@ __device__ void forward_walk(const DevGraph &g, const NodeFwd *__restrict__ fw, 
                              int32_t n0, int32_t o0, int64_t idx, FwdOut out, uint32_t *count_out, int *err,
                              const DeepArena &da, int64_t lane_global, uint4 *script, int64_t pos, int64_t n_pos, uint32_t *used_out) {
     static_assert(!SCRIPT || (!EMIT && !DEEP), "the script is written by the product count kernel");
-    constexpr int R = DEEP ? 0 : GKI_FWD_REG_LEVELS;
+    constexpr int R = DEEP ? 0 : FWD_REG_LEVELS;
     uint32_t used = 0;                        // SCRIPT: entries written, 0xFF = this start position does not fit
     // Per level four 64-bit words: (node, meta) with meta = bases collected (8 bits) | "forced traversal" (8) | variant
     // nodes on the path (16); the successors still to take (cur, end); the hash so far; the smallest allele frequency on the
@@ -386,7 +358,7 @@ __device__ void forward_walk(const DevGraph &g, const NodeFwd *__restrict__ fw, 
 // neighbours, and they wait for it (a refilling state-machine form of the walk was tried against that and was slower:
 // profiles/r04_forward_node_records_ab.txt).
 template <bool EMIT, bool DEEP = false, bool SCRIPT = false>
-__global__ __launch_bounds__(DEEP ? 64 : GKI_FWD_BLOCK, DEEP ? 1 : GKI_FWD_WAVES) void k_forward(DevGraph g, const NodeFwd *__restrict__ fw, int k, int M, int one_node, const uint8_t *__restrict__ follow,
+__global__ __launch_bounds__(DEEP ? 64 : FWD_BLOCK, DEEP ? 1 : FWD_WAVES) void k_forward(DevGraph g, const NodeFwd *__restrict__ fw, int k, int M, int one_node, const uint8_t *__restrict__ follow,
                                                 const int32_t *__restrict__ nodes,
                                                 const int32_t *__restrict__ offsets, int64_t n_pos,
                                                 uint32_t *__restrict__ cnt, const int64_t *__restrict__ rec_start, FwdOut out,
@@ -491,37 +463,49 @@ __global__ __launch_bounds__(256) void k_build_fwd(DevGraph g, NodeFwd *__restri
 namespace {
 // the search's per-node records: built by the first search on a graph (and again after gki_graph_prepare), 32 B per node
 int fwd_nodes_ready(gki_graph *gr) {
-    if (gr->fwd_nodes) return GKI_OK;
-    NodeFwd *p = nullptr;
-    if (gki_dev_malloc(&p, (size_t)gr->d.n_nodes * sizeof(NodeFwd)) != hipSuccess) {
+    if (gr->fwd_nodes.get()) return GKI_OK;
+    if (gr->fwd_nodes.alloc((size_t)gr->d.n_nodes * sizeof(NodeFwd)) != hipSuccess) {
         (void)hipGetLastError();
         return gki_set_error(GKI_ERR_HIP, "forward search: no memory for %lld node records", (long long)gr->d.n_nodes);
     }
-    hipLaunchKernelGGL(k_build_fwd, dim3(stream_grid(gr->d.n_nodes, 256)), dim3(256), 0, 0, gr->d, p);
+    hipLaunchKernelGGL(k_build_fwd, dim3(stream_grid(gr->d.n_nodes, 256)), dim3(256), 0, 0, gr->d, gr->fwd_nodes.get<NodeFwd>());
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(0);
-    if (e != hipSuccess) { (void)gki_dev_free(p); HIP_TRY(e); }
-    gr->fwd_nodes = p;
+    if (e != hipSuccess) { gr->fwd_nodes.reset(); HIP_TRY(e); }
     return GKI_OK;
 }
 
 // the slow path's arena: grown by the call that needs it, returned to the pool when the search is over
 void deep_release(gki_graph *gr) {
-    if (gr->fwd_deep.base) (void)gki_dev_free(gr->fwd_deep.base);
-    gr->fwd_deep = DeepArena{nullptr, 0, 0, 0};
-    gr->fwd_deep_bytes = 0;
+    gr->fwd_deep.release();
+    gr->fwd_deep.cap = 0;
 }
 int deep_grow(gki_graph *gr, int next_cap) {
-    const int64_t lanes = 64 * 256, bytes = lanes * (int64_t)next_cap * FW_CELL;
-    if (bytes > gr->fwd_deep_bytes) {
-        if (gr->fwd_deep.base) (void)gki_dev_free(gr->fwd_deep.base);
-        gr->fwd_deep.base = nullptr; gr->fwd_deep_bytes = 0;
-        if (gki_dev_malloc((void **)&gr->fwd_deep.base, (size_t)bytes) != hipSuccess)
-            return gki_set_error(GKI_ERR_HIP, "forward search: no memory for %lld bytes of deep stacks", (long long)bytes);
-        gr->fwd_deep_bytes = bytes;
-    }
-    gr->fwd_deep.lanes = lanes; gr->fwd_deep.cap = next_cap; gr->fwd_deep.pad = 0;
+    if (gr->fwd_deep.grow(next_cap, FW_CELL) != hipSuccess)
+        return gki_set_error(GKI_ERR_HIP, "forward search: no memory for %lld bytes of deep stacks",
+                             (long long)(DeepArenaOwner::LANES * (int64_t)next_cap * FW_CELL));
     return GKI_OK;
+}
+
+// what every pass of one search is given
+struct FwdCall {
+    int k, M, one_node;
+    const uint8_t *follow;
+    const int32_t *nodes, *offsets;
+    int64_t n_pos;
+    int *d_err;
+};
+
+// One launch of the walking kernel without a script to write, k_forward<EMIT, DEEP>.  The product kernel: one lane for each
+// of `n_lanes` start positions; da.cap > 0: the deep variant on the arena's lanes.  used / list / list_n: see k_forward.
+void launch_walk(gki_graph *gr, const FwdCall &c, bool emit, const DeepArena &da, int64_t n_lanes, uint32_t *cnt, const int64_t *rec_start,
+                 const FwdOut &out, uint8_t *used, int64_t *list, int64_t list_n) {
+    const bool deep = da.cap > 0;
+    const dim3 grid((unsigned)(deep ? da.lanes / 64 : ceil_div(n_lanes, FWD_BLOCK))), block(deep ? 64 : FWD_BLOCK);
+    with_bools([&](auto EMIT, auto DEEP) {
+        hipLaunchKernelGGL((k_forward<decltype(EMIT)::value, decltype(DEEP)::value>), grid, block, 0, 0, gr->d, gr->fwd_nodes.get<NodeFwd>(), c.k, c.M, c.one_node, c.follow,
+                           c.nodes, c.offsets, c.n_pos, cnt, rec_start, out, c.d_err, da, (uint4 *)nullptr, used, list, list_n);
+    }, emit, deep);
 }
 
 }  // namespace
@@ -535,62 +519,54 @@ int gki_forward_count(gki_graph *gr, int k, int max_variant_nodes, int one_node,
     GKI_TRY(gki_check_graph_device(gr, "gki_forward_count"));
     if (n_pos <= 0) { HIP_TRY(hipMemset(d_rec_start, 0, 8)); return GKI_OK; }
     GKI_TRY(fwd_nodes_ready(gr));
-    deep_release(gr);                     // a slow-path arena of an earlier search goes back to the pool (up to 5.6 GB)
+    deep_release(gr);                     // a slow-path arena of an earlier search goes back to the pool (up to 5.6 GB); the
+                                          // product kernel first, and the emit call that follows uses what this call settles on
     int64_t tmp_bytes = gki_scan_tmp_bytes(n_pos);
     DevBuf cnt_b, tmp, d_err_b;
     HIP_TRY(cnt_b.alloc((size_t)n_pos * 4));
     HIP_TRY(tmp.alloc((size_t)tmp_bytes));
     HIP_TRY(d_err_b.alloc(8));                          // [0] the error word, [1] start positions that did not fit the script
     uint32_t *cnt = cnt_b.get<uint32_t>();
-    int *d_err = d_err_b.get<int>();
-    FwdOut none{nullptr, nullptr, nullptr, nullptr, nullptr};
-    const int M = max_variant_nodes > 250 ? 250 : max_variant_nodes;
-    gr->fwd_deep.cap = 0;                 // the product kernel first; the emit call that follows uses what this call settles on
+    const FwdOut none{nullptr, nullptr, nullptr, nullptr, nullptr};
+    const FwdCall c{k, max_variant_nodes > 250 ? 250 : max_variant_nodes, one_node, (const uint8_t *)d_follow, (const int32_t *)d_nodes,
+                    (const int32_t *)d_offsets, n_pos, d_err_b.get<int>()};
     // the script for the emit call (see FW_SLOTS above); without memory for it the emit call walks as it always did
     script_drop(gr);
     FwdScript &sc = gr->fwd_script;
-    if (GKI_FWD_SCRIPT && (!one_node || GKI_FWD_SCRIPT_ONE)) {
-        if (gki_dev_malloc(&sc.entries, (size_t)n_pos * FW_SLOTS * FW_ENTRY_U4 * 16) != hipSuccess ||
-            gki_dev_malloc((void **)&sc.ncomp, (size_t)n_pos) != hipSuccess) { (void)hipGetLastError(); script_drop(gr); }
-        else {
-            sc.over_cap = n_pos < (1 << 20) ? n_pos : (1 << 20);
-            if (gki_dev_malloc((void **)&sc.over_list, (size_t)sc.over_cap * 8) != hipSuccess) { (void)hipGetLastError(); sc.over_list = nullptr; sc.over_cap = 0; }
-        }
+    if (sc.entries.alloc((size_t)n_pos * FW_SLOTS * FW_ENTRY_U4 * 16) != hipSuccess || sc.ncomp.alloc((size_t)n_pos) != hipSuccess) {
+        (void)hipGetLastError(); script_drop(gr);
+    } else {
+        sc.over_cap = n_pos < (1 << 20) ? n_pos : (1 << 20);
+        if (sc.over_list.alloc((size_t)sc.over_cap * 8) != hipSuccess) { (void)hipGetLastError(); sc.over_cap = 0; }
     }
     int64_t total = 0; int word[2] = {0, 0};
     auto passes = [&]() -> int {
         for (;;) {
-            const DeepArena da = gr->fwd_deep;
-            HIP_TRY(hipMemset(d_err, 0, 8));
-            if (da.cap > 0) {
-                script_drop(gr);                // the slow path writes no script
-                hipLaunchKernelGGL((k_forward<false, true>), dim3((unsigned)(da.lanes / 64)), dim3(64), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
-                                   (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, cnt, (const int64_t *)nullptr, none, d_err, da,
-                                   (uint4 *)nullptr, (uint8_t *)nullptr, (int64_t *)nullptr, (int64_t)0);
-            } else if (sc.entries)
-                hipLaunchKernelGGL((k_forward<false, false, true>), dim3((unsigned)ceil_div(n_pos, GKI_FWD_BLOCK)), dim3(GKI_FWD_BLOCK), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
-                                   (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, cnt, (const int64_t *)nullptr, none, d_err, da,
-                                   (uint4 *)sc.entries, sc.ncomp, sc.over_list, sc.over_cap);
+            const DeepArena da = gr->fwd_deep.view();
+            HIP_TRY(hipMemset(c.d_err, 0, 8));
+            if (da.cap > 0) script_drop(gr);            // the slow path writes no script
+            if (sc.entries.get())
+                hipLaunchKernelGGL((k_forward<false, false, true>), dim3((unsigned)ceil_div(n_pos, FWD_BLOCK)), dim3(FWD_BLOCK), 0, 0, gr->d, gr->fwd_nodes.get<NodeFwd>(), c.k, c.M, c.one_node, c.follow,
+                                   c.nodes, c.offsets, n_pos, cnt, (const int64_t *)nullptr, none, c.d_err, da,
+                                   sc.entries.get<uint4>(), sc.ncomp.get<uint8_t>(), sc.over_list.get<int64_t>(), sc.over_cap);
             else
-                hipLaunchKernelGGL((k_forward<false, false>), dim3((unsigned)ceil_div(n_pos, GKI_FWD_BLOCK)), dim3(GKI_FWD_BLOCK), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
-                                   (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, cnt, (const int64_t *)nullptr, none, d_err, da,
-                                   (uint4 *)nullptr, (uint8_t *)nullptr, (int64_t *)nullptr, (int64_t)0);
+                launch_walk(gr, c, false, da, n_pos, cnt, nullptr, none, nullptr, nullptr, 0);
             if (hipGetLastError() != hipSuccess) return gki_set_error(GKI_ERR_HIP, "k_forward launch failed");
             GKI_TRY(gki_scan_u32_to_i64(cnt, n_pos, (int64_t *)d_rec_start, tmp.get(), tmp_bytes, 0));
             HIP_TRY(hipMemcpy(&total, (const int64_t *)d_rec_start + n_pos, 8, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(word, d_err, 8, hipMemcpyDeviceToHost));
-            // bit 1: a stack of the walk was too short -- again with the deep variant, twice the levels each time round
-            const int next_cap = da.cap == 0 ? 4 * FMAX : 2 * da.cap;
-            if (!(word[0] & 2) || (word[0] & 4) || next_cap > GKI_MAX_DEEP_WINDOW_NODES) return GKI_OK;
+            HIP_TRY(hipMemcpy(word, c.d_err, 8, hipMemcpyDeviceToHost));
+            // bit 1: a stack of the walk was too short -- again with the deep variant (gki_deep_next_cap)
+            const int next_cap = gki_deep_next_cap(word[0], da.cap, 4 * FMAX);
+            if (!next_cap) return GKI_OK;
             GKI_TRY(deep_grow(gr, next_cap));
         }
     };
     const int rc = passes();
     const int herr = rc == GKI_OK ? gki_error_of_word(word[0]) : -1;
-    if (herr != GKI_OK || !sc.entries) script_drop(gr);
+    if (herr != GKI_OK || !sc.entries.get()) script_drop(gr);
     else {                                  // the emit call with these very arguments may expand the script
         sc.n_pos = n_pos; sc.overflow = word[1]; sc.nodes = d_nodes; sc.offsets = d_offsets; sc.follow = d_follow; sc.rec_start = d_rec_start;
-        sc.k = k; sc.M = M; sc.one_node = one_node ? 1 : 0; sc.valid = 1;
+        sc.k = k; sc.M = c.M; sc.one_node = one_node ? 1 : 0; sc.valid = 1;
     }
     if (rc != GKI_OK) return rc;
     if (herr == GKI_ERR_NOT_ONE_REF_SUCC)
@@ -610,9 +586,10 @@ int gki_forward_emit(gki_graph *gr, int k, int max_variant_nodes, int one_node, 
     GKI_TRY(fwd_nodes_ready(gr));
     DevBuf d_err_b;
     HIP_TRY(d_err_b.alloc(4));
-    int *d_err = d_err_b.get<int>();
-    FwdOut out{(int64_t *)d_hashes, (int32_t *)d_start_nodes, (int16_t *)d_start_offsets, (int32_t *)d_nodes_out, (double *)d_af64};
-    const int M = max_variant_nodes > 250 ? 250 : max_variant_nodes;
+    const FwdOut out{(int64_t *)d_hashes, (int32_t *)d_start_nodes, (int16_t *)d_start_offsets, (int32_t *)d_nodes_out, (double *)d_af64};
+    const FwdCall c{k, max_variant_nodes > 250 ? 250 : max_variant_nodes, one_node, (const uint8_t *)d_follow, (const int32_t *)d_nodes,
+                    (const int32_t *)d_offsets, n_pos, d_err_b.get<int>()};
+    const int64_t *rec_start = (const int64_t *)d_rec_start;
     FwdScript &sc = gr->fwd_script;
     int word = 0;
     // The arena state on the graph handle is whatever the LAST count call left (cap > 0: it needed the slow path), which
@@ -622,35 +599,25 @@ int gki_forward_emit(gki_graph *gr, int k, int max_variant_nodes, int one_node, 
     // written are written again with the same values.
     auto passes = [&]() -> int {
         for (;;) {
-            const DeepArena da = gr->fwd_deep;
-            HIP_TRY(hipMemset(d_err, 0, 4));
+            const DeepArena da = gr->fwd_deep.view();
+            HIP_TRY(hipMemset(c.d_err, 0, 4));
             const bool scripted = sc.valid && da.cap == 0 && sc.n_pos == n_pos && sc.nodes == d_nodes && sc.offsets == d_offsets && sc.follow == d_follow &&
-                                  sc.rec_start == d_rec_start && sc.k == k && sc.M == M && sc.one_node == (one_node ? 1 : 0);
-            if (da.cap > 0)
-                hipLaunchKernelGGL((k_forward<true, true>), dim3((unsigned)(da.lanes / 64)), dim3(64), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
-                                   (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, (uint32_t *)nullptr, (const int64_t *)d_rec_start, out, d_err, da,
-                                   (uint4 *)nullptr, (uint8_t *)nullptr, (int64_t *)nullptr, (int64_t)0);
-            else if (scripted) {
-                hipLaunchKernelGGL(k_forward_expand, dim3((unsigned)ceil_div(n_pos * FW_SLOTS, 256)), dim3(256), 0, 0, (const uint4 *)sc.entries, sc.ncomp,
-                                   (const int64_t *)d_rec_start, n_pos, out);
+                                  sc.rec_start == d_rec_start && sc.k == k && sc.M == c.M && sc.one_node == (one_node ? 1 : 0);
+            if (scripted) {
+                hipLaunchKernelGGL(k_forward_expand, dim3((unsigned)ceil_div(n_pos * FW_SLOTS, 256)), dim3(256), 0, 0, sc.entries.get<const uint4>(), sc.ncomp.get<const uint8_t>(),
+                                   rec_start, n_pos, out);
                 // the start positions the script could not hold are walked as before: those on the count pass's list, or -- when
                 // there were more than the list holds -- whichever the script marks, one lane per start position of the call
-                if (sc.overflow > 0 && sc.overflow <= sc.over_cap)
-                    hipLaunchKernelGGL((k_forward<true, false>), dim3((unsigned)ceil_div(sc.overflow, GKI_FWD_BLOCK)), dim3(GKI_FWD_BLOCK), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
-                                       (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, (uint32_t *)nullptr, (const int64_t *)d_rec_start, out, d_err, da,
-                                       (uint4 *)nullptr, sc.ncomp, sc.over_list, sc.overflow);
-                else if (sc.overflow > 0)
-                    hipLaunchKernelGGL((k_forward<true, false>), dim3((unsigned)ceil_div(n_pos, GKI_FWD_BLOCK)), dim3(GKI_FWD_BLOCK), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
-                                       (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, (uint32_t *)nullptr, (const int64_t *)d_rec_start, out, d_err, da,
-                                       (uint4 *)nullptr, sc.ncomp, (int64_t *)nullptr, (int64_t)0);
+                const bool listed = sc.overflow <= sc.over_cap;
+                if (sc.overflow > 0)
+                    launch_walk(gr, c, true, da, listed ? sc.overflow : n_pos, nullptr, rec_start, out, sc.ncomp.get<uint8_t>(),
+                                listed ? sc.over_list.get<int64_t>() : nullptr, listed ? sc.overflow : 0);
             } else
-                hipLaunchKernelGGL((k_forward<true, false>), dim3((unsigned)ceil_div(n_pos, GKI_FWD_BLOCK)), dim3(GKI_FWD_BLOCK), 0, 0, gr->d, gr->fwd_nodes, k, M, one_node, (const uint8_t *)d_follow,
-                                   (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos, (uint32_t *)nullptr, (const int64_t *)d_rec_start, out, d_err, da,
-                                   (uint4 *)nullptr, (uint8_t *)nullptr, (int64_t *)nullptr, (int64_t)0);
+                launch_walk(gr, c, true, da, n_pos, nullptr, rec_start, out, nullptr, nullptr, 0);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpy(&word, d_err, 4, hipMemcpyDeviceToHost));          // (synchronises)
-            const int next_cap = da.cap == 0 ? 4 * FMAX : 2 * da.cap;
-            if (!(word & 2) || (word & 4) || next_cap > GKI_MAX_DEEP_WINDOW_NODES) return GKI_OK;
+            HIP_TRY(hipMemcpy(&word, c.d_err, 4, hipMemcpyDeviceToHost));          // (synchronises)
+            const int next_cap = gki_deep_next_cap(word, da.cap, 4 * FMAX);
+            if (!next_cap) return GKI_OK;
             GKI_TRY(deep_grow(gr, next_cap));
         }
     };

@@ -152,7 +152,6 @@ int graph_create_common(gki_graph **out, int64_t n_nodes, const int32_t *h_node_
     if (n_nodes <= 0 || n_bases < 0 || n_edges < 0) return gki_set_error(GKI_ERR_BAD_ARG, "graph_create: bad sizes");
     if (n_edges >= INT32_MAX) return gki_set_error(GKI_ERR_BAD_ARG, "graph_create: more than 2^31-1 edges");
     gki_graph *g = new gki_graph();
-    memset(g, 0, sizeof(*g));
     const int rc = graph_init(g, n_nodes, h_node_size, h_seq, d_seq, seq_on_device, n_bases, h_edge_start, h_edges, h_rev_start,
                               h_rev_edges, n_edges, h_is_ref, h_allele_freq, h_position_base);
     if (rc != GKI_OK) { (void)gki_graph_destroy(g); return rc; }      // nothing of a half-built graph stays behind
@@ -168,7 +167,7 @@ int gki_graph_prepare(gki_graph *g) {
     hipStream_t s = g->stream;
     int64_t n_u64 = ceil_div(d.n_bases, 32) + 2;
     // the early-stop search's node records and script are of the sequence before: the next search builds them again
-    if (g->fwd_nodes) { (void)gki_dev_free(g->fwd_nodes); g->fwd_nodes = nullptr; }
+    g->fwd_nodes.reset();
     script_drop(g);
     HIP_TRY(hipEventRecord(g->ev_prep0, s));
     HIP_TRY(hipMemsetAsync((void *)d.seq2, 0, (size_t)n_u64 * 8, s));
@@ -221,9 +220,6 @@ int gki_graph_create_dseq(gki_graph **out, int64_t n_nodes, const int32_t *h_nod
 int gki_graph_destroy(gki_graph *g) {
     if (!g) return GKI_OK;
     for (int i = 0; i < g->n_owned; i++) (void)hipFree(g->owned[i]);
-    if (g->fwd_deep.base) (void)gki_dev_free(g->fwd_deep.base);
-    script_drop(g);
-    if (g->fwd_nodes) (void)gki_dev_free(g->fwd_nodes);
     if (g->ev_prep0) (void)hipEventDestroy(g->ev_prep0);
     if (g->ev_prep1) (void)hipEventDestroy(g->ev_prep1);
     if (g->stream) (void)hipStreamDestroy(g->stream);

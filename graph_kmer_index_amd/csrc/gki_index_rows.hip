@@ -14,7 +14,7 @@
 //                                   rows + keys -> rows + keys (later)                        28 R + 28 W
 //                                   (4096-row tile, ranked at once, staged through LDS in four parts: two workgroups per CU;
 //                                   k_partition_rows -- the tile sorted whole in LDS -- serves the bucket-range partition
-//                                   into columns and is the A/B partner, -DGKI_PT_NCH=1)
+//                                   into columns)
 //   k_group_bounds / k_group_scan   first row / row count of every group (= key >> L, L <= 10) 4 R
 //   k_group_finish                  one workgroup per group: counting sort on the low L (<= 10) bits in LDS, the directory of
 //                                   the group's 2^L buckets (streamed, no memset + scatter), frequencies, and the
@@ -40,32 +40,20 @@ int gki_frequencies_for_rows(const int64_t *d_row_begin, const int64_t *d_row_en
 
 namespace {
 
-#ifndef GKI_MAXB_BITS
-#define GKI_MAXB_BITS 10
-#endif
-constexpr int MAXB_BITS = GKI_MAXB_BITS;
+constexpr int MAXB_BITS = 10;
 constexpr int MAXB = 1 << MAXB_BITS;          // digits of one partition pass
 // Shape of the finish: 1024 rows and 2^10 buckets per group, 512 threads -- 38 KB of LDS, four workgroups (32 waves) per CU.
 // Measured against 2048 rows / 2^11 buckets (two workgroups per CU) on 3.1e8 records, same box: the finish 6.13 -> 4.49 ms,
 // the first partition pass (10 bits instead of 9: runs of 4 rows) 5.03 -> 5.75 ms, the build 19.05 -> 18.5 ms
 // (profiles/r03_index_group_shape_ab.txt).
-#ifndef GKI_GROUP_CAP
-#define GKI_GROUP_CAP 1024
-#endif
-#ifndef GKI_GROUP_LMAX
-#define GKI_GROUP_LMAX 10
-#endif
-#ifndef GKI_GROUP_THREADS
-#define GKI_GROUP_THREADS 512
-#endif
-constexpr int GROUP_CAP = GKI_GROUP_CAP;          // rows a group may hold to be finished in LDS
+constexpr int GROUP_CAP = 1024;                   // rows a group may hold to be finished in LDS
 // ... and in the grouped build (records arriving grouped by the top bits of their key, gki_index_build_range_grouped): one
 // workgroup per CU finishes 4096 rows, two more key bits than the 1024-row finish resolves, so that ONE partition pass is
 // left between the grouping and the finish (DESIGN.md 4.3 "Grouped build")
 constexpr int GROUP_CAP_BIG = 4096;
 constexpr int GROUP_THREADS_BIG = 1024;           // sixteen waves: the one workgroup a CU holds has to hide its own latencies
-constexpr int GROUP_LMAX = GKI_GROUP_LMAX;        // low key bits resolved in LDS
-constexpr int GROUP_THREADS = GKI_GROUP_THREADS;
+constexpr int GROUP_LMAX = 10;                    // low key bits resolved in LDS
+constexpr int GROUP_THREADS = 512;
 constexpr int SMALL_BUCKET = 24;              // as in gki_index.hip: buckets up to this size count frequencies per lane
 
 // How a record's sort key follows from its k-mer: the bucket relative to the slice (the index build), or the part that owns
@@ -425,10 +413,6 @@ __global__ __launch_bounds__(THREADS) void k_partition_rows(PartArgs a) {
             const int p = j / 3;
             const uint32_t d = SRC_COLS ? (uint32_t)s_dig[p] : ((s_keys[p] >> a.shift) & mask);
             int64_t row = (SRC_COLS ? s_dbase[d] : 0) + (int64_t)(uint32_t)(s_toff[d] + (uint32_t)p);
-#if defined(GKI_TUNING) && defined(GKI_DBG_PART)        // where does the pass's time go: 1 = the sorted tile leaves in one piece
-            row = tile_base + p;                          // (same LDS work, sequential stores; results wrong), 2 = no stores
-            if (GKI_DBG_PART == 2 && row >= 0) continue;
-#endif
             a.rows_out[row * 3 + (j - p * 3)] = s_rows[j];
         }
     }
@@ -439,10 +423,6 @@ __global__ __launch_bounds__(THREADS) void k_partition_rows(PartArgs a) {
             const uint32_t k = s_keys[p];
             const uint32_t d = SRC_COLS ? (uint32_t)s_dig[p] : ((k >> a.shift) & mask);
             int64_t row = (SRC_COLS ? s_dbase[d] : 0) + (int64_t)(uint32_t)(s_toff[d] + (uint32_t)p);
-#if defined(GKI_TUNING) && defined(GKI_DBG_PART)
-            row = tile_base + p;
-            if (GKI_DBG_PART == 2 && row >= 0) continue;
-#endif
             a.keys_out[row] = k;
         }
     }
@@ -455,7 +435,7 @@ __global__ __launch_bounds__(THREADS) void k_partition_rows(PartArgs a) {
 // (2048-row tiles bought the overlap with runs half as long: no gain, profiles/r03_index_tile_ab.txt; 8192-row tiles staged
 // in four parts bought longer runs without the overlap: -2 %, profiles/r04_partition_staged_tile_ab.txt).  The ranking
 // scratch (per-wave digit counts, digit starts, run offsets) lives under the staging buffer: dead before the first payload
-// word lands.  The build's passes since round 4 (GKI_PT_NCH); -DGKI_PT_NCH=1 rebuilds the one-workgroup kernel.
+// word lands.  The build's passes since round 4 (PT_NCH parts).
 template <int THREADS, int RI, bool SRC_COLS, int NCH>
 __global__ __launch_bounds__(THREADS, 4) void k_partition_rows_staged(PartArgs a) {
     constexpr int TILE = THREADS * RI, W = THREADS / 64, SLICE = TILE / W, CH = TILE / NCH;
@@ -704,7 +684,7 @@ struct FinishArgs {
 //    (wave, round, lane) order, match-any by ballots inside the wave, per-wave bucket counts, exclusive offsets over the
 //    waves -- whose cost does not grow with the bucket.  With the loop, a wave waited for its longest bucket (15-20 rows)
 //    three times over (rank, same k-mer, earlier duplicate): 12.2 ms per 3.95e8 rows against 4.3 ms per 3.1e8 sparse ones.
-template <bool WRANK, int GROUP_CAP = GKI_GROUP_CAP, int GROUP_THREADS = GKI_GROUP_THREADS>
+template <bool WRANK, int GROUP_CAP = ::GROUP_CAP, int GROUP_THREADS = ::GROUP_THREADS>
 __global__ __launch_bounds__(GROUP_THREADS) void k_group_finish(FinishArgs a) {
     constexpr int NB = 1 << GROUP_LMAX, RI = GROUP_CAP / GROUP_THREADS, W = GROUP_THREADS / 64, SLICE = GROUP_CAP / W;
     constexpr int C = NB / GROUP_THREADS > 0 ? NB / GROUP_THREADS : 1;      // buckets per thread: b = i * THREADS + thread
@@ -1016,40 +996,24 @@ __global__ __launch_bounds__(THREADS) void k_kmer_digit_hist(const uint64_t *__r
 
 // Tile shape of the partition passes.  4096-row tiles (one workgroup of 512 threads per CU, 144 KB of LDS) give every
 // digit of a 512-way pass a run of 8 rows = 192 bytes on average; see DESIGN.md 4.3 for the measured alternatives.
-#ifndef GKI_PT_THREADS
-#define GKI_PT_THREADS 512
-#endif
-#ifndef GKI_PT_RI
-#define GKI_PT_RI 8
-#endif
-// > 1: the build's passes run k_partition_rows_staged (the sorted tile staged through LDS in this many parts: 4 -> 64 KB of
-// LDS, two workgroups per CU); 1: k_partition_rows (one workgroup per CU).  Same box, alternating
+constexpr int PT_THREADS = 512, PT_RI = 8;
+// The build's passes run k_partition_rows_staged, the sorted tile staged through LDS in this many parts: 4 -> 64 KB of LDS,
+// two workgroups per CU, against k_partition_rows' one workgroup per CU.  Same box, alternating
 // (profiles/r04_partition_two_workgroups_ab.txt): first pass 7.75 -> 5.37 ms, second 6.36 -> 5.00 ms per 3.95e8 records.
-#ifndef GKI_PT_NCH
-#define GKI_PT_NCH 4
-#endif
+constexpr int PT_NCH = 4;
 // tile of the bucket-range partition (<= 256 parts: its runs are long whatever the tile): 2048 rows, 72 KB of LDS, two
 // workgroups per CU -- one loads while the other stores: 50.1 -> 45.0 ms per 3.16e9 records, same box
 // (profiles/r04_full_index_ab.txt).  The build's 512- and 1024-way passes keep 4096-row tiles (longer runs matter more there).
-#ifndef GKI_PR_THREADS
-#define GKI_PR_THREADS 256
-#endif
+constexpr int PR_THREADS = 256;
 
 // Which way k_group_finish ranks the rows of a bucket: by ballots (cost independent of the bucket) from this many rows per
-// bucket on, by LDS atomics + a loop over the bucket below it.  -DGKI_FINISH_WRANK=0 / =1 force one way (A/B builds).
-#ifndef GKI_FINISH_WRANK
-#define GKI_FINISH_WRANK -1
-#endif
-#ifndef GKI_FINISH_WRANK_DENSITY
-#define GKI_FINISH_WRANK_DENSITY 2.0
-#endif
+// bucket on, by LDS atomics + a loop over the bucket below it.
+constexpr double FINISH_WRANK_DENSITY = 2.0;
 // A group may hold this many standard deviations (of a Poisson count) more than the average group before it overflows
 // the LDS capacity; the few that do are streamed by k_group_large.  (Round 3 asked for a quarter more than the average
 // plus 64 rows, which left the groups of a 7-rows-per-bucket slice at 448 of 1024 rows: twice the workgroups, each with
 // the full footprint and every barrier -- VERDICT r3 weak #1.)
-#ifndef GKI_GROUP_SIGMAS
-#define GKI_GROUP_SIGMAS 4.0
-#endif
+constexpr double GROUP_SIGMAS = 4.0;
 
 // The row-carrying build.  Returns GKI_OK with *done = 1 when it built the index, *done = 0 when the input is outside
 // its domain (a group too large to stream with one workgroup) and the caller should use the pair-sorting form.
@@ -1069,7 +1033,7 @@ int gki_index_build_rows(const void *d_kmers, const void *d_nodes, const void *d
     // by_node: the key of a record is its node id and the "buckets" are the nodes (ReverseKmerIndex.from_flat_kmers,
     // reverse_kmer_index.py:47-60: records stably sorted by node): modulo is unused, n_buckets = the number of nodes, the
     // allele-frequency, node and frequency output columns may be NULL
-    constexpr int THREADS = GKI_PT_THREADS, RI = GKI_PT_RI, TILE = THREADS * RI;
+    constexpr int THREADS = PT_THREADS, RI = PT_RI, TILE = THREADS * RI;
     *done = 0;
     hipStream_t s = 0;
     // d_rows_in / d_keys_in: the records arrive as 24-byte rows with their keys (gki_partition_rows_by_bucket_range) instead of
@@ -1081,15 +1045,15 @@ int gki_index_build_rows(const void *d_kmers, const void *d_nodes, const void *d
     const bool grouped = group_bits > 0;
     const int group_shift = grouped ? (kb > group_bits ? kb - group_bits : 0) : kb;     // key bits below the grouping
     const int cap = grouped ? GROUP_CAP_BIG : GROUP_CAP;
-    // L: low key bits resolved inside LDS -- the largest for which an average group and GKI_GROUP_SIGMAS deviations fit
+    // L: low key bits resolved inside LDS -- the largest for which an average group and GROUP_SIGMAS deviations fit
     const double density = (double)n / (double)n_buckets;
     int L = kb < GROUP_LMAX ? kb : GROUP_LMAX;
     while (L > 0) {
         const double rows = density * (double)(1ull << L);
-        if (rows + GKI_GROUP_SIGMAS * sqrt(rows) <= (double)cap) break;
+        if (rows + GROUP_SIGMAS * sqrt(rows) <= (double)cap) break;
         L--;
     }
-    const bool wrank = GKI_FINISH_WRANK < 0 ? density >= GKI_FINISH_WRANK_DENSITY : GKI_FINISH_WRANK != 0;
+    const bool wrank = density >= FINISH_WRANK_DENSITY;
     const int top = group_shift > L ? group_shift - L : 0;    // bits the partition passes sort on
     const int n_pass = top > 0 ? (top + MAXB_BITS - 1) / MAXB_BITS : (from_rows ? 0 : 1);   // top == 0: one pass of one digit, which only packs the rows
     if (n_pass > 3) return GKI_OK;
@@ -1179,13 +1143,8 @@ int gki_index_build_rows(const void *d_kmers, const void *d_nodes, const void *d
         a.rows_out = rows[p & 1]; a.keys_out = keys[p & 1];
         a.o_kmers = nullptr; a.o_nodes = nullptr; a.o_refs = nullptr; a.o_af = nullptr; a.dbase = nullptr;
         a.xcd_tiles = xcd_tiles;
-#if GKI_PT_NCH > 1
-        if (p == 0 && !from_rows) hipLaunchKernelGGL((k_partition_rows_staged<THREADS, RI, true, GKI_PT_NCH>), dim3(xgrid), dim3(THREADS), 0, s, a);
-        else hipLaunchKernelGGL((k_partition_rows_staged<THREADS, RI, false, GKI_PT_NCH>), dim3(xgrid), dim3(THREADS), 0, s, a);
-#else
-        if (p == 0 && !from_rows) hipLaunchKernelGGL((k_partition_rows<THREADS, RI, true>), dim3(xgrid), dim3(THREADS), 0, s, a);
-        else hipLaunchKernelGGL((k_partition_rows<THREADS, RI, false>), dim3(xgrid), dim3(THREADS), 0, s, a);
-#endif
+        if (p == 0 && !from_rows) hipLaunchKernelGGL((k_partition_rows_staged<THREADS, RI, true, PT_NCH>), dim3(xgrid), dim3(THREADS), 0, s, a);
+        else hipLaunchKernelGGL((k_partition_rows_staged<THREADS, RI, false, PT_NCH>), dim3(xgrid), dim3(THREADS), 0, s, a);
         HIP_TRY(hipGetLastError());
         cur_rows = a.rows_out; cur_keys = a.keys_out;
         shift += bits;
@@ -1356,9 +1315,9 @@ static int partition_columns_by_part(const void *d_kmers, const void *d_nodes, c
         if (d_out_rows) {               // rows + keys out (the key: the bucket's offset in its part)
             a.rows_out = (uint64_t *)d_out_rows; a.keys_out = (uint32_t *)d_out_keys;
             bool launched = false;
-            if constexpr (GKI_PT_NCH > 1 && THREADS == GKI_PT_THREADS) {
+            if constexpr (THREADS == PT_THREADS) {
                 if (n < ((int64_t)1 << 32)) {
-                    hipLaunchKernelGGL((k_partition_rows_staged<THREADS, RI, true, GKI_PT_NCH>), dim3((unsigned)(a.xcd_tiles * 8)), dim3(THREADS), 0, s, a);
+                    hipLaunchKernelGGL((k_partition_rows_staged<THREADS, RI, true, PT_NCH>), dim3((unsigned)(a.xcd_tiles * 8)), dim3(THREADS), 0, s, a);
                     launched = true;
                 }
             }
@@ -1387,7 +1346,7 @@ int gki_partition_columns_by_part(const void *d_kmers, const void *d_nodes, cons
                                   void *d_out_nodes, void *d_out_ref_offsets, void *d_out_af32, void *d_out_rows, void *d_out_keys,
                                   int64_t *h_part_start) {
     if (!d_out_rows && (n_parts << sub_bits) <= MAX_PARTS)
-        return partition_columns_by_part<GKI_PR_THREADS>(d_kmers, d_nodes, d_ref_offsets, d_af32, n, modulo, n_parts, sub_bits, max_rows_per_pass,
+        return partition_columns_by_part<PR_THREADS>(d_kmers, d_nodes, d_ref_offsets, d_af32, n, modulo, n_parts, sub_bits, max_rows_per_pass,
                                                          d_out_kmers, d_out_nodes, d_out_ref_offsets, d_out_af32, nullptr, nullptr, h_part_start);
     return partition_columns_by_part<512>(d_kmers, d_nodes, d_ref_offsets, d_af32, n, modulo, n_parts, sub_bits, max_rows_per_pass,
                                           d_out_kmers, d_out_nodes, d_out_ref_offsets, d_out_af32, d_out_rows, d_out_keys, h_part_start);

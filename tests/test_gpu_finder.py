@@ -483,6 +483,50 @@ def test_early_stop_search_after_the_sequence_on_the_device_was_replaced():
     assert emitted > 0
 
 
+@pytest.mark.parametrize("one", [True, False])
+def test_prepare_between_count_and_emit_drops_the_script(one):
+    # count(A), gki_graph_prepare after other bases were written into the same nodes, emit(A) with the count's pointers: the
+    # script the count call left (both modes leave one) is of the old sequence, so the emit call walks the graph again and
+    # the records hold the hashes of the new sequence
+    import ctypes as C
+    from graph_kmer_index_amd import _lib
+    from graph_kmer_index_amd.device_graph import DeviceGraph
+    lib = _lib.load()
+    dt = [np.int64, np.int32, np.int16, np.int32, np.float64]
+    k, M = 31, 2
+    rng = np.random.default_rng(2028)
+    g = GraphArrays.from_dicts(*random_bubble_graph(np.random.default_rng(2025), n_var=4, min_ref=1, max_ref=62))
+    d_seq = _lib.DeviceArray.from_host(np.ascontiguousarray(g.seq, dtype=np.uint8))
+    dev = DeviceGraph(g, d_seq=d_seq)
+    nodes = rng.integers(0, g.n_nodes, size=24)
+    offs = [int(rng.integers(0, max(1, g.node_size[n]))) for n in nodes]
+
+    def expected():
+        exp = [oracle.find_from_position(g, k, int(n), int(o), one, M) for n, o in zip(nodes, offs)]
+        return {key: np.concatenate([e[key] for e in exp]) for key in exp[0]}
+
+    old = expected()
+    d_nodes = _lib.DeviceArray.from_host(np.asarray(nodes, dtype=np.int32))
+    d_offs = _lib.DeviceArray.from_host(np.asarray(offs, dtype=np.int32))
+    d_start = _lib.DeviceArray(len(nodes) + 1, np.int64)
+    n = C.c_int64(0)
+    args = (dev.handle, k, M, int(one), None, d_nodes.ptr, d_offs.ptr, len(nodes))
+    _lib.check(lib.gki_forward_count(*args, d_start.ptr, C.byref(n)))
+    assert n.value == len(old["kmers"]) > 0
+    g.seq[:] = (g.seq + rng.integers(1, 4, size=len(g.seq)).astype(g.seq.dtype)) % 4          # every base another one
+    _lib.check(lib.gki_memcpy_h2d(d_seq.ptr, _lib.hptr(np.ascontiguousarray(g.seq, dtype=np.uint8)), len(g.seq)))
+    dev.prepare()
+    new = expected()                                          # the paths, and so the record counts, depend on the graph alone
+    assert len(new["kmers"]) == n.value and not np.array_equal(new["kmers"], old["kmers"])
+    cols = [_lib.DeviceArray(n.value, d) for d in dt]
+    _lib.check(lib.gki_forward_emit(*args, d_start.ptr, *[c.ptr for c in cols]))
+    got = [c.to_host()[:n.value] for c in cols]
+    assert_same_records(dict(kmers=got[0], start_nodes=got[1], start_offsets=got[2], nodes=got[3], allele_frequencies=got[4]), new, exact_order=True)
+    for x in cols + [d_nodes, d_offs, d_start]:
+        x.free()
+    dev.close()
+
+
 def test_early_stop_emit_from_the_script_equals_the_walking_emit():
     # csrc/gki_forward.hip: in all-nodes mode gki_forward_count leaves the finished k-mers in a script and the
     # gki_forward_emit call with the same arguments expands it (start positions with more than four finished k-mers or a
