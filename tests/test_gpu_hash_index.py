@@ -521,8 +521,9 @@ def test_device_flat_kmers_reverse_complement_and_concatenation():
 
 
 def test_scalar_getters_one_launch_and_batched_frequency_helpers():
-    """get / get_frequency through gki_index_get_small (one launch, pinned staging) and the batched
-    FlatKmers.sum_of_kmer_frequencies / maximum_kmer_frequency, against the oracle's get."""
+    """The scalar getters get / get_frequency, which answer from the index's host arrays (no launch), and the batched
+    get_frequencies / FlatKmers.sum_of_kmer_frequencies / maximum_kmer_frequency, against the oracle's get.  The
+    one-launch device form, gki_index_get_small, is not called here: tests/test_gpu_read_side_edges.py covers it."""
     import time
     from graph_kmer_index_amd import CollisionFreeKmerIndex, FlatKmers
     rng = np.random.default_rng(12)
