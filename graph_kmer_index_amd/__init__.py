@@ -20,8 +20,10 @@ from .read_kmers import ReadKmers  # noqa: F401
 from .nplist import NpList  # noqa: F401
 from .snp_kmer_finder import SnpKmerFinder  # noqa: F401
 from .reference_kmer_index import ReferenceKmerIndex  # noqa: F401
+from .kmer_counter import KmerCounter  # noqa: F401
+from .kmer_frequency_index import KmerFrequencyIndex  # noqa: F401
 
 __all__ = ["letter_sequence_to_numeric", "numeric_to_letter_sequence", "kmer_to_hash_fast",
            "sequence_to_kmer_hash", "kmer_hash_to_sequence", "FlatKmers", "FlatKmers2", "DeviceFlatKmers",
            "GraphArrays", "DeviceGraph", "CriticalGraphPaths", "DenseKmerFinder", "CollisionFreeKmerIndex", "KmerIndex", "CounterKmerIndex", "ReverseKmerIndex", "ReadKmers", "NpList",
-           "SnpKmerFinder", "ReferenceKmerIndex"]
+           "SnpKmerFinder", "ReferenceKmerIndex", "KmerCounter", "KmerFrequencyIndex"]

@@ -103,12 +103,21 @@ SYMBOLS = {
     "gki_forward_emit": (_I32, [_P, _I32, _I32, _I32, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P]),
     "gki_uvk_starts": (_I32, [_P, _P, _P, _I64, _P, _I64, _I32, _P, _P, _P, C.POINTER(_I64)]),
     "gki_uvk_summarize": (_I32, [_P, C.POINTER(IndexView), _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "gki_uvk_summarize_counter": (_I32, [_P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "gki_uvk_select": (_I32, [_P, _I64, _I32, _I32, _P, _P, _P, C.POINTER(_I64)]),
     "gki_uvk_emit": (_I32, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gki_sv_sample_count": (_I32, [_P, C.POINTER(IndexView), _P, _I64, _I32, _I64, _P, C.POINTER(_I64), C.POINTER(_P),
                                    C.POINTER(C.c_float)]),
     "gki_sv_sample_emit": (_I32, [_P, _P, _P, _P, _P, C.POINTER(C.c_float)]),
     "gki_sv_sample_destroy": (_I32, [_P]),
+    "gki_sv_sample_count_counter": (_I32, [_P, _P, _P, _I64, _I32, _I64, _P, C.POINTER(_I64), C.POINTER(_P),
+                                           C.POINTER(C.c_float)]),
+    "gki_unique_counts_count": (_I32, [_P, _I64, _I64, _I32, C.POINTER(_I64), C.POINTER(_P), C.POINTER(C.c_float)]),
+    "gki_unique_counts_emit": (_I32, [_P, _P, _P, C.POINTER(C.c_float)]),
+    "gki_unique_counts_destroy": (_I32, [_P]),
+    "gki_counter_create": (_I32, [_P, _P, _I64, _I32, C.POINTER(_P)]),
+    "gki_counter_lookup": (_I32, [_P, _P, _I64, _P]),
+    "gki_counter_destroy": (_I32, [_P]),
     "gki_index_build": (_I32, [_P, _P, _P, _P, _I64, _U64, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gki_partition_by_bucket_range": (_I32, [_P, _P, _P, _P, _I64, _U64, _I32, _P, _P, _P, _P, C.POINTER(_I64)]),
     "gki_partition_by_bucket_range_chunked": (_I32, [_P, _P, _P, _P, _I64, _U64, _I32, _I64, _P, _P, _P, _P, C.POINTER(_I64)]),

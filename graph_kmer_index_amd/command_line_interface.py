@@ -9,6 +9,9 @@ collision_free_kmer_index.py:393-402).
         -k 31 -i index.npz -p position_id -D True -v variants.vcf -o variant_kmers
     python -m graph_kmer_index_amd.command_line_interface sample_kmers_from_structural_variants -g graph.npz \
         -V variant_to_nodes.npz -k 31 -i index.npz -o sv_kmers
+    python -m graph_kmer_index_amd.command_line_interface count_kmers -f linear_kmers.npz -o counter
+    python -m graph_kmer_index_amd.command_line_interface sample_kmers_from_structural_variants -g graph.npz \
+        -V variant_to_nodes.npz -k 31 -I counter.npz -o sv_kmers
     python -m graph_kmer_index_amd.command_line_interface merge_flat_kmers -f variant_kmers.npz,sv_kmers.npz -o all_variant_kmers
     python -m graph_kmer_index_amd.command_line_interface make_reverse -f variant_kmers.npz -o reverse
     python -m graph_kmer_index_amd.command_line_interface make -t 16 -s 1 -k 31 -r True -R ref.fa -n chr1 -G <size> -o linear_kmers
@@ -176,6 +179,40 @@ class _DefaultPositionId:
         return self._base[np.asarray(nodes, dtype=np.int64)] + np.asarray(offsets, dtype=np.int64)
 
 
+def load_frequency_source(args, command):
+    """-i: a CollisionFreeKmerIndex with frequencies; when it is absent, -I: a KmerCounter written by count_kmers
+    (command_line_interface.py:308-310 of the reference)."""
+    if args.kmer_index is not None:
+        return CollisionFreeKmerIndex.from_file(args.kmer_index)
+    if args.kmer_counter is None:
+        raise ValueError("%s: -i (a CollisionFreeKmerIndex with frequencies) or -I (a KmerCounter from count_kmers) is "
+                         "required" % command)
+    from .kmer_counter import KmerCounter
+    try:
+        return KmerCounter.from_file(args.kmer_counter)
+    except (FileNotFoundError, ValueError) as e:
+        raise type(e)("%s: %s (a counter written by this package's count_kmers is expected; the reference's pickled "
+                      "npstructures table given with -I is not supported)" % (command, e))
+
+
+def count_kmers(args):
+    """command_line_interface.py:670-681: the unique k-mers of a flat with their counts, every -s'th record taken."""
+    from .kmer_counter import KmerCounter
+    counter = KmerCounter.from_flat_kmersv2(FlatKmers.from_file(args.flat_kmers), args.modulo, args.subsample_ratio)
+    counter.to_file(args.out_file_name)
+    logging.info("Wrote counter of %d k-mers to %s" % (len(counter._kmers), args.out_file_name))
+
+
+def make_kmer_frequencies(args):
+    """command_line_interface.py:499-509."""
+    from .kmer_frequency_index import KmerFrequencyIndex
+    from .reference_kmer_index import ReferenceKmerIndex
+    ref_kmers = ReferenceKmerIndex.from_file(args.reference_kmers)
+    index = KmerFrequencyIndex.from_kmers(ref_kmers.kmers)
+    index.to_file(args.out_file_name)
+    logging.info("Wrote to file %s" % args.out_file_name)
+
+
 def make_unique_variant_kmers(args):
     """command_line_interface.py:299-389, dense path: one finder per `-c` chunk of VCF data lines (`_nodes_found` starts
     empty at every chunk), run here as one device batch.  `-t` is accepted; the chunks' outputs do not depend on it."""
@@ -186,18 +223,17 @@ def make_unique_variant_kmers(args):
     if _bool(args.simple):
         raise NotImplementedError("make_unique_variant_kmers: -S (simple selection) is not supported; the supported "
                                   "mode is -D True without -S")
-    for flag, value in (("-N", args.node_to_variants), ("-H", args.haplotype_matrix), ("-I", args.kmer_counter)):
+    for flag, value in (("-N", args.node_to_variants), ("-H", args.haplotype_matrix)):
         if value is not None:
-            raise NotImplementedError("make_unique_variant_kmers: %s is not supported (dense path with a "
-                                      "CollisionFreeKmerIndex from -i only)" % flag)
-    if args.kmer_index is None:
-        raise ValueError("make_unique_variant_kmers: -i (a CollisionFreeKmerIndex with frequencies) is required")
+            raise NotImplementedError("make_unique_variant_kmers: %s is not supported (dense path with a frequency "
+                                      "source from -i or -I only)" % flag)
+    frequencies = load_frequency_source(args, "make_unique_variant_kmers")
     if args.vcf is None:
         raise ValueError("make_unique_variant_kmers: -v (the VCF) is required")
     graph = load_graph(args.graph)
     finder = UniqueVariantKmersFinder(graph, load_variant_to_nodes(args.variant_to_nodes), VariantArrays.from_vcf(args.vcf),
                                       args.kmer_size, args.max_variant_nodes,
-                                      kmer_index_with_frequencies=CollisionFreeKmerIndex.from_file(args.kmer_index),
+                                      kmer_index_with_frequencies=frequencies,
                                       do_not_choose_lowest_frequency_kmers=_bool(args.do_not_choose_lowest_frequency_kmers),
                                       use_dense_kmer_finder=True,
                                       position_id_index=load_position_id(args.position_id_index, graph),
@@ -213,13 +249,9 @@ def sample_kmers_from_structural_variants_command(args):
     (merge_flat_kmers).  `-t` is accepted; all nodes run as one device batch."""
     from .structural_variants import sample_kmers_from_structural_variants
     from .unique_variant_kmers import load_variant_to_nodes
-    if args.kmer_counter is not None:
-        raise NotImplementedError("sample_kmers_from_structural_variants: -I is not supported (a "
-                                  "CollisionFreeKmerIndex from -i only)")
-    if args.kmer_index is None:
-        raise ValueError("sample_kmers_from_structural_variants: -i (a CollisionFreeKmerIndex with frequencies) is required")
+    frequencies = load_frequency_source(args, "sample_kmers_from_structural_variants")
     flat = sample_kmers_from_structural_variants(load_graph(args.graph), load_variant_to_nodes(args.variant_to_nodes),
-                                                 CollisionFreeKmerIndex.from_file(args.kmer_index), args.kmer_size)
+                                                 frequencies, args.kmer_size)
     flat.to_file(args.out_file_name)
     logging.info("Wrote %d k-mers of structural variant nodes to %s" % (len(flat._hashes), args.out_file_name))
 
@@ -365,6 +397,17 @@ def build_parser():
     p.add_argument("-o", "--out-file-name", required=True)
     p.add_argument("-t", "--n-threads", required=False, default=1, type=int)
     p.set_defaults(func=sample_kmers_from_structural_variants_command)
+    p = sub.add_parser("count_kmers")
+    p.add_argument("-f", "--flat-kmers", required=True)
+    p.add_argument("-o", "--out-file-name", required=True)
+    p.add_argument("-m", "--modulo", required=False, type=int, default=0)
+    p.add_argument("-s", "--subsample-ratio", required=False, type=int, default=1,
+                   help="1 to keep every kmer, 2 for every other etc")
+    p.set_defaults(func=count_kmers)
+    p = sub.add_parser("make_kmer_frequency_index")
+    p.add_argument("-r", "--reference-kmers", required=True)
+    p.add_argument("-o", "--out-file-name", required=True)
+    p.set_defaults(func=make_kmer_frequencies)
     return parser
 
 

@@ -46,6 +46,7 @@ class DevBuf {
     hipError_t alloc(size_t bytes) { reset(); return gki_dev_malloc(&p_, bytes); }
     void reset() { if (p_) { (void)gki_dev_free(p_); p_ = nullptr; } }
     template <class T = void> T *get() const { return static_cast<T *>(p_); }
+    void swap(DevBuf &o) { void *t = p_; p_ = o.p_; o.p_ = t; }
 
   private:
     void *p_ = nullptr;
@@ -123,6 +124,37 @@ __device__ __forceinline__ uint32_t gki_first_hit_frequency(const int32_t *__res
     }
     return 0;
 }
+
+// ---------------------------------------------------------------------------------- KmerCounter on the device
+// Sorted distinct keys of key_bits bits with their counts (gki_count.hip), behind a prefix directory: dir[p] is the first
+// position whose top dir_bits of key_bits bits are >= p (2^dir_bits + 1 entries, the last one n).  A lookup is one
+// directory sector, a binary search inside the bucket (a few keys: 2^dir_bits is n / 4 .. n / 2), one count.
+struct GkiCounterView {
+    const uint64_t *keys;
+    const int64_t *counts;
+    const int64_t *dir;
+    int64_t n;
+    int key_bits, dir_bits;
+};
+// KmerCounter.get_frequency (kmer_counter.py:72-74): the count of h, 0 when it is absent; no reverse complement
+__device__ __forceinline__ int64_t gki_counter_frequency(const GkiCounterView &c, uint64_t h) {
+    if (c.key_bits < 64 && (h >> c.key_bits) != 0ull) return 0;
+    const uint64_t p = c.dir_bits ? h >> (c.key_bits - c.dir_bits) : 0ull;
+    int64_t lo = c.dir[p];
+    const int64_t end = c.dir[p + 1];
+    int64_t hi = end;
+    while (lo < hi) {                                    // the first key of the bucket that is >= h
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (c.keys[mid] < h) lo = mid + 1; else hi = mid;
+    }
+    return lo < end && c.keys[lo] == h ? c.counts[lo] : 0;
+}
+// the keys and counts are the caller's and must outlive the counter; the directory is its own
+struct gki_counter {
+    GkiCounterView v = {};
+    DevBuf dir;
+    int device = 0;
+};
 
 // ---------------------------------------------------------------------------------- device graph view
 struct alignas(32) NodeWalk { // everything the boundary walk needs about a node, one aligned 32-B record

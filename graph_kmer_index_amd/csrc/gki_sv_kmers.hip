@@ -11,7 +11,7 @@
 //   k_sv_records  one lane per record: the hash read again from the position, the node, offset 0, allele frequency 1
 //
 // Every output is sized by an exact count.  Every per-lane quantity is a scalar in registers.
-#include "gki_common.h"
+#include "gki_frequency.h"
 #include <memory>
 
 // What the count call leaves for the emit call.  The graph must outlive the plan.
@@ -26,18 +26,6 @@ struct gki_sv_plan {
 };
 
 namespace {
-
-constexpr int SV_CHUNK = 16;                 // consecutive bitmap words a wave takes at a time in the probe pass
-
-struct SvIndex {
-    const int32_t *hashes_to_index;
-    const uint32_t *n_kmers;
-    const uint64_t *kmers;
-    const uint16_t *frequencies;
-    int64_t n;
-    GkiMod mod;
-    uint64_t bucket_begin, n_buckets;
-};
 
 __global__ __launch_bounds__(256) void k_sv_words(const int32_t *__restrict__ cand, int64_t n_cand,
                                                   const int32_t *__restrict__ node_size, int64_t n_nodes, int k,
@@ -55,51 +43,11 @@ __global__ __launch_bounds__(256) void k_sv_words(const int32_t *__restrict__ ca
     }
 }
 
-// the wave's number: uniform, fits 32 bits (a grid has at most 2048 * 4 waves)
-__device__ __forceinline__ int64_t sv_wave() {
-    return __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
-}
-
-// the candidate that owns bitmap word w < word_start[n_cand]: the last one that begins at or before w (candidates
-// without words share their begin with the next one and lose)
-__device__ __forceinline__ int64_t sv_cand_of(const int64_t *__restrict__ word_start, int64_t n_cand, int64_t w) {
-    int64_t lo = 0, hi = n_cand;                         // word_start[lo] <= w < word_start[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (word_start[mid] <= w) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(256) void k_sv_probe(const int32_t *__restrict__ cand, const int64_t *__restrict__ word_start,
                                                   int64_t n_cand, int64_t n_words, const int32_t *__restrict__ node_size,
                                                   const int64_t *__restrict__ seq_start, const uint64_t *__restrict__ seq2,
-                                                  int k, int64_t max_frequency, SvIndex ix, uint64_t *__restrict__ bitmap) {
-    const int lane = threadIdx.x & 63;
-    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    const int64_t n_chunks = (n_words + SV_CHUNK - 1) / SV_CHUNK;
-    for (int64_t c = sv_wave(); c < n_chunks; c += n_waves) {
-        int64_t w = c * SV_CHUNK;
-        const int64_t w_end = w + SV_CHUNK < n_words ? w + SV_CHUNK : n_words;
-        int64_t i = sv_cand_of(word_start, n_cand, w);       // uniform: scalar loads
-        for (; w < w_end; ++w) {
-            while (word_start[i + 1] <= w) ++i;              // w < n_words = word_start[n_cand] ends it
-            const int32_t node = cand[i];
-            const int64_t n_win = (int64_t)node_size[node] - k + 1;
-            const int64_t j = (w - word_start[i]) * 64 + lane;
-            bool valid = false;
-            if (j < n_win) {
-                const uint64_t h = gki_extract(seq2, seq_start[node] + j, k);
-                const uint32_t f = gki_first_hit_frequency(ix.hashes_to_index, ix.n_kmers, ix.kmers, ix.frequencies, ix.n,
-                                                           ix.mod, ix.bucket_begin, ix.n_buckets, h) +
-                                   gki_first_hit_frequency(ix.hashes_to_index, ix.n_kmers, ix.kmers, ix.frequencies, ix.n,
-                                                           ix.mod, ix.bucket_begin, ix.n_buckets, gki_revcomp31(h));
-                valid = (int64_t)f < max_frequency;
-            }
-            const uint64_t word = __ballot(valid);           // windows past the node's last one stay 0
-            if (lane == 0) bitmap[w] = word;
-        }
-    }
+                                                  int k, int64_t max_frequency, GkiIndexSource ix, uint64_t *__restrict__ bitmap) {
+    sv_probe_body(cand, word_start, n_cand, n_words, node_size, seq_start, seq2, k, max_frequency, ix, bitmap);
 }
 
 // the value lane l (uniform) holds, in scalar registers
@@ -164,20 +112,18 @@ __global__ __launch_bounds__(256) void k_sv_records(const int64_t *__restrict__ 
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-int gki_sv_sample_count(gki_graph *g, const gki_index_view *ix, const void *d_cand_nodes, int64_t n_cand, int k,
-                        int64_t max_frequency, void *d_rec_start, int64_t *n_records, gki_sv_plan **plan_out,
-                        float *kernel_ms) {
+// gki_sv_sample_count with either frequency source: the index, or the counter when there is one
+int sv_sample_count(gki_graph *g, const gki_index_view *ix, const gki_counter *counter, const void *d_cand_nodes,
+                    int64_t n_cand, int k, int64_t max_frequency, void *d_rec_start, int64_t *n_records,
+                    gki_sv_plan **plan_out, float *kernel_ms) {
     *n_records = 0;
     *plan_out = nullptr;
     if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0.f;
     if (k < 1 || k > GKI_MAX_K) return gki_set_error(GKI_ERR_BAD_ARG, "k must be in 1..31");
     if (max_frequency < 0) return gki_set_error(GKI_ERR_BAD_ARG, "gki_sv_sample_count: max_frequency must not be negative");
     if (n_cand < 0 || n_cand > (1ll << 31)) return gki_set_error(GKI_ERR_BAD_ARG, "gki_sv_sample_count: bad candidate count");
-    if (ix == nullptr || ix->modulo == 0) return gki_set_error(GKI_ERR_BAD_ARG, "gki_sv_sample_count: no frequency index");
+    if (counter == nullptr && (ix == nullptr || ix->modulo == 0))
+        return gki_set_error(GKI_ERR_BAD_ARG, "gki_sv_sample_count: no frequency index");
     GKI_TRY(gki_check_graph_device(g, "gki_sv_sample_count"));
     std::unique_ptr<gki_sv_plan> p(new gki_sv_plan());
     p->g = g;
@@ -220,19 +166,13 @@ int gki_sv_sample_count(gki_graph *g, const gki_index_view *ix, const void *d_ca
     HIP_TRY(p->bitmap.alloc((size_t)(p->n_words > 0 ? p->n_words : 1) * 8));
     // 2. the valid bitmap: every word of it is written
     if (kernel_ms) HIP_TRY(hipEventRecord(ev.e0, 0));
-    if (p->n_words > 0) {
-        SvIndex s;
-        s.hashes_to_index = (const int32_t *)ix->d_hashes_to_index;
-        s.n_kmers = (const uint32_t *)ix->d_n_kmers;
-        s.kmers = (const uint64_t *)ix->d_kmers;
-        s.frequencies = (const uint16_t *)ix->d_frequencies;
-        s.n = ix->n;
-        s.mod = gki_mod_of(ix->modulo);
-        s.bucket_begin = ix->bucket_begin;
-        s.n_buckets = ix->n_buckets ? ix->n_buckets : ix->modulo;
+    if (p->n_words > 0 && counter != nullptr) {
+        GKI_TRY(gki_launch_sv_probe_counter(counter, cand, p->word_start.get<const int64_t>(), n_cand, p->n_words, d, k,
+                                            max_frequency, p->bitmap.get<uint64_t>()));
+    } else if (p->n_words > 0) {
         hipLaunchKernelGGL(k_sv_probe, dim3(stream_grid(ceil_div(p->n_words, SV_CHUNK) * 64, 256)), dim3(256), 0, 0, cand,
                            p->word_start.get<const int64_t>(), n_cand, p->n_words, d.node_size, d.seq_start, d.seq2, k,
-                           max_frequency, s, p->bitmap.get<uint64_t>());
+                           max_frequency, gki_index_source(ix), p->bitmap.get<uint64_t>());
         HIP_TRY(hipGetLastError());
     }
     if (kernel_ms) { HIP_TRY(hipEventRecord(ev.e1, 0)); HIP_TRY(hipEventRecord(ev2.e0, 0)); }
@@ -254,6 +194,28 @@ int gki_sv_sample_count(gki_graph *g, const gki_index_view *ix, const void *d_ca
     *n_records = p->n_records;
     *plan_out = p.release();
     return GKI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gki_sv_sample_count(gki_graph *g, const gki_index_view *ix, const void *d_cand_nodes, int64_t n_cand, int k,
+                        int64_t max_frequency, void *d_rec_start, int64_t *n_records, gki_sv_plan **plan_out,
+                        float *kernel_ms) {
+    return sv_sample_count(g, ix, nullptr, d_cand_nodes, n_cand, k, max_frequency, d_rec_start, n_records, plan_out, kernel_ms);
+}
+
+int gki_sv_sample_count_counter(gki_graph *g, const gki_counter *counter, const void *d_cand_nodes, int64_t n_cand, int k,
+                                int64_t max_frequency, void *d_rec_start, int64_t *n_records, gki_sv_plan **plan_out,
+                                float *kernel_ms) {
+    if (counter == nullptr) {
+        *n_records = 0;
+        *plan_out = nullptr;
+        return gki_set_error(GKI_ERR_BAD_ARG, "gki_sv_sample_count_counter: no counter");
+    }
+    return sv_sample_count(g, nullptr, counter, d_cand_nodes, n_cand, k, max_frequency, d_rec_start, n_records, plan_out,
+                           kernel_ms);
 }
 
 int gki_sv_sample_emit(gki_sv_plan *p, void *d_hashes, void *d_nodes, void *d_ref_offsets, void *d_af32, float *kernel_ms) {

@@ -10,11 +10,9 @@
 //   gki_uvk_emit       one lane per variant: the chosen start's records of the stored nodes, in emission order
 //
 // Every per-lane quantity is a scalar in registers: no arrays, no scratch.
-#include "gki_common.h"
+#include "gki_frequency.h"
 
 namespace {
-
-constexpr int UVK_WINDOW_CAP = 500;          // kmer_finder.py:137-160: kmers_found keeps the first 500 windows
 
 __global__ __launch_bounds__(256) void k_uvk_starts(const int64_t *__restrict__ lin_start, const int32_t *__restrict__ lin_node,
                                                     const int32_t *__restrict__ node_size, int64_t n_lin,
@@ -48,64 +46,12 @@ __global__ __launch_bounds__(256) void k_uvk_starts(const int64_t *__restrict__ 
     }
 }
 
-// A new window begins at record r unless r continues the previous record's window: same hash, same end position, a
-// larger node (a window's records are its distinct nodes in ascending order, and two windows that end at the same
-// position both hold the node they end in, so the next window's first node is never above the previous one's last).
-__device__ __forceinline__ bool uvk_new_window(const int64_t *__restrict__ hashes, const int32_t *__restrict__ start_nodes,
-                                               const int16_t *__restrict__ start_offsets, const int32_t *__restrict__ nodes,
-                                               int64_t r, int64_t rs) {
-    return r == rs || hashes[r] != hashes[r - 1] || start_nodes[r] != start_nodes[r - 1] ||
-           start_offsets[r] != start_offsets[r - 1] || nodes[r] <= nodes[r - 1];
-}
-
 __global__ __launch_bounds__(256) void k_uvk_summarize(
     const int64_t *__restrict__ rec_start, int64_t n_pos, int P, const int64_t *__restrict__ hashes,
     const int32_t *__restrict__ start_nodes, const int16_t *__restrict__ start_offsets, const int32_t *__restrict__ nodes,
-    const int32_t *__restrict__ ref_nodes, const int32_t *__restrict__ alt_nodes,
-    const int32_t *__restrict__ hashes_to_index, const uint32_t *__restrict__ n_kmers, const uint64_t *__restrict__ kmers,
-    const uint16_t *__restrict__ frequencies, int64_t n_index, GkiMod mod, uint64_t bucket_begin, uint64_t n_buckets,
+    const int32_t *__restrict__ ref_nodes, const int32_t *__restrict__ alt_nodes, GkiIndexSource ix,
     gki_uvk_summary *__restrict__ out) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_pos; i += stride) {
-        const int64_t v = i / P;
-        const int32_t ref = ref_nodes[v], alt = alt_nodes[v];
-        const bool same = ref == alt;
-        const int64_t rs = rec_start[i], re = rec_start[i + 1];
-        // records inside the first 500 windows: [rs, lim); at most 500 records hold at most 500 windows
-        int64_t lim = re;
-        if (re - rs > UVK_WINDOW_CAP) {
-            int w = 0;
-            for (int64_t r = rs; r < re; ++r) {
-                if (uvk_new_window(hashes, start_nodes, start_offsets, nodes, r, rs)) {
-                    if (w == UVK_WINDOW_CAP) { lim = r; break; }
-                    ++w;
-                }
-            }
-        }
-        uint32_t n_ref = 0, n_alt = 0, f_ref = 0, f_alt = 0, flags = same ? 2u : 0u;
-        for (int64_t r = rs; r < re; ++r) {
-            const int32_t nd = nodes[r];
-            const bool is_ref = nd == ref, is_alt = !same && nd == alt;
-            if (!is_ref && !is_alt) continue;
-            const uint64_t h = (uint64_t)hashes[r];
-            const uint32_t f = gki_first_hit_frequency(hashes_to_index, n_kmers, kmers, frequencies, n_index, mod,
-                                                       bucket_begin, n_buckets, h) +
-                               gki_first_hit_frequency(hashes_to_index, n_kmers, kmers, frequencies, n_index, mod,
-                                                       bucket_begin, n_buckets, gki_revcomp31(h));
-            if (is_ref) { ++n_ref; f_ref = f > f_ref ? f : f_ref; }
-            else { ++n_alt; f_alt = f > f_alt ? f : f_alt; }
-            if (r < lim && !(flags & 1u)) {
-                if (same) flags |= 1u;                  // kmers_ref and kmers_variant are the same non-empty set
-                else if (is_alt) {                      // an earlier-or-later ref record of the first 500 windows with h
-                    for (int64_t q = rs; q < lim; ++q)
-                        if (nodes[q] == ref && hashes[q] == (int64_t)h) { flags |= 1u; break; }
-                }
-            }
-        }
-        gki_uvk_summary s;
-        s.n_ref = n_ref; s.n_alt = n_alt; s.f_ref = f_ref; s.f_alt = f_alt; s.flags = flags;
-        out[i] = s;
-    }
+    uvk_summarize_body(rec_start, n_pos, P, hashes, start_nodes, start_offsets, nodes, ref_nodes, alt_nodes, ix, out);
 }
 
 __global__ __launch_bounds__(256) void k_uvk_select(const gki_uvk_summary *__restrict__ summ, int64_t n_var, int P, int lowest,
@@ -194,14 +140,29 @@ int gki_uvk_summarize(gki_graph *g, const gki_index_view *ix, const void *d_rec_
     GKI_TRY(gki_check_graph_device(g, "gki_uvk_summarize"));
     const int64_t n_pos = n_var * n_starts_per_variant;
     if (n_pos <= 0) return GKI_OK;
-    const uint64_t n_buckets = ix->n_buckets ? ix->n_buckets : ix->modulo;
     hipLaunchKernelGGL(k_uvk_summarize, dim3(stream_grid(n_pos, 256)), dim3(256), 0, 0, (const int64_t *)d_rec_start, n_pos,
                        n_starts_per_variant, (const int64_t *)d_hashes, (const int32_t *)d_start_nodes,
                        (const int16_t *)d_start_offsets, (const int32_t *)d_nodes, (const int32_t *)d_ref_nodes,
-                       (const int32_t *)d_alt_nodes, (const int32_t *)ix->d_hashes_to_index, (const uint32_t *)ix->d_n_kmers,
-                       (const uint64_t *)ix->d_kmers, (const uint16_t *)ix->d_frequencies, ix->n, gki_mod_of(ix->modulo),
-                       ix->bucket_begin, n_buckets, (gki_uvk_summary *)d_summary);
+                       (const int32_t *)d_alt_nodes, gki_index_source(ix), (gki_uvk_summary *)d_summary);
     HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(0));
+    return GKI_OK;
+}
+
+int gki_uvk_summarize_counter(gki_graph *g, const gki_counter *counter, const void *d_rec_start, int64_t n_var,
+                              int n_starts_per_variant, const void *d_hashes, const void *d_start_nodes,
+                              const void *d_start_offsets, const void *d_nodes, const void *d_ref_nodes,
+                              const void *d_alt_nodes, void *d_summary) {
+    if (n_starts_per_variant < 1) return gki_set_error(GKI_ERR_BAD_ARG, "gki_uvk_summarize_counter: no start position per variant");
+    if (counter == nullptr) return gki_set_error(GKI_ERR_BAD_ARG, "gki_uvk_summarize_counter: no counter");
+    GKI_TRY(gki_check_graph_device(g, "gki_uvk_summarize_counter"));
+    const int64_t n_pos = n_var * n_starts_per_variant;
+    if (n_pos <= 0) return GKI_OK;
+    GKI_TRY(gki_launch_uvk_summarize_counter(counter, (const int64_t *)d_rec_start, n_pos, n_starts_per_variant,
+                                             (const int64_t *)d_hashes, (const int32_t *)d_start_nodes,
+                                             (const int16_t *)d_start_offsets, (const int32_t *)d_nodes,
+                                             (const int32_t *)d_ref_nodes, (const int32_t *)d_alt_nodes,
+                                             (gki_uvk_summary *)d_summary));
     HIP_TRY(hipStreamSynchronize(0));
     return GKI_OK;
 }

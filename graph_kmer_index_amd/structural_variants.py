@@ -1,7 +1,8 @@
 """sample_kmers_from_structural_variants with the reference's signature (structural_variants.py:6-43), on MI355X.
 
 For every (ref_node, var_node) pair of `variant_to_nodes`, ref first, a node longer than k + 5 bases gives the k-mers of
-its own sequence (windows 0 .. size - k) whose `kmer_index_with_frequencies.get_frequency` is below `max_frequency`,
+its own sequence (windows 0 .. size - k) whose `kmer_index_with_frequencies.get_frequency` (a CollisionFreeKmerIndex: the
+k-mer plus its 31-mer reverse complement; a KmerCounter: the k-mer alone) is below `max_frequency`,
 thinned from the left so that two chosen windows never overlap; every chosen window is one record (hash, node, 0).  A
 node listed twice gives its records twice.  The reference asks get_frequency once per base of every big node; here all
 windows of all nodes are one device batch (csrc/gki_sv_kmers.hip, include/gki.h gki_sv_sample_*): a probe pass that
@@ -16,6 +17,7 @@ from .collision_free_kmer_index import CollisionFreeKmerIndex
 from .device_graph import DeviceGraph
 from .flat_kmers import DeviceFlatKmers, FlatKmers
 from .graph import GraphArrays
+from .kmer_counter import KmerCounter
 
 last_timings = {}          # of the latest call: seconds per stage, kernel milliseconds per pass
 last_counts = {}
@@ -39,9 +41,9 @@ def sample_kmers_from_structural_variants_on_device(graph, variant_to_nodes, kme
     """sample_kmers_from_structural_variants with the columns left in HBM: DeviceFlatKmers in the merged layout
     (uint64, uint32, uint64 zeros, float32 ones), ready for DeviceFlatKmers.from_multiple_flat_kmers."""
     global last_timings, last_counts
-    if not isinstance(kmer_index_with_frequencies, CollisionFreeKmerIndex):
-        raise NotImplementedError("the frequency index must be graph_kmer_index_amd's CollisionFreeKmerIndex "
-                                  "(got %s); the npstructures KmerCounter source is not supported"
+    if not isinstance(kmer_index_with_frequencies, (CollisionFreeKmerIndex, KmerCounter)):
+        raise NotImplementedError("the frequency source must be graph_kmer_index_amd's CollisionFreeKmerIndex or "
+                                  "KmerCounter (got %s); the reference's npstructures-backed KmerCounter is not supported"
                                   % type(kmer_index_with_frequencies).__name__)
     k, max_frequency = int(k), int(max_frequency)
     if not 1 <= k <= 31:
@@ -60,15 +62,23 @@ def sample_kmers_from_structural_variants_on_device(graph, variant_to_nodes, kme
     # nodes that fail the size test give nothing (node 0 / "no node" entries among them): dropped here, order kept
     cand = np.ascontiguousarray(nodes[arrays.node_size[nodes] > k + 5], dtype=np.int32)
     dg = DeviceGraph.of(arrays)
-    view = kmer_index_with_frequencies._device_index().view()
+    # a KmerCounter answers with the count of the hash alone, the index adds its 31-mer reverse complement's
+    if isinstance(kmer_index_with_frequencies, KmerCounter):
+        counter, view = kmer_index_with_frequencies._device_counter(), None
+    else:
+        counter, view = None, kmer_index_with_frequencies._device_index().view()
     t["host_prepare"] = time.perf_counter() - t0
     t1 = time.perf_counter()
     d_cand = _lib.DeviceArray.from_host(cand) if len(cand) else _lib.DeviceArray(1, np.int32)
     n_rec, plan = _lib._I64(0), _lib.C.c_void_p()
     ms, ms_emit = (_lib.C.c_float * 2)(), (_lib.C.c_float * 1)()
     try:
-        _lib.check(lib.gki_sv_sample_count(dg.handle, _lib.C.byref(view), d_cand.ptr, len(cand), k, max_frequency, None,
-                                           _lib.C.byref(n_rec), _lib.C.byref(plan), ms))
+        if counter is not None:
+            _lib.check(lib.gki_sv_sample_count_counter(dg.handle, counter.handle, d_cand.ptr, len(cand), k, max_frequency,
+                                                       None, _lib.C.byref(n_rec), _lib.C.byref(plan), ms))
+        else:
+            _lib.check(lib.gki_sv_sample_count(dg.handle, _lib.C.byref(view), d_cand.ptr, len(cand), k, max_frequency, None,
+                                               _lib.C.byref(n_rec), _lib.C.byref(plan), ms))
         t["count"] = time.perf_counter() - t1
         t2 = time.perf_counter()
         out = DeviceFlatKmers.allocate(n_rec.value)

@@ -28,6 +28,7 @@ from .collision_free_kmer_index import CollisionFreeKmerIndex
 from .device_graph import DeviceGraph
 from .flat_kmers import DeviceFlatKmers, FlatKmers
 from .graph import GraphArrays
+from .kmer_counter import KmerCounter
 
 WINDOW_CAP = 500          # kmer_finder.py:137-160
 SUMMARY_DTYPE = np.dtype([("n_ref", np.uint32), ("n_alt", np.uint32), ("f_ref", np.uint32), ("f_alt", np.uint32),
@@ -190,10 +191,10 @@ class UniqueVariantKmersFinder:
         if use_simple:
             raise NotImplementedError("use_simple=True is not supported: the supported mode is the dense path with "
                                       "use_simple=False (find_unique_kmers_over_variant)")
-        if not isinstance(kmer_index_with_frequencies, CollisionFreeKmerIndex):
-            raise NotImplementedError("the frequency index must be graph_kmer_index_amd's CollisionFreeKmerIndex "
-                                      "(got %s); the npstructures KmerCounter source is not supported"
-                                      % type(kmer_index_with_frequencies).__name__)
+        if not isinstance(kmer_index_with_frequencies, (CollisionFreeKmerIndex, KmerCounter)):
+            raise NotImplementedError("the frequency source must be graph_kmer_index_amd's CollisionFreeKmerIndex or "
+                                      "KmerCounter (got %s); the reference's npstructures-backed KmerCounter is not "
+                                      "supported" % type(kmer_index_with_frequencies).__name__)
         assert position_id_index is not None, "Position id index must be set when using dense kmer finder"
         self.graph = graph
         self.variant_to_nodes = variant_to_nodes
@@ -324,9 +325,14 @@ class UniqueVariantKmersFinder:
         t3 = time.perf_counter()
         d_ref, d_alt = h(ref), h(alt)
         d_summ = _lib.DeviceArray(n_pos * SUMMARY_DTYPE.itemsize, np.uint8)
-        view = self._kmer_index_with_frequencies._device_index().view()
-        _lib.check(lib.gki_uvk_summarize(dg.handle, _lib.C.byref(view), d_rec.ptr, n_var, P, d_hashes.ptr, d_snodes.ptr,
-                                         d_soffs.ptr, d_rnodes.ptr, d_ref.ptr, d_alt.ptr, d_summ.ptr))
+        source = self._kmer_index_with_frequencies
+        cols_and_nodes = (d_rec.ptr, n_var, P, d_hashes.ptr, d_snodes.ptr, d_soffs.ptr, d_rnodes.ptr, d_ref.ptr, d_alt.ptr,
+                          d_summ.ptr)
+        if isinstance(source, KmerCounter):              # the count of the hash alone: no reverse complement added
+            _lib.check(lib.gki_uvk_summarize_counter(dg.handle, source._device_counter().handle, *cols_and_nodes))
+        else:
+            view = source._device_index().view()
+            _lib.check(lib.gki_uvk_summarize(dg.handle, _lib.C.byref(view), *cols_and_nodes))
         t["summarize"] = time.perf_counter() - t3
         # 4. selection; variants sharing a node with another variant of their chunk resolved in order on the host
         t4 = time.perf_counter()

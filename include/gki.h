@@ -458,6 +458,13 @@ int gki_uvk_starts(gki_graph *g, const void *d_lin_start, const void *d_lin_node
 int gki_uvk_summarize(gki_graph *g, const gki_index_view *ix, const void *d_rec_start, int64_t n_var,
                       int n_starts_per_variant, const void *d_hashes, const void *d_start_nodes, const void *d_start_offsets,
                       const void *d_nodes, const void *d_ref_nodes, const void *d_alt_nodes, void *d_summary);
+/* gki_uvk_summarize with a gki_counter (below) as frequency source: f_ref / f_alt are maxima of KmerCounter.get_frequency,
+ * the count of the hash alone with no reverse complement added, stored as 2^32 - 1 when above it. */
+typedef struct gki_counter gki_counter;
+int gki_uvk_summarize_counter(gki_graph *g, const gki_counter *counter, const void *d_rec_start, int64_t n_var,
+                              int n_starts_per_variant, const void *d_hashes, const void *d_start_nodes,
+                              const void *d_start_offsets, const void *d_nodes, const void *d_ref_nodes,
+                              const void *d_alt_nodes, void *d_summary);
 int gki_uvk_select(const void *d_summary, int64_t n_var, int n_starts_per_variant, int choose_lowest,
                    const void *d_store_mask, void *d_choice, void *d_out_start, int64_t *n_records);
 int gki_uvk_emit(gki_graph *g, const void *d_rec_start, int64_t n_var, int n_starts_per_variant, const void *d_choice,
@@ -487,6 +494,34 @@ int gki_sv_sample_count(gki_graph *g, const gki_index_view *ix, const void *d_ca
 int gki_sv_sample_emit(gki_sv_plan *plan, void *d_hashes, void *d_nodes, void *d_ref_offsets, void *d_af32,
                        float *kernel_ms);
 int gki_sv_sample_destroy(gki_sv_plan *plan);
+/* gki_sv_sample_count with a gki_counter as frequency source (window j is valid when the count of its hash alone is below
+ * max_frequency); the plan is emitted and destroyed like any other. */
+int gki_sv_sample_count_counter(gki_graph *g, const gki_counter *counter, const void *d_cand_nodes, int64_t n_cand, int k,
+                                int64_t max_frequency, void *d_rec_start, int64_t *n_records, gki_sv_plan **plan,
+                                float *kernel_ms);
+
+/* ---------------------------------------------------------------- k-mer counting (KmerCounter, KmerFrequencyIndex)
+ * np.unique(kmers[::stride], return_counts=True) of the reference (kmer_counter.py:24-43, kmer_frequency_index.py:18-25) on
+ * the device: a key-only stable radix sort, least significant 8-bit digit first, then run lengths.
+ * gki_unique_counts_count: d_kmers uint64[n], every stride-th of them taken (stride >= 1), read in place and never
+ *   written; key_bits in 1..64 (2k for k-mer hashes): digits above it are not sorted on, a key that does not fit is
+ *   GKI_ERR_BAD_ARG.  n in 0..2^33.  *n_unique = number of distinct keys, *plan what the emit call needs (release it with
+ *   gki_unique_counts_destroy).  kernel_ms (nullable) float[2]: the sort, the run-head count with its scan.  A failed
+ *   allocation is GKI_ERR_HIP with HIP's out-of-memory message, and nothing stays allocated.
+ * gki_unique_counts_emit: d_unique uint64[n_unique] ascending, d_counts int64[n_unique] exact.  kernel_ms (nullable)
+ *   float[1]. */
+typedef struct gki_unique_plan gki_unique_plan;
+int gki_unique_counts_count(const void *d_kmers, int64_t n, int64_t stride, int key_bits, int64_t *n_unique,
+                            gki_unique_plan **plan, float *kernel_ms);
+int gki_unique_counts_emit(gki_unique_plan *plan, void *d_unique, void *d_counts, float *kernel_ms);
+int gki_unique_counts_destroy(gki_unique_plan *plan);
+/* A counter over ascending distinct keys (uint64[n_unique], all below 2^key_bits) and their counts (int64[n_unique]), both
+ * of which must outlive it: a prefix directory over the keys' top bits (2^P + 1 int64 entries, 2^P in (n / 4, n / 2], at
+ * most 2^28) narrows a lookup to a bucket of a few keys.  gki_counter_lookup: d_out int64[q], the count of every query
+ * (uint64[q]) or 0 when it is absent -- KmerCounter.get_frequency (kmer_counter.py:72-74), no reverse complement. */
+int gki_counter_create(const void *d_unique, const void *d_counts, int64_t n_unique, int key_bits, gki_counter **out);
+int gki_counter_lookup(gki_counter *c, const void *d_queries, int64_t q, void *d_out);
+int gki_counter_destroy(gki_counter *c);
 
 /* ---------------------------------------------------------------- probe table (read-side hot loop)
  * A device-only re-layout of an index for counting: dir uint2[modulo] = {first record, count (16 bit, saturating)
