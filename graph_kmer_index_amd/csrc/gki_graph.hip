@@ -417,7 +417,7 @@ int gki_classify_nodes(int64_t n_nodes, const int32_t *node_size, const int64_t 
 int gki_critical_paths(int64_t n_nodes, const int32_t *node_size, const int64_t *edge_start, const int32_t *edges,
                        const int64_t *rev_start, const uint8_t *is_ref, const int32_t *chrom_start, int n_chrom,
                        int k, uint32_t *out_nodes, uint16_t *out_offsets, int64_t *n_out) {
-    int64_t found = 0;
+    int64_t found = 0, first_minus_one = -1;
     *n_out = 0;
     for (int c = 0; c < n_chrom; c++) {
         int64_t cur = chrom_start[c];
@@ -432,12 +432,15 @@ int gki_critical_paths(int64_t n_nodes, const int32_t *node_size, const int64_t 
             const int64_t size = node_size[cur];
             if (depth == 0 && size != 0 && since_join <= k && since_join + size >= k) {
                 const int64_t off = (int64_t)k - since_join - 1;
-                if (off < 0)
-                    return gki_set_error(GKI_ERR_BAD_ARG, "critical paths: node %lld is reached after exactly k bases "
-                                         "of single-edge chain; the reference raises here (uint16 offset -1)", (long long)cur);
-                out_nodes[found] = (uint32_t)cur;
-                out_offsets[found] = (uint16_t)off;
-                found++;
+                if (off < 0) {
+                    // the reference keeps walking: -1 only fails when the offsets become uint16 after ALL walks (:104),
+                    // so a branch error further on, in this chromosome or a later one, is the one it raises (:96-100)
+                    if (first_minus_one < 0) first_minus_one = cur;
+                } else {
+                    out_nodes[found] = (uint32_t)cur;
+                    out_offsets[found] = (uint16_t)off;
+                    found++;
+                }
             }
             const int64_t e0 = edge_start[cur], e1 = edge_start[cur + 1];
             depth += e1 - e0;
@@ -455,6 +458,9 @@ int gki_critical_paths(int64_t n_nodes, const int32_t *node_size, const int64_t 
             }
         }
     }
+    if (first_minus_one >= 0)
+        return gki_set_error(GKI_ERR_BAD_ARG, "critical paths: node %lld is reached after exactly k bases "
+                             "of single-edge chain; the reference raises here (uint16 offset -1)", (long long)first_minus_one);
     *n_out = found;
     return GKI_OK;
 }
