@@ -161,8 +161,9 @@ __device__ void forward_walk(const DevGraph &g, const NodeFwd *__restrict__ fw, 
     static_assert(!SCRIPT || (!EMIT && !DEEP), "the script is written by the product count kernel");
     constexpr int R = DEEP ? 0 : FWD_REG_LEVELS;
     uint32_t used = 0;                        // SCRIPT: entries written, 0xFF = this start position does not fit
-    // Per level four 64-bit words: (node, meta) with meta = bases collected (8 bits) | "forced traversal" (8) | variant
-    // nodes on the path (16); the successors still to take (cur, end); the hash so far; the smallest allele frequency on the
+    // Per level four 64-bit words: (node, meta) with meta = bases collected (8 bits) | "forced traversal" (7) | "outside the
+    // window" (1, level 0 only: see outside0 below) | variant nodes on the path (16); the successors still to take (cur, end);
+    // the hash so far; the smallest allele frequency on the
     // path so far (it comes with the node's record, so a finished k-mer asks for nothing).  The level that completes a k-mer
     // (every path's last) is never stored.  `last` (forced traversal only) is touched only when a follow set is given.
     typename StackOf<int32_t, FMAX, DEEP>::type last;
@@ -176,7 +177,8 @@ __device__ void forward_walk(const DevGraph &g, const NodeFwd *__restrict__ fw, 
 #define FW_META_OF(x_) ((uint32_t)((x_) >> 32))
 #define FW_MK(have_, forced_, vc_) ((uint32_t)(have_) | ((uint32_t)(forced_) << 8) | ((uint32_t)(vc_) << 16))
 #define FW_HAVE_OF(m_) ((int)((m_) & 0xFFu))
-#define FW_FORCED_OF(m_) ((int)(((m_) >> 8) & 0xFFu))
+#define FW_FORCED_OF(m_) ((int)(((m_) >> 8) & 0x7Fu))
+#define FW_OUTSIDE_OF(m_) ((int)(((m_) >> 15) & 1u))
 #define FW_VC_OF(m_) ((int)((m_) >> 16))
     const int cap = DEEP ? da.cap : FMAX;
     int steps_left = FW_BUDGET;
@@ -187,7 +189,12 @@ __device__ void forward_walk(const DevGraph &g, const NodeFwd *__restrict__ fw, 
     // level 0: the start node from offset o0 (an empty start node contributes no base)
     int L = 0, have0 = 0;
     uint64_t h0 = 0;
-    const double maf0 = fmin((double)INFINITY, w0.af);
+    // A start position at the END of a node with bases (o0 == size > 0): the reference's loop over the node's bases does not
+    // run (kmer_finder.py:268) and the search goes on in the successors with an empty path -- the start node is in no
+    // record, its allele frequency in no minimum, and it does not count as a variant node.  (An EMPTY start node is on the
+    // path: :261-265.)  Level 0 still holds the node, for its successors; its meta says that the window begins behind it.
+    const int outside0 = o0 == w0.size && w0.size > 0 ? 1 : 0;
+    const double maf0 = outside0 ? (double)INFINITY : fmin((double)INFINITY, w0.af);
     {
         const int avail = w0.size - o0;
         const int t = avail < k ? avail : k;
@@ -204,8 +211,8 @@ __device__ void forward_walk(const DevGraph &g, const NodeFwd *__restrict__ fw, 
         }
         have0 = t;
         if (t < k) {                           // (t == k: window complete inside the start node, handled below)
-            const int vc0 = w0.is_ref ? 0 : 1, forced0 = any_followed(g, follow, n0) ? 1 : 0;
-            lv_set(nm_r, nm_st, 0, (uint64_t)(uint32_t)n0 | ((uint64_t)FW_MK(t, forced0, vc0) << 32));
+            const int vc0 = w0.is_ref || outside0 ? 0 : 1, forced0 = any_followed(g, follow, n0) ? 1 : 0;
+            lv_set(nm_r, nm_st, 0, (uint64_t)(uint32_t)n0 | ((uint64_t)FW_MK(t, forced0 | outside0 << 7, vc0) << 32));
             lv_set(hs_r, hs_st, 0, h0);
             lv_set(mf_r, mf_st, 0, maf0);
             lv_set(ce_r, ce_st, 0, forced0 ? FW_CE((int32_t)g.edge_start[n0], (int32_t)g.edge_start[n0 + 1]) : succ_begin(g, w0, n0));
@@ -269,6 +276,33 @@ __device__ void forward_walk(const DevGraph &g, const NodeFwd *__restrict__ fw, 
         const double mafL = fmin(lv_get(mf_r, mf_st, j), wq.af);
         auto node_at = [&](int i) -> int32_t { return i == L ? q : FW_NODE_OF(lv_get(nm_r, nm_st, i)); };      // (level L itself is not stored)
         if (hv + t == k) {                          // first k-mer of this path: emit and stop (early stop, :326-330)
+            if (__builtin_expect(FW_OUTSIDE_OF(FW_META_OF(lv_get(nm_r, nm_st, 0))), 0)) {
+                // the window begins at level 1 (see outside0): its nodes are levels 1 .. L, one record per node by selection
+                int32_t mn = q;
+                for (int i = 1; i < L; i++) { const int32_t ni = node_at(i); mn = ni < mn ? ni : mn; }
+                if (EMIT) {
+                    if (one_node) {
+                        put_record<true>(out, idx, hL, q, t - 1, mn, mafL); idx++;
+                    } else {
+                        int32_t last = INT_MIN;
+                        for (int r = 0; r < L; r++) {
+                            int32_t best = INT_MAX;
+                            for (int i = 1; i <= L; i++) { const int32_t ni = node_at(i); if (ni > last && ni < best) best = ni; }
+                            put_record<false>(out, idx, hL, q, t - 1, best, mafL); idx++;
+                            last = best;
+                        }
+                    }
+                }
+                if (SCRIPT && used != 0xFFu) {                   // (in all-nodes mode such a start position is walked by the emit pass)
+                    if (one_node && used < (uint32_t)FW_SLOTS) {
+                        const int32_t one[FW_SN] = {mn, 0, 0, 0, 0};
+                        script_write(script, pos, (int)used, n_pos, hL, mafL, q, t - 1, 1, true, one);
+                        used++;
+                    } else used = 0xFFu;
+                }
+                count += one_node ? 1u : (uint32_t)L;
+                continue;
+            }
             const int Lw = L + 1;
             // the path's nodes when there are at most FW_SN of them (slots beyond the path: 0), whether their ids ascend, and
             // the smallest of them
