@@ -1,33 +1,25 @@
 // CollisionFreeKmerIndex on MI355X: bucket = kmer % modulo, records stably sorted by bucket,
 // bucket directory (first position + length), per-kmer frequencies, batched probe.
 //
-// Build = 4 kernels families:
-//   k_bucket_keys      bucket of every record (u64 % modulo) + identity permutation
-//   radix passes       stable LSD radix sort of (bucket, index) pairs, 8 bits per pass, only the
-//                      bits modulo-1 occupies; per pass: tile histograms -> scan -> ranked scatter with an
-//                      in-LDS reorder so every digit's run leaves the CU as one contiguous store
-//   k_pack_rows / k_gather_rows   the payload packed into 32-byte rows, permuted once by the sorted index
-//   k_directory / k_frequencies_*   bucket heads, lengths, distinct-ref_offset counts
+// This file holds
+//   the entry points      gki_index_build*, gki_partition_*by_bucket_range*, gki_reverse_index_build, gki_flag_repeated_kmers:
+//                         argument checks, then the row-carrying form or the bucket-range partition (gki_index_rows.hip)
+//   the pair-sorting form what the row-carrying form hands back (a group of buckets too large to stream with one workgroup,
+//                         2^31 records and more in the reverse index) and what its parity tests compare it with:
+//                         k_sort_keys (key of every record + the identity permutation), a stable LSD radix sort of the
+//                         (key, index) pairs, 8 bits per pass, only the bits the largest key occupies (per pass: tile
+//                         histograms -> scan -> ranked scatter with an in-LDS reorder so every digit's run leaves the CU as one
+//                         contiguous store), k_pack_rows / k_gather_rows (the payload packed into 16- or 32-byte rows,
+//                         permuted once by the sorted index), k_directory / k_node_directory
+//   frequencies           k_frequencies_small for the pair-sorting form; k_frequencies_ranges + k_frequencies_large for the
+//                         buckets of more than SMALL_BUCKET records that either form leaves open
+//   the lookups           k_lookup, k_count_nodes, k_get_small
 // Inside a bucket records keep their input order (stable sort), which is also what the oracle's
 // stable restatement produces, so the build is comparable element by element.
-#include "gki_common.h"
+#include "gki_index_internal.h"
 #include <cstring>
 #include <cstdlib>
 #include <mutex>
-
-int gki_index_build_rows(const void *d_kmers, const void *d_nodes, const void *d_ref_offsets, const void *d_af32, int64_t n,
-                         uint64_t modulo, uint64_t bucket_begin, uint64_t n_buckets, int skip_frequencies,
-                         int group_bits, const int64_t *h_group_start, const void *d_rows_in, const void *d_keys_in,
-                         void *d_hashes_to_index, void *d_n_kmers, void *d_out_kmers, void *d_out_nodes,
-                         void *d_out_ref_offsets, void *d_out_af32, void *d_out_frequencies, void *d_out_permutation, int *done,
-                         int by_node);
-int gki_partition_columns_by_part(const void *d_kmers, const void *d_nodes, const void *d_ref_offsets, const void *d_af32, int64_t n,
-                                  uint64_t modulo, int n_parts, int sub_bits, int64_t max_rows_per_pass, void *d_out_kmers,
-                                  void *d_out_nodes, void *d_out_ref_offsets, void *d_out_af32, void *d_out_rows, void *d_out_keys,
-                                  int64_t *h_part_start);
-int gki_frequencies_for_rows(const int64_t *d_row_begin, const int64_t *d_row_end, int n_ranges, uint64_t modulo,
-                             uint64_t bucket_begin, const void *d_hashes_to_index, const void *d_n_kmers,
-                             const void *d_kmers, const void *d_refs, void *d_freq, int64_t n, hipStream_t s);
 
 namespace {
 
@@ -36,15 +28,17 @@ constexpr int RI = 16;              // items per thread
 constexpr int RTILE = RB * RI;      // 4096 items per tile
 constexpr int RBINS = 256;
 
-__global__ __launch_bounds__(256) void k_bucket_keys(const uint64_t *__restrict__ kmers, int64_t n, uint64_t modulo,
-                                                     uint64_t bucket_begin, uint64_t n_buckets,
-                                                     uint32_t *__restrict__ keys, uint32_t *__restrict__ idx,
-                                                     int *__restrict__ out_of_range) {
+// The sort key of every record and the identity permutation: the bucket relative to the slice (collision_free_kmer_index.py:433)
+// or, BY_NODE, the node id with sl.n_buckets = the number of nodes.  A key outside the slice is flagged and replaced by one
+// inside it (the directory is never indexed out of range).
+template <bool BY_NODE>
+__global__ __launch_bounds__(256) void k_sort_keys(const void *__restrict__ src, int64_t n, Slice sl, uint32_t *__restrict__ keys,
+                                                   uint32_t *__restrict__ idx, int *__restrict__ bad) {
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint64_t b = kmers[i] % modulo - bucket_begin;       // collision_free_kmer_index.py:433
-        if (b >= n_buckets) *out_of_range = 1;
-        keys[i] = b < n_buckets ? (uint32_t)b : 0u;
+        uint64_t b = BY_NODE ? (uint64_t)((const uint32_t *)src)[i] : ((const uint64_t *)src)[i] % sl.modulo - sl.bucket_begin;
+        if (b >= sl.n_buckets) { *bad = 1; b = BY_NODE ? sl.n_buckets - 1 : 0; }
+        keys[i] = (uint32_t)b;
         idx[i] = (uint32_t)i;
     }
 }
@@ -153,30 +147,26 @@ __global__ __launch_bounds__(RB) void k_radix_scatter(const uint32_t *__restrict
 // (measured: 30 ms of a 50 ms build at 3.2e8 records).  The columns are first packed into 32-byte rows (one
 // streaming pass), so the random access is one sector per record; the permuted rows are unpacked into the output
 // columns with coalesced stores.
-struct Row { uint64_t kmer, ref; uint32_t node; float af; uint64_t pad; };     // 32 B
-
-__global__ __launch_bounds__(256) void k_pack_rows(const uint64_t *__restrict__ kmers, const uint32_t *__restrict__ nodes,
-                                                   const uint64_t *__restrict__ refs, const float *__restrict__ af, int64_t n,
-                                                   uint4 *__restrict__ rows) {
+// Q 16-byte words per row: (k-mer, ref offset) and, Q = 2, (node, allele frequency, -, -); the reverse index has the first only.
+template <int Q>
+__global__ __launch_bounds__(256) void k_pack_rows(RecordCols c, int64_t n, uint4 *__restrict__ rows) {
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint64_t k = kmers[i], r = refs[i];
-        rows[2 * i] = make_uint4((uint32_t)k, (uint32_t)(k >> 32), (uint32_t)r, (uint32_t)(r >> 32));
-        rows[2 * i + 1] = make_uint4(nodes[i], __float_as_uint(af[i]), 0u, 0u);
+        const uint64_t k = c.kmers[i], r = c.refs[i];
+        rows[Q * i] = make_uint4((uint32_t)k, (uint32_t)(k >> 32), (uint32_t)r, (uint32_t)(r >> 32));
+        if (Q == 2) rows[Q * i + 1] = make_uint4(c.nodes[i], c.af[i], 0u, 0u);
     }
 }
 
-__global__ __launch_bounds__(256) void k_gather_rows(const uint32_t *__restrict__ idx, int64_t n, const uint4 *__restrict__ rows,
-                                                     uint64_t *__restrict__ o_kmers, uint32_t *__restrict__ o_nodes,
-                                                     uint64_t *__restrict__ o_refs, float *__restrict__ o_af) {
+template <int Q>
+__global__ __launch_bounds__(256) void k_gather_rows(const uint32_t *__restrict__ idx, int64_t n, const uint4 *__restrict__ rows, RecordColsOut o) {
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const int64_t j = idx[i];
-        const uint4 a = rows[2 * j], b = rows[2 * j + 1];
-        o_kmers[i] = ((uint64_t)a.y << 32) | a.x;
-        o_refs[i] = ((uint64_t)a.w << 32) | a.z;
-        o_nodes[i] = b.x;
-        o_af[i] = __uint_as_float(b.y);
+        const uint4 a = rows[Q * j], b = Q == 2 ? rows[Q * j + 1] : a;
+        o.kmers[i] = ((uint64_t)a.y << 32) | a.x;
+        o.refs[i] = ((uint64_t)a.w << 32) | a.z;
+        if (Q == 2) { o.nodes[i] = b.x; o.af[i] = b.y; }
     }
 }
 
@@ -204,8 +194,6 @@ __global__ __launch_bounds__(256) void k_directory(const uint32_t *__restrict__ 
         n_kmers[b] = (uint32_t)(e - i);
     }
 }
-
-constexpr int SMALL_BUCKET = 24;
 
 // set_frequencies (collision_free_kmer_index.py:267-293): for every record, the number of distinct
 // ref_offsets among the records of its bucket that carry the same k-mer.  Buckets of up to
@@ -371,12 +359,6 @@ __global__ __launch_bounds__(256) void k_count_nodes(IndexDev ix, const uint64_t
 }
 
 
-static int key_bits(uint64_t max_key) {
-    int bits = 0;
-    while (bits < 32 && (max_key >> bits) != 0) bits++;
-    return bits;
-}
-
 // Stable LSD sort of (key, value) pairs on the low `bits` bits of the key; ping-pongs between the two
 // buffers of each pair, *cur_out = index of the buffers holding the result.
 static int radix_sort_pairs(uint32_t *keys[2], uint32_t *vals[2], int64_t n, int bits, uint32_t *hist, uint32_t *offs,
@@ -443,16 +425,6 @@ __global__ __launch_bounds__(256) void k_narrow_counts(const uint32_t *__restric
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = (uint16_t)in[i];
 }
 
-__global__ __launch_bounds__(256) void k_node_keys(const uint32_t *__restrict__ nodes, int64_t n, uint64_t n_nodes, uint32_t *__restrict__ keys,
-                                                   uint32_t *__restrict__ idx, int *__restrict__ bad) {
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        uint32_t v = nodes[i];
-        if ((uint64_t)v >= n_nodes) { *bad = 1; v = (uint32_t)(n_nodes - 1); }      // (the directory is never indexed out of range)
-        keys[i] = v; idx[i] = (uint32_t)i;
-    }
-}
-
 // Node directory of the reverse index, two streaming passes and no search: PASS 0 -- the head of a run records where the
 // node's records start; PASS 1 (launched after it) -- the tail of a run records how many there are.  A node has tens of
 // records, so "the head lane finds the end of its run" (run_end: 16 steps, then a binary search over the rest of the
@@ -471,33 +443,12 @@ __global__ __launch_bounds__(256) void k_node_directory(const uint32_t *__restri
     }
 }
 
-__global__ __launch_bounds__(256) void k_pack_pairs(const uint64_t *__restrict__ a, const uint64_t *__restrict__ b, int64_t n,
-                                                    uint4 *__restrict__ rows) {
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint64_t x = a[i], y = b[i];
-        rows[i] = make_uint4((uint32_t)x, (uint32_t)(x >> 32), (uint32_t)y, (uint32_t)(y >> 32));
-    }
-}
-
-__global__ __launch_bounds__(256) void k_gather_pairs(const uint32_t *__restrict__ idx, int64_t n, const uint4 *__restrict__ rows,
-                                                      uint64_t *__restrict__ o_a, uint64_t *__restrict__ o_b) {
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint4 r = rows[idx[i]];
-        o_a[i] = ((uint64_t)r.y << 32) | r.x;
-        o_b[i] = ((uint64_t)r.w << 32) | r.z;
-    }
-}
-
 }  // namespace
 
 // Frequencies of the buckets in large_list (more than SMALL_BUCKET records each): sizes -> scratch offsets -> one block
 // per bucket.  `sizes` is scratch for n_large uint32.
-static int frequencies_large_pass(const uint32_t *large_list, unsigned int n_large, uint32_t *sizes, const void *d_hashes_to_index,
-                                  const void *d_n_kmers, const void *d_kmers, const void *d_refs, void *d_freq, hipStream_t s) {
-    hipLaunchKernelGGL(k_large_sizes, dim3(stream_grid(n_large, 256)), dim3(256), 0, s, large_list, n_large,
-                       (const uint32_t *)d_n_kmers, sizes);
+static int frequencies_large_pass(const uint32_t *large_list, unsigned int n_large, uint32_t *sizes, const IndexOut &out, hipStream_t s) {
+    hipLaunchKernelGGL(k_large_sizes, dim3(stream_grid(n_large, 256)), dim3(256), 0, s, large_list, n_large, out.n_kmers, sizes);
     HIP_TRY(hipGetLastError());
     const int64_t tmp2_bytes = gki_scan_tmp_bytes(n_large);
     DevBuf starts, tmp2, scratch;
@@ -508,9 +459,8 @@ static int frequencies_large_pass(const uint32_t *large_list, unsigned int n_lar
     HIP_TRY(hipMemcpy(&total, starts.get<int64_t>() + n_large, 8, hipMemcpyDeviceToHost));
     HIP_TRY(scratch.alloc((size_t)total * sizeof(Pair)));
     const unsigned grid = n_large < 2048 ? n_large : 2048;
-    hipLaunchKernelGGL(k_frequencies_large, dim3(grid), dim3(256), 0, s, large_list, n_large, (const int32_t *)d_hashes_to_index,
-                       (const uint32_t *)d_n_kmers, (const uint64_t *)d_kmers, (const uint64_t *)d_refs, starts.get<const int64_t>(),
-                       scratch.get<Pair>(), (uint16_t *)d_freq);
+    hipLaunchKernelGGL(k_frequencies_large, dim3(grid), dim3(256), 0, s, large_list, n_large, out.h2i, out.n_kmers, out.cols.kmers,
+                       out.cols.refs, starts.get<const int64_t>(), scratch.get<Pair>(), out.freq);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
     return GKI_OK;
@@ -548,9 +498,8 @@ __global__ __launch_bounds__(256) void k_frequencies_ranges(const int64_t *__res
     }
 }
 
-int gki_frequencies_for_rows(const int64_t *d_row_begin, const int64_t *d_row_end, int n_ranges, uint64_t modulo,
-                             uint64_t bucket_begin, const void *d_hashes_to_index, const void *d_n_kmers, const void *d_kmers,
-                             const void *d_refs, void *d_freq, int64_t n, hipStream_t s) {
+int gki_frequencies_for_rows(const int64_t *d_row_begin, const int64_t *d_row_end, int n_ranges, const Slice &slice,
+                             const IndexOut &out, int64_t n, hipStream_t s) {
     if (n_ranges <= 0) return GKI_OK;
     const size_t cap = (size_t)(n / SMALL_BUCKET + 1);
     DevBuf large_list, sizes, n_large_d;
@@ -559,17 +508,126 @@ int gki_frequencies_for_rows(const int64_t *d_row_begin, const int64_t *d_row_en
     HIP_TRY(n_large_d.alloc(16));
     HIP_TRY(hipMemsetAsync(n_large_d.get(), 0, 4, s));
     hipLaunchKernelGGL(k_frequencies_ranges, dim3(n_ranges < 4096 ? n_ranges : 4096), dim3(256), 0, s, d_row_begin, d_row_end,
-                       n_ranges, modulo, bucket_begin, (const int32_t *)d_hashes_to_index, (const uint32_t *)d_n_kmers,
-                       (const uint64_t *)d_kmers, (const uint64_t *)d_refs, (uint16_t *)d_freq, large_list.get<uint32_t>(),
-                       n_large_d.get<unsigned int>());
+                       n_ranges, slice.modulo, slice.bucket_begin, out.h2i, out.n_kmers, out.cols.kmers, out.cols.refs, out.freq,
+                       large_list.get<uint32_t>(), n_large_d.get<unsigned int>());
     HIP_TRY(hipGetLastError());
     unsigned int n_large = 0;
     HIP_TRY(hipMemcpyAsync(&n_large, n_large_d.get(), 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (n_large > 0)
-        GKI_TRY(frequencies_large_pass(large_list.get<uint32_t>(), n_large, sizes.get<uint32_t>(), d_hashes_to_index, d_n_kmers,
-                                       d_kmers, d_refs, d_freq, s));
+    if (n_large > 0) GKI_TRY(frequencies_large_pass(large_list.get<uint32_t>(), n_large, sizes.get<uint32_t>(), out, s));
     return GKI_OK;
+}
+
+// ------------------------------------------------------------------------------------ host layer of the entry points
+static IndexOut index_out(void *h2i, void *n_kmers, void *kmers, void *nodes, void *refs, void *af, void *freq, void *perm) {
+    return {(int32_t *)h2i, (uint32_t *)n_kmers, record_cols_out(kmers, nodes, refs, af), (uint16_t *)freq, (uint32_t *)perm};
+}
+
+// a build's slice of the buckets, its grouping (where the entry point takes one) and the int32 directory's limit
+static int check_slice_args(const Slice &sl, int64_t n, const Grouping *gr = nullptr) {
+    if (sl.modulo == 0 || sl.modulo > 0xFFFFFFFFull) return gki_set_error(GKI_ERR_BAD_ARG, "modulo must be in 1..2^32-1");
+    if (sl.n_buckets == 0 || sl.bucket_begin + sl.n_buckets > sl.modulo)
+        return gki_set_error(GKI_ERR_BAD_ARG, "bucket range [%llu, +%llu) outside [0, modulo)", (unsigned long long)sl.bucket_begin,
+                             (unsigned long long)sl.n_buckets);
+    if (gr && (gr->group_bits < 0 || gr->group_bits > 10 || (gr->group_bits > 0 && !gr->h_group_start)))
+        return gki_set_error(GKI_ERR_BAD_ARG, "group_bits must be in 0..10, with the group bounds when > 0");
+    if (n >= (1ll << 31))
+        return gki_set_error(GKI_ERR_OVERFLOW, "%lld records: the reference's directory is int32 "
+                             "(collision_free_kmer_index.py:453); shard the build", (long long)n);
+    return GKI_OK;
+}
+
+static int check_part_args(const PartSpec &sp) {
+    if (sp.modulo == 0 || sp.modulo > 0xFFFFFFFFull) return gki_set_error(GKI_ERR_BAD_ARG, "modulo must be in 1..2^32-1");
+    if (sp.n_parts < 1 || sp.n_parts > 256) return gki_set_error(GKI_ERR_BAD_ARG, "n_parts must be in 1..256");
+    if (sp.sub_bits < 0 || (sp.n_parts << sp.sub_bits) > 1024) return gki_set_error(GKI_ERR_BAD_ARG, "n_parts << group_bits must not exceed 1024");
+    return GKI_OK;
+}
+
+// The front of the pair-sorting form: the key of every record (BY_NODE: its node id, else its bucket in `sl`) with the
+// identity permutation, stably sorted by key: sorted keys in ss.keys[*cur], sorted permutation in ss.vals[*cur].
+// h_bad (may be NULL: no key can lie outside): read back before the sort, set = a key outside the slice; nothing is
+// sorted then and the caller words the refusal.
+template <bool BY_NODE>
+static int sort_by_key(SortScratch &ss, const void *d_src, int64_t n, const Slice &sl, hipStream_t s, int *cur, int *h_bad) {
+    GKI_TRY(ss.alloc(n));
+    int *bad = (int *)ss.hist;                    // hist is not in use yet
+    HIP_TRY(hipMemsetAsync(bad, 0, 4, s));
+    hipLaunchKernelGGL(k_sort_keys<BY_NODE>, dim3(stream_grid(n, 256)), dim3(256), 0, s, d_src, n, sl, ss.keys[0], ss.vals[0], bad);
+    HIP_TRY(hipGetLastError());
+    if (h_bad) {
+        HIP_TRY(hipMemcpyAsync(h_bad, bad, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (*h_bad) return GKI_OK;
+    }
+    return ss.sort(n, key_bits(sl.n_buckets - 1), s, cur);
+}
+
+// The payload permuted by the sorted index through rows of Q 16-byte words (k_pack_rows).  rows_b is the caller's: its free
+// waits for the device and belongs at the caller's end.
+template <int Q>
+static int permute_payload(DevBuf &rows_b, const RecordCols &c, const uint32_t *perm, int64_t n, const RecordColsOut &o, hipStream_t s) {
+    HIP_TRY(rows_b.alloc((size_t)n * 16 * Q));
+    hipLaunchKernelGGL(k_pack_rows<Q>, dim3(stream_grid(n, 256)), dim3(256), 0, s, c, n, rows_b.get<uint4>());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_gather_rows<Q>, dim3(stream_grid(n, 256)), dim3(256), 0, s, perm, n, rows_b.get<const uint4>(), o);
+    HIP_TRY(hipGetLastError());
+    return GKI_OK;
+}
+
+// the pair-sorting form of the build (arguments checked by the caller)
+static int build_pairs(const RecordCols &cols, int64_t n, const Slice &sl, int skip_frequencies, const IndexOut &out) {
+    hipStream_t s = 0;
+    HIP_TRY(hipMemsetAsync(out.h2i, 0, (size_t)sl.n_buckets * 4, s));              // :453
+    HIP_TRY(hipMemsetAsync(out.n_kmers, 0, (size_t)sl.n_buckets * 4, s));          // :456
+    if (n <= 0) { HIP_TRY(hipStreamSynchronize(s)); return GKI_OK; }
+    HIP_TRY(hipMemsetAsync(out.freq, 0, (size_t)n * 2, s));                        // :270
+    SortScratch ss;
+    DevBuf rows_b;
+    int cur = 0, h_bad = 0;
+    GKI_TRY(sort_by_key<false>(ss, cols.kmers, n, sl, s, &cur, sl.n_buckets != sl.modulo ? &h_bad : nullptr));
+    if (h_bad) return gki_set_error(GKI_ERR_BAD_ARG, "a record's bucket lies outside [%llu, +%llu)",
+                                    (unsigned long long)sl.bucket_begin, (unsigned long long)sl.n_buckets);
+    uint32_t **keys = ss.keys, **vals = ss.vals;
+    GKI_TRY(permute_payload<2>(rows_b, cols, vals[cur], n, out.cols, s));
+    if (out.perm) HIP_TRY(hipMemcpyAsync(out.perm, vals[cur], (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(k_directory, dim3(stream_grid(n, 256)), dim3(256), 0, s, keys[cur], n, out.h2i, out.n_kmers);
+    HIP_TRY(hipGetLastError());
+    if (!skip_frequencies) {
+        // large-bucket work list: at most n / SMALL_BUCKET entries; reuse the spare key/val buffers
+        uint32_t *large_list = keys[1 - cur];
+        unsigned int *n_large_d = (unsigned int *)ss.hist;
+        HIP_TRY(hipMemsetAsync(n_large_d, 0, 4, s));
+        hipLaunchKernelGGL(k_frequencies_small, dim3(stream_grid(n, 256)), dim3(256), 0, s, keys[cur], n, out.h2i, out.n_kmers,
+                           out.cols.kmers, out.cols.refs, out.freq, large_list, n_large_d);
+        HIP_TRY(hipGetLastError());
+        unsigned int n_large = 0;
+        HIP_TRY(hipMemcpyAsync(&n_large, n_large_d, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (n_large > 0) GKI_TRY(frequencies_large_pass(large_list, n_large, vals[1 - cur], out, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return GKI_OK;
+}
+
+// The row-carrying form (gki_index_rows.hip); the pair-sorting form takes over for inputs outside its domain (it sorts on
+// the whole key: a grouping of the input is of no use to it and does no harm)
+static int build_range(const RecordCols &cols, int64_t n, const Slice &sl, const Grouping &gr, int skip_frequencies, const IndexOut &out) {
+    GKI_TRY(check_slice_args(sl, n, &gr));
+    if (n > 0) {
+        const int r = gki_index_build_rows(cols, RowsIn{}, n, sl, gr, skip_frequencies, 0, out);
+        if (r != GKI_NOT_BUILT) return r;
+    }
+    return build_pairs(cols, n, sl, skip_frequencies, out);
+}
+
+// (arguments checked by the caller)
+static int partition(const RecordCols &cols, int64_t n, const PartSpec &sp, const RecordColsOut &out_cols, const RowsOut &out_rows,
+                     int64_t *h_start) {
+    for (int p = 0; p <= (sp.n_parts << sp.sub_bits); p++) h_start[p] = 0;
+    if (n <= 0) return GKI_OK;
+    // stable passes of the row-carrying build's partition kernel (gki_index_rows.hip)
+    return gki_partition_columns_by_part(cols, n, sp, out_cols, out_rows, h_start);
 }
 
 extern "C" {
@@ -578,66 +636,11 @@ int gki_index_build_pairs(const void *d_kmers, const void *d_nodes, const void *
                           uint64_t modulo, uint64_t bucket_begin, uint64_t n_buckets, int skip_frequencies,
                           void *d_hashes_to_index, void *d_n_kmers, void *d_out_kmers, void *d_out_nodes,
                           void *d_out_ref_offsets, void *d_out_af32, void *d_out_frequencies, void *d_out_permutation) {
-    if (modulo == 0 || modulo > 0xFFFFFFFFull) return gki_set_error(GKI_ERR_BAD_ARG, "modulo must be in 1..2^32-1");
-    if (n_buckets == 0 || bucket_begin + n_buckets > modulo)
-        return gki_set_error(GKI_ERR_BAD_ARG, "bucket range [%llu, +%llu) outside [0, modulo)", (unsigned long long)bucket_begin,
-                             (unsigned long long)n_buckets);
-    if (n >= (1ll << 31))
-        return gki_set_error(GKI_ERR_OVERFLOW, "%lld records: the reference's directory is int32 "
-                             "(collision_free_kmer_index.py:453); shard the build", (long long)n);
-    hipStream_t s = 0;
-    HIP_TRY(hipMemsetAsync(d_hashes_to_index, 0, (size_t)n_buckets * 4, s));       // :453
-    HIP_TRY(hipMemsetAsync(d_n_kmers, 0, (size_t)n_buckets * 4, s));               // :456
-    if (n <= 0) { HIP_TRY(hipStreamSynchronize(s)); return GKI_OK; }
-    HIP_TRY(hipMemsetAsync(d_out_frequencies, 0, (size_t)n * 2, s));               // :270
-    SortScratch ss;
-    DevBuf rows_b;
-    GKI_TRY(ss.alloc(n));
-    uint32_t **keys = ss.keys, **vals = ss.vals, *hist = ss.hist;
-    int *bad = (int *)hist;                       // hist is not in use yet
-    HIP_TRY(hipMemsetAsync(bad, 0, 4, s));
-    hipLaunchKernelGGL(k_bucket_keys, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const uint64_t *)d_kmers, n, modulo,
-                       bucket_begin, n_buckets, keys[0], vals[0], bad);
-    HIP_TRY(hipGetLastError());
-    if (n_buckets != modulo) {
-        int h_bad = 0;
-        HIP_TRY(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (h_bad) return gki_set_error(GKI_ERR_BAD_ARG, "a record's bucket lies outside [%llu, +%llu)",
-                                        (unsigned long long)bucket_begin, (unsigned long long)n_buckets);
-    }
-    int cur = 0;
-    GKI_TRY(ss.sort(n, key_bits(n_buckets - 1), s, &cur));
-    HIP_TRY(rows_b.alloc((size_t)n * 32));
-    uint4 *rows = rows_b.get<uint4>();
-    hipLaunchKernelGGL(k_pack_rows, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const uint64_t *)d_kmers,
-                       (const uint32_t *)d_nodes, (const uint64_t *)d_ref_offsets, (const float *)d_af32, n, rows);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_gather_rows, dim3(stream_grid(n, 256)), dim3(256), 0, s, vals[cur], n, (const uint4 *)rows,
-                       (uint64_t *)d_out_kmers, (uint32_t *)d_out_nodes, (uint64_t *)d_out_ref_offsets, (float *)d_out_af32);
-    HIP_TRY(hipGetLastError());
-    if (d_out_permutation) HIP_TRY(hipMemcpyAsync(d_out_permutation, vals[cur], (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(k_directory, dim3(stream_grid(n, 256)), dim3(256), 0, s, keys[cur], n, (int32_t *)d_hashes_to_index,
-                       (uint32_t *)d_n_kmers);
-    HIP_TRY(hipGetLastError());
-    if (!skip_frequencies) {
-        // large-bucket work list: at most n / SMALL_BUCKET entries; reuse the spare key/val buffers
-        uint32_t *large_list = keys[1 - cur];
-        unsigned int *n_large_d = (unsigned int *)hist;
-        HIP_TRY(hipMemsetAsync(n_large_d, 0, 4, s));
-        hipLaunchKernelGGL(k_frequencies_small, dim3(stream_grid(n, 256)), dim3(256), 0, s, keys[cur], n,
-                           (const int32_t *)d_hashes_to_index, (const uint32_t *)d_n_kmers, (const uint64_t *)d_out_kmers,
-                           (const uint64_t *)d_out_ref_offsets, (uint16_t *)d_out_frequencies, large_list, n_large_d);
-        HIP_TRY(hipGetLastError());
-        unsigned int n_large = 0;
-        HIP_TRY(hipMemcpyAsync(&n_large, n_large_d, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (n_large > 0)
-            GKI_TRY(frequencies_large_pass(large_list, n_large, vals[1 - cur], d_hashes_to_index, d_n_kmers, d_out_kmers,
-                                           d_out_ref_offsets, d_out_frequencies, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    return GKI_OK;
+    const Slice sl = {modulo, bucket_begin, n_buckets};
+    GKI_TRY(check_slice_args(sl, n));
+    return build_pairs(record_cols(d_kmers, d_nodes, d_ref_offsets, d_af32), n, sl, skip_frequencies,
+                       index_out(d_hashes_to_index, d_n_kmers, d_out_kmers, d_out_nodes, d_out_ref_offsets, d_out_af32, d_out_frequencies,
+                                 d_out_permutation));
 }
 
 int gki_index_build_range_grouped(const void *d_kmers, const void *d_nodes, const void *d_ref_offsets, const void *d_af32, int64_t n,
@@ -645,87 +648,56 @@ int gki_index_build_range_grouped(const void *d_kmers, const void *d_nodes, cons
                                   int group_bits, const int64_t *h_group_start,
                                   void *d_hashes_to_index, void *d_n_kmers, void *d_out_kmers, void *d_out_nodes,
                                   void *d_out_ref_offsets, void *d_out_af32, void *d_out_frequencies, void *d_out_permutation) {
-    if (modulo == 0 || modulo > 0xFFFFFFFFull) return gki_set_error(GKI_ERR_BAD_ARG, "modulo must be in 1..2^32-1");
-    if (n_buckets == 0 || bucket_begin + n_buckets > modulo)
-        return gki_set_error(GKI_ERR_BAD_ARG, "bucket range [%llu, +%llu) outside [0, modulo)", (unsigned long long)bucket_begin,
-                             (unsigned long long)n_buckets);
-    if (group_bits < 0 || group_bits > 10 || (group_bits > 0 && !h_group_start))
-        return gki_set_error(GKI_ERR_BAD_ARG, "group_bits must be in 0..10, with the group bounds when > 0");
-    if (n >= (1ll << 31))
-        return gki_set_error(GKI_ERR_OVERFLOW, "%lld records: the reference's directory is int32 "
-                             "(collision_free_kmer_index.py:453); shard the build", (long long)n);
-    if (n > 0) {
-        // the row-carrying form (gki_index_rows.hip); the pair-sorting form below takes over for inputs outside its domain
-        // (it sorts on the whole key: a grouping of the input is of no use to it and does no harm)
-        int done = 0;
-        GKI_TRY(gki_index_build_rows(d_kmers, d_nodes, d_ref_offsets, d_af32, n, modulo, bucket_begin, n_buckets, skip_frequencies,
-                                     group_bits, h_group_start, nullptr, nullptr, d_hashes_to_index, d_n_kmers, d_out_kmers, d_out_nodes,
-                                     d_out_ref_offsets, d_out_af32, d_out_frequencies, d_out_permutation, &done, 0));
-        if (done) return GKI_OK;
-    }
-    return gki_index_build_pairs(d_kmers, d_nodes, d_ref_offsets, d_af32, n, modulo, bucket_begin, n_buckets, skip_frequencies,
-                                 d_hashes_to_index, d_n_kmers, d_out_kmers, d_out_nodes, d_out_ref_offsets, d_out_af32,
-                                 d_out_frequencies, d_out_permutation);
+    return build_range(record_cols(d_kmers, d_nodes, d_ref_offsets, d_af32), n, {modulo, bucket_begin, n_buckets}, {group_bits, h_group_start},
+                       skip_frequencies,
+                       index_out(d_hashes_to_index, d_n_kmers, d_out_kmers, d_out_nodes, d_out_ref_offsets, d_out_af32, d_out_frequencies,
+                                 d_out_permutation));
 }
 
 int gki_index_build_range(const void *d_kmers, const void *d_nodes, const void *d_ref_offsets, const void *d_af32, int64_t n,
                           uint64_t modulo, uint64_t bucket_begin, uint64_t n_buckets, int skip_frequencies,
                           void *d_hashes_to_index, void *d_n_kmers, void *d_out_kmers, void *d_out_nodes,
                           void *d_out_ref_offsets, void *d_out_af32, void *d_out_frequencies, void *d_out_permutation) {
-    return gki_index_build_range_grouped(d_kmers, d_nodes, d_ref_offsets, d_af32, n, modulo, bucket_begin, n_buckets, skip_frequencies,
-                                         0, nullptr, d_hashes_to_index, d_n_kmers, d_out_kmers, d_out_nodes, d_out_ref_offsets,
-                                         d_out_af32, d_out_frequencies, d_out_permutation);
+    return build_range(record_cols(d_kmers, d_nodes, d_ref_offsets, d_af32), n, {modulo, bucket_begin, n_buckets}, {0, nullptr}, skip_frequencies,
+                       index_out(d_hashes_to_index, d_n_kmers, d_out_kmers, d_out_nodes, d_out_ref_offsets, d_out_af32, d_out_frequencies,
+                                 d_out_permutation));
 }
 
 int gki_index_build(const void *d_kmers, const void *d_nodes, const void *d_ref_offsets, const void *d_af32, int64_t n,
                     uint64_t modulo, int skip_frequencies, void *d_hashes_to_index, void *d_n_kmers, void *d_out_kmers,
                     void *d_out_nodes, void *d_out_ref_offsets, void *d_out_af32, void *d_out_frequencies,
                     void *d_out_permutation) {
-    return gki_index_build_range(d_kmers, d_nodes, d_ref_offsets, d_af32, n, modulo, 0, modulo, skip_frequencies,
-                                 d_hashes_to_index, d_n_kmers, d_out_kmers, d_out_nodes, d_out_ref_offsets, d_out_af32,
-                                 d_out_frequencies, d_out_permutation);
+    return build_range(record_cols(d_kmers, d_nodes, d_ref_offsets, d_af32), n, {modulo, 0, modulo}, {0, nullptr}, skip_frequencies,
+                       index_out(d_hashes_to_index, d_n_kmers, d_out_kmers, d_out_nodes, d_out_ref_offsets, d_out_af32, d_out_frequencies,
+                                 d_out_permutation));
 }
 
 int gki_partition_by_bucket_range_grouped(const void *d_kmers, const void *d_nodes, const void *d_ref_offsets, const void *d_af32,
                                           int64_t n, uint64_t modulo, int n_parts, int group_bits, int64_t max_rows_per_pass,
                                           void *d_out_kmers, void *d_out_nodes, void *d_out_ref_offsets, void *d_out_af32,
                                           int64_t *h_start) {
-    if (modulo == 0 || modulo > 0xFFFFFFFFull) return gki_set_error(GKI_ERR_BAD_ARG, "modulo must be in 1..2^32-1");
-    if (n_parts < 1 || n_parts > 256) return gki_set_error(GKI_ERR_BAD_ARG, "n_parts must be in 1..256");
-    if (group_bits < 0 || (n_parts << group_bits) > 1024) return gki_set_error(GKI_ERR_BAD_ARG, "n_parts << group_bits must not exceed 1024");
-    for (int p = 0; p <= (n_parts << group_bits); p++) h_start[p] = 0;
-    if (n <= 0) return GKI_OK;
-    // stable passes of the row-carrying build's partition kernel, columns in, columns out (gki_index_rows.hip)
-    return gki_partition_columns_by_part(d_kmers, d_nodes, d_ref_offsets, d_af32, n, modulo, n_parts, group_bits, max_rows_per_pass,
-                                         d_out_kmers, d_out_nodes, d_out_ref_offsets, d_out_af32, nullptr, nullptr, h_start);
+    const PartSpec sp = {modulo, n_parts, group_bits, max_rows_per_pass};
+    GKI_TRY(check_part_args(sp));
+    return partition(record_cols(d_kmers, d_nodes, d_ref_offsets, d_af32), n, sp,
+                     record_cols_out(d_out_kmers, d_out_nodes, d_out_ref_offsets, d_out_af32), RowsOut{}, h_start);
 }
 
 int gki_partition_rows_by_bucket_range(const void *d_kmers, const void *d_nodes, const void *d_ref_offsets, const void *d_af32,
                                        int64_t n, uint64_t modulo, int n_parts, int group_bits, int64_t max_rows_per_pass,
                                        void *d_rows, void *d_keys, int64_t *h_start) {
-    if (modulo == 0 || modulo > 0xFFFFFFFFull) return gki_set_error(GKI_ERR_BAD_ARG, "modulo must be in 1..2^32-1");
-    if (n_parts < 1 || n_parts > 256) return gki_set_error(GKI_ERR_BAD_ARG, "n_parts must be in 1..256");
-    if (group_bits < 0 || (n_parts << group_bits) > 1024) return gki_set_error(GKI_ERR_BAD_ARG, "n_parts << group_bits must not exceed 1024");
+    const PartSpec sp = {modulo, n_parts, group_bits, max_rows_per_pass};
+    GKI_TRY(check_part_args(sp));
     if (!d_rows || !d_keys) return gki_set_error(GKI_ERR_BAD_ARG, "rows and keys buffers are needed");
-    for (int p = 0; p <= (n_parts << group_bits); p++) h_start[p] = 0;
-    if (n <= 0) return GKI_OK;
-    return gki_partition_columns_by_part(d_kmers, d_nodes, d_ref_offsets, d_af32, n, modulo, n_parts, group_bits, max_rows_per_pass,
-                                         nullptr, nullptr, nullptr, nullptr, d_rows, d_keys, h_start);
+    return partition(record_cols(d_kmers, d_nodes, d_ref_offsets, d_af32), n, sp, RecordColsOut{}, {(uint64_t *)d_rows, (uint32_t *)d_keys}, h_start);
 }
 
 int gki_index_build_range_from_rows(const void *d_rows, const void *d_keys, int64_t n, uint64_t modulo, uint64_t bucket_begin,
                                     uint64_t n_buckets, int skip_frequencies, int group_bits, const int64_t *h_group_start,
                                     void *d_hashes_to_index, void *d_n_kmers, void *d_out_kmers, void *d_out_nodes,
                                     void *d_out_ref_offsets, void *d_out_af32, void *d_out_frequencies) {
-    if (modulo == 0 || modulo > 0xFFFFFFFFull) return gki_set_error(GKI_ERR_BAD_ARG, "modulo must be in 1..2^32-1");
-    if (n_buckets == 0 || bucket_begin + n_buckets > modulo)
-        return gki_set_error(GKI_ERR_BAD_ARG, "bucket range [%llu, +%llu) outside [0, modulo)", (unsigned long long)bucket_begin,
-                             (unsigned long long)n_buckets);
-    if (group_bits < 0 || group_bits > 10 || (group_bits > 0 && !h_group_start))
-        return gki_set_error(GKI_ERR_BAD_ARG, "group_bits must be in 0..10, with the group bounds when > 0");
-    if (n >= (1ll << 31))
-        return gki_set_error(GKI_ERR_OVERFLOW, "%lld records: the reference's directory is int32 "
-                             "(collision_free_kmer_index.py:453); shard the build", (long long)n);
+    const Slice sl = {modulo, bucket_begin, n_buckets};
+    const Grouping gr = {group_bits, h_group_start};
+    GKI_TRY(check_slice_args(sl, n, &gr));
     hipStream_t s = 0;
     if (n <= 0) {
         HIP_TRY(hipMemsetAsync(d_hashes_to_index, 0, (size_t)n_buckets * 4, s));       // :453
@@ -734,14 +706,13 @@ int gki_index_build_range_from_rows(const void *d_rows, const void *d_keys, int6
         return GKI_OK;
     }
     if (!d_rows || !d_keys) return gki_set_error(GKI_ERR_BAD_ARG, "rows and keys are needed");
-    int done = 0;
-    GKI_TRY(gki_index_build_rows(nullptr, nullptr, nullptr, nullptr, n, modulo, bucket_begin, n_buckets, skip_frequencies, group_bits,
-                                 h_group_start, d_rows, d_keys, d_hashes_to_index, d_n_kmers, d_out_kmers, d_out_nodes,
-                                 d_out_ref_offsets, d_out_af32, d_out_frequencies, nullptr, &done, 0));
-    if (!done)
+    const int r = gki_index_build_rows(RecordCols{}, {(const uint64_t *)d_rows, (const uint32_t *)d_keys}, n, sl, gr, skip_frequencies, 0,
+                                       index_out(d_hashes_to_index, d_n_kmers, d_out_kmers, d_out_nodes, d_out_ref_offsets, d_out_af32,
+                                                 d_out_frequencies, nullptr));
+    if (r == GKI_NOT_BUILT)
         return gki_set_error(GKI_ERR_OUT_OF_DOMAIN, "the records are outside the row-carrying build's domain (a group of neighbouring buckets with "
                              "more than 2^22 records): build this slice from its columns (gki_index_build_range)");
-    return GKI_OK;
+    return r;
 }
 
 int gki_partition_by_bucket_range_chunked(const void *d_kmers, const void *d_nodes, const void *d_ref_offsets, const void *d_af32,
@@ -767,14 +738,10 @@ int gki_flag_repeated_kmers(const void *d_kmers, int64_t n, void *d_flags) {
     hipStream_t s = 0;
     SortScratch ss;
     DevBuf first, cnt;
-    GKI_TRY(ss.alloc(n));
+    int cur = 0;
+    GKI_TRY(sort_by_key<false>(ss, d_kmers, n, {modulo, 0, modulo}, s, &cur, nullptr));
     HIP_TRY(first.alloc((size_t)modulo * 4));
     HIP_TRY(cnt.alloc((size_t)modulo * 4));
-    hipLaunchKernelGGL(k_bucket_keys, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const uint64_t *)d_kmers, n, modulo,
-                       (uint64_t)0, modulo, ss.keys[0], ss.vals[0], (int *)ss.hist);
-    HIP_TRY(hipGetLastError());
-    int cur = 0;
-    GKI_TRY(ss.sort(n, key_bits(modulo - 1), s, &cur));
     hipLaunchKernelGGL(k_directory, dim3(stream_grid(n, 256)), dim3(256), 0, s, ss.keys[cur], n, first.get<int32_t>(), cnt.get<uint32_t>());
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_flag_repeats, dim3(stream_grid(n, 256)), dim3(256), 0, s, ss.keys[cur], ss.vals[cur],
@@ -789,6 +756,9 @@ int gki_reverse_index_build(const void *d_nodes, const void *d_kmers, const void
     if (n_nodes <= 0 || n_nodes > (1ll << 32)) return gki_set_error(GKI_ERR_BAD_ARG, "n_nodes must be in 1..2^32");
     if (n >= (1ll << 32)) return gki_set_error(GKI_ERR_OVERFLOW, "%lld records do not fit the uint32 directory", (long long)n);
     hipStream_t s = 0;
+    const RecordCols cols = record_cols(d_kmers, d_nodes, d_ref_offsets, nullptr);
+    const RecordColsOut out_cols = record_cols_out(d_out_kmers, nullptr, d_out_ref_offsets, nullptr);
+    const Slice nodes = {1, 0, (uint64_t)n_nodes};            // the "buckets" are the nodes
     // GKI_REVERSE_FORM=pairs (read per call): the pair-sorting form, for the parity tests of the path behind the row form
     const char *form = getenv("GKI_REVERSE_FORM");
     const bool pairs_only = form && strcmp(form, "pairs") == 0;
@@ -798,48 +768,32 @@ int gki_reverse_index_build(const void *d_nodes, const void *d_kmers, const void
         // directory passes (round 4; the pair-sorting form below stays for what lies outside its domain)
         DevBuf nk32;
         HIP_TRY(nk32.alloc((size_t)n_nodes * 4));
-        int done = 0;
-        GKI_TRY(gki_index_build_rows(d_kmers, d_nodes, d_ref_offsets, nullptr, n, 1, 0, (uint64_t)n_nodes, 1, 0, nullptr, nullptr, nullptr,
-                                     d_index_positions, nk32.get(), d_out_kmers, nullptr, d_out_ref_offsets, nullptr, nullptr, nullptr, &done, 1));
-        if (done) {
+        const int r = gki_index_build_rows(cols, RowsIn{}, n, nodes, Grouping{}, 1, 1,
+                                           {(int32_t *)d_index_positions, nk32.get<uint32_t>(), out_cols, nullptr, nullptr});
+        if (r == GKI_OK) {
             hipLaunchKernelGGL(k_narrow_counts, dim3(stream_grid(n_nodes, 256)), dim3(256), 0, s, nk32.get<const uint32_t>(), n_nodes,
                                (uint16_t *)d_n_hashes);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(s));
-            return GKI_OK;
         }
+        if (r != GKI_NOT_BUILT) return r;
     }                                                 // (nk32 is freed before the pair-sorting form allocates)
     HIP_TRY(hipMemsetAsync(d_index_positions, 0, (size_t)n_nodes * 4, s));      // reverse_kmer_index.py:53
     HIP_TRY(hipMemsetAsync(d_n_hashes, 0, (size_t)n_nodes * 2, s));             // :54
     if (n <= 0) { HIP_TRY(hipStreamSynchronize(s)); return GKI_OK; }
     SortScratch ss;
-    DevBuf rows, bad;
-    GKI_TRY(ss.alloc(n));
-    HIP_TRY(rows.alloc((size_t)n * 16));
-    HIP_TRY(bad.alloc(4));
-    HIP_TRY(hipMemsetAsync(bad.get(), 0, 4, s));
-    uint32_t **keys = ss.keys, **vals = ss.vals;
-    hipLaunchKernelGGL(k_node_keys, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const uint32_t *)d_nodes, n, (uint64_t)n_nodes, keys[0], vals[0],
-                       bad.get<int>());
-    HIP_TRY(hipGetLastError());
-    int cur = 0;
-    GKI_TRY(ss.sort(n, key_bits((uint64_t)n_nodes - 1), s, &cur));
-    hipLaunchKernelGGL(k_pack_pairs, dim3(stream_grid(n, 256)), dim3(256), 0, s, (const uint64_t *)d_kmers,
-                       (const uint64_t *)d_ref_offsets, n, rows.get<uint4>());
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_gather_pairs, dim3(stream_grid(n, 256)), dim3(256), 0, s, vals[cur], n, rows.get<const uint4>(),
-                       (uint64_t *)d_out_kmers, (uint64_t *)d_out_ref_offsets);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_node_directory<0>, dim3(stream_grid(n, 256)), dim3(256), 0, s, keys[cur], n,
-                       (uint32_t *)d_index_positions, (uint16_t *)d_n_hashes);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_node_directory<1>, dim3(stream_grid(n, 256)), dim3(256), 0, s, keys[cur], n,
-                       (uint32_t *)d_index_positions, (uint16_t *)d_n_hashes);
-    HIP_TRY(hipGetLastError());
-    int h_bad = 0;
-    HIP_TRY(hipMemcpyAsync(&h_bad, bad.get(), 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    DevBuf rows;
+    int cur = 0, h_bad = 0;
+    GKI_TRY(sort_by_key<true>(ss, d_nodes, n, nodes, s, &cur, &h_bad));
     if (h_bad) return gki_set_error(GKI_ERR_BAD_ARG, "a record's node id is not below n_nodes = %lld", (long long)n_nodes);
+    GKI_TRY(permute_payload<1>(rows, cols, ss.vals[cur], n, out_cols, s));
+    hipLaunchKernelGGL(k_node_directory<0>, dim3(stream_grid(n, 256)), dim3(256), 0, s, ss.keys[cur], n,
+                       (uint32_t *)d_index_positions, (uint16_t *)d_n_hashes);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_node_directory<1>, dim3(stream_grid(n, 256)), dim3(256), 0, s, ss.keys[cur], n,
+                       (uint32_t *)d_index_positions, (uint16_t *)d_n_hashes);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
     return GKI_OK;
 }
 

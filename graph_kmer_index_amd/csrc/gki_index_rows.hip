@@ -30,13 +30,9 @@
 //
 // Stability: every pass keeps equal digits in input order and the in-LDS sort ranks equal buckets by row position, so
 // the result equals the first form's (and the oracle's stable build) element by element.
-#include "gki_common.h"
+#include "gki_index_internal.h"
 #include <math.h>
 #include <vector>
-
-int gki_frequencies_for_rows(const int64_t *d_row_begin, const int64_t *d_row_end, int n_ranges, uint64_t modulo,
-                             uint64_t bucket_begin, const void *d_hashes_to_index, const void *d_n_kmers,
-                             const void *d_kmers, const void *d_refs, void *d_freq, int64_t n, hipStream_t s);
 
 namespace {
 
@@ -54,7 +50,8 @@ constexpr int GROUP_CAP_BIG = 4096;
 constexpr int GROUP_THREADS_BIG = 1024;           // sixteen waves: the one workgroup a CU holds has to hide its own latencies
 constexpr int GROUP_LMAX = 10;                    // low key bits resolved in LDS
 constexpr int GROUP_THREADS = 512;
-constexpr int SMALL_BUCKET = 24;              // as in gki_index.hip: buckets up to this size count frequencies per lane
+constexpr int MAX_PARTS = 256;
+constexpr int PB_WORDS = 2 * MAX_PARTS + 1; // LDS copy: part_begin[0 .. n_parts], then sub_shift[0 .. n_parts)
 
 // How a record's sort key follows from its k-mer: the bucket relative to the slice (the index build), or the part that owns
 // the bucket (gki_partition_by_bucket_range: part p owns buckets [modulo * p / n_parts, modulo * (p + 1) / n_parts)).
@@ -68,9 +65,22 @@ struct KeyRule {
     int sub_bits;                           // > 0 (with parts): key = part << sub_bits | the top sub_bits bits of the bucket's
     const uint32_t *part_begin;             //   offset in its part, i.e. (bucket - part_begin[part]) >> sub_shift[part]
     const uint32_t *sub_shift;              //   [n_parts] on the device
+
+    static KeyRule bucket(const Slice &sl) {
+        KeyRule k = {};
+        k.mod = gki_mod_of(sl.modulo); k.bucket_begin = sl.bucket_begin; k.n_buckets = sl.n_buckets; k.parts_log2 = -1;
+        return k;
+    }
+    static KeyRule node() { KeyRule k = bucket(Slice{1, 0, 0}); k.by_node = 1; return k; }
+    // table: part_begin[0 .. n_parts] and, MAX_PARTS + 1 words on, sub_shift[0 .. n_parts), on the device
+    static KeyRule part(uint64_t modulo, int n_parts, int sub_bits, const uint32_t *table) {
+        KeyRule k = bucket(Slice{modulo, 0, modulo});
+        k.n_parts = n_parts; k.sub_bits = sub_bits; k.parts_per_bucket = (float)((double)n_parts / (double)modulo);
+        for (int l = 0; l <= 8; l++) if ((1 << l) == n_parts) k.parts_log2 = l;
+        k.part_begin = table; k.sub_shift = table + MAX_PARTS + 1;
+        return k;
+    }
 };
-constexpr int MAX_PARTS = 256;
-constexpr int PB_WORDS = 2 * MAX_PARTS + 1; // LDS copy: part_begin[0 .. n_parts], then sub_shift[0 .. n_parts)
 
 // the part table into LDS (PART rule only); callers synchronise before the first key_of
 __device__ __forceinline__ void stage_parts(const KeyRule &k, uint32_t *s_pb) {
@@ -133,15 +143,15 @@ __global__ __launch_bounds__(256) void k_tile_descs(const int64_t *__restrict__ 
 
 struct PartArgs {
     const TileDesc *tiles;         // NULL: tile t is rows [t * TILE, +TILE), its histogram column offs[d * n_tiles + t]
-    const uint32_t *keys_in;                                                                          // !SRC_COLS
-    const uint64_t *c_kmers; const uint32_t *c_nodes; const uint64_t *c_refs; const uint32_t *c_af;   // SRC_COLS: the key follows
-    KeyRule rule;                                                                                     //   from the k-mer by `rule`
-    const uint64_t *rows_in;                                                                          // !SRC_COLS
+    const uint32_t *keys_in;       // !SRC_COLS
+    RecordCols c;                  // SRC_COLS: the key follows
+    KeyRule rule;                  //   from the k-mer by `rule`
+    const uint64_t *rows_in;       // !SRC_COLS
     int64_t n, n_tiles;
     int shift, bits;
     const uint32_t *offs;          // [bins * n_tiles] exclusive scan of the bin-major tile histograms
     uint64_t *rows_out; uint32_t *keys_out;
-    uint64_t *o_kmers; uint32_t *o_nodes; uint64_t *o_refs; uint32_t *o_af;   // DST_COLS: the sorted tile leaves as four columns,
+    RecordColsOut o;               // DST_COLS: the sorted tile leaves as four columns,
     const int64_t *dbase;          //   digit d's runs at rows dbase[d] + (offs - offs of the digit's first run): the caller lays the
                                    //   parts of several chunks out behind each other (more than 2^31 records in all)
     int carry_index;               // the row's input index rides in place of the allele frequency (permutation wanted)
@@ -149,9 +159,17 @@ struct PartArgs {
                                    // (whose runs are adjacent in memory) go through the same XCD's L2
 };
 
-__device__ __forceinline__ int64_t tile_of_block(int64_t n_tiles, int xcd_tiles) {
-    if (xcd_tiles <= 0) return blockIdx.x;
-    return (int64_t)(blockIdx.x & 7) * xcd_tiles + (blockIdx.x >> 3);
+// The tile of this block: rows [tile_base, +n_here) and the histogram column hist[obase + digit * ostride].  False: the grid
+// (whole rounds of the eight XCDs) has no tile for this block.
+struct TileSpan { int64_t tile_base, obase, ostride, n_here; };
+template <int TILE>
+__device__ __forceinline__ bool tile_span(int64_t n, int64_t n_tiles, int xcd_tiles, const TileDesc *__restrict__ tiles, int bins, TileSpan &sp) {
+    const int64_t tile = xcd_tiles <= 0 ? (int64_t)blockIdx.x : (int64_t)(blockIdx.x & 7) * xcd_tiles + (blockIdx.x >> 3);
+    if (tile >= n_tiles) return false;
+    sp.tile_base = tile * TILE; sp.obase = tile; sp.ostride = n_tiles;
+    sp.n_here = (n - sp.tile_base) < TILE ? (n - sp.tile_base) : TILE;
+    if (tiles) { const TileDesc td = tiles[tile]; sp.tile_base = td.row0; sp.n_here = td.n; sp.obase = td.tiles_before * bins + td.t; sp.ostride = td.stride; }
+    return true;
 }
 
 // A tile's digit histogram into hist[digit * n_tiles + tile] (bin-major: the exclusive scan of that array is every run's
@@ -175,38 +193,41 @@ __device__ __forceinline__ void few_flush(const FewDigits &c, uint32_t *h, int b
         if (lane == 0 && tot) atomicAdd(&h[d], tot);
     }
 }
+// The body of the histogram kernels: key_of_row(r, valid) is the sort key of row r * THREADS + thread of the tile (h: the digit
+// counts in LDS, zeroed a barrier ago)
+template <int THREADS, int RI, class KeyOfRow>
+__device__ __forceinline__ void count_digits(const TileSpan &sp, int shift, int bits, uint32_t *h, uint32_t *__restrict__ hist, KeyOfRow key_of_row) {
+    const int bins = 1 << bits;
+    const uint32_t mask = (uint32_t)bins - 1u;
+    FewDigits c = {0ull, 0ull};
+#pragma unroll
+    for (int r = 0; r < RI; r++) {
+        const bool valid = r * THREADS + threadIdx.x < sp.n_here;
+        const uint32_t key = key_of_row(r, valid);
+        if (bits <= 4) few_add(c, (key >> shift) & mask, valid);
+        else if (valid) atomicAdd(&h[(key >> shift) & mask], 1u);
+    }
+    if (bits <= 4) few_flush(c, h, bins);
+    __syncthreads();
+    for (int d = threadIdx.x; d < bins; d += THREADS) hist[sp.obase + (int64_t)d * sp.ostride] = h[d];
+}
 
 template <int THREADS, int RI>
 __global__ __launch_bounds__(THREADS) void k_digit_hist(const uint32_t *__restrict__ keys, int64_t n, int shift, int bits,
                                                         uint32_t *__restrict__ hist, int64_t n_tiles, int xcd_tiles,
                                                         const TileDesc *__restrict__ tiles) {
     __shared__ uint32_t h[MAXB];
-    const int64_t tile = tile_of_block(n_tiles, xcd_tiles);
-    if (tile >= n_tiles) return;
-    const int bins = 1 << bits;
-    for (int d = threadIdx.x; d < bins; d += THREADS) h[d] = 0;
+    TileSpan sp;
+    if (!tile_span<THREADS * RI>(n, n_tiles, xcd_tiles, tiles, 1 << bits, sp)) return;
+    for (int d = threadIdx.x; d < (1 << bits); d += THREADS) h[d] = 0;
     __syncthreads();
-    int64_t base = tile * (THREADS * RI), obase = tile, ostride = n_tiles;
-    int64_t n_here = n - base < THREADS * RI ? n - base : THREADS * RI;
-    if (tiles) { const TileDesc td = tiles[tile]; base = td.row0; n_here = td.n; obase = td.tiles_before * bins + td.t; ostride = td.stride; }
-    const uint32_t mask = (uint32_t)bins - 1u;
     uint32_t key[RI];
 #pragma unroll
     for (int r = 0; r < RI; r++) {
         const int e = r * THREADS + threadIdx.x;
-        key[r] = e < n_here ? keys[base + e] : 0u;
+        key[r] = e < sp.n_here ? keys[sp.tile_base + e] : 0u;
     }
-    if (bits <= 4) {
-        FewDigits c = {0ull, 0ull};
-#pragma unroll
-        for (int r = 0; r < RI; r++) few_add(c, (key[r] >> shift) & mask, r * THREADS + threadIdx.x < n_here);
-        few_flush(c, h, bins);
-    } else {
-#pragma unroll
-        for (int r = 0; r < RI; r++) if (r * THREADS + threadIdx.x < n_here) atomicAdd(&h[(key[r] >> shift) & mask], 1u);
-    }
-    __syncthreads();
-    for (int d = threadIdx.x; d < bins; d += THREADS) hist[obase + (int64_t)d * ostride] = h[d];
+    count_digits<THREADS, RI>(sp, shift, bits, h, hist, [&](int r, bool) { return key[r]; });
 }
 
 // Exclusive scan of v over the THREADS threads of the block (lds: THREADS / 64 + 1 words)
@@ -248,51 +269,36 @@ __device__ __forceinline__ void wave_rank(const uint32_t (&dig)[RI], const bool 
     }
 }
 
-// One stable partition pass over a tile of THREADS * RI rows.
-// SRC_COLS: the tile comes from the four columns, every thread loading whole rows in ranking order (coalesced per column) and
-// computing their keys from the k-mers (no key array read); otherwise rows + keys of the previous pass, the payload words
-// loaded by position (coalesced) and dropped into their rows' slots through a 16-bit destination table.
-template <int THREADS, int RI, bool SRC_COLS, bool DST_COLS = false>
-__global__ __launch_bounds__(THREADS) void k_partition_rows(PartArgs a) {
-    constexpr int TILE = THREADS * RI, W = THREADS / 64, SLICE = TILE / W;
-    __shared__ __attribute__((aligned(16))) uint64_t s_rows[TILE * 3];
-    __shared__ uint32_t s_keys[TILE];
-    __shared__ uint16_t s_dest[SRC_COLS ? 1 : TILE];
-    // the per-wave digit counts live under the staging rows: dead (a barrier ago) before the first payload word lands
-    static_assert((size_t)TILE * 24 >= (size_t)W * MAXB * 2, "the per-wave digit counts fit under the rows");
-    uint16_t (*const s_wcnt)[MAXB] = reinterpret_cast<uint16_t (*)[MAXB]>(s_rows);     // [W][MAXB]
-    __shared__ uint32_t s_dstart[MAXB];
-    __shared__ uint32_t s_toff[MAXB];
-    __shared__ uint32_t s_scan[W + 1];
-    __shared__ uint32_t s_pb[SRC_COLS ? PB_WORDS : 1];
-    __shared__ int64_t s_dbase[SRC_COLS ? (THREADS >= 512 ? MAXB : MAX_PARTS) : 1];        // (1024 digits only on the large tile)
-    __shared__ uint16_t s_dig[SRC_COLS ? TILE : 1];    // by slot: the digit (with the part rule it does not follow from the stored key)
-    const int64_t tile = tile_of_block(a.n_tiles, a.xcd_tiles);
-    if (tile >= a.n_tiles) return;
+// ------------------------------------------------------------------------------------ the front end of a partition pass
+// What k_partition_rows and k_partition_rows_staged do alike, up to every row's slot in the sorted tile.  The LDS arrays
+// are the kernels' (their sizes and what they lie under differ) and are handed in.
+//
+// (1) everything a thread needs from global memory, issued up front.  A thread ranks the rows wave * SLICE + r * 64 + lane of
+// the tile: valid, key and dig belong to those.
+// SRC_COLS: the tile comes from the four columns, every thread loading whole rows in ranking order (coalesced per column:
+// w0, w1, w2 are the row's words) and computing their keys from the k-mers (no key array read; tile_keys, once the part table
+// staged here is visible); otherwise rows + keys of the previous pass, the payload words loaded by position (coalesced: w0,
+// w1, w2 are the words r * THREADS + thread, + TILE, + 2 TILE of the tile's 3 * n_here).
+template <int THREADS, int RI, bool SRC_COLS>
+__device__ __forceinline__ void load_tile(const PartArgs &a, const TileSpan &sp, uint32_t *s_pb, bool (&valid)[RI], uint32_t (&key)[RI],
+                                          uint32_t (&dig)[RI], uint64_t (&w0)[RI], uint64_t (&w1)[RI], uint64_t (&w2)[RI]) {
+    constexpr int TILE = THREADS * RI, SLICE = TILE / (THREADS / 64);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int bins = 1 << a.bits;
-    const uint32_t mask = (uint32_t)bins - 1u;
-    int64_t tile_base = tile * TILE, obase = tile, ostride = a.n_tiles;
-    int n_here = (int)((a.n - tile_base) < TILE ? (a.n - tile_base) : TILE);
-    if (a.tiles) { const TileDesc td = a.tiles[tile]; tile_base = td.row0; n_here = td.n; obase = td.tiles_before * bins + td.t; ostride = td.stride; }
-
-    // (1) everything this thread will need from global memory, issued up front
-    uint32_t key[RI], dig[RI];
-    bool valid[RI];
-    uint64_t w0[RI], w1[RI], w2[RI];
+    const int64_t tile_base = sp.tile_base;
+    const int n_here = (int)sp.n_here;
     if (SRC_COLS) {
 #pragma unroll
         for (int r = 0; r < RI; r++) {
             const int e = wave * SLICE + r * 64 + lane;
             valid[r] = e < n_here;
-            w0[r] = valid[r] ? a.c_kmers[tile_base + e] : 0ull;
-            w1[r] = valid[r] ? a.c_refs[tile_base + e] : 0ull;
-            w2[r] = valid[r] ? ((uint64_t)a.c_nodes[tile_base + e] |
-                                ((uint64_t)(a.carry_index ? (uint32_t)(tile_base + e) : a.c_af ? a.c_af[tile_base + e] : 0u) << 32)) : 0ull;
+            w0[r] = valid[r] ? a.c.kmers[tile_base + e] : 0ull;
+            w1[r] = valid[r] ? a.c.refs[tile_base + e] : 0ull;
+            w2[r] = valid[r] ? ((uint64_t)a.c.nodes[tile_base + e] |
+                                ((uint64_t)(a.carry_index ? (uint32_t)(tile_base + e) : a.c.af ? a.c.af[tile_base + e] : 0u) << 32)) : 0ull;
         }
         stage_parts(a.rule, s_pb);
-        for (int d = threadIdx.x; d < bins; d += THREADS) s_dbase[d] = a.dbase ? a.dbase[d] : 0;
     } else {
+        const uint32_t mask = (1u << a.bits) - 1u;
 #pragma unroll
         for (int r = 0; r < RI; r++) {
             const int e = wave * SLICE + r * 64 + lane;
@@ -309,56 +315,102 @@ __global__ __launch_bounds__(THREADS) void k_partition_rows(PartArgs a) {
             w2[r] = j + 2 * TILE < 3 * n_here ? src[j + 2 * TILE] : 0ull;
         }
     }
+}
+// SRC_COLS, after the barrier behind load_tile: the key that travels with each row and the digit this pass sorts on
+template <int RI>
+__device__ __forceinline__ void tile_keys(const PartArgs &a, const uint32_t *s_pb, const bool (&valid)[RI], const uint64_t (&w0)[RI],
+                                          const uint64_t (&w2)[RI], uint32_t (&key)[RI], uint32_t (&dig)[RI]) {
+    const uint32_t mask = (1u << a.bits) - 1u;
+    bool bad = false;                                       // (the histogram kernel has reported it)
+#pragma unroll
+    for (int r = 0; r < RI; r++) {
+        key[r] = 0u;
+        uint32_t sort_key = 0u;
+        if (a.rule.by_node) { key[r] = valid[r] ? (uint32_t)w2[r] : 0u; sort_key = key[r]; }
+        else if (valid[r]) sort_key = key_of(a.rule, s_pb, w0[r], &bad, &key[r]);
+        dig[r] = (sort_key >> a.shift) & mask;
+    }
+}
+// (2) ranks inside the wave, digit counts per wave (s_wcnt[W][MAXB], zeroed a barrier ago); (3) per digit: exclusive offsets
+// over the waves (left in s_wcnt), the digit's start in the sorted tile (s_dstart) and, by run_to(digit, that start), where
+// its run goes.  Ends on a barrier.
+template <int THREADS, int RI, class RunTo>
+__device__ __forceinline__ void rank_tile(const uint32_t (&dig)[RI], const bool (&valid)[RI], int bits, uint16_t (*s_wcnt)[MAXB],
+                                          uint32_t *s_dstart, uint32_t *s_scan, uint32_t (&rank)[RI], RunTo run_to) {
+    constexpr int W = THREADS / 64;
+    const int bins = 1 << bits;
+    wave_rank<RI>(dig, valid, bits, s_wcnt[threadIdx.x >> 6], rank);
+    __syncthreads();
+    constexpr int C = MAXB / THREADS > 0 ? MAXB / THREADS : 1;      // digits per thread
+    uint32_t tot[C], sum = 0;
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        const int d = threadIdx.x * C + c;
+        tot[c] = 0;
+        if (d < bins) {
+            uint32_t run = 0;
+#pragma unroll
+            for (int w = 0; w < W; w++) { const uint32_t x = s_wcnt[w][d]; s_wcnt[w][d] = (uint16_t)run; run += x; }
+            tot[c] = run;
+        }
+        sum += tot[c];
+    }
+    uint32_t total;
+    uint32_t ex = block_excl<THREADS>(sum, s_scan, &total);
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        const int d = threadIdx.x * C + c;
+        if (d < bins) {
+            s_dstart[d] = ex;
+            run_to(d, ex);
+            ex += tot[c];
+        }
+    }
+    __syncthreads();
+}
+// (4) the slot of a row in the sorted tile: the start of its digit, the rows of the digit in earlier waves, its rank in its own
+__device__ __forceinline__ uint32_t tile_slot(const uint32_t *s_dstart, const uint16_t *wcnt /* this wave's */, uint32_t dig, uint32_t rank) {
+    return s_dstart[dig] + wcnt[dig] + rank;
+}
+
+// One stable partition pass over a tile of THREADS * RI rows, the sorted tile whole in LDS.  Rows + keys in (!SRC_COLS): the
+// payload words are dropped into their rows' slots through a 16-bit destination table.
+template <int THREADS, int RI, bool SRC_COLS, bool DST_COLS = false>
+__global__ __launch_bounds__(THREADS) void k_partition_rows(PartArgs a) {
+    constexpr int TILE = THREADS * RI, W = THREADS / 64, SLICE = TILE / W;
+    __shared__ __attribute__((aligned(16))) uint64_t s_rows[TILE * 3];
+    __shared__ uint32_t s_keys[TILE];
+    __shared__ uint16_t s_dest[SRC_COLS ? 1 : TILE];
+    // the per-wave digit counts live under the staging rows: dead (a barrier ago) before the first payload word lands
+    static_assert((size_t)TILE * 24 >= (size_t)W * MAXB * 2, "the per-wave digit counts fit under the rows");
+    uint16_t (*const s_wcnt)[MAXB] = reinterpret_cast<uint16_t (*)[MAXB]>(s_rows);     // [W][MAXB]
+    __shared__ uint32_t s_dstart[MAXB];
+    __shared__ uint32_t s_toff[MAXB];
+    __shared__ uint32_t s_scan[W + 1];
+    __shared__ uint32_t s_pb[SRC_COLS ? PB_WORDS : 1];
+    __shared__ int64_t s_dbase[SRC_COLS ? (THREADS >= 512 ? MAXB : MAX_PARTS) : 1];        // (1024 digits only on the large tile)
+    __shared__ uint16_t s_dig[SRC_COLS ? TILE : 1];    // by slot: the digit (with the part rule it does not follow from the stored key)
+    const int bins = 1 << a.bits;
+    TileSpan sp;
+    if (!tile_span<TILE>(a.n, a.n_tiles, a.xcd_tiles, a.tiles, bins, sp)) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t mask = (uint32_t)bins - 1u;
+    const int n_here = (int)sp.n_here;
+
+    uint32_t key[RI], dig[RI];
+    bool valid[RI];
+    uint64_t w0[RI], w1[RI], w2[RI];
+    load_tile<THREADS, RI, SRC_COLS>(a, sp, s_pb, valid, key, dig, w0, w1, w2);
+    if (SRC_COLS) for (int d = threadIdx.x; d < bins; d += THREADS) s_dbase[d] = a.dbase ? a.dbase[d] : 0;
     for (int d = threadIdx.x; d < W * MAXB / 2; d += THREADS) reinterpret_cast<uint32_t *>(s_rows)[d] = 0;          // s_wcnt
     __syncthreads();
-    if (SRC_COLS) {
-        bool bad = false;                                       // (the histogram kernel has reported it)
-#pragma unroll
-        for (int r = 0; r < RI; r++) {
-            key[r] = 0u;
-            uint32_t sort_key = 0u;
-            if (a.rule.by_node) { key[r] = valid[r] ? (uint32_t)w2[r] : 0u; sort_key = key[r]; }
-            else if (valid[r]) sort_key = key_of(a.rule, s_pb, w0[r], &bad, &key[r]);
-            dig[r] = (sort_key >> a.shift) & mask;
-        }
-    }
+    if (SRC_COLS) tile_keys<RI>(a, s_pb, valid, w0, w2, key, dig);
 
-    // (2) ranks inside the wave, digit counts per wave
     uint32_t rank[RI];
-    wave_rank<RI>(dig, valid, a.bits, s_wcnt[wave], rank);
-    __syncthreads();
-
-    // (3) per digit: exclusive offsets over the waves, the digit's start in the sorted tile, and where its run goes
-    {
-        constexpr int C = MAXB / THREADS > 0 ? MAXB / THREADS : 1;      // digits per thread
-        uint32_t tot[C], sum = 0;
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-            const int d = threadIdx.x * C + c;
-            tot[c] = 0;
-            if (d < bins) {
-                uint32_t run = 0;
-#pragma unroll
-                for (int w = 0; w < W; w++) { const uint32_t x = s_wcnt[w][d]; s_wcnt[w][d] = (uint16_t)run; run += x; }
-                tot[c] = run;
-            }
-            sum += tot[c];
-        }
-        uint32_t total;
-        uint32_t ex = block_excl<THREADS>(sum, s_scan, &total);
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-            const int d = threadIdx.x * C + c;
-            if (d < bins) {
-                s_dstart[d] = ex;
-                // DST_COLS: relative to the digit's first run (the caller's dbase[d] is where that one goes)
-                // with dbase: relative to the digit's first run (the caller's dbase[d] is where that one goes)
-                s_toff[d] = a.offs[obase + (int64_t)d * ostride] - (SRC_COLS && a.dbase ? a.offs[(int64_t)d * a.n_tiles] : 0u) - ex;
-                ex += tot[c];
-            }
-        }
-    }
-    __syncthreads();
+    rank_tile<THREADS, RI>(dig, valid, a.bits, s_wcnt, s_dstart, s_scan, rank, [&](int d, uint32_t ex) {
+        // with dbase: relative to the digit's first run (the caller's dbase[d] is where that one goes)
+        s_toff[d] = a.offs[sp.obase + (int64_t)d * sp.ostride] - (SRC_COLS && a.dbase ? a.offs[(int64_t)d * a.n_tiles] : 0u) - ex;
+    });
 
     // (4) destination slot of every row of the tile; (5) payload words into their rows' slots
     uint32_t slot[RI];
@@ -366,7 +418,7 @@ __global__ __launch_bounds__(THREADS) void k_partition_rows(PartArgs a) {
     for (int r = 0; r < RI; r++) {
         slot[r] = 0;
         if (valid[r]) {
-            slot[r] = s_dstart[dig[r]] + s_wcnt[wave][dig[r]] + rank[r];
+            slot[r] = tile_slot(s_dstart, s_wcnt[wave], dig[r], rank[r]);
             s_keys[slot[r]] = key[r];
             if (SRC_COLS) s_dig[slot[r]] = (uint16_t)dig[r];
             else s_dest[wave * SLICE + r * 64 + lane] = (uint16_t)slot[r];
@@ -399,8 +451,8 @@ __global__ __launch_bounds__(THREADS) void k_partition_rows(PartArgs a) {
                 const uint32_t d = s_dig[p];
                 const int64_t row = s_dbase[d] + (int64_t)(uint32_t)(s_toff[d] + (uint32_t)p);
                 const uint64_t w2 = s_rows[p * 3 + 2];
-                a.o_kmers[row] = s_rows[p * 3]; a.o_refs[row] = s_rows[p * 3 + 1];
-                a.o_nodes[row] = (uint32_t)w2; a.o_af[row] = (uint32_t)(w2 >> 32);
+                a.o.kmers[row] = s_rows[p * 3]; a.o.refs[row] = s_rows[p * 3 + 1];
+                a.o.nodes[row] = (uint32_t)w2; a.o.af[row] = (uint32_t)(w2 >> 32);
             }
         }
         return;
@@ -450,104 +502,33 @@ __global__ __launch_bounds__(THREADS, 4) void k_partition_rows_staged(PartArgs a
     uint16_t (*const s_wcnt)[MAXB] = reinterpret_cast<uint16_t (*)[MAXB]>(s_rows);                  // [W][MAXB]
     uint32_t *const s_dstart = reinterpret_cast<uint32_t *>(s_rows) + (size_t)W * MAXB / 2;        // [MAXB]
     uint32_t *const s_toff = s_dstart + MAXB;                                                       // [MAXB]
-    const int64_t tile = tile_of_block(a.n_tiles, a.xcd_tiles);
-    if (tile >= a.n_tiles) return;
+    TileSpan sp;
+    if (!tile_span<TILE>(a.n, a.n_tiles, a.xcd_tiles, a.tiles, 1 << a.bits, sp)) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int bins = 1 << a.bits;
-    const uint32_t mask = (uint32_t)bins - 1u;
-    int64_t tile_base = tile * TILE, obase = tile, ostride = a.n_tiles;
-    int n_here = (int)((a.n - tile_base) < TILE ? (a.n - tile_base) : TILE);
-    if (a.tiles) { const TileDesc td = a.tiles[tile]; tile_base = td.row0; n_here = td.n; obase = td.tiles_before * bins + td.t; ostride = td.stride; }
+    const int n_here = (int)sp.n_here;
 
-    // (1) everything from global memory, issued up front
     uint32_t key[RI], dig[RI];
     bool valid[RI];
     uint64_t w0[RI], w1[RI], w2[RI];
-    if (SRC_COLS) {
-#pragma unroll
-        for (int r = 0; r < RI; r++) {
-            const int e = wave * SLICE + r * 64 + lane;
-            valid[r] = e < n_here;
-            w0[r] = valid[r] ? a.c_kmers[tile_base + e] : 0ull;
-            w1[r] = valid[r] ? a.c_refs[tile_base + e] : 0ull;
-            w2[r] = valid[r] ? ((uint64_t)a.c_nodes[tile_base + e] |
-                                ((uint64_t)(a.carry_index ? (uint32_t)(tile_base + e) : a.c_af ? a.c_af[tile_base + e] : 0u) << 32)) : 0ull;
-        }
-        stage_parts(a.rule, s_pb);
-    } else {
-#pragma unroll
-        for (int r = 0; r < RI; r++) {
-            const int e = wave * SLICE + r * 64 + lane;
-            valid[r] = e < n_here;
-            key[r] = valid[r] ? a.keys_in[tile_base + e] : 0u;
-            dig[r] = valid[r] ? ((key[r] >> a.shift) & mask) : 0u;
-        }
-        const uint64_t *src = a.rows_in + tile_base * 3;
-#pragma unroll
-        for (int r = 0; r < RI; r++) {
-            const int j = r * THREADS + threadIdx.x;            // word j of the tile's 3 * n_here words
-            w0[r] = j < 3 * n_here ? src[j] : 0ull;
-            w1[r] = j + TILE < 3 * n_here ? src[j + TILE] : 0ull;
-            w2[r] = j + 2 * TILE < 3 * n_here ? src[j + 2 * TILE] : 0ull;
-        }
-    }
+    load_tile<THREADS, RI, SRC_COLS>(a, sp, s_pb, valid, key, dig, w0, w1, w2);
     for (int d = threadIdx.x; d < W * MAXB / 2; d += THREADS) reinterpret_cast<uint32_t *>(s_rows)[d] = 0;      // s_wcnt
     __syncthreads();
-    if (SRC_COLS) {
-        bool bad = false;                                       // (the histogram kernel has reported it)
-#pragma unroll
-        for (int r = 0; r < RI; r++) {
-            key[r] = 0u;
-            uint32_t sort_key = 0u;
-            if (a.rule.by_node) { key[r] = valid[r] ? (uint32_t)w2[r] : 0u; sort_key = key[r]; }
-            else if (valid[r]) sort_key = key_of(a.rule, s_pb, w0[r], &bad, &key[r]);
-            dig[r] = (sort_key >> a.shift) & mask;
-        }
-    }
-    // (2) ranks inside the wave, digit counts per wave
+    if (SRC_COLS) tile_keys<RI>(a, s_pb, valid, w0, w2, key, dig);
     uint32_t rank[RI];
-    wave_rank<RI>(dig, valid, a.bits, s_wcnt[wave], rank);
-    __syncthreads();
-    // (3) per digit: exclusive offsets over the waves, the digit's start in the sorted tile, and where its run goes
-    {
-        constexpr int C = MAXB / THREADS > 0 ? MAXB / THREADS : 1;      // digits per thread
-        uint32_t tot[C], sum = 0;
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-            const int d = threadIdx.x * C + c;
-            tot[c] = 0;
-            if (d < bins) {
-                uint32_t run = 0;
-#pragma unroll
-                for (int w = 0; w < W; w++) { const uint32_t x = s_wcnt[w][d]; s_wcnt[w][d] = (uint16_t)run; run += x; }
-                tot[c] = run;
-            }
-            sum += tot[c];
-        }
-        uint32_t total;
-        uint32_t ex = block_excl<THREADS>(sum, s_scan, &total);
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-            const int d = threadIdx.x * C + c;
-            if (d < bins) {
-                s_dstart[d] = ex;
-                // with dbase (the bucket-range partition into rows: the caller lays the digits of several chunks out behind
-                // each other) the run goes to dbase[d] + its offset among the chunk's runs of the digit; the output has
-                // fewer than 2^32 rows (checked by the host), so 32-bit arithmetic carries it
-                s_toff[d] = (SRC_COLS && a.dbase ? (uint32_t)a.dbase[d] - a.offs[(int64_t)d * a.n_tiles] : 0u) +
-                            a.offs[obase + (int64_t)d * ostride] - ex;
-                ex += tot[c];
-            }
-        }
-    }
-    __syncthreads();
+    rank_tile<THREADS, RI>(dig, valid, a.bits, s_wcnt, s_dstart, s_scan, rank, [&](int d, uint32_t ex) {
+        // with dbase (the bucket-range partition into rows: the caller lays the digits of several chunks out behind
+        // each other) the run goes to dbase[d] + its offset among the chunk's runs of the digit; the output has
+        // fewer than 2^32 rows (checked by the host), so 32-bit arithmetic carries it
+        s_toff[d] = (SRC_COLS && a.dbase ? (uint32_t)a.dbase[d] - a.offs[(int64_t)d * a.n_tiles] : 0u) +
+                    a.offs[sp.obase + (int64_t)d * sp.ostride] - ex;
+    });
     // (4) slot and output row of every row of the tile
     uint32_t slot[RI];
 #pragma unroll
     for (int r = 0; r < RI; r++) {
         slot[r] = 0xFFFFFFFFu;
         if (valid[r]) {
-            slot[r] = s_dstart[dig[r]] + s_wcnt[wave][dig[r]] + rank[r];
+            slot[r] = tile_slot(s_dstart, s_wcnt[wave], dig[r], rank[r]);
             s_keys[slot[r]] = key[r];
             s_out[slot[r]] = s_toff[dig[r]] + slot[r];
             if (!SRC_COLS) s_dest[wave * SLICE + r * 64 + lane] = (uint16_t)slot[r];
@@ -668,9 +649,8 @@ struct FinishArgs {
     int lbits;                     // bits that tell the buckets of one group apart (= L; fewer in the last, clipped group never matters)
     uint64_t n_buckets;
     int skip_frequencies;
-    int32_t *h2i; uint32_t *nk;
-    uint64_t *o_kmers; uint32_t *o_nodes; uint64_t *o_refs; uint32_t *o_af; uint16_t *o_freq;
-    uint32_t *o_perm; const uint32_t *af_in;     // rows carry their input index: permutation out, allele frequency fetched by it
+    IndexOut out;
+    const uint32_t *af_in;         // out.perm: rows carry their input index -- permutation out, allele frequency fetched by it
     uint32_t *big_buckets; unsigned int *n_big; uint32_t big_cap;    // buckets of more than SMALL_BUCKET rows (frequencies later)
     int xcd_groups;
 };
@@ -770,8 +750,8 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_group_finish(FinishArgs a) {
         // the directory of the group, streamed (this replaces the memset + scatter of the first form)
         for (uint32_t b = threadIdx.x; b < nbk; b += GROUP_THREADS) {
             const uint32_t c = s_cnt[b];
-            a.h2i[gb + b] = c ? (int32_t)(s + s_pos[b]) : 0;     // collision_free_kmer_index.py:453-454
-            a.nk[gb + b] = c;                                    // :456-457
+            a.out.h2i[gb + b] = c ? (int32_t)(s + s_pos[b]) : 0;     // collision_free_kmer_index.py:453-454
+            a.out.n_kmers[gb + b] = c;                                    // :456-457
         }
 #pragma unroll
         for (int r = 0; r < RI; r++) {
@@ -789,8 +769,8 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_group_finish(FinishArgs a) {
         __syncthreads();                                             // from here on: start of bucket b = s_pos[b] - s_cnt[b]
         for (uint32_t b = threadIdx.x; b < nbk; b += GROUP_THREADS) {
             const uint32_t c = s_cnt[b];
-            a.h2i[gb + b] = c ? (int32_t)(s + s_pos[b] - c) : 0;     // collision_free_kmer_index.py:453-454
-            a.nk[gb + b] = c;                                        // :456-457
+            a.out.h2i[gb + b] = c ? (int32_t)(s + s_pos[b] - c) : 0;     // collision_free_kmer_index.py:453-454
+            a.out.n_kmers[gb + b] = c;                                        // :456-457
         }
 #pragma unroll
         for (int r = 0; r < RI; r++) {
@@ -828,10 +808,10 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_group_finish(FinishArgs a) {
         if (p < m) {
             const uint64_t km = s_kmer[p], rf = s_ref[p];
             const int64_t o = (int64_t)s + p;
-            a.o_kmers[o] = km; a.o_refs[o] = rf;
-            if (a.o_nodes) a.o_nodes[o] = s_node[p];             // (NULL node / allele-frequency / frequency columns: the reverse index)
-            if (a.o_perm) { const uint32_t idx = s_af[p]; a.o_perm[o] = idx; a.o_af[o] = a.af_in[idx]; }
-            else if (a.o_af) a.o_af[o] = s_af[p];
+            a.out.cols.kmers[o] = km; a.out.cols.refs[o] = rf;
+            if (a.out.cols.nodes) a.out.cols.nodes[o] = s_node[p];             // (NULL node / allele-frequency / frequency columns: the reverse index)
+            if (a.out.perm) { const uint32_t idx = s_af[p]; a.out.perm[o] = idx; a.out.cols.af[o] = a.af_in[idx]; }
+            else if (a.out.cols.af) a.out.cols.af[o] = s_af[p];
             uint32_t f = 0;
             if (!a.skip_frequencies) {
                 const uint32_t b = s_lk[p], c = s_cnt[b], b0 = WRANK ? s_pos[b] : s_pos[b] - c;
@@ -860,7 +840,7 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_group_finish(FinishArgs a) {
                     if (at < a.big_cap) a.big_buckets[at] = (uint32_t)(gb + b);
                 }
             }
-            if (a.o_freq) a.o_freq[o] = (uint16_t)f;
+            if (a.out.freq) a.out.freq[o] = (uint16_t)f;
         }
     }
 }
@@ -896,8 +876,8 @@ __global__ __launch_bounds__(256) void k_group_large(FinishArgs a, const uint32_
         __syncthreads();
         for (uint32_t b = threadIdx.x; b < nbk; b += 256) {
             const uint32_t c = s_cnt[b];
-            a.h2i[gb + b] = c ? (int32_t)(s + s_start[b]) : 0;
-            a.nk[gb + b] = c;
+            a.out.h2i[gb + b] = c ? (int32_t)(s + s_start[b]) : 0;
+            a.out.n_kmers[gb + b] = c;
         }
         __syncthreads();
         // ordered scatter: chunks of 256 rows, the four waves of a chunk one after the other; s_start[b] runs ahead as
@@ -920,11 +900,11 @@ __global__ __launch_bounds__(256) void k_group_large(FinishArgs a, const uint32_
                     __builtin_amdgcn_wave_barrier();
                     if (before == 0) s_start[b] = slot + (uint32_t)__popcll(same);
                     const int64_t o = (int64_t)s + slot;
-                    a.o_kmers[o] = w0; a.o_refs[o] = w1;
-                    if (a.o_nodes) a.o_nodes[o] = (uint32_t)w2;
-                    if (a.o_perm) { const uint32_t idx = (uint32_t)(w2 >> 32); a.o_perm[o] = idx; a.o_af[o] = a.af_in[idx]; }
-                    else if (a.o_af) a.o_af[o] = (uint32_t)(w2 >> 32);
-                    if (a.o_freq) a.o_freq[o] = 0;
+                    a.out.cols.kmers[o] = w0; a.out.cols.refs[o] = w1;
+                    if (a.out.cols.nodes) a.out.cols.nodes[o] = (uint32_t)w2;
+                    if (a.out.perm) { const uint32_t idx = (uint32_t)(w2 >> 32); a.out.perm[o] = idx; a.out.cols.af[o] = a.af_in[idx]; }
+                    else if (a.out.cols.af) a.out.cols.af[o] = (uint32_t)(w2 >> 32);
+                    if (a.out.freq) a.out.freq[o] = 0;
                 }
                 __syncthreads();
             }
@@ -945,12 +925,6 @@ __global__ __launch_bounds__(256) void k_open_ranges(const uint32_t *__restrict_
     }
 }
 
-int key_bits(uint64_t max_key) {
-    int bits = 0;
-    while (bits < 32 && (max_key >> bits) != 0) bits++;
-    return bits;
-}
-
 }  // namespace
 
 // The tile's histogram of the first pass's digit, the keys computed from the k-mers by `rule` (and not stored: the first
@@ -962,36 +936,23 @@ __global__ __launch_bounds__(THREADS) void k_kmer_digit_hist(const uint64_t *__r
                                                              const TileDesc *__restrict__ tiles, int *__restrict__ out_of_range) {
     __shared__ uint32_t h[MAXB];
     __shared__ uint32_t s_pb[PB_WORDS];
-    const int64_t tile = tile_of_block(n_tiles, xcd_tiles);
-    if (tile >= n_tiles) return;
-    const int bins = 1 << bits;
-    for (int d = threadIdx.x; d < bins; d += THREADS) h[d] = 0;
+    TileSpan sp;
+    if (!tile_span<THREADS * RI>(n, n_tiles, xcd_tiles, tiles, 1 << bits, sp)) return;
+    for (int d = threadIdx.x; d < (1 << bits); d += THREADS) h[d] = 0;
     stage_parts(rule, s_pb);
     __syncthreads();
-    int64_t base = tile * (THREADS * RI), obase = tile, ostride = n_tiles;
-    int64_t n_here = n - base < THREADS * RI ? n - base : THREADS * RI;
-    if (tiles) { const TileDesc td = tiles[tile]; base = td.row0; n_here = td.n; obase = td.tiles_before * bins + td.t; ostride = td.stride; }
-    const uint32_t mask = (uint32_t)bins - 1u;
     uint64_t km[RI];
 #pragma unroll
     for (int r = 0; r < RI; r++) {
         const int e = r * THREADS + threadIdx.x;
-        km[r] = e < n_here ? kmers[base + e] : 0ull;
+        km[r] = e < sp.n_here ? kmers[sp.tile_base + e] : 0ull;
     }
     bool bad = false;
-    FewDigits c = {0ull, 0ull};
-#pragma unroll
-    for (int r = 0; r < RI; r++) {
-        const bool valid = r * THREADS + threadIdx.x < n_here;
+    count_digits<THREADS, RI>(sp, shift, bits, h, hist, [&](int r, bool valid) {
         uint32_t stored;
-        const uint32_t key = valid ? key_of(rule, s_pb, km[r], &bad, &stored) : 0u;
-        if (bits <= 4) few_add(c, (key >> shift) & mask, valid);
-        else if (valid) atomicAdd(&h[(key >> shift) & mask], 1u);
-    }
-    if (bits <= 4) few_flush(c, h, bins);
+        return valid ? key_of(rule, s_pb, km[r], &bad, &stored) : 0u;
+    });
     if (bad) *out_of_range = 1;
-    __syncthreads();
-    for (int d = threadIdx.x; d < bins; d += THREADS) hist[obase + (int64_t)d * ostride] = h[d];
 }
 
 // Tile shape of the partition passes.  4096-row tiles (one workgroup of 512 threads per CU, 144 KB of LDS) give every
@@ -1015,8 +976,7 @@ constexpr double FINISH_WRANK_DENSITY = 2.0;
 // the full footprint and every barrier -- VERDICT r3 weak #1.)
 constexpr double GROUP_SIGMAS = 4.0;
 
-// The row-carrying build.  Returns GKI_OK with *done = 1 when it built the index, *done = 0 when the input is outside
-// its domain (a group too large to stream with one workgroup) and the caller should use the pair-sorting form.
+// The row-carrying build (what it returns and by_node: gki_index_internal.h).
 //
 // Grouped build (group_bits > 0, h_group_start[2^group_bits + 1]): the records arrive grouped by the top group_bits bits of
 // their key -- group g = key >> (key bits - group_bits) holds rows [h_group_start[g], h_group_start[g + 1]), as
@@ -1024,23 +984,18 @@ constexpr double GROUP_SIGMAS = 4.0;
 // them and the finish, every group on its own (segmented tiles), and the finish takes 4096-row groups: for the slices
 // of a whole-genome index (26 key bits, 7 records per bucket) that is 7 bits grouped + ONE pass of 10 + 9 in LDS, where
 // the ungrouped build needs two passes of 10 + 9 and 7 in LDS.
-int gki_index_build_rows(const void *d_kmers, const void *d_nodes, const void *d_ref_offsets, const void *d_af32, int64_t n,
-                         uint64_t modulo, uint64_t bucket_begin, uint64_t n_buckets, int skip_frequencies,
-                         int group_bits, const int64_t *h_group_start, const void *d_rows_in, const void *d_keys_in,
-                         void *d_hashes_to_index, void *d_n_kmers, void *d_out_kmers, void *d_out_nodes,
-                         void *d_out_ref_offsets, void *d_out_af32, void *d_out_frequencies, void *d_out_permutation, int *done,
-                         int by_node) {
-    // by_node: the key of a record is its node id and the "buckets" are the nodes (ReverseKmerIndex.from_flat_kmers,
-    // reverse_kmer_index.py:47-60: records stably sorted by node): modulo is unused, n_buckets = the number of nodes, the
-    // allele-frequency, node and frequency output columns may be NULL
+int gki_index_build_rows(const RecordCols &cols, const RowsIn &rows_in, int64_t n, const Slice &slice, const Grouping &grouping,
+                         int skip_frequencies, int by_node, const IndexOut &out) {
     constexpr int THREADS = PT_THREADS, RI = PT_RI, TILE = THREADS * RI;
-    *done = 0;
     hipStream_t s = 0;
-    // d_rows_in / d_keys_in: the records arrive as 24-byte rows with their keys (gki_partition_rows_by_bucket_range) instead of
-    // as four columns: the first pass is then a pass like every other, or -- when the grouping left nothing to sort above the
+    const uint64_t n_buckets = slice.n_buckets;
+    const int group_bits = grouping.group_bits;
+    const int64_t *h_group_start = grouping.h_group_start;
+    // rows_in: the records arrive as 24-byte rows with their keys (gki_partition_rows_by_bucket_range) instead of as four
+    // columns: the first pass is then a pass like every other, or -- when the grouping left nothing to sort above the
     // finish -- there is none
-    const bool from_rows = d_rows_in != nullptr;
-    if (from_rows && d_out_permutation) return gki_set_error(GKI_ERR_BAD_ARG, "a build from rows has no permutation to give");
+    const bool from_rows = rows_in.rows != nullptr;
+    if (from_rows && out.perm) return gki_set_error(GKI_ERR_BAD_ARG, "a build from rows has no permutation to give");
     const int kb = key_bits(n_buckets - 1);
     const bool grouped = group_bits > 0;
     const int group_shift = grouped ? (kb > group_bits ? kb - group_bits : 0) : kb;     // key bits below the grouping
@@ -1056,7 +1011,7 @@ int gki_index_build_rows(const void *d_kmers, const void *d_nodes, const void *d
     const bool wrank = density >= FINISH_WRANK_DENSITY;
     const int top = group_shift > L ? group_shift - L : 0;    // bits the partition passes sort on
     const int n_pass = top > 0 ? (top + MAXB_BITS - 1) / MAXB_BITS : (from_rows ? 0 : 1);   // top == 0: one pass of one digit, which only packs the rows
-    if (n_pass > 3) return GKI_OK;
+    if (n_pass > 3) return GKI_NOT_BUILT;
     const int64_t n_groups = (int64_t)(((n_buckets - 1) >> L) + 1);
     // tiles: plain, or cut at the group bounds
     // (the descriptors are written on the device, k_tile_descs: the host hands over three numbers per group, not one
@@ -1080,9 +1035,7 @@ int gki_index_build_rows(const void *d_kmers, const void *d_nodes, const void *d
     const int64_t tmp_bytes = gki_scan_tmp_bytes(hist_n);
     const uint32_t large_cap = 1u << 16;
     const uint32_t big_cap = (uint32_t)(n / SMALL_BUCKET + 1);
-    KeyRule rule;
-    rule.mod = gki_mod_of(modulo); rule.bucket_begin = bucket_begin; rule.n_buckets = n_buckets; rule.n_parts = 0; rule.sub_bits = 0;
-    rule.part_begin = nullptr; rule.sub_shift = nullptr; rule.parts_per_bucket = 0.f; rule.parts_log2 = -1; rule.by_node = by_node;
+    const KeyRule rule = by_node ? KeyRule::node() : KeyRule::bucket(slice);
     // (declared after h_seg: their frees wait for the device, so the upload that reads h_seg has finished before it goes)
     DevBuf stats_b, tiles_b, seg_b, rows_b[2], keys_b[2], hist_b, offs_b, tmp, gbegin_b, gend_b, large_b, big_b, rng_b;
     HIP_TRY(stats_b.alloc(64));
@@ -1115,8 +1068,8 @@ int gki_index_build_rows(const void *d_kmers, const void *d_nodes, const void *d
     HIP_TRY(hipMemsetAsync(gbegin, 0, (size_t)n_groups * 4, s));
     HIP_TRY(hipMemsetAsync(gend, 0, (size_t)n_groups * 4, s));
     // partition passes on the top bits, least significant digit first, each stable
-    const uint64_t *cur_rows = (const uint64_t *)d_rows_in;
-    const uint32_t *cur_keys = (const uint32_t *)d_keys_in;
+    const uint64_t *cur_rows = rows_in.rows;
+    const uint32_t *cur_keys = rows_in.keys;
     int shift = L;
     for (int p = 0; p < n_pass; p++) {
         const int bits = (top - (shift - L) + (n_pass - p) - 1) / (n_pass - p);       // remaining bits spread evenly (an odd bit
@@ -1125,24 +1078,20 @@ int gki_index_build_rows(const void *d_kmers, const void *d_nodes, const void *d
         const int xcd_tiles = (int)ceil_div(n_tiles, 8);
         const unsigned xgrid = (unsigned)(xcd_tiles * 8);
         if (p == 0 && by_node)
-            hipLaunchKernelGGL((k_digit_hist<THREADS, RI>), dim3(xgrid), dim3(THREADS), 0, s, (const uint32_t *)d_nodes, n, shift, bits,
+            hipLaunchKernelGGL((k_digit_hist<THREADS, RI>), dim3(xgrid), dim3(THREADS), 0, s, cols.nodes, n, shift, bits,
                                hist, n_tiles, xcd_tiles, d_tiles);
         else if (p == 0 && !from_rows)
-            hipLaunchKernelGGL((k_kmer_digit_hist<THREADS, RI>), dim3(xgrid), dim3(THREADS), 0, s, (const uint64_t *)d_kmers,
+            hipLaunchKernelGGL((k_kmer_digit_hist<THREADS, RI>), dim3(xgrid), dim3(THREADS), 0, s, cols.kmers,
                                n, rule, shift, bits, hist, n_tiles, xcd_tiles, d_tiles, (int *)(stats + 3));
         else
             hipLaunchKernelGGL((k_digit_hist<THREADS, RI>), dim3(xgrid), dim3(THREADS), 0, s, cur_keys, n, shift, bits,
                                hist, n_tiles, xcd_tiles, d_tiles);
         HIP_TRY(hipGetLastError());
         GKI_TRY(gki_scan_u32_to_u32(hist, bins_n, offs, tmp.get(), tmp_bytes, s));
-        PartArgs a;
-        a.tiles = d_tiles;
-        a.keys_in = cur_keys; a.c_kmers = (const uint64_t *)d_kmers; a.c_nodes = (const uint32_t *)d_nodes;
-        a.c_refs = (const uint64_t *)d_ref_offsets; a.c_af = (const uint32_t *)d_af32; a.rule = rule; a.rows_in = cur_rows;
-        a.n = n; a.n_tiles = n_tiles; a.shift = shift; a.bits = bits; a.offs = offs; a.carry_index = d_out_permutation != nullptr;
-        a.rows_out = rows[p & 1]; a.keys_out = keys[p & 1];
-        a.o_kmers = nullptr; a.o_nodes = nullptr; a.o_refs = nullptr; a.o_af = nullptr; a.dbase = nullptr;
-        a.xcd_tiles = xcd_tiles;
+        PartArgs a = {};
+        a.tiles = d_tiles; a.keys_in = cur_keys; a.c = cols; a.rule = rule; a.rows_in = cur_rows;
+        a.n = n; a.n_tiles = n_tiles; a.shift = shift; a.bits = bits; a.offs = offs; a.carry_index = out.perm != nullptr;
+        a.rows_out = rows[p & 1]; a.keys_out = keys[p & 1]; a.xcd_tiles = xcd_tiles;
         if (p == 0 && !from_rows) hipLaunchKernelGGL((k_partition_rows_staged<THREADS, RI, true, PT_NCH>), dim3(xgrid), dim3(THREADS), 0, s, a);
         else hipLaunchKernelGGL((k_partition_rows_staged<THREADS, RI, false, PT_NCH>), dim3(xgrid), dim3(THREADS), 0, s, a);
         HIP_TRY(hipGetLastError());
@@ -1158,21 +1107,19 @@ int gki_index_build_rows(const void *d_kmers, const void *d_nodes, const void *d
     unsigned int h_stats[4] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(h_stats, stats, 16, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (h_stats[3]) return gki_set_error(GKI_ERR_BAD_ARG, "a record's bucket lies outside [%llu, +%llu)", (unsigned long long)bucket_begin, (unsigned long long)n_buckets);
+    if (h_stats[3]) return gki_set_error(GKI_ERR_BAD_ARG, "a record's bucket lies outside [%llu, +%llu)", (unsigned long long)slice.bucket_begin, (unsigned long long)n_buckets);
     // one workgroup streams a large group: fine for the repeats of a genome, not for an index that IS one bucket
-    if (h_stats[1] > large_cap || h_stats[0] > (1u << 22)) return GKI_OK;          // *done stays 0
-    FinishArgs f;
+    if (h_stats[1] > large_cap || h_stats[0] > (1u << 22)) return GKI_NOT_BUILT;
+    FinishArgs f = {};
     f.rows = cur_rows; f.keys = cur_keys; f.gbegin = gbegin; f.gend = gend; f.n_groups = n_groups; f.L = L; f.lbits = L;
-    f.n_buckets = n_buckets; f.skip_frequencies = skip_frequencies; f.h2i = (int32_t *)d_hashes_to_index;
-    f.nk = (uint32_t *)d_n_kmers; f.o_kmers = (uint64_t *)d_out_kmers; f.o_nodes = (uint32_t *)d_out_nodes;
-    f.o_refs = (uint64_t *)d_out_ref_offsets; f.o_af = (uint32_t *)d_out_af32; f.o_freq = (uint16_t *)d_out_frequencies;
-    f.o_perm = (uint32_t *)d_out_permutation; f.af_in = (const uint32_t *)d_af32;
+    f.n_buckets = n_buckets; f.skip_frequencies = skip_frequencies; f.out = out; f.af_in = cols.af;
     f.big_buckets = big; f.n_big = stats + 2; f.big_cap = big_cap;
     f.xcd_groups = (int)ceil_div(n_groups, 8);
-    if (grouped && wrank) hipLaunchKernelGGL((k_group_finish<true, GROUP_CAP_BIG, GROUP_THREADS_BIG>), dim3((unsigned)(f.xcd_groups * 8)), dim3(GROUP_THREADS_BIG), 0, s, f);
-    else if (grouped) hipLaunchKernelGGL((k_group_finish<false, GROUP_CAP_BIG, GROUP_THREADS_BIG>), dim3((unsigned)(f.xcd_groups * 8)), dim3(GROUP_THREADS_BIG), 0, s, f);
-    else if (wrank) hipLaunchKernelGGL((k_group_finish<true>), dim3((unsigned)(f.xcd_groups * 8)), dim3(GROUP_THREADS), 0, s, f);
-    else hipLaunchKernelGGL((k_group_finish<false>), dim3((unsigned)(f.xcd_groups * 8)), dim3(GROUP_THREADS), 0, s, f);
+    with_bools([&](auto wr, auto big_groups) {
+        constexpr bool BIG = decltype(big_groups)::value;
+        constexpr int CAP = BIG ? GROUP_CAP_BIG : GROUP_CAP, FT = BIG ? GROUP_THREADS_BIG : GROUP_THREADS;
+        hipLaunchKernelGGL((k_group_finish<decltype(wr)::value, CAP, FT>), dim3((unsigned)(f.xcd_groups * 8)), dim3(FT), 0, s, f);
+    }, wrank, grouped);
     HIP_TRY(hipGetLastError());
     if (h_stats[1] > 0) {
         const unsigned n_large = h_stats[1];
@@ -1189,15 +1136,12 @@ int gki_index_build_rows(const void *d_kmers, const void *d_nodes, const void *d
             HIP_TRY(rng_b.alloc((size_t)n_ranges * 16));
             int64_t *rng = rng_b.get<int64_t>();
             hipLaunchKernelGGL(k_open_ranges, dim3(stream_grid(n_ranges, 256)), dim3(256), 0, s, large, h_stats[1], gbegin, gend,
-                               big, h_stats[2], (const int32_t *)d_hashes_to_index, (const uint32_t *)d_n_kmers, rng,
-                               rng + n_ranges);
+                               big, h_stats[2], out.h2i, out.n_kmers, rng, rng + n_ranges);
             HIP_TRY(hipGetLastError());
-            GKI_TRY(gki_frequencies_for_rows(rng, rng + n_ranges, n_ranges, modulo, bucket_begin, d_hashes_to_index, d_n_kmers,
-                                             d_out_kmers, d_out_ref_offsets, d_out_frequencies, n, s));
+            GKI_TRY(gki_frequencies_for_rows(rng, rng + n_ranges, n_ranges, slice, out, n, s));
         }
     }
     HIP_TRY(hipStreamSynchronize(s));
-    *done = 1;
     return GKI_OK;
 }
 
@@ -1245,10 +1189,9 @@ __global__ __launch_bounds__(1024) void k_part_bases(ChunkOffs co, int n_digits,
 }  // namespace
 
 template <int THREADS>
-static int partition_columns_by_part(const void *d_kmers, const void *d_nodes, const void *d_ref_offsets, const void *d_af32, int64_t n,
-                                     uint64_t modulo, int n_parts, int sub_bits, int64_t max_rows_per_pass, void *d_out_kmers,
-                                     void *d_out_nodes, void *d_out_ref_offsets, void *d_out_af32, void *d_out_rows, void *d_out_keys,
-                                     int64_t *h_part_start) {
+static int partition_columns_by_part(const RecordCols &cols, int64_t n, const PartSpec &spec, const RecordColsOut &out_cols,
+                                     const RowsOut &out_rows, int64_t *h_part_start) {
+    const auto [modulo, n_parts, sub_bits, max_rows_per_pass] = spec;
     constexpr int RI = 8, TILE = THREADS * RI;
     hipStream_t s = 0;
     const int n_digits = n_parts << sub_bits;
@@ -1267,11 +1210,6 @@ static int partition_columns_by_part(const void *d_kmers, const void *d_nodes, c
     }
     ChunkOffs co;
     co.n_chunks = n_chunks;
-    KeyRule rule;
-    rule.mod = gki_mod_of(modulo); rule.bucket_begin = 0; rule.n_buckets = modulo; rule.n_parts = n_parts; rule.sub_bits = sub_bits;
-    rule.parts_per_bucket = (float)((double)n_parts / (double)modulo);
-    rule.parts_log2 = -1; rule.by_node = 0;
-    for (int l = 0; l <= 8; l++) if ((1 << l) == n_parts) rule.parts_log2 = l;
     const int64_t max_tiles = ceil_div(n < chunk_rows ? n : chunk_rows, TILE);
     const int64_t tmp_bytes = gki_scan_tmp_bytes((int64_t)bins * max_tiles);
     // (declared after h_pb: their frees wait for the device, so the upload that reads h_pb has finished before it goes)
@@ -1287,7 +1225,7 @@ static int partition_columns_by_part(const void *d_kmers, const void *d_nodes, c
     int *bad = bad_b.get<int>();
     HIP_TRY(hipMemcpyAsync(pb, h_pb, PB_WORDS * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(bad, 0, 4, s));
-    rule.part_begin = pb; rule.sub_shift = pb + MAX_PARTS + 1;
+    const KeyRule rule = KeyRule::part(modulo, n_parts, sub_bits, pb);
     for (int c = 0; c < n_chunks; c++) {
         const int64_t c0 = (int64_t)c * chunk_rows, nc = (n - c0) < chunk_rows ? (n - c0) : chunk_rows;
         const int64_t n_tiles = ceil_div(nc, TILE), hist_n = (int64_t)bins * n_tiles;
@@ -1295,7 +1233,7 @@ static int partition_columns_by_part(const void *d_kmers, const void *d_nodes, c
         HIP_TRY(offs_b[c].alloc((size_t)(hist_n + 1) * 4));
         co.offs[c] = offs_b[c].get<const uint32_t>();
         const int xcd_tiles = (int)ceil_div(n_tiles, 8);
-        hipLaunchKernelGGL((k_kmer_digit_hist<THREADS, RI>), dim3((unsigned)(xcd_tiles * 8)), dim3(THREADS), 0, s, (const uint64_t *)d_kmers + c0,
+        hipLaunchKernelGGL((k_kmer_digit_hist<THREADS, RI>), dim3((unsigned)(xcd_tiles * 8)), dim3(THREADS), 0, s, cols.kmers + c0,
                            nc, rule, 0, bits, hist, n_tiles, xcd_tiles, (const TileDesc *)nullptr, bad);
         HIP_TRY(hipGetLastError());
         GKI_TRY(gki_scan_u32_to_u32(hist, hist_n, offs_b[c].get<uint32_t>(), tmp.get(), tmp_bytes, s));
@@ -1304,27 +1242,17 @@ static int partition_columns_by_part(const void *d_kmers, const void *d_nodes, c
     HIP_TRY(hipGetLastError());
     for (int c = 0; c < n_chunks; c++) {
         const int64_t c0 = (int64_t)c * chunk_rows, nc = (n - c0) < chunk_rows ? (n - c0) : chunk_rows;
-        PartArgs a;
-        a.tiles = nullptr;
-        a.keys_in = nullptr; a.c_kmers = (const uint64_t *)d_kmers + c0; a.c_nodes = (const uint32_t *)d_nodes + c0;
-        a.c_refs = (const uint64_t *)d_ref_offsets + c0; a.c_af = (const uint32_t *)d_af32 + c0; a.rule = rule; a.rows_in = nullptr;
-        a.n = nc; a.n_tiles = co.n_tiles[c]; a.shift = 0; a.bits = bits; a.offs = co.offs[c]; a.rows_out = nullptr; a.keys_out = nullptr;
-        a.o_kmers = (uint64_t *)d_out_kmers; a.o_nodes = (uint32_t *)d_out_nodes; a.o_refs = (uint64_t *)d_out_ref_offsets;
-        a.o_af = (uint32_t *)d_out_af32; a.dbase = dbase + (int64_t)c * bins; a.carry_index = 0;
-        a.xcd_tiles = (int)ceil_div(a.n_tiles, 8);
-        if (d_out_rows) {               // rows + keys out (the key: the bucket's offset in its part)
-            a.rows_out = (uint64_t *)d_out_rows; a.keys_out = (uint32_t *)d_out_keys;
-            bool launched = false;
-            if constexpr (THREADS == PT_THREADS) {
-                if (n < ((int64_t)1 << 32)) {
-                    hipLaunchKernelGGL((k_partition_rows_staged<THREADS, RI, true, PT_NCH>), dim3((unsigned)(a.xcd_tiles * 8)), dim3(THREADS), 0, s, a);
-                    launched = true;
-                }
-            }
-            if (!launched)
-                hipLaunchKernelGGL((k_partition_rows<THREADS, RI, true, false>), dim3((unsigned)(a.xcd_tiles * 8)), dim3(THREADS), 0, s, a);
-        } else
-            hipLaunchKernelGGL((k_partition_rows<THREADS, RI, true, true>), dim3((unsigned)(a.xcd_tiles * 8)), dim3(THREADS), 0, s, a);
+        PartArgs a = {};
+        a.c = cols.at(c0); a.rule = rule; a.n = nc; a.n_tiles = co.n_tiles[c]; a.bits = bits; a.offs = co.offs[c];
+        a.o = out_cols; a.dbase = dbase + (int64_t)c * bins; a.xcd_tiles = (int)ceil_div(a.n_tiles, 8);
+        a.rows_out = out_rows.rows; a.keys_out = out_rows.keys;
+        const dim3 grid((unsigned)(a.xcd_tiles * 8));
+        if (!out_rows.rows)
+            hipLaunchKernelGGL((k_partition_rows<THREADS, RI, true, true>), grid, dim3(THREADS), 0, s, a);
+        else if constexpr (THREADS == PT_THREADS) {     // rows + keys out (the key: the bucket's offset in its part): the large tile only
+            if (n < ((int64_t)1 << 32)) hipLaunchKernelGGL((k_partition_rows_staged<THREADS, RI, true, PT_NCH>), grid, dim3(THREADS), 0, s, a);
+            else hipLaunchKernelGGL((k_partition_rows<THREADS, RI, true, false>), grid, dim3(THREADS), 0, s, a);
+        }
         HIP_TRY(hipGetLastError());
     }
     int h_bad = 0;
@@ -1337,17 +1265,13 @@ static int partition_columns_by_part(const void *d_kmers, const void *d_nodes, c
 
 // sub_bits > 0: grouped -- part p's records leave grouped by the top sub_bits bits of (bucket - part_begin[p]); h_part_start has
 // (n_parts << sub_bits) + 1 entries, entry p << sub_bits | g = first row of group g of part p.  Columns out: up to 256 digits
-// go through 2048-row tiles (two workgroups per CU), more through 4096-row tiles.  Rows out (d_out_rows / d_out_keys instead of
+// go through 2048-row tiles (two workgroups per CU), more through 4096-row tiles.  Rows out (out_rows instead of
 // the four columns: 24-byte rows and the bucket's offset in its part as the key): 4096-row tiles -- a run of four ROWS is
 // 96 + 16 contiguous bytes where four records of four columns are runs of 32, 32, 16 and 16 (1024 digits into columns: 98 ms per
 // 3.16e9 records, into rows 61).
-int gki_partition_columns_by_part(const void *d_kmers, const void *d_nodes, const void *d_ref_offsets, const void *d_af32, int64_t n,
-                                  uint64_t modulo, int n_parts, int sub_bits, int64_t max_rows_per_pass, void *d_out_kmers,
-                                  void *d_out_nodes, void *d_out_ref_offsets, void *d_out_af32, void *d_out_rows, void *d_out_keys,
-                                  int64_t *h_part_start) {
-    if (!d_out_rows && (n_parts << sub_bits) <= MAX_PARTS)
-        return partition_columns_by_part<PR_THREADS>(d_kmers, d_nodes, d_ref_offsets, d_af32, n, modulo, n_parts, sub_bits, max_rows_per_pass,
-                                                         d_out_kmers, d_out_nodes, d_out_ref_offsets, d_out_af32, nullptr, nullptr, h_part_start);
-    return partition_columns_by_part<512>(d_kmers, d_nodes, d_ref_offsets, d_af32, n, modulo, n_parts, sub_bits, max_rows_per_pass,
-                                          d_out_kmers, d_out_nodes, d_out_ref_offsets, d_out_af32, d_out_rows, d_out_keys, h_part_start);
+int gki_partition_columns_by_part(const RecordCols &cols, int64_t n, const PartSpec &spec, const RecordColsOut &out_cols,
+                                  const RowsOut &out_rows, int64_t *h_part_start) {
+    if (!out_rows.rows && (spec.n_parts << spec.sub_bits) <= MAX_PARTS)
+        return partition_columns_by_part<PR_THREADS>(cols, n, spec, out_cols, out_rows, h_part_start);
+    return partition_columns_by_part<PT_THREADS>(cols, n, spec, out_cols, out_rows, h_part_start);
 }

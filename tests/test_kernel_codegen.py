@@ -150,3 +150,34 @@ def test_footprints_of_the_index_build_kernels(index_rows_asm):
         assert r[name]["lds"] <= 163840 and r[name]["vgpr"] <= 256, (name, r[name])
     for name in ("k_kmer_digit_hist<512, 8>", "k_kmer_digit_hist<256, 8>", "k_digit_hist<512, 8>"):
         assert r[name]["vgpr"] <= 64 and r[name]["lds"] <= 16384, (name, r[name])      # 8 waves per SIMD; the LDS leaves the thread limit (4 x 512) in charge
+
+
+# name: (VGPRs + AGPRs, LDS bytes, scratch bytes) as compiled at the commit before the tile kernels were factored into shared
+# __forceinline__ helpers (tile_span, load_tile, rank_tile, count_digits): the helpers must leave the kernels as they were
+INDEX_ROWS_PARENT = {
+    "k_partition_rows_staged<512, 8, true, 4>": (108, 59448, 0),
+    "k_partition_rows_staged<512, 8, false, 4>": (128, 65576, 12),
+    "k_partition_rows<256, 8, true, true>": (104, 65576, 0),
+    "k_partition_rows<512, 8, true, true>": (98, 124984, 0),
+    "k_partition_rows<512, 8, true, false>": (106, 141368, 0),       # rows out beyond 2^32 records: compiled, never run by a test
+    "k_kmer_digit_hist<512, 8>": (28, 14344, 0),
+    "k_kmer_digit_hist<256, 8>": (28, 10248, 0),
+    "k_digit_hist<512, 8>": (28, 12288, 0),
+    "k_group_finish<true, 1024, 512>": (49, 36968, 0),
+    "k_group_finish<false, 1024, 512>": (44, 39016, 0),
+    "k_group_finish<true, 4096, 1024>": (73, 123016, 0),
+    "k_group_finish<false, 4096, 1024>": (62, 131208, 0),
+}
+
+
+def test_index_build_kernels_are_what_they_were_before_the_shared_tile_helpers(index_rows_asm):
+    r = _resources(index_rows_asm)
+    for name, (vgpr, lds, scratch) in INDEX_ROWS_PARENT.items():
+        assert r[name]["lds"] == lds and r[name]["scratch"] == scratch and r[name]["vgpr"] <= vgpr, (name, r[name])
+    # the 2048-row tile never leaves as rows: that instantiation (65 KB of LDS in the code object) is gone
+    assert "k_partition_rows<256, 8, true, false>" not in r
+    assert sorted(k for k in r if k.startswith("k_partition_rows")) == sorted(k for k in INDEX_ROWS_PARENT if k.startswith("k_partition_rows"))
+    # the build's passes: two workgroups per CU
+    blocks_by_lds = lambda b: 163840 // b
+    for name in ("k_partition_rows_staged<512, 8, true, 4>", "k_partition_rows_staged<512, 8, false, 4>"):
+        assert blocks_by_lds(r[name]["lds"]) >= 2, (name, r[name])
