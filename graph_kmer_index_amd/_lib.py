@@ -106,6 +106,9 @@ SYMBOLS = {
     "gki_uvk_summarize_counter": (_I32, [_P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "gki_uvk_select": (_I32, [_P, _I64, _I32, _I32, _P, _P, _P, C.POINTER(_I64)]),
     "gki_uvk_emit": (_I32, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gki_uvk_simple_starts": (_I32, [_P, _P, _P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, C.POINTER(_I64)]),
+    "gki_forward_node_count": (_I32, [_P, _I32, _I32, _P, _P, _P, _I64, _P, C.POINTER(_I64)]),
+    "gki_forward_node_emit": (_I32, [_P, _I32, _I32, _P, _P, _P, _I64, _P, _P, _P, _P, _P]),
     "gki_sv_sample_count": (_I32, [_P, C.POINTER(IndexView), _P, _I64, _I32, _I64, _P, C.POINTER(_I64), C.POINTER(_P),
                                    C.POINTER(C.c_float)]),
     "gki_sv_sample_emit": (_I32, [_P, _P, _P, _P, _P, C.POINTER(C.c_float)]),

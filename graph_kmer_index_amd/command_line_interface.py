@@ -215,14 +215,26 @@ def make_kmer_frequencies(args):
 
 def make_unique_variant_kmers(args):
     """command_line_interface.py:299-389, dense path: one finder per `-c` chunk of VCF data lines (`_nodes_found` starts
-    empty at every chunk), run here as one device batch.  `-t` is accepted; the chunks' outputs do not depend on it."""
-    from .unique_variant_kmers import UniqueVariantKmersFinder, VariantArrays, load_variant_to_nodes
+    empty at every chunk), run here as one device batch.  `-t` is accepted; the chunks' outputs do not depend on it.
+    `-S True` (simple selection, find_kmers_over_variant): one batch of per-node searches, no frequency source; -D is not
+    consulted, -i / -I are not needed, -N and -H are ignored as in the reference, and -c / -t do not change the output
+    (this mode keeps no state from variant to variant)."""
+    from .unique_variant_kmers import (UniqueVariantKmersFinder, VariantArrays, find_kmers_over_variants,
+                                       load_variant_to_nodes)
+    if _bool(args.simple):
+        if args.vcf is None:
+            raise ValueError("make_unique_variant_kmers: -v (the VCF) is required")
+        graph = load_graph(args.graph)
+        position_id = None if args.position_id_index is None else load_position_id(args.position_id_index, graph)
+        flat = find_kmers_over_variants(graph, load_variant_to_nodes(args.variant_to_nodes),
+                                        VariantArrays.from_vcf(args.vcf), args.kmer_size, args.max_variant_nodes,
+                                        position_id_index=position_id)
+        flat.to_file(args.out_file_name)
+        logging.info("Wrote %d k-mers (simple selection) to %s" % (len(flat._hashes), args.out_file_name))
+        return
     if not _bool(args.use_dense_kmer_finder):
         raise NotImplementedError("make_unique_variant_kmers: only the dense path is supported; pass -D True "
                                   "(the SnpKmerFinder path is not ported)")
-    if _bool(args.simple):
-        raise NotImplementedError("make_unique_variant_kmers: -S (simple selection) is not supported; the supported "
-                                  "mode is -D True without -S")
     for flag, value in (("-N", args.node_to_variants), ("-H", args.haplotype_matrix)):
         if value is not None:
             raise NotImplementedError("make_unique_variant_kmers: %s is not supported (dense path with a frequency "

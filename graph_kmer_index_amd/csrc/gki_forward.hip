@@ -28,6 +28,16 @@ __device__ __forceinline__ void put_record(const FwdOut &out, int64_t idx, uint6
     fst<NT>(&out.node[idx], node); fst<NT>(&out.af[idx], af);
 }
 
+// Output of the per-node search (FollowNode below): FlatKmers columns written by the walk itself, one record per finished
+// k-mer whose path holds the start position's target node.  Written once, never read here: non-temporal like one-node mode.
+struct NodeOut { uint64_t *hash; uint32_t *node; uint64_t *pos; float *af; };
+__device__ __forceinline__ void put_node_record(const NodeOut &out, const int64_t *__restrict__ pos_base, int64_t idx, uint64_t h, int32_t end_node,
+                                                int end_off, int32_t node, double af) {
+    fst<true>(&out.hash[idx], h); fst<true>(&out.node[idx], (uint32_t)node);
+    fst<true>(&out.pos[idx], (uint64_t)(pos_base[end_node] + (int64_t)end_off));          // PositionId.get of the END position, offset at full width
+    fst<true>(&out.af[idx], (float)af);
+}
+
 // "Script" of a search (round 3): the emit pass used to repeat the count pass's whole walk.  Instead the
 // count pass writes every finished k-mer down -- hash, end position, minimum allele frequency, the path's nodes, the
 // number of the k-mer's first record among its start position's -- in one of FW_SLOTS 48-byte entries per start position,
@@ -82,6 +92,33 @@ __device__ __forceinline__ bool any_followed(const DevGraph &g, const uint8_t *_
     for (int64_t e = g.edge_start[node]; e < g.edge_start[node + 1]; e++) if (follow[g.edges[e]]) return true;
     return false;
 }
+
+// What a walk follows and what it stores.
+// FollowMask (gki_forward_count / _emit): one only_follow_nodes set for the whole batch, no store filter, the v2 columns.
+// FollowNode (gki_forward_node_count / _emit): only_follow_nodes = only_store_nodes = {target}, the target being the start
+// position's own (find_kmers_over_variant_node, unique_variant_kmers.py:91-94).  A node has at most one forced successor, the
+// target itself: a forced level holds it as its one inline successor (see succ_begin), so there is no set to iterate, no
+// `last`, and no order caveat.  A finished k-mer gives one record, of the target, when the target is on its path.
+struct FollowMask {
+    static constexpr bool NODE = false;
+    const uint8_t *__restrict__ follow;
+    FwdOut out;
+    __device__ __forceinline__ bool uses_last() const { return follow != nullptr; }
+    __device__ __forceinline__ bool forced(const DevGraph &g, const NodeFwd &, int32_t node) const { return any_followed(g, follow, node); }
+};
+struct FollowNode {
+    static constexpr bool NODE = true;
+    int32_t target;
+    const int64_t *__restrict__ pos_base;
+    NodeOut out;
+    __device__ __forceinline__ bool uses_last() const { return false; }
+    // (the node's record holds up to two successors: no trip to the edge list for them)
+    __device__ __forceinline__ bool forced(const DevGraph &g, const NodeFwd &w, int32_t node) const {
+        if (w.cnt <= 2) return (w.cnt >= 1 && w.e0 == target) || (w.cnt == 2 && w.e1 == target);
+        for (int64_t e = g.edge_start[node]; e < g.edge_start[node + 1]; e++) if (g.edges[e] == target) return true;
+        return false;
+    }
+};
 
 // kmer_finder.py:397-402: at the limit only the linear-ref successor is followed, and the reference asserts that there is
 // exactly one (no assertion when the node has no successors :390 or when the step is forced :397).
@@ -150,16 +187,29 @@ __device__ __forceinline__ uint64_t succ_begin(const DevGraph &g, const NodeFwd 
     return FW_CE(w.e0, w.cnt == 0xFFFF ? (int32_t)g.edge_start[n + 1] : w.e0 + (int32_t)w.cnt);
 }
 
+// The (cur, end) pair of a level whose step is forced: the whole edge list, filtered by the follow set as it is walked
+// (FollowMask); the target as the one inline successor (FollowNode).
+__device__ __forceinline__ uint64_t forced_begin(const DevGraph &g, const FollowMask &, int32_t n) {
+    return FW_CE((int32_t)g.edge_start[n], (int32_t)g.edge_start[n + 1]);
+}
+__device__ __forceinline__ uint64_t forced_begin(const DevGraph &, const FollowNode &p, int32_t) { return FW_CE(p.target, INT_MIN); }
+__device__ __forceinline__ const uint8_t *follow_set(const FollowMask &p) { return p.follow; }
+__device__ __forceinline__ const uint8_t *follow_set(const FollowNode &) { return nullptr; }
+__device__ __forceinline__ FwdOut v2_columns(const FollowMask &p) { return p.out; }
+__device__ __forceinline__ FwdOut v2_columns(const FollowNode &) { return FwdOut{nullptr, nullptr, nullptr, nullptr, nullptr}; }   // (never written)
+
 // DEEP = false: the product kernel, its levels in registers and, beyond those, FMAX levels per lane in scratch.  DEEP = true:
 // the slow path for forward windows over more nodes than that (sixteen or more empty nodes before the first k-mer is
 // complete), the same walk with its levels in a global-memory arena of da.cap levels per lane (gki_forward_count grows it
 // until the walk fits).
-template <bool EMIT, bool DEEP, bool SCRIPT>
-__device__ void forward_walk(const DevGraph &g, const NodeFwd *__restrict__ fw, int k, int M, bool one_node, const uint8_t *__restrict__ follow,
-                             int32_t n0, int32_t o0, int64_t idx, FwdOut out, uint32_t *count_out, int *err,
+template <bool EMIT, bool DEEP, bool SCRIPT, class POL>
+__device__ void forward_walk(const DevGraph &g, const NodeFwd *__restrict__ fw, int k, int M, bool one_node, const POL &pol,
+                             int32_t n0, int32_t o0, int64_t idx, uint32_t *count_out, int *err,
                              const DeepArena &da, int64_t lane_global, uint4 *script, int64_t pos, int64_t n_pos, uint32_t *used_out) {
     static_assert(!SCRIPT || (!EMIT && !DEEP), "the script is written by the product count kernel");
+    static_assert(!SCRIPT || !POL::NODE, "the per-node search writes no script");
     constexpr int R = DEEP ? 0 : FWD_REG_LEVELS;
+    const FwdOut out = v2_columns(pol);
     uint32_t used = 0;                        // SCRIPT: entries written, 0xFF = this start position does not fit
     // Per level four 64-bit words: (node, meta) with meta = bases collected (8 bits) | "forced traversal" (7) | "outside the
     // window" (1, level 0 only: see outside0 below) | variant nodes on the path (16); the successors still to take (cur, end);
@@ -211,18 +261,24 @@ __device__ void forward_walk(const DevGraph &g, const NodeFwd *__restrict__ fw, 
         }
         have0 = t;
         if (t < k) {                           // (t == k: window complete inside the start node, handled below)
-            const int vc0 = w0.is_ref || outside0 ? 0 : 1, forced0 = any_followed(g, follow, n0) ? 1 : 0;
+            const int vc0 = w0.is_ref || outside0 ? 0 : 1, forced0 = pol.forced(g, w0, n0) ? 1 : 0;
             lv_set(nm_r, nm_st, 0, (uint64_t)(uint32_t)n0 | ((uint64_t)FW_MK(t, forced0 | outside0 << 7, vc0) << 32));
             lv_set(hs_r, hs_st, 0, h0);
             lv_set(mf_r, mf_st, 0, maf0);
-            lv_set(ce_r, ce_st, 0, forced0 ? FW_CE((int32_t)g.edge_start[n0], (int32_t)g.edge_start[n0 + 1]) : succ_begin(g, w0, n0));
-            if (follow) last[0] = INT_MIN;
+            lv_set(ce_r, ce_st, 0, forced0 ? forced_begin(g, pol, n0) : succ_begin(g, w0, n0));
+            if (pol.uses_last()) last[0] = INT_MIN;
             L = 1;
             if (!EMIT && !forced0 && vc0 >= M) check_one_ref_successor(g, n0, err);
         }
     }
     // completion inside the start node
     if (have0 == k) {
+        if constexpr (POL::NODE) {                 // the path is the start node alone
+            const bool hit = n0 == pol.target;
+            if (EMIT && hit) put_node_record(pol.out, pol.pos_base, idx, h0, n0, o0 + k - 1, n0, w0.af);
+            *count_out = hit ? 1u : 0u;
+            return;
+        }
         if (EMIT) {
             put_record<false>(out, idx, h0, n0, o0 + k - 1, n0, w0.af);
         }
@@ -242,7 +298,7 @@ __device__ void forward_walk(const DevGraph &g, const NodeFwd *__restrict__ fw, 
         const uint64_t nmj = lv_get(nm_r, nm_st, j);
         const uint32_t mj = FW_META_OF(nmj);
         int32_t q;
-        if (FW_FORCED_OF(mj)) {
+        if (!POL::NODE && FW_FORCED_OF(mj)) {
             // :386-388 forced traversal: only the successors in the follow set.  The reference iterates a Python set
             // there, and CPython orders a set of small ints by hash & table mask, not by value (list({7, 8}) is
             // [8, 7]): among SEVERAL forced successors of one node the reference's order is an accident of the
@@ -252,7 +308,7 @@ __device__ void forward_walk(const DevGraph &g, const NodeFwd *__restrict__ fw, 
             q = INT_MAX;
             for (int32_t e = (int32_t)g.edge_start[FW_NODE_OF(nmj)]; e < endj; e++) {
                 const int32_t c = g.edges[e];
-                if (follow[c] && c > last[j] && c < q) q = c;
+                if (follow_set(pol)[c] && c > last[j] && c < q) q = c;
             }
             if (q == INT_MAX) { lv_set(ce_r, ce_st, j, FW_CE(endj, endj)); continue; }
             last[j] = q;
@@ -276,6 +332,17 @@ __device__ void forward_walk(const DevGraph &g, const NodeFwd *__restrict__ fw, 
         const double mafL = fmin(lv_get(mf_r, mf_st, j), wq.af);
         auto node_at = [&](int i) -> int32_t { return i == L ? q : FW_NODE_OF(lv_get(nm_r, nm_st, i)); };      // (level L itself is not stored)
         if (hv + t == k) {                          // first k-mer of this path: emit and stop (early stop, :326-330)
+            if constexpr (POL::NODE) {
+                // only_store_nodes = {target}: one record when the target is among the window's nodes -- levels 0 .. L, or
+                // 1 .. L when the window begins behind the start node (see outside0)
+                bool hit = q == pol.target;
+                for (int i = FW_OUTSIDE_OF(FW_META_OF(lv_get(nm_r, nm_st, 0))); i < L; i++) hit = hit || node_at(i) == pol.target;
+                if (hit) {
+                    if (EMIT) { put_node_record(pol.out, pol.pos_base, idx, hL, q, t - 1, pol.target, mafL); idx++; }
+                    count++;
+                }
+                continue;
+            }
             if (__builtin_expect(FW_OUTSIDE_OF(FW_META_OF(lv_get(nm_r, nm_st, 0))), 0)) {
                 // the window begins at level 1 (see outside0): its nodes are levels 1 .. L, one record per node by selection
                 int32_t mn = q;
@@ -356,12 +423,12 @@ __device__ void forward_walk(const DevGraph &g, const NodeFwd *__restrict__ fw, 
             count += one_node ? 1u : (uint32_t)Lw;
             continue;
         }
-        const int forcedL = any_followed(g, follow, q) ? 1 : 0;
-        lv_set(ce_r, ce_st, L, forcedL ? FW_CE((int32_t)g.edge_start[q], (int32_t)g.edge_start[q + 1]) : succ_begin(g, wq, q));
+        const int forcedL = pol.forced(g, wq, q) ? 1 : 0;
+        lv_set(ce_r, ce_st, L, forcedL ? forced_begin(g, pol, q) : succ_begin(g, wq, q));
         lv_set(nm_r, nm_st, L, (uint64_t)(uint32_t)q | ((uint64_t)FW_MK(hv + t, forcedL, vcL) << 32));
         lv_set(hs_r, hs_st, L, hL);
         lv_set(mf_r, mf_st, L, mafL);
-        if (follow) last[L] = INT_MIN;
+        if (pol.uses_last()) last[L] = INT_MIN;
         if (!EMIT && !forcedL && vcL >= M) check_one_ref_successor(g, q, err);
         L++;
         // (out of budget: the walk ends through its ordinary exit, see STEP_BUDGET in csrc/gki_finder.hip)
@@ -409,13 +476,30 @@ __global__ __launch_bounds__(DEEP ? 64 : FWD_BLOCK, DEEP ? 1 : FWD_WAVES) void k
         if (EMIT && used && !list && used[i] != 0xFF) continue;          // written by the expansion of the script
         const int32_t n0 = nodes[i];
         if (n0 < 0 || n0 >= g.n_nodes) { if (!EMIT) cnt[i] = 0; if (SCRIPT) used[i] = 0; continue; }
-        forward_walk<EMIT, DEEP, SCRIPT>(g, fw, k, M, one_node != 0, follow, n0, offsets[i], EMIT ? rec_start[i] : 0, out, &c, err, da, lane_global,
+        forward_walk<EMIT, DEEP, SCRIPT>(g, fw, k, M, one_node != 0, FollowMask{follow, out}, n0, offsets[i], EMIT ? rec_start[i] : 0, &c, err, da, lane_global,
                                          script, i, n_pos, &u);
         if (!EMIT) cnt[i] = c;
         if (SCRIPT) {
             used[i] = (uint8_t)u;
             if (u == 0xFFu) { const int slot = atomicAdd(err + 1, 1); if (slot < list_n) list[slot] = i; }
         }
+    }
+}
+
+// The per-node search: start position i follows and stores targets[i] alone.  Same launch shapes as k_forward; no script.
+template <bool EMIT, bool DEEP = false>
+__global__ __launch_bounds__(DEEP ? 64 : FWD_BLOCK, DEEP ? 1 : FWD_WAVES) void k_forward_node(DevGraph g, const NodeFwd *__restrict__ fw, int k, int M, const int32_t *__restrict__ targets,
+                                                     const int32_t *__restrict__ nodes, const int32_t *__restrict__ offsets, int64_t n_pos,
+                                                     uint32_t *__restrict__ cnt, const int64_t *__restrict__ rec_start, NodeOut out,
+                                                     int *__restrict__ err, DeepArena da) {
+    const int64_t lane_global = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int64_t i = lane_global; i < n_pos; i += DEEP ? da.lanes : n_pos) {
+        uint32_t c = 0, u = 0;
+        const int32_t n0 = nodes[i];
+        if (n0 < 0 || n0 >= g.n_nodes) { if (!EMIT) cnt[i] = 0; continue; }
+        forward_walk<EMIT, DEEP, false>(g, fw, k, M, false, FollowNode{targets[i], g.pos_base, out}, n0, offsets[i], EMIT ? rec_start[i] : 0, &c, err, da,
+                                        lane_global, (uint4 *)nullptr, i, n_pos, &u);
+        if (!EMIT) cnt[i] = c;
     }
 }
 
@@ -542,9 +626,93 @@ void launch_walk(gki_graph *gr, const FwdCall &c, bool emit, const DeepArena &da
     }, emit, deep);
 }
 
+// what a count pass answers for its error word
+int count_error(int herr, int word) {
+    if (herr == GKI_ERR_NOT_ONE_REF_SUCC)
+        return gki_set_error(herr, "a path at the variant limit ends a node that does not have exactly one linear-ref "
+                             "successor: the reference asserts here (kmer_finder.py:402)");
+    if (herr) return gki_set_error(herr, (word & 4) ? "the paths from one start position take more than %d descents to enumerate: too many paths"
+                                   : "a forward k-window crosses more than %d nodes", (word & 4) ? FW_BUDGET : GKI_MAX_DEEP_WINDOW_NODES - 2);
+    return GKI_OK;
+}
+
+// what every pass of one per-node search is given
+struct NodeCall {
+    int k, M;
+    const int32_t *targets, *nodes, *offsets;
+    int64_t n_pos;
+};
+
+// One pass of the per-node search, k_forward_node<EMIT, DEEP>, repeated with the deep variant on a grown arena until no
+// stack of the walk was too short (as gki_forward_count / gki_forward_emit do).  after(): what follows the launch of each
+// round (the count pass's scan).  *word_out: the error word of the last round.
+template <class After>
+int node_passes(gki_graph *gr, const NodeCall &c, bool emit, uint32_t *cnt, const int64_t *rec_start, const NodeOut &out, int *d_err, int *word_out, After after) {
+    for (;;) {
+        const DeepArena da = gr->fwd_deep.view();
+        const bool deep = da.cap > 0;
+        HIP_TRY(hipMemset(d_err, 0, 4));
+        const dim3 grid((unsigned)(deep ? da.lanes / 64 : ceil_div(c.n_pos, FWD_BLOCK))), block(deep ? 64 : FWD_BLOCK);
+        with_bools([&](auto EMIT, auto DEEP) {
+            hipLaunchKernelGGL((k_forward_node<decltype(EMIT)::value, decltype(DEEP)::value>), grid, block, 0, 0, gr->d, gr->fwd_nodes.get<NodeFwd>(), c.k, c.M,
+                               c.targets, c.nodes, c.offsets, c.n_pos, cnt, rec_start, out, d_err, da);
+        }, emit, deep);
+        if (hipGetLastError() != hipSuccess) return gki_set_error(GKI_ERR_HIP, "k_forward_node launch failed");
+        GKI_TRY(after());
+        HIP_TRY(hipMemcpy(word_out, d_err, 4, hipMemcpyDeviceToHost));          // (synchronises)
+        const int next_cap = gki_deep_next_cap(*word_out, da.cap, 4 * FMAX);
+        if (!next_cap) return GKI_OK;
+        GKI_TRY(deep_grow(gr, next_cap));
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int gki_forward_node_count(gki_graph *gr, int k, int max_variant_nodes, const void *d_targets, const void *d_nodes, const void *d_offsets,
+                           int64_t n_pos, void *d_rec_start, int64_t *n_records) {
+    *n_records = 0;
+    if (k < 1 || k > GKI_MAX_K) return gki_set_error(GKI_ERR_BAD_ARG, "k must be in 1..31");
+    GKI_TRY(gki_check_graph_device(gr, "gki_forward_node_count"));
+    if (n_pos <= 0) { HIP_TRY(hipMemset(d_rec_start, 0, 8)); return GKI_OK; }
+    GKI_TRY(fwd_nodes_ready(gr));
+    deep_release(gr);                     // the product kernel first; the emit call uses what this call settles on
+    const int64_t tmp_bytes = gki_scan_tmp_bytes(n_pos);
+    DevBuf cnt_b, tmp, d_err_b;
+    HIP_TRY(cnt_b.alloc((size_t)n_pos * 4));
+    HIP_TRY(tmp.alloc((size_t)tmp_bytes));
+    HIP_TRY(d_err_b.alloc(4));
+    const NodeCall c{k, max_variant_nodes > 250 ? 250 : max_variant_nodes, (const int32_t *)d_targets, (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos};
+    int word = 0;
+    GKI_TRY(node_passes(gr, c, false, cnt_b.get<uint32_t>(), nullptr, NodeOut{nullptr, nullptr, nullptr, nullptr}, d_err_b.get<int>(), &word, [&]() -> int {
+        return gki_scan_u32_to_i64(cnt_b.get<uint32_t>(), n_pos, (int64_t *)d_rec_start, tmp.get(), tmp_bytes, 0);
+    }));
+    GKI_TRY(count_error(gki_error_of_word(word), word));
+    int64_t total = 0;
+    HIP_TRY(hipMemcpy(&total, (const int64_t *)d_rec_start + n_pos, 8, hipMemcpyDeviceToHost));
+    *n_records = total;
+    return GKI_OK;
+}
+
+int gki_forward_node_emit(gki_graph *gr, int k, int max_variant_nodes, const void *d_targets, const void *d_nodes, const void *d_offsets,
+                          int64_t n_pos, const void *d_rec_start, void *d_hashes, void *d_nodes_out, void *d_position_ids, void *d_af32) {
+    if (n_pos <= 0) return GKI_OK;
+    GKI_TRY(gki_check_graph_device(gr, "gki_forward_node_emit"));
+    GKI_TRY(fwd_nodes_ready(gr));
+    DevBuf d_err_b;
+    HIP_TRY(d_err_b.alloc(4));
+    const NodeCall c{k, max_variant_nodes > 250 ? 250 : max_variant_nodes, (const int32_t *)d_targets, (const int32_t *)d_nodes, (const int32_t *)d_offsets, n_pos};
+    const NodeOut out{(uint64_t *)d_hashes, (uint32_t *)d_nodes_out, (uint64_t *)d_position_ids, (float *)d_af32};
+    int word = 0;
+    // (like gki_forward_emit, the emit pass settles the depth itself: the arena on the handle is whatever the last count left)
+    const int rc = node_passes(gr, c, true, nullptr, (const int64_t *)d_rec_start, out, d_err_b.get<int>(), &word, []() -> int { return GKI_OK; });
+    deep_release(gr);
+    if (rc != GKI_OK) return rc;
+    const int herr = gki_error_of_word(word);
+    if (herr) return gki_set_error(herr, "the emit pass of the per-node search left records unwritten (error word %d)", word);
+    return GKI_OK;
+}
 
 int gki_forward_count(gki_graph *gr, int k, int max_variant_nodes, int one_node, const void *d_follow, const void *d_nodes,
                       const void *d_offsets, int64_t n_pos, void *d_rec_start, int64_t *n_records) {
@@ -603,11 +771,7 @@ int gki_forward_count(gki_graph *gr, int k, int max_variant_nodes, int one_node,
         sc.k = k; sc.M = c.M; sc.one_node = one_node ? 1 : 0; sc.valid = 1;
     }
     if (rc != GKI_OK) return rc;
-    if (herr == GKI_ERR_NOT_ONE_REF_SUCC)
-        return gki_set_error(herr, "a path at the variant limit ends a node that does not have exactly one linear-ref "
-                             "successor: the reference asserts here (kmer_finder.py:402)");
-    if (herr) return gki_set_error(herr, (word[0] & 4) ? "the paths from one start position take more than %d descents to enumerate: too many paths"
-                                   : "a forward k-window crosses more than %d nodes", (word[0] & 4) ? FW_BUDGET : GKI_MAX_DEEP_WINDOW_NODES - 2);
+    GKI_TRY(count_error(herr, word[0]));
     *n_records = total;
     return GKI_OK;
 }

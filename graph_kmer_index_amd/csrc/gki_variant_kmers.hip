@@ -9,10 +9,30 @@
 //   gki_uvk_select     one lane per variant: rules 5-6 over its summaries for a given store set, record counts, scan
 //   gki_uvk_emit       one lane per variant: the chosen start's records of the stored nodes, in emission order
 //
+// Simple selection (find_kmers_over_variant, :66-111): gki_uvk_simple_starts, one lane per (variant, allele), then the
+// per-node search gki_forward_node_count / gki_forward_node_emit (csrc/gki_forward.hip), which writes the output itself.
+//
 // Every per-lane quantity is a scalar in registers: no arrays, no scratch.
 #include "gki_frequency.h"
 
 namespace {
+
+// (node, offset) at graph ref offset x: the last linear-ref node of nonzero size whose first base is at or before x.
+// false: x lies before the first node, or past the end of the node found (past the linear path, or in a gap of it).
+__device__ __forceinline__ bool lin_locate(const int64_t *__restrict__ lin_start, const int32_t *__restrict__ lin_node,
+                                           const int32_t *__restrict__ node_size, int64_t n_lin, int64_t x, int32_t *node, int32_t *off) {
+    int64_t lo = 0, hi = n_lin;                      // answer in [lo, hi): lin_start[lo] <= x < lin_start[hi]
+    *node = 0; *off = 0;
+    if (!(n_lin > 0 && x >= lin_start[0])) return false;
+    while (hi - lo > 1) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (lin_start[mid] <= x) lo = mid; else hi = mid;
+    }
+    *node = lin_node[lo];
+    const int64_t d = x - lin_start[lo];
+    *off = (int32_t)d;
+    return d < (int64_t)node_size[*node];
+}
 
 __global__ __launch_bounds__(256) void k_uvk_starts(const int64_t *__restrict__ lin_start, const int32_t *__restrict__ lin_node,
                                                     const int32_t *__restrict__ node_size, int64_t n_lin,
@@ -25,24 +45,38 @@ __global__ __launch_bounds__(256) void k_uvk_starts(const int64_t *__restrict__ 
         const int64_t v = i / P;
         const int j = (int)(i - v * P);
         const int64_t x = var_ref_offset[v] - (2 + 4 * (P - 1 - j));     // [POS - i for i in range(2, k-2)][::4][::-1]
-        // the last linear node whose first base is at or before x
-        int64_t lo = 0, hi = n_lin;                      // answer in [lo, hi): lin_start[lo] <= x < lin_start[hi]
-        int32_t node = 0, off = 0;
-        bool ok = n_lin > 0 && x >= lin_start[0];
-        if (ok) {
-            while (hi - lo > 1) {
-                const int64_t mid = lo + ((hi - lo) >> 1);
-                if (lin_start[mid] <= x) lo = mid; else hi = mid;
-            }
-            node = lin_node[lo];
-            const int64_t d = x - lin_start[lo];
-            ok = d < (int64_t)node_size[node];
-            off = (int32_t)d;
-        }
-        if (!ok) { atomicMin(first_bad, (unsigned long long)v); node = 0; off = 0; }
+        int32_t node, off;
+        if (!lin_locate(lin_start, lin_node, node_size, n_lin, x, &node, &off)) { atomicMin(first_bad, (unsigned long long)v); node = 0; off = 0; }
         out_nodes[i] = node;
         out_offsets[i] = off;
         out_variant[i] = (int32_t)v;
+    }
+}
+
+// Simple selection, unique_variant_kmers.py:72-89: search 2 v + a of variant v is for its ref (a = 0) or alt (a = 1) node.
+// A SNP starts at (node, 0) of a node with bases; an indel, and a SNP's empty node, at the linear-ref position 8 bases before
+// P, with P = POS for an indel and POS - 1 for a SNP as 0-based chromosome offsets (var_ref_offset holds the chromosome's
+// graph ref offset + the 1-based VCF POS, as for k_uvk_starts).
+__global__ __launch_bounds__(256) void k_uvk_simple_starts(const int64_t *__restrict__ lin_start, const int32_t *__restrict__ lin_node,
+                                                           const int32_t *__restrict__ node_size, int64_t n_nodes, int64_t n_lin,
+                                                           const int64_t *__restrict__ var_ref_offset, const uint8_t *__restrict__ is_snp,
+                                                           const int32_t *__restrict__ ref_nodes, const int32_t *__restrict__ alt_nodes, int64_t n_var,
+                                                           int32_t *__restrict__ out_nodes, int32_t *__restrict__ out_offsets,
+                                                           int32_t *__restrict__ out_targets, unsigned long long *__restrict__ first_bad) {
+    const int64_t n = n_var * 2;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const int64_t v = i >> 1;
+        const int32_t target = (i & 1) ? alt_nodes[v] : ref_nodes[v];
+        const bool snp = is_snp[v] != 0;
+        int32_t node = 0, off = 0;
+        bool ok = target >= 0 && (int64_t)target < n_nodes;
+        if (ok && snp && node_size[target] > 0) node = target;
+        else if (ok) ok = lin_locate(lin_start, lin_node, node_size, n_lin, var_ref_offset[v] - (snp ? 9 : 8), &node, &off);
+        if (!ok) { atomicMin(first_bad, (unsigned long long)v); node = 0; off = 0; }
+        out_nodes[i] = node;
+        out_offsets[i] = off;
+        out_targets[i] = target;
     }
 }
 
@@ -125,6 +159,26 @@ int gki_uvk_starts(gki_graph *g, const void *d_lin_start, const void *d_lin_node
     hipLaunchKernelGGL(k_uvk_starts, dim3(stream_grid(n, 256)), dim3(256), 0, 0, (const int64_t *)d_lin_start,
                        (const int32_t *)d_lin_node, g->d.node_size, n_lin, (const int64_t *)d_var_ref_offset, n_var,
                        n_starts_per_variant, (int32_t *)d_nodes, (int32_t *)d_offsets, (int32_t *)d_variant, bad.get<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    unsigned long long h = ~0ull;
+    HIP_TRY(hipMemcpy(&h, bad.get(), 8, hipMemcpyDeviceToHost));
+    if (h != ~0ull) *first_bad_variant = (int64_t)h;
+    return GKI_OK;
+}
+
+int gki_uvk_simple_starts(gki_graph *g, const void *d_lin_start, const void *d_lin_node, int64_t n_lin, const void *d_var_ref_offset,
+                          const void *d_is_snp, const void *d_ref_nodes, const void *d_alt_nodes, int64_t n_var, void *d_nodes,
+                          void *d_offsets, void *d_targets, int64_t *first_bad_variant) {
+    *first_bad_variant = -1;
+    GKI_TRY(gki_check_graph_device(g, "gki_uvk_simple_starts"));
+    if (n_var <= 0) return GKI_OK;
+    DevBuf bad;
+    HIP_TRY(bad.alloc(8));
+    HIP_TRY(hipMemset(bad.get(), 0xFF, 8));
+    hipLaunchKernelGGL(k_uvk_simple_starts, dim3(stream_grid(n_var * 2, 256)), dim3(256), 0, 0, (const int64_t *)d_lin_start,
+                       (const int32_t *)d_lin_node, g->d.node_size, g->d.n_nodes, n_lin, (const int64_t *)d_var_ref_offset,
+                       (const uint8_t *)d_is_snp, (const int32_t *)d_ref_nodes, (const int32_t *)d_alt_nodes, n_var, (int32_t *)d_nodes,
+                       (int32_t *)d_offsets, (int32_t *)d_targets, bad.get<unsigned long long>());
     HIP_TRY(hipGetLastError());
     unsigned long long h = ~0ull;
     HIP_TRY(hipMemcpy(&h, bad.get(), 8, hipMemcpyDeviceToHost));

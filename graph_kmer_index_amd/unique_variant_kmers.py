@@ -17,6 +17,11 @@ The positional accessors obgraph would supply are restated from the graph's arra
   * the node at a ref offset is the linear-ref node of nonzero size that covers it, the offset is the distance into it
 A start before 0 or past the linear path is a ValueError naming the variant (the reference's answer there depends on
 obgraph's arrays).  When the graph object has obgraph's accessors, a sample of starts is checked against them.
+
+Simple selection (`use_simple=True` of the reference, unique_variant_kmers.py:66-111): find_kmers_over_variants below.  For
+every variant one search for its ref node and one for its alt node, each with only_store_nodes = only_follow_nodes =
+{node}; no frequency source, no choice among start positions, no `_nodes_found`.  All searches run as one batch of the
+per-node search (include/gki.h gki_uvk_simple_starts, gki_forward_node_*), which writes the FlatKmers columns itself.
 """
 import logging
 import time
@@ -41,9 +46,10 @@ def start_distances(k):
 
 
 class VariantArrays:
-    """Variants as arrays: VCF POS (1-based), chromosome (as in the VCF), line number (data lines from 0)."""
+    """Variants as arrays: VCF POS (1-based), chromosome (as in the VCF), line number (data lines from 0), and
+    optionally is_snp (1 SNP, 0 another type, -1 type not set), which only simple selection reads."""
 
-    def __init__(self, positions, chromosomes, line_numbers):
+    def __init__(self, positions, chromosomes, line_numbers, is_snp=None):
         self.positions = np.ascontiguousarray(positions, dtype=np.int64)
         n = len(self.positions)
         if np.isscalar(chromosomes) or isinstance(chromosomes, str):
@@ -52,6 +58,9 @@ class VariantArrays:
         self.line_numbers = np.ascontiguousarray(line_numbers, dtype=np.int64)
         if len(self.chromosomes) != n or len(self.line_numbers) != n:
             raise ValueError("positions, chromosomes and line numbers differ in length")
+        self.is_snp = None if is_snp is None else np.ascontiguousarray(is_snp, dtype=np.int8)
+        if self.is_snp is not None and len(self.is_snp) != n:
+            raise ValueError("positions and is_snp differ in length")
 
     def __len__(self):
         return len(self.positions)
@@ -61,25 +70,28 @@ class VariantArrays:
         variants = list(variants)
         for v in variants:
             assert v.vcf_line_number is not None, "Variant line number must be specified"     # :251
+        types = [getattr(v, "type", None) for v in variants]
         return cls([v.position for v in variants], np.array([v.chromosome for v in variants], dtype=object),
-                   [v.vcf_line_number for v in variants])
+                   [v.vcf_line_number for v in variants], [-1 if t is None else int(t == "SNP") for t in types])
 
     @classmethod
     def from_vcf(cls, file_name):
-        """CHROM, POS and line number of every data line (lines not starting with '#'), numbered from 0."""
+        """CHROM, POS and line number of every data line (lines not starting with '#'), numbered from 0; is_snp from REF
+        and ALT, a SNP when both are one base long (as obgraph types a variant), not set on a line without them."""
         import gzip
         opener = gzip.open if str(file_name).endswith(".gz") else open
-        chroms, positions = [], []
+        chroms, positions, is_snp = [], [], []
         with opener(file_name, "rt") as f:
             for line in f:
                 if line.startswith("#") or not line.strip():
                     continue
-                fields = line.split("\t", 2)
+                fields = line.rstrip("\r\n").split("\t", 5)
                 if len(fields) < 2:
                     raise ValueError("VCF data line %d has fewer than two columns" % len(positions))
                 chroms.append(fields[0])
                 positions.append(int(fields[1]))
-        return cls(positions, np.array(chroms, dtype=object), np.arange(len(positions)))
+                is_snp.append(-1 if len(fields) < 5 else int(len(fields[3]) == 1 and len(fields[4]) == 1))
+        return cls(positions, np.array(chroms, dtype=object), np.arange(len(positions)), is_snp)
 
 
 def load_variant_to_nodes(file_name):
@@ -157,6 +169,34 @@ def _as_int(x):
         return None
 
 
+def _graph_ref_offsets(lin, va, active):
+    """Graph ref offset of POS of every active variant: its chromosome's start offset + POS."""
+    chrom = va.chromosomes[active]
+    uniq, inv = np.unique(chrom.astype(str), return_inverse=True) if chrom.dtype == object else \
+        np.unique(chrom, return_inverse=True)
+    first_of = np.zeros(len(uniq), np.int64)
+    first_of[inv[::-1]] = np.arange(len(inv))[::-1]
+    base = np.array([lin.chromosome_offset(chrom[i]) for i in first_of], dtype=np.int64)
+    return np.ascontiguousarray(base[inv] + va.positions[active])
+
+
+def _graph_on_device(arrays, position_id_index):
+    """The graph in HBM with the position ids of `position_id_index` (None: the default ones): the package's cached upload
+    when they are the default ones, otherwise a new upload."""
+    if position_id_index is None:
+        return DeviceGraph.of(arrays)
+    n = arrays.n_nodes
+    base = np.asarray(position_id_index.get(np.arange(n), np.zeros(n, dtype=np.int64))).astype(np.int64)
+    return DeviceGraph.of(arrays) if np.array_equal(base, arrays.position_id_base()) else \
+        DeviceGraph(arrays, position_base=base)
+
+
+def _outside_linear_reference(va, src):
+    return ValueError("variant %d (line %d, chromosome %s, POS %d): a start position lies before 0 or past the "
+                      "linear reference (the reference's answer is undefined there)"
+                      % (src, int(va.line_numbers[src]), va.chromosomes[src], int(va.positions[src])))
+
+
 def choose_position(summaries, mask, lowest):
     """Rules 5-6 for one variant (host form of k_uvk_select): summaries = P gki_uvk_summary records, mask bit 0/1 = ref /
     alt stored.  Returns (chosen start, nodes of the chosen flat as a set of 'ref' / 'alt')."""
@@ -189,8 +229,9 @@ class UniqueVariantKmersFinder:
             raise NotImplementedError("only the dense path is supported: UniqueVariantKmersFinder(..., "
                                       "use_dense_kmer_finder=True, position_id_index=...) (SnpKmerFinder is not ported)")
         if use_simple:
-            raise NotImplementedError("use_simple=True is not supported: the supported mode is the dense path with "
-                                      "use_simple=False (find_unique_kmers_over_variant)")
+            raise NotImplementedError("use_simple=True is not accepted by the constructor: simple selection is "
+                                      "find_kmers_over_variants(graph, variant_to_nodes, variants, k, max_variant_nodes, "
+                                      "position_id_index) of this module, and make_unique_variant_kmers -S True")
         if not isinstance(kmer_index_with_frequencies, (CollisionFreeKmerIndex, KmerCounter)):
             raise NotImplementedError("the frequency source must be graph_kmer_index_amd's CollisionFreeKmerIndex or "
                                       "KmerCounter (got %s); the reference's npstructures-backed KmerCounter is not "
@@ -222,10 +263,7 @@ class UniqueVariantKmersFinder:
         default ones, otherwise an upload owned by this finder."""
         if self._dg is not None and self._dg[0] is arrays:
             return self._dg[1]
-        n = arrays.n_nodes
-        base = np.asarray(self._position_id_index.get(np.arange(n), np.zeros(n, dtype=np.int64))).astype(np.int64)
-        dg = DeviceGraph.of(arrays) if np.array_equal(base, arrays.position_id_base()) else \
-            DeviceGraph(arrays, position_base=base)
+        dg = _graph_on_device(arrays, self._position_id_index)
         self._dg = (arrays, dg)
         return dg
 
@@ -280,13 +318,7 @@ class UniqueVariantKmersFinder:
             return DeviceFlatKmers.allocate(0)
         ref, alt = np.ascontiguousarray(ref[active], np.int32), np.ascontiguousarray(alt[active], np.int32)
         lin = LinearReference(arrays, self.graph)
-        chrom = va.chromosomes[active]
-        uniq, inv = np.unique(chrom.astype(str), return_inverse=True) if chrom.dtype == object else \
-            np.unique(chrom, return_inverse=True)
-        first_of = np.zeros(len(uniq), np.int64)
-        first_of[inv[::-1]] = np.arange(len(inv))[::-1]
-        base = np.array([lin.chromosome_offset(chrom[i]) for i in first_of], dtype=np.int64)
-        ref_offsets = np.ascontiguousarray(base[inv] + va.positions[active])
+        ref_offsets = _graph_ref_offsets(lin, va, active)
         dg = self._device_graph(arrays)
         t["host_prepare"] = time.perf_counter() - t0
 
@@ -305,10 +337,7 @@ class UniqueVariantKmersFinder:
                                       d_nodes.ptr, d_offs.ptr, d_var.ptr, _lib.C.byref(bad)))
         sync_time("starts", t1)
         if bad.value >= 0:
-            src = int(active[bad.value])
-            raise ValueError("variant %d (line %d, chromosome %s, POS %d): a start position lies before 0 or past the "
-                             "linear reference (the reference's answer is undefined there)"
-                             % (src, int(va.line_numbers[src]), va.chromosomes[src], int(va.positions[src])))
+            raise _outside_linear_reference(va, int(active[bad.value]))
         self._check_against_obgraph(lin, va, active, ref_offsets, d_nodes, d_offs, P)
         # 2. the forward search over all starts, no store filter
         t2 = time.perf_counter()
@@ -403,3 +432,117 @@ class UniqueVariantKmersFinder:
         self.last_timings["end_to_end"] = time.perf_counter() - t0
         logging.info("N variants with kmers found: %d" % self.last_counts.get("active", 0))
         return flat
+
+    # ------------------------------------------------------------------ simple selection, one variant at a time
+    def find_kmers_over_variant_node(self, variant, node):
+        """unique_variant_kmers.py:66-98: the k-mers of one search for `node` of `variant` (FlatKmers)."""
+        return self.find_kmers_over_variant(variant, node, None)
+
+    def find_kmers_over_variant(self, variant, ref_node, variant_node):
+        """unique_variant_kmers.py:107-111: the search for the ref node, then the one for the variant node (FlatKmers).
+        Nodes are taken as given (the skip of node 0 belongs to the loop over all variants)."""
+        va = VariantArrays([variant.position], np.array([variant.chromosome], dtype=object), [0],
+                           [-1 if getattr(variant, "type", None) is None else int(variant.type == "SNP")])
+        one = variant_node is None
+        d, _ = _simple_selection(self.graph, va, np.array([ref_node], np.int64),
+                                 np.array([ref_node if one else variant_node], np.int64), self.k, self._max_variant_nodes,
+                                 self._position_id_index, n_searches=1 if one else 2, skip_zero_nodes=False)
+        flat = d.to_flat_kmers()
+        d.free()
+        return flat
+
+
+def _simple_selection(graph, va, ref_all, alt_all, k, max_variant_nodes, position_id_index, n_searches=None,
+                      skip_zero_nodes=True):
+    """The batch behind find_kmers_over_variants: (DeviceFlatKmers, facts).  ref_all / alt_all: the nodes of every variant
+    of `va`.  n_searches: only the first so many of the 2 * active searches are run (the one-node call of the finder)."""
+    t, t0 = {}, time.perf_counter()
+    ref, alt = np.asarray(ref_all).astype(np.int64), np.asarray(alt_all).astype(np.int64)
+    active = np.nonzero((ref != 0) & (alt != 0))[0] if skip_zero_nodes else np.arange(len(va))         # :254-255
+    n_var = len(active)
+    assert n_var == 0 or (va.is_snp is not None and not np.any(va.is_snp[active] < 0)), "Variant type must be set"  # :73
+    _lib.require_device()
+    lib = _lib.load()
+    arrays = GraphArrays.from_obgraph(graph)
+    facts = dict(variants=len(va), active=n_var, searches=0, records=0, timings=t)
+    if n_var == 0:
+        return DeviceFlatKmers.allocate(0), facts
+    ref, alt = ref[active], alt[active]
+    outside = np.nonzero((np.minimum(ref, alt) < 0) | (np.maximum(ref, alt) >= arrays.n_nodes))[0]
+    if len(outside):
+        src = int(active[outside[0]])
+        raise ValueError("variant %d (line %d): node %d / %d is not a node of the graph (%d nodes)"
+                         % (src, int(va.line_numbers[src]), int(ref[outside[0]]), int(alt[outside[0]]), arrays.n_nodes))
+    ref, alt = np.ascontiguousarray(ref, np.int32), np.ascontiguousarray(alt, np.int32)
+    is_snp = np.ascontiguousarray(va.is_snp[active] != 0, np.uint8)
+    lin = LinearReference(arrays, graph)
+    ref_offsets = _graph_ref_offsets(lin, va, active)
+    dg = _graph_on_device(arrays, position_id_index)
+    t["host_prepare"] = time.perf_counter() - t0
+    buffers = []
+
+    def keep(b):
+        buffers.append(b)
+        return b
+
+    try:
+        # 1. the start and the target of both searches of every variant
+        t1 = time.perf_counter()
+        h = _lib.DeviceArray.from_host
+        d_lin_start, d_lin_node, d_ro = keep(h(lin.starts)), keep(h(lin.nodes)), keep(h(ref_offsets))
+        d_snp, d_ref, d_alt = keep(h(is_snp)), keep(h(ref)), keep(h(alt))
+        n_pos = 2 * n_var
+        d_nodes, d_offs, d_targets = (keep(_lib.DeviceArray(n_pos, np.int32)) for _ in range(3))
+        bad = _lib._I64(-1)
+        _lib.check(lib.gki_uvk_simple_starts(dg.handle, d_lin_start.ptr, d_lin_node.ptr, len(lin.nodes), d_ro.ptr, d_snp.ptr,
+                                             d_ref.ptr, d_alt.ptr, n_var, d_nodes.ptr, d_offs.ptr, d_targets.ptr,
+                                             _lib.C.byref(bad)))
+        t["starts"] = time.perf_counter() - t1
+        if bad.value >= 0:
+            raise _outside_linear_reference(va, int(active[bad.value]))
+        if n_searches is not None:
+            n_pos = min(n_pos, int(n_searches))
+        # 2. the per-node search: count, then the FlatKmers columns straight from the walk
+        t2 = time.perf_counter()
+        d_rec = keep(_lib.DeviceArray(n_pos + 1, np.int64))
+        n_rec = _lib._I64(0)
+        args = (dg.handle, int(k), int(max_variant_nodes), d_targets.ptr, d_nodes.ptr, d_offs.ptr, n_pos, d_rec.ptr)
+        _lib.check(lib.gki_forward_node_count(*args, _lib.C.byref(n_rec)))
+        t["count"] = time.perf_counter() - t2
+        t3 = time.perf_counter()
+        out = DeviceFlatKmers.allocate(n_rec.value)
+        if n_rec.value:
+            try:
+                _lib.check(lib.gki_forward_node_emit(*args, out.hashes.ptr, out.nodes.ptr, out.ref_offsets.ptr,
+                                                     out.allele_frequencies.ptr))
+            except Exception:
+                out.free()
+                raise
+        t["emit"] = time.perf_counter() - t3
+    finally:
+        for b in buffers:
+            b.free()
+    facts.update(searches=n_pos, records=int(n_rec.value))
+    return out, facts
+
+
+def find_kmers_over_variants_on_device(graph, variant_to_nodes, variants, k=31, max_variant_nodes=6, position_id_index=None):
+    """find_kmers_over_variants with the columns left in HBM: DeviceFlatKmers (uint64, uint32, uint64, float32)."""
+    va = variants if isinstance(variants, VariantArrays) else VariantArrays.from_objects(variants)
+    ref_all, alt_all = np.asarray(variant_to_nodes.ref_nodes), np.asarray(variant_to_nodes.var_nodes)
+    lines = va.line_numbers
+    out, _ = _simple_selection(graph, va, ref_all[lines] if len(va) else np.zeros(0, np.int64),
+                               alt_all[lines] if len(va) else np.zeros(0, np.int64), k, max_variant_nodes, position_id_index)
+    return out
+
+
+def find_kmers_over_variants(graph, variant_to_nodes, variants, k=31, max_variant_nodes=6, position_id_index=None):
+    """What the reference's UniqueVariantKmersFinder(..., use_simple=True).find_unique_kmers() returns
+    (unique_variant_kmers.py:66-111, 241-269): for every variant in order (skipped when its ref or alt node is 0) the
+    k-mers of the search for its ref node, then of the search for its alt node -- FlatKmers, hash / node / position id of
+    the k-mer's end / minimum allele frequency of its path.  position_id_index None: the graph's default position ids
+    (PositionId.from_graph).  One device batch; no frequency source."""
+    d = find_kmers_over_variants_on_device(graph, variant_to_nodes, variants, k, max_variant_nodes, position_id_index)
+    flat = d.to_flat_kmers()
+    d.free()
+    return flat

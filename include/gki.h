@@ -472,6 +472,38 @@ int gki_uvk_emit(gki_graph *g, const void *d_rec_start, int64_t n_var, int n_sta
                  const void *d_hashes, const void *d_start_nodes, const void *d_start_offsets, const void *d_nodes,
                  const void *d_af64, void *d_out_hashes, void *d_out_nodes, void *d_out_ref_offsets, void *d_out_af32);
 
+/* ---------------------------------------------------------------- variant k-mers by simple selection
+ * unique_variant_kmers.py:66-111, 241-269 (use_simple=True, make_unique_variant_kmers -S True): for every variant one
+ * early-stop search for its ref node, then one for its alt node, each with only_store_nodes = only_follow_nodes = {node}.
+ * No frequency index, no choice among start positions.  Steps (graph_kmer_index_amd/unique_variant_kmers.py drives them):
+ * gki_uvk_simple_starts -> gki_forward_node_count -> gki_forward_node_emit.  Search 2 v is variant v's ref node, 2 v + 1
+ * its alt node.
+ *
+ * gki_uvk_simple_starts: d_lin_start / d_lin_node / d_var_ref_offset as for gki_uvk_starts; d_is_snp uint8[n_var] (REF and
+ *   ALT one base long); d_ref_nodes / d_alt_nodes int32[n_var].  Writes int32[2 n_var] each: the start (node, offset) and
+ *   the search's target node.  A SNP's node with bases starts at (node, 0); an indel's node, and a SNP's empty node, at
+ *   the linear-ref position 8 bases before P (0-based chromosome offset P = POS for an indel, POS - 1 for a SNP).
+ *   *first_bad_variant = the lowest variant with such a start before 0 or past the linear path, or with a node outside
+ *   the graph (-1: none); its starts get (0, 0).
+ * gki_forward_node_count / _emit: the early-stop search of gki_forward_* in which start position i follows and stores
+ *   d_targets[i] alone: where a node on the path has the target among its successors only the target is taken and the
+ *   variant limit is waived for that step; a finished k-mer gives one record, of the target, when the target is on its
+ *   path.  Records of start i are [rec_start[i], rec_start[i+1]) in depth-first successor order.  Output = FlatKmers
+ *   columns written by the walk: d_hashes uint64, d_nodes_out uint32, d_position_ids uint64 = position base of the END
+ *   node + END offset (at full width, not through an int16 column), d_af32 float32 = the path's minimum allele frequency.
+ *   Errors, the slow path for deep windows and its arena are those of gki_forward_count / gki_forward_emit
+ *   (GKI_ERR_NOT_ONE_REF_SUCC where the reference asserts, GKI_ERR_WINDOW_TOO_DEEP for the refusals).  The count pass
+ *   leaves no script for the emit pass: the emit pass always walks, so any sequence of calls is answered alike. */
+int gki_uvk_simple_starts(gki_graph *g, const void *d_lin_start, const void *d_lin_node, int64_t n_lin,
+                          const void *d_var_ref_offset, const void *d_is_snp, const void *d_ref_nodes,
+                          const void *d_alt_nodes, int64_t n_var, void *d_nodes, void *d_offsets, void *d_targets,
+                          int64_t *first_bad_variant);
+int gki_forward_node_count(gki_graph *g, int k, int max_variant_nodes, const void *d_targets, const void *d_nodes,
+                           const void *d_offsets, int64_t n_pos, void *d_rec_start, int64_t *n_records);
+int gki_forward_node_emit(gki_graph *g, int k, int max_variant_nodes, const void *d_targets, const void *d_nodes,
+                          const void *d_offsets, int64_t n_pos, const void *d_rec_start, void *d_hashes,
+                          void *d_nodes_out, void *d_position_ids, void *d_af32);
+
 /* ---------------------------------------------------------------- sample_kmers_from_structural_variants
  * structural_variants.py:6-43: extra signature k-mers of big variant nodes.  d_cand_nodes int32[n_cand] are the nodes in
  * visiting order (every (ref, var) pair flattened, ref first; duplicates stay and give their records again).  A candidate
