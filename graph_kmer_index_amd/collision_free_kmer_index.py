@@ -380,16 +380,29 @@ class CounterKmerIndex:
         if self._counts is not None:
             self._counts.zero()
 
-    def count_kmers(self, kmers, update_counter=True):
-        if not update_counter:
-            self.reset()
+    def _device_table(self):
         if self._index is None:                       # constructed from bare arrays: build the table once
             z = np.zeros(len(self.kmers), np.uint64)
             self._index = DeviceIndex.build(DeviceFlatKmers.from_flat_kmers(
                 FlatKmers(np.asarray(self.kmers).astype(np.uint64), np.asarray(self.nodes).astype(np.uint32), z,
                           z.astype(np.float32))), self._modulo, skip_frequencies=True)
-        self._counts = self._index.count_nodes(np.asarray(kmers).astype(np.int64).view(np.uint64), self._n_nodes(),
-                                               max_hits=2 ** 62, counts=self._counts)
+        return self._index
+
+    def count_kmers(self, kmers, update_counter=True):
+        if not update_counter:
+            self.reset()
+        self._counts = self._device_table().count_nodes(np.asarray(kmers).astype(np.int64).view(np.uint64), self._n_nodes(),
+                                                        max_hits=2 ** 62, counts=self._counts)
+
+    def count_reads_file(self, file_name, k, update_counter=True, fmt=None):
+        """`count_kmers` of every k-mer of every read of a FASTA / FASTQ file, forward and reverse complement (what
+        ReadKmers.from_fasta_file yields, read_kmers.py:21-26), parsed and hashed on the device (read_files.py).  No
+        reference counterpart: kmer_mapper does this step next to the reference."""
+        from .read_files import count_nodes_from_file
+        if not update_counter:
+            self.reset()
+        self._counts = count_nodes_from_file(self._device_table(), file_name, k, self._n_nodes(), strands=3,
+                                             max_hits=2 ** 62, counts=self._counts, fmt=fmt)[0]
 
     def get_node_counts(self, min_nodes=0):
         """float64 like np.bincount with weights (:39-40)."""
@@ -552,6 +565,21 @@ class CollisionFreeKmerIndex:
             letters = np.frombuffer(b"".join(enc), dtype=np.uint8)
         counts, _, _ = self._device_index().count_nodes_from_reads(letters, read_start, k, n_nodes,
                                                                    3 if include_reverse_complement else 1, max_hits)
+        out = counts.to_host(n_nodes)
+        counts.free()
+        return out
+
+    def map_reads_file(self, file_name, k, n_nodes=None, max_hits=2 ** 62, include_reverse_complement=True, fmt=None,
+                       chunk_bytes=None):
+        """`map_reads` of the reads of a FASTA / FASTQ file (`.gz` through gzip on the host), which is parsed on the
+        device and streamed in pieces of `chunk_bytes` (read_files.count_nodes_from_file).  n_nodes None: max_node_id() + 1.
+        fmt None: 'fasta' / 'fastq' by the file's first byte."""
+        from . import read_files
+        if n_nodes is None:
+            n_nodes = int(self.max_node_id()) + 1
+        counts = read_files.count_nodes_from_file(
+            self._device_index(), file_name, k, n_nodes, 3 if include_reverse_complement else 1, max_hits, fmt=fmt,
+            chunk_bytes=read_files.DEFAULT_CHUNK_BYTES if chunk_bytes is None else chunk_bytes)[0]
         out = counts.to_host(n_nodes)
         counts.free()
         return out

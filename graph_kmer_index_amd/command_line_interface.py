@@ -15,6 +15,7 @@ collision_free_kmer_index.py:393-402).
     python -m graph_kmer_index_amd.command_line_interface merge_flat_kmers -f variant_kmers.npz,sv_kmers.npz -o all_variant_kmers
     python -m graph_kmer_index_amd.command_line_interface make_reverse -f variant_kmers.npz -o reverse
     python -m graph_kmer_index_amd.command_line_interface make -t 16 -s 1 -k 31 -r True -R ref.fa -n chr1 -G <size> -o linear_kmers
+    python -m graph_kmer_index_amd.command_line_interface map -i index.npz -f reads.fq.gz -k 31 -o node_counts
 
 `-g` takes an obgraph file when obgraph is installed, else a GraphArrays .npz (GraphArrays.to_file).  `index -t N` runs
 one process per GPU (at most N, at most the visible devices), each on its own range of critical-path numbers, and
@@ -308,6 +309,18 @@ def merge_flat_kmers(args):
     logging.info("Wrote merged index to %s" % args.out_file_name)
 
 
+def map_reads_file(args):
+    """Reads file -> the node-count vector a genotyper consumes: the role of `kmer_mapper map` next to the reference (its
+    flags are not reproduced).  The file is parsed, hashed and probed on the device (read_files.py)."""
+    index = CollisionFreeKmerIndex.from_file(args.kmer_index)
+    counts = index.map_reads_file(args.reads, args.kmer_size, args.n_nodes, max_hits=args.max_hits,
+                                  include_reverse_complement=_bool(args.include_reverse_complement), fmt=args.format,
+                                  chunk_bytes=args.chunk_bytes)
+    out = args.out_file_name if args.out_file_name.endswith(".npy") else args.out_file_name + ".npy"
+    np.save(out, counts.astype(np.uint32))
+    logging.info("Wrote %d node counts (%d hits) to %s" % (len(counts), int(counts.sum(dtype=np.int64)), out))
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description="graph_kmer_index on MI355X (in-scope sub-commands)")
     sub = parser.add_subparsers()
@@ -420,6 +433,19 @@ def build_parser():
     p.add_argument("-r", "--reference-kmers", required=True)
     p.add_argument("-o", "--out-file-name", required=True)
     p.set_defaults(func=make_kmer_frequencies)
+    p = sub.add_parser("map")
+    p.add_argument("-i", "--kmer-index", required=True)
+    p.add_argument("-f", "--reads", required=True, help="FASTA or FASTQ, optionally .gz")
+    p.add_argument("-k", "--kmer-size", required=False, type=int, default=31)
+    p.add_argument("-o", "--out-file-name", required=True, help="np.save of the uint32 node counts")
+    p.add_argument("-n", "--n-nodes", required=False, type=int, default=None, help="default: the index's max node id + 1")
+    p.add_argument("-r", "--include-reverse-complement", required=False, type=_bool, default=True)
+    p.add_argument("-m", "--max-hits", required=False, type=int, default=2 ** 62)
+    p.add_argument("-c", "--chunk-bytes", required=False, type=int, default=None)
+    p.add_argument("-F", "--format", required=False, choices=("fasta", "fastq"), default=None,
+                   help="default: by the file's first byte")
+    p.add_argument("-t", "--n-threads", required=False, default=1, type=int)
+    p.set_defaults(func=map_reads_file)
     return parser
 
 

@@ -582,6 +582,32 @@ int gki_probe_reads_count_nodes(gki_probe *p, const void *d_reads, const void *d
                                 int strands, int64_t max_hits, void *d_counts, int64_t n_counts, int64_t *n_kmers,
                                 int64_t *n_hits);
 
+/* ---------------------------------------------------------------- reads files (FASTA / FASTQ text -> the layout above)
+ * The raw ASCII bytes of a reads file in HBM, or of a piece of one that ends at a line end, become what gki_hash_reads and
+ * gki_probe_reads_count_nodes take: the letters of all reads back to back and read_start.  Count, allocate, emit, in the
+ * manner of gki_hash_reads(.., NULL, ..); both calls parse the buffer themselves and nothing is kept between them.
+ *   line    ends at '\n'; the last one may lack it: n_lines = number of '\n' + (n_bytes > 0 and the last byte is not '\n').
+ *   strip   str.strip() of ASCII text, at both ends: 0x09-0x0D, 0x1C-0x1F, 0x20 (so CRLF files work; a lone '\r' inside
+ *           a line is unsupported input).
+ *   FASTA   read_kmers.py:18-25: a line whose first raw byte is '>' is a header, every other line, stripped, is one read
+ *           (a multi-line record is several reads; " >x" is a read).
+ *   FASTQ   by position only (quality lines may begin with '>' or '@'): with g = (line_phase + the line's number in the
+ *           buffer) % 4, line g == 1 is a read; *n_bad_lines counts the lines g == 0 that do not begin with '@' and the
+ *           lines g == 2 that do not begin with '+'.  line_phase = lines before this buffer, mod 4 (0..3; ignored for
+ *           FASTA), so that a file may be cut after any '\n'.
+ *   reads   read r is the r-th such line; one that is empty after the strip is a read of length 0.  Letters are copied
+ *           unchanged: case, N and the rest are the hash kernels' business.
+ * d_bytes uint8[n_bytes] (any alignment; 16-byte aligned buffers take the fast loads), d_letters uint8[letters_capacity],
+ * d_read_start int64[read_start_capacity]; the emit call writes *n_letters letters and *n_reads + 1 offsets and returns
+ * GKI_ERR_BAD_ARG, writing nothing, when either capacity is too small.  GKI_ERR_BAD_ARG also for another format or phase
+ * and for a single read of 2^32 letters or more; every total is 64-bit and a line may be of any length below that. */
+#define GKI_READS_FASTA 0
+#define GKI_READS_FASTQ 1
+int gki_reads_parse_count(const void *d_bytes, int64_t n_bytes, int format, int line_phase, int64_t *n_lines,
+                          int64_t *n_reads, int64_t *n_letters, int64_t *n_bad_lines);
+int gki_reads_parse_emit(const void *d_bytes, int64_t n_bytes, int format, int line_phase, void *d_letters,
+                         int64_t letters_capacity, void *d_read_start, int64_t read_start_capacity);
+
 /* Measurement aid: independent random 8-byte loads per second the device sustains from a table of table_bytes (every
  * load that misses L2 is one 64-byte request -- the unit the probe kernels are bound by, not bytes).  Runs n_loads loads
  * twice and reports the second launch.  bench.py reports the read-side rate as a fraction of this. */
