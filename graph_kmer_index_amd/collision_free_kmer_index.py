@@ -570,16 +570,17 @@ class CollisionFreeKmerIndex:
         return out
 
     def map_reads_file(self, file_name, k, n_nodes=None, max_hits=2 ** 62, include_reverse_complement=True, fmt=None,
-                       chunk_bytes=None):
-        """`map_reads` of the reads of a FASTA / FASTQ file (`.gz` through gzip on the host), which is parsed on the
-        device and streamed in pieces of `chunk_bytes` (read_files.count_nodes_from_file).  n_nodes None: max_node_id() + 1.
-        fmt None: 'fasta' / 'fastq' by the file's first byte."""
+                       chunk_bytes=None, inflate="auto"):
+        """`map_reads` of the reads of a FASTA / FASTQ file, which is parsed on the device and streamed in pieces of
+        `chunk_bytes` (read_files.count_nodes_from_file).  `.gz`: a BGZF file is inflated on the device, any other gzip on
+        the host; inflate 'host' / 'device' forces either.  n_nodes None: max_node_id() + 1.
+        fmt None: 'fasta' / 'fastq' by the first byte of the text."""
         from . import read_files
         if n_nodes is None:
             n_nodes = int(self.max_node_id()) + 1
         counts = read_files.count_nodes_from_file(
             self._device_index(), file_name, k, n_nodes, 3 if include_reverse_complement else 1, max_hits, fmt=fmt,
-            chunk_bytes=read_files.DEFAULT_CHUNK_BYTES if chunk_bytes is None else chunk_bytes)[0]
+            chunk_bytes=read_files.DEFAULT_CHUNK_BYTES if chunk_bytes is None else chunk_bytes, inflate=inflate)[0]
         out = counts.to_host(n_nodes)
         counts.free()
         return out

@@ -315,7 +315,7 @@ def map_reads_file(args):
     index = CollisionFreeKmerIndex.from_file(args.kmer_index)
     counts = index.map_reads_file(args.reads, args.kmer_size, args.n_nodes, max_hits=args.max_hits,
                                   include_reverse_complement=_bool(args.include_reverse_complement), fmt=args.format,
-                                  chunk_bytes=args.chunk_bytes)
+                                  chunk_bytes=args.chunk_bytes, inflate=args.inflate)
     out = args.out_file_name if args.out_file_name.endswith(".npy") else args.out_file_name + ".npy"
     np.save(out, counts.astype(np.uint32))
     logging.info("Wrote %d node counts (%d hits) to %s" % (len(counts), int(counts.sum(dtype=np.int64)), out))
@@ -435,7 +435,7 @@ def build_parser():
     p.set_defaults(func=make_kmer_frequencies)
     p = sub.add_parser("map")
     p.add_argument("-i", "--kmer-index", required=True)
-    p.add_argument("-f", "--reads", required=True, help="FASTA or FASTQ, optionally .gz")
+    p.add_argument("-f", "--reads", required=True, help="FASTA or FASTQ, optionally .gz (gzip or BGZF)")
     p.add_argument("-k", "--kmer-size", required=False, type=int, default=31)
     p.add_argument("-o", "--out-file-name", required=True, help="np.save of the uint32 node counts")
     p.add_argument("-n", "--n-nodes", required=False, type=int, default=None, help="default: the index's max node id + 1")
@@ -444,6 +444,9 @@ def build_parser():
     p.add_argument("-c", "--chunk-bytes", required=False, type=int, default=None)
     p.add_argument("-F", "--format", required=False, choices=("fasta", "fastq"), default=None,
                    help="default: by the file's first byte")
+    p.add_argument("--inflate", required=False, choices=("auto", "host", "device"), default="auto",
+                   help="where a .gz file is inflated: auto = BGZF on the device, other gzip on the host; device refuses a "
+                        "file that is not BGZF")
     p.add_argument("-t", "--n-threads", required=False, default=1, type=int)
     p.set_defaults(func=map_reads_file)
     return parser

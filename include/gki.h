@@ -38,6 +38,8 @@ extern "C" {
 #define GKI_ERR_OUT_OF_DOMAIN 8  /* gki_index_build_range_from_rows: the records lie outside the row-carrying build's domain (a
                                      group of neighbouring buckets with more than 2^22 records); build that slice from its
                                      columns (gki_index_build_range hands it to the pair-sorting form) */
+#define GKI_ERR_INFLATE 9        /* gki_bgzf_inflate: a block's DEFLATE stream is malformed, or its output is not of the size or
+                                     the CRC-32 its member states; first_bad_block / first_bad_status say which and how */
 
 #define GKI_MAX_WINDOW_NODES 48        /* stacks of the product kernels (scratch) */
 #define GKI_MAX_DEEP_WINDOW_NODES 12288 /* stacks of the slow path (a global-memory arena, grown 192, 384, ... levels): beyond
@@ -607,6 +609,33 @@ int gki_reads_parse_count(const void *d_bytes, int64_t n_bytes, int format, int 
                           int64_t *n_reads, int64_t *n_letters, int64_t *n_bad_lines);
 int gki_reads_parse_emit(const void *d_bytes, int64_t n_bytes, int format, int line_phase, void *d_letters,
                          int64_t letters_capacity, void *d_read_start, int64_t read_start_capacity);
+
+/* ---------------------------------------------------------------- BGZF (blocked gzip: the .gz reads files of bgzip / htslib)
+ * A BGZF file is a chain of gzip members of at most 64 KiB, each with its compressed size in a 'BC' extra subfield, so
+ * every member's raw DEFLATE payload, CRC-32 and ISIZE are found without inflating anything (graph_kmer_index_amd/bgzf.py
+ * does that on the host).  gki_bgzf_inflate inflates n_blocks payloads of one device buffer side by side: block b reads
+ * d_in[payload_start[b], payload_start[b] + payload_len[b]) and writes d_out[out_start[b], out_start[b + 1]), whose length
+ * is the member's ISIZE, then compares the CRC-32 of what it wrote with crc32[b].  No dictionary: a distance reaches no
+ * further back than the block's own output.
+ *   d_payload_start int64[n_blocks], d_payload_len int32[n_blocks], d_crc32 uint32[n_blocks], d_out_start int64[n_blocks + 1],
+ *   all in HBM.  GKI_ERR_BAD_ARG, before anything is inflated, unless every payload lies inside n_in, out_start is
+ *   non-decreasing from >= 0 to <= out_capacity and no block's output exceeds 65 536 bytes.  n_blocks == 0 does nothing.
+ *   GKI_ERR_INFLATE when a block fails: *first_bad_block is the lowest such block and *first_bad_status why (-1 and 0
+ *   otherwise); every other block's output is written all the same.  The status values (csrc/gki_inflate_core.h):
+ *     1 the input ends inside the stream      2 block type 3                     3 stored LEN / NLEN mismatch
+ *     4 invalid code lengths (over-subscribed, incomplete, too many, a repeat past the end, no end-of-block code)
+ *     5 repeat code 16 first                  6 literal/length symbol 286, 287   7 distance symbol 30, 31
+ *     8 distance before the block's start     9 more output than ISIZE           10 less output than ISIZE
+ *     11 input bytes behind the final block   12 CRC-32 mismatch                 13 bits that are no code of the set
+ * gki_bgzf_inflate_kernel_ms: the device time of the inflate kernel alone in the calling thread's last gki_bgzf_inflate
+ * (events around the one launch; 0 when that call launched nothing), for tools/bench_read_files.py.
+ * gki_last_byte_position: *position = the greatest p with d_bytes[p] == value (0..255), -1 when there is none -- where
+ * the streaming route cuts a piece of inflated text behind its last line end, without copying the text to the host. */
+int gki_bgzf_inflate(const void *d_in, int64_t n_in, const void *d_payload_start, const void *d_payload_len,
+                     const void *d_crc32, const void *d_out_start, int64_t n_blocks, void *d_out, int64_t out_capacity,
+                     int64_t *first_bad_block, int *first_bad_status);
+int gki_bgzf_inflate_kernel_ms(float *ms);
+int gki_last_byte_position(const void *d_bytes, int64_t n_bytes, int value, int64_t *position);
 
 /* Measurement aid: independent random 8-byte loads per second the device sustains from a table of table_bytes (every
  * load that misses L2 is one 64-byte request -- the unit the probe kernels are bound by, not bytes).  Runs n_loads loads

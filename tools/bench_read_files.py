@@ -12,12 +12,19 @@ temporary directory as a FASTA and as a FASTQ file (fixed-width names, constant 
                                   parse emit, probe.  One warm-up pass, then --reps passes; the median is reported.
   (c) device_copy_of_file_bytes   a device-to-device copy of every piece's bytes, in the same passes: the byte-bound
                                   floor of the parse kernels.
-All three routes' counts are checked equal.  Prints one JSON object and a few summary lines."""
-import argparse, ctypes as C, json, os, statistics, sys, tempfile, time
+  (d) bgzf                        the same two files written once as BGZF (bgzf.write_bgzf, level 6): compressed size, the
+                                  host route (Python's gzip, which reads BGZF as multi-member gzip: what a .gz file took
+                                  before the device inflate) and the device route end to end, and the device route with a
+                                  clock around each stage: file read with the member scan (and, beside it, the scan alone over
+                                  the same pieces), upload, inflate (the whole inflate_on_device call, and the inflate
+                                  kernel's own device time from gki_bgzf_inflate_kernel_ms with GB/s of its output), line
+                                  cut, parse, probe.
+All routes' counts are checked equal.  Prints one JSON object and a few summary lines."""
+import argparse, ctypes as C, json, mmap, os, statistics, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
-from graph_kmer_index_amd import _lib, DenseKmerFinder, CriticalGraphPaths, read_files
+from graph_kmer_index_amd import _lib, DenseKmerFinder, CriticalGraphPaths, bgzf, read_files
 from graph_kmer_index_amd.flat_kmers import DeviceFlatKmers
 from graph_kmer_index_amd.collision_free_kmer_index import DeviceIndex
 from graph_kmer_index_amd.graph import synthetic_snp_graph, synthetic_haplotype_sequence
@@ -116,6 +123,76 @@ def staged_file_route(idx, path, k, n_nodes, max_hits, chunk_bytes):
     return out, st
 
 
+def staged_bgzf_route(idx, path, k, n_nodes, max_hits, chunk_bytes):
+    """read_files._count_nodes_from_bgzf's loop with a clock around each stage."""
+    lib = _lib.load()
+    sync = lambda: _lib.check(lib.gki_device_synchronize())
+    st = dict(file_read_s=0.0, member_scan_s=0.0, upload_s=0.0, inflate_s=0.0, inflate_kernel_s=0.0, line_cut_s=0.0, parse_s=0.0,
+              probe_s=0.0)
+    counts = _lib.DeviceArray(n_nodes, np.uint32); counts.zero()
+    code, phase, n_reads, n_out, tail = None, 0, 0, 0, None
+    kernel_ms = C.c_float(0)
+
+    def parse_and_probe(d, n):
+        nonlocal phase, n_reads
+        t = time.perf_counter()
+        letters, read_start, reads, lines, bad = read_files._parse(d, n, code, phase); sync()
+        st["parse_s"] += time.perf_counter() - t
+        assert bad == 0
+        t = time.perf_counter()
+        idx.count_nodes_from_reads(letters, read_start, k, n_nodes, 3, max_hits, counts); sync()
+        st["probe_s"] += time.perf_counter() - t
+        letters.free(); read_start.free()
+        n_reads += reads
+        phase = (phase + lines) % 4
+
+    t_all = time.perf_counter()
+    with open(path, "rb") as f:
+        pieces = read_files.iter_bgzf_pieces(f, chunk_bytes, path)
+        while True:
+            t = time.perf_counter()
+            item = next(pieces, None)
+            st["file_read_s"] += time.perf_counter() - t
+            if item is None:
+                break
+            piece, members, _ = item
+            t = time.perf_counter()
+            assert len(bgzf.scan_all(piece)[0]) == len(members)                # the scan again, alone: its share of file_read_s
+            st["member_scan_s"] += time.perf_counter() - t
+            t = time.perf_counter()
+            d = _lib.DeviceArray.from_host(np.frombuffer(piece, dtype=np.uint8)); sync()
+            st["upload_s"] += time.perf_counter() - t
+            prefix = tail.n if tail is not None else 0
+            t = time.perf_counter()
+            text = bgzf.inflate_on_device(d, members, prefix); sync()
+            st["inflate_s"] += time.perf_counter() - t
+            _lib.check(lib.gki_bgzf_inflate_kernel_ms(C.byref(kernel_ms)))
+            st["inflate_kernel_s"] += kernel_ms.value * 1e-3
+            d.free()
+            n_out += text.n - prefix
+            if prefix:
+                _lib.check(lib.gki_memcpy_d2d(text.ptr, tail.ptr, prefix)); tail.free()
+            tail = None
+            if code is None:
+                code = read_files.FORMATS[read_files.detect_format(text.to_host(1))]
+            t = time.perf_counter()
+            cut = read_files._last_newline(text, text.n) + 1
+            st["line_cut_s"] += time.perf_counter() - t
+            if cut:
+                parse_and_probe(text, cut)
+            if cut < text.n:
+                tail = _lib.DeviceArray(text.n - cut, np.uint8)
+                _lib.check(lib.gki_memcpy_d2d(tail.ptr, text.ptr.value + cut, text.n - cut))
+            text.free()
+    if tail is not None:
+        parse_and_probe(tail, tail.n); tail.free()
+    st["s"] = time.perf_counter() - t_all - st["member_scan_s"]
+    st["reads"], st["inflated_bytes"] = n_reads, n_out
+    out = counts.to_host(n_nodes)
+    counts.free()
+    return out, st
+
+
 def median_of(runs):
     return {key: statistics.median(r[key] for r in runs) for key in runs[0]}
 
@@ -186,6 +263,36 @@ def main():
                       "parse_over_device_copy": parse / m["device_copy_s"], "parse_over_probe": parse / m["probe_s"],
                       "parse_bytes_per_s": m["file_bytes"] / parse, "device_copy_bytes_per_s": 2 * m["file_bytes"] / m["device_copy_s"]})
             res["map_reads_file_" + name] = m
+        for name, path in (("fasta", fa), ("fastq", fq)):
+            packed = path + ".gz"
+            t = time.perf_counter()
+            with open(path, "rb") as fh, mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) as text:
+                bgzf.write_bgzf(packed, text, level=6, threads=16)
+            row = {"write_bgzf_s": time.perf_counter() - t, "compressed_bytes": os.path.getsize(packed)}
+            assert read_files.reads_file_route(packed) == "bgzf-device"
+            runs, host, device = [], [], []
+            for rep in range(args.reps + 1):                               # the same order as above: warm-up, then reps
+                for route, times in (("host", host), ("device", device)):
+                    t = time.perf_counter()
+                    counts, reads, _, _ = read_files.count_nodes_from_file(idx, packed, k, n_nodes, 3, mh,
+                                                                           chunk_bytes=args.chunk_bytes, inflate=route)
+                    _lib.check(lib.gki_device_synchronize())
+                    dt = time.perf_counter() - t
+                    same["bgzf_%s_%s" % (name, route)] = bool(np.array_equal(counts.to_host(n_nodes), want)) and reads == n_reads
+                    counts.free()
+                    if rep:
+                        times.append(dt)
+                got, st = staged_bgzf_route(idx, packed, k, n_nodes, mh, args.chunk_bytes)
+                same["bgzf_%s_staged" % name] = bool(np.array_equal(got, want))
+                if rep:
+                    runs.append(st)
+            m = median_of(runs)
+            h, d = statistics.median(host), statistics.median(device)
+            m.update(row)
+            m.update({"host_gzip_end_to_end_s": h, "host_gzip_all_s": host, "host_gzip_reads_per_s": n_reads / h,
+                      "device_end_to_end_s": d, "device_all_s": device, "device_reads_per_s": n_reads / d,
+                      "device_over_host_speedup": h / d, "inflate_output_bytes_per_s": m["inflated_bytes"] / m["inflate_kernel_s"]})
+            res["bgzf_" + name] = m
         res["counts_equal"] = same
     print(json.dumps(res))
     a = res["host_lines_then_map_reads"]
@@ -198,6 +305,14 @@ def main():
                                 m["parse_count_s"], m["parse_emit_s"], m["probe_s"]))
         print("(c) device copy of the %s bytes: %.4f s; parse = %.1f x the copy, %.2f x the probe"
               % (name.upper(), m["device_copy_s"], m["parse_over_device_copy"], m["parse_over_probe"]))
+    for name in ("fasta", "fastq"):
+        m = res["bgzf_" + name]
+        print("(d) BGZF %s: %.0f MB compressed; host gzip %.3f s = %.3g reads/s; device %.3f s = %.3g reads/s (%.2f x); file read "
+              "%.3f (member scan alone %.3f), upload %.3f, inflate call %.3f (kernel %.3f = %.2f GB/s out), line cut %.3f, "
+              "parse %.3f, probe %.3f s"
+              % (name.upper(), m["compressed_bytes"] / 1e6, m["host_gzip_end_to_end_s"], m["host_gzip_reads_per_s"],
+                 m["device_end_to_end_s"], m["device_reads_per_s"], m["device_over_host_speedup"], m["file_read_s"], m["member_scan_s"],
+                 m["upload_s"], m["inflate_s"], m["inflate_kernel_s"], m["inflate_output_bytes_per_s"] / 1e9, m["line_cut_s"], m["parse_s"], m["probe_s"]))
     print("counts equal: %s" % same)
     return 0 if all(same.values()) else 1
 
