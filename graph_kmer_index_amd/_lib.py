@@ -288,3 +288,44 @@ class DeviceView(DeviceArray):
 
     def free(self):
         self.ptr = None
+
+
+class DeviceScope:
+    """The owner of a block's device temporaries (what DevBuf is to the C++ host code): whatever is made through the
+    scope or handed to `keep` is freed when the `with` block is left, however it is left, last made first.  Freeing
+    something early is a plain `.free()` on it (the scope's own free is then a no-op)."""
+
+    def __init__(self):
+        self._owned = []
+
+    def __enter__(self):
+        return self
+
+    def keep(self, obj):
+        """Own `obj` (anything with a free()); returns it."""
+        self._owned.append(obj)
+        return obj
+
+    def array(self, n, dtype):
+        return self.keep(DeviceArray(n, dtype))
+
+    def on_device(self, a, dtype):
+        """A DeviceArray is returned as it is and stays its owner's; anything else is uploaded as `dtype` and owned."""
+        if isinstance(a, DeviceArray):
+            return a
+        return self.keep(DeviceArray.from_host(np.asarray(a).astype(dtype, copy=False)))
+
+    def release(self, obj):
+        """Take `obj` out of the scope and return it: the caller owns it from here."""
+        self._owned = [o for o in self._owned if o is not obj]
+        return obj
+
+    def __exit__(self, exc_type, exc, tb):
+        failed = None
+        while self._owned:
+            try:
+                self._owned.pop().free()
+            except Exception as e:                   # the others still go back
+                failed = failed or e
+        if failed is not None and exc_type is None:
+            raise failed

@@ -3,7 +3,9 @@ size in a 'BC' extra subfield.  The host walks the member headers (a few bytes p
 the device inflates all members of a piece side by side (gki_bgzf_inflate, csrc/gki_inflate.hip).
 
 A plain gzip file -- one member, or several without the 'BC' subfield -- is one serial DEFLATE stream per member and is
-not BGZF: `is_bgzf` says no and the reads-file route keeps it on the host (read_files.py)."""
+not BGZF: `is_bgzf` says no and the reads-file route keeps it on the host (read_files.py).
+
+`inflate_on_device` is one piece's inflate; read_files.bgzf_text_pieces streams a file through it."""
 import ctypes as C
 import struct
 import zlib
@@ -156,41 +158,21 @@ def inflate_on_device(buf, members, prefix=0):
     np.cumsum(cols[:, 3], out=out_start[1:])
     out_start[1:] += prefix
     total = int(out_start[n])
-    if isinstance(buf, _lib.DeviceArray) and buf.dtype.itemsize != 1:
-        raise ValueError("a device buffer of bytes is uint8")
-    out = _byte_array(total)
-    if n == 0:
-        return out
-    owned = []                                    # everything on the device that this call frees, whatever happens
-    try:
-        if isinstance(buf, _lib.DeviceArray):
-            d_in, n_in = buf, buf.n
-        else:
-            a = np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf, dtype=np.uint8)
-            n_in = a.size
-            d_in = _lib.DeviceArray.from_host(a if a.size else np.zeros(1, np.uint8))
-            owned.append(d_in)
-        for col, dtype in ((cols[:, 0], np.int64), (cols[:, 1], np.int32), (cols[:, 2], np.uint32), (out_start, np.int64)):
-            owned.append(_lib.DeviceArray.from_host(col.astype(dtype)))
-        bad, status = C.c_int64(-1), C.c_int(0)
-        rc = _lib.load().gki_bgzf_inflate(d_in.ptr, n_in, owned[-4].ptr, owned[-3].ptr, owned[-2].ptr, owned[-1].ptr, n,
-                                          out.ptr, total, C.byref(bad), C.byref(status))
-        if rc == GKI_ERR_INFLATE:
-            raise BgzfInflateError(bad.value, status.value, out)
-        _lib.check(rc)
-    except BgzfInflateError:
-        raise                                     # the output travels with the error
-    except BaseException:
-        out.free()
-        raise
-    finally:
-        for d in owned:
-            d.free()
-    return out
-
-
-def _byte_array(n):
-    """A uint8 DeviceArray of n bytes; one of no bytes still owns an allocation (of one byte), so that it has a pointer."""
-    a = _lib.DeviceArray(max(n, 1), np.uint8)
-    a.n = n
-    return a
+    if isinstance(buf, _lib.DeviceArray):
+        if buf.dtype.itemsize != 1:
+            raise ValueError("a device buffer of bytes is uint8")
+    elif not isinstance(buf, np.ndarray):
+        buf = np.frombuffer(buf, dtype=np.uint8)
+    with _lib.DeviceScope() as s:
+        out = s.array(total, np.uint8)
+        if n:
+            d_in = s.on_device(buf, np.uint8)
+            d_cols = [s.on_device(col, dtype) for col, dtype in ((cols[:, 0], np.int64), (cols[:, 1], np.int32),
+                                                                 (cols[:, 2], np.uint32), (out_start, np.int64))]
+            bad, status = C.c_int64(-1), C.c_int(0)
+            rc = _lib.load().gki_bgzf_inflate(d_in.ptr, d_in.n, *[d.ptr for d in d_cols], n, out.ptr, total, C.byref(bad),
+                                              C.byref(status))
+            if rc == GKI_ERR_INFLATE:
+                raise BgzfInflateError(bad.value, status.value, s.release(out))     # the output travels with the error
+            _lib.check(rc)
+        return s.release(out)

@@ -45,24 +45,25 @@ class DeviceIndex:
         n = dflat.n
         na = max(n, 1)
         nb = int(modulo if n_buckets is None else n_buckets)
-        out = cls(n, modulo, _lib.DeviceArray(nb, np.int32), _lib.DeviceArray(nb, np.uint32),
-                  _lib.DeviceArray(na, np.uint64), _lib.DeviceArray(na, np.uint32), _lib.DeviceArray(na, np.uint64),
-                  _lib.DeviceArray(na, np.float32), _lib.DeviceArray(na, np.uint16), bucket_begin, nb)
-        perm = _lib.DeviceArray(na, np.uint32) if want_permutation else None
-        out.permutation = perm
-        head = (dflat.hashes.ptr, dflat.nodes.ptr, dflat.ref_offsets.ptr, dflat.allele_frequencies.ptr, n, int(modulo),
-                int(bucket_begin), nb, int(bool(skip_frequencies)))
-        tail = (out.hashes_to_index.ptr, out.n_kmers.ptr, out.kmers.ptr, out.nodes.ptr, out.ref_offsets.ptr,
-                out.allele_frequencies.ptr, out.frequencies.ptr, None if perm is None else perm.ptr)
-        if group_start is not None and not pairs_form:
-            group_bits = (len(group_start) - 1).bit_length() - 1
-            assert len(group_start) == (1 << group_bits) + 1
-            bounds = (C.c_int64 * len(group_start))(*[int(x) for x in group_start])
-            _lib.check(_lib.load().gki_index_build_range_grouped(*head, group_bits, bounds, *tail))
-        else:
-            fn = _lib.load().gki_index_build_pairs if pairs_form else _lib.load().gki_index_build_range
-            _lib.check(fn(*head, *tail))
-        return out
+        with _lib.DeviceScope() as s:
+            out = s.keep(cls(n, modulo, _lib.DeviceArray(nb, np.int32), _lib.DeviceArray(nb, np.uint32),
+                             _lib.DeviceArray(na, np.uint64), _lib.DeviceArray(na, np.uint32), _lib.DeviceArray(na, np.uint64),
+                             _lib.DeviceArray(na, np.float32), _lib.DeviceArray(na, np.uint16), bucket_begin, nb))
+            perm = s.array(na, np.uint32) if want_permutation else None
+            head = (dflat.hashes.ptr, dflat.nodes.ptr, dflat.ref_offsets.ptr, dflat.allele_frequencies.ptr, n, int(modulo),
+                    int(bucket_begin), nb, int(bool(skip_frequencies)))
+            tail = (out.hashes_to_index.ptr, out.n_kmers.ptr, out.kmers.ptr, out.nodes.ptr, out.ref_offsets.ptr,
+                    out.allele_frequencies.ptr, out.frequencies.ptr, None if perm is None else perm.ptr)
+            if group_start is not None and not pairs_form:
+                group_bits = (len(group_start) - 1).bit_length() - 1
+                assert len(group_start) == (1 << group_bits) + 1
+                bounds = (C.c_int64 * len(group_start))(*[int(x) for x in group_start])
+                _lib.check(_lib.load().gki_index_build_range_grouped(*head, group_bits, bounds, *tail))
+            else:
+                fn = _lib.load().gki_index_build_pairs if pairs_form else _lib.load().gki_index_build_range
+                _lib.check(fn(*head, *tail))
+            out.permutation = s.release(perm)
+            return s.release(out)
 
     @classmethod
     def build_from_rows(cls, rows, keys, n, modulo, skip_frequencies=False, bucket_begin=0, n_buckets=None, group_start=None):
@@ -70,49 +71,47 @@ class DeviceIndex:
         _lib.require_device()
         na = max(n, 1)
         nb = int(modulo if n_buckets is None else n_buckets)
-        out = cls(n, modulo, _lib.DeviceArray(nb, np.int32), _lib.DeviceArray(nb, np.uint32),
-                  _lib.DeviceArray(na, np.uint64), _lib.DeviceArray(na, np.uint32), _lib.DeviceArray(na, np.uint64),
-                  _lib.DeviceArray(na, np.float32), _lib.DeviceArray(na, np.uint16), bucket_begin, nb)
         group_bits, bounds = 0, None
         if group_start is not None:
             group_bits = (len(group_start) - 1).bit_length() - 1
             assert len(group_start) == (1 << group_bits) + 1
             bounds = (C.c_int64 * len(group_start))(*[int(x) for x in group_start])
-        _lib.check(_lib.load().gki_index_build_range_from_rows(
-            rows.ptr, keys.ptr, int(n), int(modulo), int(bucket_begin), nb, int(bool(skip_frequencies)), group_bits, bounds,
-            out.hashes_to_index.ptr, out.n_kmers.ptr, out.kmers.ptr, out.nodes.ptr, out.ref_offsets.ptr,
-            out.allele_frequencies.ptr, out.frequencies.ptr))
-        return out
+        with _lib.DeviceScope() as s:
+            out = s.keep(cls(n, modulo, _lib.DeviceArray(nb, np.int32), _lib.DeviceArray(nb, np.uint32),
+                             _lib.DeviceArray(na, np.uint64), _lib.DeviceArray(na, np.uint32), _lib.DeviceArray(na, np.uint64),
+                             _lib.DeviceArray(na, np.float32), _lib.DeviceArray(na, np.uint16), bucket_begin, nb))
+            _lib.check(_lib.load().gki_index_build_range_from_rows(
+                rows.ptr, keys.ptr, int(n), int(modulo), int(bucket_begin), nb, int(bool(skip_frequencies)), group_bits,
+                bounds, out.hashes_to_index.ptr, out.n_kmers.ptr, out.kmers.ptr, out.nodes.ptr, out.ref_offsets.ptr,
+                out.allele_frequencies.ptr, out.frequencies.ptr))
+            return s.release(out)
 
     def lookup_positions(self, queries, max_hits=10, use_probe_table=True):
         """Batched CollisionFreeKmerIndex.get: (hit_start int64[q+1], position int64[hits] into the payload
         arrays, query index int64[hits]) as NumPy arrays.  use_probe_table=False probes the reference-layout arrays
         (gki_index_lookup_*) instead of the probe table (gki_probe_lookup_*)."""
         lib = _lib.load()
-        q = np.ascontiguousarray(np.asarray(queries)).astype(np.uint64)
-        nq = len(q)
-        dq = _lib.DeviceArray.from_host(q if nq else np.zeros(1, np.uint64))
-        hs = _lib.DeviceArray(nq + 1, np.int64)
         n_hits = C.c_int64(0)
         mh = int(min(max_hits, 2 ** 62))
-        if use_probe_table:
-            table = self.probe_table()
-            _lib.check(lib.gki_probe_lookup_count(table, dq.ptr, nq, mh, hs.ptr, C.byref(n_hits)))
-        else:
-            view = self.view()
-            _lib.check(lib.gki_index_lookup_count(C.byref(view), dq.ptr, nq, mh, hs.ptr, C.byref(n_hits)))
-        m = n_hits.value
-        pos, qi = _lib.DeviceArray(max(m, 1), np.int64), _lib.DeviceArray(max(m, 1), np.int64)
-        if m:
+        with _lib.DeviceScope() as s:
+            dq = s.on_device(queries, np.uint64)
+            nq = dq.n
+            hs = s.array(nq + 1, np.int64)
             if use_probe_table:
-                _lib.check(lib.gki_probe_lookup_emit(table, dq.ptr, nq, mh, hs.ptr, qi.ptr, pos.ptr))
+                table = self.probe_table()
+                _lib.check(lib.gki_probe_lookup_count(table, dq.ptr, nq, mh, hs.ptr, C.byref(n_hits)))
             else:
-                _lib.check(lib.gki_index_lookup_emit(C.byref(view), dq.ptr, nq, mh, hs.ptr, None, None, qi.ptr, None, None,
-                                                     pos.ptr))
-        out = (hs.to_host(), pos.to_host(m), qi.to_host(m))
-        for b in (dq, hs, pos, qi):
-            b.free()
-        return out
+                view = self.view()
+                _lib.check(lib.gki_index_lookup_count(C.byref(view), dq.ptr, nq, mh, hs.ptr, C.byref(n_hits)))
+            m = n_hits.value
+            pos, qi = s.array(m, np.int64), s.array(m, np.int64)
+            if m:
+                if use_probe_table:
+                    _lib.check(lib.gki_probe_lookup_emit(table, dq.ptr, nq, mh, hs.ptr, qi.ptr, pos.ptr))
+                else:
+                    _lib.check(lib.gki_index_lookup_emit(C.byref(view), dq.ptr, nq, mh, hs.ptr, None, None, qi.ptr, None,
+                                                         None, pos.ptr))
+            return hs.to_host(), pos.to_host(), qi.to_host()
 
     def get_small(self, queries, max_hits=10, capacity=1024):
         """CollisionFreeKmerIndex.get for up to 64 k-mers in one launch (gki_index_get_small): per query (number of
@@ -137,64 +136,44 @@ class DeviceIndex:
     def contains(self, queries):
         """`kmer in index` for every query (gki_probe_contains).  queries: NumPy array or DeviceArray of uint64.
         Returns a DeviceArray uint8[q] of 0 / 1."""
-        own = not isinstance(queries, _lib.DeviceArray)
-        dq = _lib.DeviceArray.from_host(np.ascontiguousarray(np.asarray(queries)).astype(np.uint64)) if own else queries
-        flags = _lib.DeviceArray(max(dq.n, 1), np.uint8)
-        _lib.check(_lib.load().gki_probe_contains(self.probe_table(), dq.ptr, dq.n, flags.ptr))
-        flags.n = dq.n
-        if own:
-            dq.free()
-        return flags
+        with _lib.DeviceScope() as s:
+            dq = s.on_device(queries, np.uint64)
+            flags = s.array(dq.n, np.uint8)
+            _lib.check(_lib.load().gki_probe_contains(self.probe_table(), dq.ptr, dq.n, flags.ptr))
+            return s.release(flags)
 
     def count_nodes(self, queries, n_nodes, max_hits=10, counts=None, use_probe_table=True, return_hits=False):
         """Fused probe + node histogram.  queries: NumPy array or DeviceArray of uint64.  Returns a DeviceArray
         uint32[n_nodes] (accumulates into `counts` when given).  use_probe_table=False probes the reference-layout
         arrays directly (gki_index_count_nodes) instead of the probe table (gki_probe_count_nodes)."""
         lib = _lib.load()
-        if counts is None:
-            counts = _lib.DeviceArray(max(int(n_nodes), 1), np.uint32)
-            counts.zero()
-        own = not isinstance(queries, _lib.DeviceArray)
-        dq = _lib.DeviceArray.from_host(np.ascontiguousarray(np.asarray(queries)).astype(np.uint64)) if own else queries
         mh = int(min(max_hits, 2 ** 62))
         n_hits = C.c_int64(-1)
-        if use_probe_table:
-            _lib.check(lib.gki_probe_count_nodes(self.probe_table(), dq.ptr, dq.n, mh, counts.ptr, int(n_nodes),
-                                                 C.byref(n_hits)))
-        else:
-            view = self.view()
-            _lib.check(lib.gki_index_count_nodes(C.byref(view), dq.ptr, dq.n, mh, counts.ptr, int(n_nodes)))
-        if own:
-            dq.free()
+        with _lib.DeviceScope() as s:
+            counts = zeroed_counts(s, n_nodes) if counts is None else counts
+            dq = s.on_device(queries, np.uint64)
+            if use_probe_table:
+                _lib.check(lib.gki_probe_count_nodes(self.probe_table(), dq.ptr, dq.n, mh, counts.ptr, int(n_nodes),
+                                                     C.byref(n_hits)))
+            else:
+                view = self.view()
+                _lib.check(lib.gki_index_count_nodes(C.byref(view), dq.ptr, dq.n, mh, counts.ptr, int(n_nodes)))
+            s.release(counts)
         return (counts, n_hits.value) if return_hits else counts
 
     def count_nodes_from_reads(self, letters, read_start, k, n_nodes, strands=3, max_hits=10, counts=None):
         """Read hashing fused with the probe (gki_probe_reads_count_nodes): letters = ASCII uint8 of all reads
         (NumPy or DeviceArray), read_start int64[n_reads+1]; strands bit 0 forward, bit 1 reverse complement.
         Returns (counts DeviceArray uint32[n_nodes], k-mers probed, hits)."""
-        lib = _lib.load()
-        if counts is None:
-            counts = _lib.DeviceArray(max(int(n_nodes), 1), np.uint32)
-            counts.zero()
-        owned = []
-
-        def dev(a, dtype):
-            if isinstance(a, _lib.DeviceArray):
-                return a
-            a = np.ascontiguousarray(a, dtype=dtype)
-            d = _lib.DeviceArray.from_host(a if a.size else np.zeros(1, dtype))
-            owned.append(d)
-            return d
         n_reads = len(read_start) - 1
-        d_letters, d_start = dev(letters, np.uint8), dev(read_start, np.int64)
         n_kmers, n_hits = C.c_int64(0), C.c_int64(0)
-        try:
-            _lib.check(lib.gki_probe_reads_count_nodes(self.probe_table(), d_letters.ptr, d_start.ptr, n_reads, int(k),
-                                                       int(strands), int(min(max_hits, 2 ** 62)), counts.ptr, int(n_nodes),
-                                                       C.byref(n_kmers), C.byref(n_hits)))
-        finally:
-            for d in owned:
-                d.free()
+        with _lib.DeviceScope() as s:
+            counts = zeroed_counts(s, n_nodes) if counts is None else counts
+            d_letters, d_start = s.on_device(letters, np.uint8), s.on_device(read_start, np.int64)
+            _lib.check(_lib.load().gki_probe_reads_count_nodes(
+                self.probe_table(), d_letters.ptr, d_start.ptr, n_reads, int(k), int(strands), int(min(max_hits, 2 ** 62)),
+                counts.ptr, int(n_nodes), C.byref(n_kmers), C.byref(n_hits)))
+            s.release(counts)
         return counts, n_kmers.value, n_hits.value
 
     def __del__(self):
@@ -214,8 +193,15 @@ class DeviceIndex:
             a.free()
 
 
+def zeroed_counts(scope, n_nodes):
+    """A node histogram of zeros in `scope`, for the caller to release."""
+    counts = scope.array(max(int(n_nodes), 1), np.uint32)
+    counts.zero()
+    return counts
+
+
 def bucket_range(modulo, n_parts, part):
-    """Buckets [begin, end) owned by `part` (gki_partition_by_bucket_range)."""
+    """Buckets [begin, end) of `part` (gki_partition_by_bucket_range)."""
     return modulo * part // n_parts, modulo * (part + 1) // n_parts
 
 
@@ -329,23 +315,22 @@ class PartitionedDeviceIndex:
         return DeviceIndex.build(sl, modulo, skip_frequencies, bucket_begin=lo, n_buckets=hi - lo, group_start=groups)
 
     def count_nodes(self, queries, n_nodes, max_hits=10, counts=None):
-        own = not isinstance(queries, _lib.DeviceArray)
-        dq = _lib.DeviceArray.from_host(np.ascontiguousarray(np.asarray(queries)).astype(np.uint64)) if own else queries
-        for p in self.parts:
-            counts = p.count_nodes(dq, n_nodes, max_hits, counts)
-        if own:
-            dq.free()
-        return counts
+        with _lib.DeviceScope() as s:
+            counts = zeroed_counts(s, n_nodes) if counts is None else counts
+            dq = s.on_device(queries, np.uint64)
+            for p in self.parts:
+                p.count_nodes(dq, n_nodes, max_hits, counts)
+            return s.release(counts)
 
     def count_nodes_from_reads(self, letters, read_start, k, n_nodes, strands=3, max_hits=10, counts=None):
-        dl = letters if isinstance(letters, _lib.DeviceArray) else _lib.DeviceArray.from_host(np.ascontiguousarray(letters, np.uint8))
-        ds = read_start if isinstance(read_start, _lib.DeviceArray) else \
-            _lib.DeviceArray.from_host(np.ascontiguousarray(read_start, np.int64))
         n_kmers = hits = 0
-        for p in self.parts:
-            counts, n_kmers, h = p.count_nodes_from_reads(dl, ds, k, n_nodes, strands, max_hits, counts)
-            hits += h
-        return counts, n_kmers, hits
+        with _lib.DeviceScope() as s:
+            counts = zeroed_counts(s, n_nodes) if counts is None else counts
+            dl, ds = s.on_device(letters, np.uint8), s.on_device(read_start, np.int64)
+            for p in self.parts:
+                _, n_kmers, h = p.count_nodes_from_reads(dl, ds, k, n_nodes, strands, max_hits, counts)
+                hits += h
+            return s.release(counts), n_kmers, hits
 
     def free(self):
         for p in self.parts:
@@ -383,9 +368,11 @@ class CounterKmerIndex:
     def _device_table(self):
         if self._index is None:                       # constructed from bare arrays: build the table once
             z = np.zeros(len(self.kmers), np.uint64)
-            self._index = DeviceIndex.build(DeviceFlatKmers.from_flat_kmers(
-                FlatKmers(np.asarray(self.kmers).astype(np.uint64), np.asarray(self.nodes).astype(np.uint32), z,
-                          z.astype(np.float32))), self._modulo, skip_frequencies=True)
+            with _lib.DeviceScope() as s:
+                dflat = s.keep(DeviceFlatKmers.from_flat_kmers(
+                    FlatKmers(np.asarray(self.kmers).astype(np.uint64), np.asarray(self.nodes).astype(np.uint32), z,
+                              z.astype(np.float32))))
+                self._index = DeviceIndex.build(dflat, self._modulo, skip_frequencies=True)
         return self._index
 
     def count_kmers(self, kmers, update_counter=True):
@@ -444,38 +431,35 @@ class CollisionFreeKmerIndex:
         if not isinstance(flat_kmers, DeviceFlatKmers):
             host_cols = [np.asarray(flat_kmers._hashes), np.asarray(flat_kmers._nodes),
                          np.asarray(flat_kmers._ref_offsets), np.asarray(flat_kmers._allele_frequencies)]
-            dflat = DeviceFlatKmers.from_flat_kmers(flat_kmers)
-        else:
-            dflat = flat_kmers
-        dev = DeviceIndex.build(dflat, modulo, skip_frequencies, want_permutation=host_cols is not None)
-        n = dflat.n
-        freq = dev.frequencies.to_host(n)
-        if skip_singletons:
-            freq = freq + np.uint16(1)                                                     # :463-465
-        dev_cols = [dev.kmers, dev.nodes, dev.ref_offsets, dev.allele_frequencies]
-        if host_cols is None:
-            cols = [c.to_host(n) for c in dev_cols]
-        else:
-            # the reference permutes the caller's arrays whatever their dtype (:436-440): columns whose dtype is the
-            # device's (up to signedness) come back from HBM, others are permuted here with the device's `sorting`
-            dflat.free()
-            perm = None
-            cols = []
-            for h, d in zip(host_cols, dev_cols):
-                if h.dtype.kind in "iu" and d.dtype.kind in "iu" and h.dtype.itemsize == d.dtype.itemsize \
-                        or h.dtype == d.dtype:
-                    cols.append(d.to_host(n).view(h.dtype))
-                else:
-                    if perm is None:
-                        perm = dev.permutation.to_host(n).astype(np.int64)
-                    cols.append(h[perm])
-            dev.permutation.free()
-            dev.permutation = None
-        obj = cls(dev.hashes_to_index.to_host(), dev.n_kmers.to_host(), cols[1], cols[2], cols[0], modulo, freq, cols[3])
-        if skip_singletons:
-            dev.free()            # device frequencies differ from the host ones by the +1
-        else:
-            obj._device = dev
+        with _lib.DeviceScope() as s:
+            dflat = flat_kmers if host_cols is None else s.keep(DeviceFlatKmers.from_flat_kmers(flat_kmers))
+            dev = s.keep(DeviceIndex.build(dflat, modulo, skip_frequencies, want_permutation=host_cols is not None))
+            n = dflat.n
+            freq = dev.frequencies.to_host(n)
+            if skip_singletons:
+                freq = freq + np.uint16(1)                                                     # :463-465
+            dev_cols = [dev.kmers, dev.nodes, dev.ref_offsets, dev.allele_frequencies]
+            if host_cols is None:
+                cols = [c.to_host(n) for c in dev_cols]
+            else:
+                # the reference permutes the caller's arrays whatever their dtype (:436-440): columns whose dtype is the
+                # device's (up to signedness) come back from HBM, others are permuted here with the device's `sorting`
+                dflat.free()                                   # early: the upload is not needed for the permutation
+                s.keep(dev.permutation)
+                perm = None
+                cols = []
+                for h, d in zip(host_cols, dev_cols):
+                    if h.dtype.kind in "iu" and d.dtype.kind in "iu" and h.dtype.itemsize == d.dtype.itemsize \
+                            or h.dtype == d.dtype:
+                        cols.append(d.to_host(n).view(h.dtype))
+                    else:
+                        if perm is None:
+                            perm = dev.permutation.to_host(n).astype(np.int64)
+                        cols.append(h[perm])
+                dev.permutation = None
+            obj = cls(dev.hashes_to_index.to_host(), dev.n_kmers.to_host(), cols[1], cols[2], cols[0], modulo, freq, cols[3])
+            if not skip_singletons:           # (with them the device frequencies differ from the host ones by the +1)
+                obj._device = s.release(dev)
         return obj
 
     def _device_index(self):
@@ -535,10 +519,8 @@ class CollisionFreeKmerIndex:
 
     def has_kmers(self, kmers):
         """kmer_mapper.in_graph_index equivalent (:214-216): membership of every query."""
-        flags = self._device_index().contains(kmers)
-        out = flags.to_host(len(kmers)).astype(bool)
-        flags.free()
-        return out
+        with _lib.DeviceScope() as s:
+            return s.keep(self._device_index().contains(kmers)).to_host(len(kmers)).astype(bool)
 
     def has_kmers_parallel(self, kmers, n_threads=1):
         """collision_free_kmer_index.py:222-232 spreads `has_kmers` over a shared-memory process pool; one batched probe
@@ -548,10 +530,8 @@ class CollisionFreeKmerIndex:
     def map_kmers(self, kmers, n_nodes):
         """kmer_mapper.map_kmers_to_graph_index equivalent (:210-212): node hit counts, probe and histogram fused
         on the device."""
-        counts = self._device_index().count_nodes(kmers, n_nodes, max_hits=2 ** 62)
-        out = counts.to_host(n_nodes)
-        counts.free()
-        return out
+        with _lib.DeviceScope() as s:
+            return s.keep(self._device_index().count_nodes(kmers, n_nodes, max_hits=2 ** 62)).to_host(n_nodes)
 
     def map_reads(self, reads, k, n_nodes, max_hits=2 ** 62, include_reverse_complement=True):
         """ReadKmers (read_kmers.py:21-26) + map_kmers in one device pass: node hit counts of all k-mers of `reads`
@@ -563,11 +543,10 @@ class CollisionFreeKmerIndex:
             read_start = np.zeros(len(enc) + 1, dtype=np.int64)
             np.cumsum([len(e) for e in enc], out=read_start[1:])
             letters = np.frombuffer(b"".join(enc), dtype=np.uint8)
-        counts, _, _ = self._device_index().count_nodes_from_reads(letters, read_start, k, n_nodes,
-                                                                   3 if include_reverse_complement else 1, max_hits)
-        out = counts.to_host(n_nodes)
-        counts.free()
-        return out
+        with _lib.DeviceScope() as s:
+            counts = s.keep(self._device_index().count_nodes_from_reads(
+                letters, read_start, k, n_nodes, 3 if include_reverse_complement else 1, max_hits)[0])
+            return counts.to_host(n_nodes)
 
     def map_reads_file(self, file_name, k, n_nodes=None, max_hits=2 ** 62, include_reverse_complement=True, fmt=None,
                        chunk_bytes=None, inflate="auto"):
@@ -578,12 +557,11 @@ class CollisionFreeKmerIndex:
         from . import read_files
         if n_nodes is None:
             n_nodes = int(self.max_node_id()) + 1
-        counts = read_files.count_nodes_from_file(
-            self._device_index(), file_name, k, n_nodes, 3 if include_reverse_complement else 1, max_hits, fmt=fmt,
-            chunk_bytes=read_files.DEFAULT_CHUNK_BYTES if chunk_bytes is None else chunk_bytes, inflate=inflate)[0]
-        out = counts.to_host(n_nodes)
-        counts.free()
-        return out
+        with _lib.DeviceScope() as s:
+            counts = s.keep(read_files.count_nodes_from_file(
+                self._device_index(), file_name, k, n_nodes, 3 if include_reverse_complement else 1, max_hits, fmt=fmt,
+                chunk_bytes=read_files.DEFAULT_CHUNK_BYTES if chunk_bytes is None else chunk_bytes, inflate=inflate)[0])
+            return counts.to_host(n_nodes)
 
     # ------------------------------------------------------------------ probes
     def _hit_positions(self, kmer):

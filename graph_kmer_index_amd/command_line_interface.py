@@ -26,6 +26,7 @@ import logging
 import sys
 import numpy as np
 
+from . import _lib
 from .collision_free_kmer_index import CollisionFreeKmerIndex
 from .critical_graph_paths import CriticalGraphPaths
 from .flat_kmers import FlatKmers
@@ -64,7 +65,7 @@ def index(args):
         logging.info("-t %d: one device visible, one process" % args.n_threads)
     shard = None
     if args.shard is not None:                       # one rank of `index -t N`: its device FIRST -- the critical paths
-        from . import _lib                           # below are computed on the device and the graph upload is cached on
+                                                     # below are computed on the device and the graph upload is cached on
         shard = tuple(int(x) for x in args.shard.split("/"))     # the graph object: both must land on this rank's GPU
         _lib.check(_lib.load().gki_set_device(shard[0] % max(1, _lib.device_count())))
     graph = load_graph(args.graph)
@@ -81,21 +82,20 @@ def index(args):
         chunk = dict(start_at_critical_path_number=a, stop_at_critical_path_number=b)
     finder = DenseKmerFinder(graph, k, critical_graph_paths=cp, max_variant_nodes=args.max_variant_nodes,
                              only_save_one_node_per_kmer=True, whitelist=whitelist, **chunk)      # :559-565
-    dflat = finder.find_flat_on_device(split_layout=False)      # with a whitelist: membership probe + compaction in HBM
-    finder.synchronize()
-    if args.include_reverse_complement and args.shard is None:                            # :616-620, still in HBM
-        from .flat_kmers import DeviceFlatKmers
-        both = DeviceFlatKmers.from_multiple_flat_kmers([dflat, dflat.get_reverse_complement_flat_kmers(k)])
-        dflat.free()
-        dflat = both
-    flat = dflat.to_flat_kmers()
-    dflat.free()
+    with _lib.DeviceScope() as s:
+        dflat = s.keep(finder.find_flat_on_device(split_layout=False))    # with a whitelist: membership probe + compaction in HBM
+        finder.synchronize()
+        if args.include_reverse_complement and args.shard is None:                        # :616-620, still in HBM
+            from .flat_kmers import DeviceFlatKmers
+            both = s.keep(DeviceFlatKmers.from_multiple_flat_kmers([dflat, s.keep(dflat.get_reverse_complement_flat_kmers(k))]))
+            dflat.free()                             # early: one copy of the records is enough from here
+            dflat = both
+        flat = dflat.to_flat_kmers()
     logging.info("N kmers in flat kmers: %d" % len(flat._hashes))
     flat.to_file(args.out_file_name)
 
 
 def _visible_devices():
-    from . import _lib
     return _lib.device_count()
 
 
@@ -282,10 +282,9 @@ def create_index(args):
     assert args.reference_name is not None, "Reference name must be specified"
     letters = read_fasta_record(args.reference_fasta, args.reference_name)
     assert len(letters) > 0, "Length of ref sequennce is 0. Seomthing is wrong"
-    dflat = make_linear_reference_flat_on_device(letters, args.kmer_size, args.spacing, args.genome_size, args.threads,
-                                                 _bool(args.include_reverse_complement))
-    flat = dflat.to_flat_kmers()
-    dflat.free()
+    with _lib.DeviceScope() as s:
+        flat = s.keep(make_linear_reference_flat_on_device(letters, args.kmer_size, args.spacing, args.genome_size,
+                                                           args.threads, _bool(args.include_reverse_complement))).to_flat_kmers()
     logging.info("N kmers in flat kmers: %d" % len(flat._hashes))
     flat.to_file(args.out_file_name)
 

@@ -1,5 +1,5 @@
 """FlatKmers / FlatKmers2 record containers with the reference's attributes and .npz layout
-(flat_kmers.py:7-154).  Columns are NumPy arrays owned by Python; the device-resident variant used
+(flat_kmers.py:7-154).  Columns are NumPy arrays that Python owns; the device-resident variant used
 between GPU stages is `DeviceFlatKmers`."""
 import logging
 import numpy as np
@@ -122,46 +122,48 @@ class DeviceFlatKmers:
 
     def get_reverse_complement_flat_kmers(self, k):
         """flat_kmers.py:127-131 on the device: reverse-complemented hashes, the other columns shared (views)."""
-        out = _lib.DeviceArray(max(self.n, 1), np.uint64)
-        _lib.check(_lib.load().gki_reverse_complement(self.hashes.ptr, self.n, int(k), out.ptr))
-        return DeviceFlatKmers(self.n, out, self.nodes.view(0, self.n), self.ref_offsets.view(0, self.n),
-                               self.allele_frequencies.view(0, self.n))
+        with _lib.DeviceScope() as s:
+            out = s.array(self.n, np.uint64)
+            _lib.check(_lib.load().gki_reverse_complement(self.hashes.ptr, self.n, int(k), out.ptr))
+            return DeviceFlatKmers(self.n, s.release(out), self.nodes.view(0, self.n), self.ref_offsets.view(0, self.n),
+                                   self.allele_frequencies.view(0, self.n))
 
     @classmethod
     def from_multiple_flat_kmers(cls, parts):
         """flat_kmers.py:71-90: concatenation, in HBM."""
         total = sum(p.n for p in parts)
-        out = cls.allocate(total)
         at = 0
         lib = _lib.load()
-        for p in parts:
-            for src, dst in ((p.hashes, out.hashes), (p.nodes, out.nodes), (p.ref_offsets, out.ref_offsets),
-                             (p.allele_frequencies, out.allele_frequencies)):
-                if p.n:
-                    _lib.check(lib.gki_memcpy_d2d(dst.view(at, p.n).ptr, src.ptr, p.n * src.dtype.itemsize))
-            at += p.n
-        return out
+        with _lib.DeviceScope() as s:
+            out = s.keep(cls.allocate(total))
+            for p in parts:
+                for src, dst in ((p.hashes, out.hashes), (p.nodes, out.nodes), (p.ref_offsets, out.ref_offsets),
+                                 (p.allele_frequencies, out.allele_frequencies)):
+                    if p.n:
+                        _lib.check(lib.gki_memcpy_d2d(dst.view(at, p.n).ptr, src.ptr, p.n * src.dtype.itemsize))
+                at += p.n
+            return s.release(out)
 
     def get_new_without_singletons(self):
         """flat_kmers.py:98-125 on the device: the 2nd and later occurrences of every hash, original order."""
-        flags = _lib.DeviceArray(max(self.n, 1), np.uint8)
-        _lib.check(_lib.load().gki_flag_repeated_kmers(self.hashes.ptr, self.n, flags.ptr))
-        out = self.compacted(flags)
-        flags.free()
-        return out
+        with _lib.DeviceScope() as s:
+            flags = s.array(self.n, np.uint8)
+            _lib.check(_lib.load().gki_flag_repeated_kmers(self.hashes.ptr, self.n, flags.ptr))
+            return self.compacted(flags)
 
     def compacted(self, flags):
         """Records whose flag (DeviceArray uint8, one per record) is set, order kept (gki_compact_flat)."""
         import ctypes as C
         keep, _ = flags.checksum(self.n)
-        out = DeviceFlatKmers.allocate(keep)
         n_out = C.c_int64(0)
-        _lib.check(_lib.load().gki_compact_flat(flags.ptr, self.n, self.hashes.ptr, self.nodes.ptr, self.ref_offsets.ptr,
-                                                self.allele_frequencies.ptr, out.hashes.ptr, out.nodes.ptr,
-                                                out.ref_offsets.ptr, out.allele_frequencies.ptr, max(keep, 1),
-                                                C.byref(n_out)))
-        assert n_out.value == keep
-        return out
+        with _lib.DeviceScope() as s:
+            out = s.keep(DeviceFlatKmers.allocate(keep))
+            _lib.check(_lib.load().gki_compact_flat(flags.ptr, self.n, self.hashes.ptr, self.nodes.ptr, self.ref_offsets.ptr,
+                                                    self.allele_frequencies.ptr, out.hashes.ptr, out.nodes.ptr,
+                                                    out.ref_offsets.ptr, out.allele_frequencies.ptr, max(keep, 1),
+                                                    C.byref(n_out)))
+            assert n_out.value == keep
+            return s.release(out)
 
     def to_flat_kmers(self):
         return FlatKmers(self.hashes.to_host(self.n), self.nodes.to_host(self.n), self.ref_offsets.to_host(self.n),

@@ -122,7 +122,7 @@ class GraphArrays:
             chromosome_start_nodes = [self.first_node]
         self._chromosome_start_nodes = [int(x) for x in chromosome_start_nodes]
         self.node_to_ref_offset = node_to_ref_offset
-        self._device = None   # cache slot owned by graph_kmer_index_amd (device handle)
+        self._device = None   # cache slot of graph_kmer_index_amd (device handle)
 
     # ------------------------------------------------------------------ builders
     @classmethod

@@ -44,45 +44,41 @@ def unique_counts_on_device(kmers, stride=1, key_bits=None):
     stride = int(stride)
     if stride < 1:
         raise ValueError("stride must be at least 1 (got %d)" % stride)
-    owned = None
     if isinstance(kmers, _lib.DeviceArray):
         if kmers.dtype.itemsize != 8 or kmers.dtype.kind not in "ui":
             raise TypeError("k-mers on the device must be uint64 or int64 (got %s)" % kmers.dtype)
-        d_kmers, n = kmers, kmers.n
         key_bits = 64 if key_bits is None else int(key_bits)
     else:
-        host = np.asarray(kmers)
-        if host.ndim != 1:
+        kmers = np.asarray(kmers)
+        if kmers.ndim != 1:
             raise ValueError("k-mers must be one-dimensional")
-        if host.dtype.kind == "i" and len(host) and host.min() < 0:
+        if kmers.dtype.kind == "i" and len(kmers) and kmers.min() < 0:
             raise ValueError("k-mers must not be negative")
-        host = np.ascontiguousarray(host, dtype=np.uint64)
-        key_bits = _bits_of(host) if key_bits is None else int(key_bits)
-        n = len(host)
-        d_kmers = owned = _lib.DeviceArray.from_host(host) if n else _lib.DeviceArray(0, np.uint64)
+        kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
+        key_bits = _bits_of(kmers) if key_bits is None else int(key_bits)
     n_unique, plan = _lib._I64(0), _lib.C.c_void_p()
     ms, ms_emit = (_lib.C.c_float * 2)(), (_lib.C.c_float * 1)()
-    try:
-        _lib.check(lib.gki_unique_counts_count(d_kmers.ptr, n, stride, key_bits, _lib.C.byref(n_unique), _lib.C.byref(plan), ms))
-        unique = _lib.DeviceArray(n_unique.value, np.uint64)
-        counts = _lib.DeviceArray(n_unique.value, np.int64)
-        _lib.check(lib.gki_unique_counts_emit(plan, unique.ptr, counts.ptr, ms_emit))
-    finally:
-        if plan.value:
-            lib.gki_unique_counts_destroy(plan)
-        if owned is not None:
-            owned.free()
+    with _lib.DeviceScope() as s:
+        d_kmers = s.on_device(kmers, np.uint64)
+        try:
+            _lib.check(lib.gki_unique_counts_count(d_kmers.ptr, d_kmers.n, stride, key_bits, _lib.C.byref(n_unique),
+                                                   _lib.C.byref(plan), ms))
+            unique = s.array(n_unique.value, np.uint64)
+            counts = s.array(n_unique.value, np.int64)
+            _lib.check(lib.gki_unique_counts_emit(plan, unique.ptr, counts.ptr, ms_emit))
+        finally:
+            if plan.value:
+                lib.gki_unique_counts_destroy(plan)
+        s.release(unique), s.release(counts)
     unique_counts_on_device.last_kernel_ms = {"sort": float(ms[0]), "run_heads": float(ms[1]), "emit": float(ms_emit[0])}
     return unique, counts
 
 
 def unique_counts(kmers, stride=1, key_bits=None):
     """np.unique(kmers[::stride], return_counts=True) through the device: (uint64 ascending, int64)."""
-    d_unique, d_counts = unique_counts_on_device(kmers, stride, key_bits)
-    out = d_unique.to_host(), d_counts.to_host()
-    d_unique.free()
-    d_counts.free()
-    return out
+    with _lib.DeviceScope() as s:
+        d_unique, d_counts = map(s.keep, unique_counts_on_device(kmers, stride, key_bits))
+        return d_unique.to_host(), d_counts.to_host()
 
 
 class DeviceCounter:
@@ -94,10 +90,29 @@ class DeviceCounter:
         _lib.check(_lib.load().gki_counter_create(d_kmers.ptr, d_counts.ptr, d_kmers.n, self.key_bits, _lib.C.byref(handle)))
         self.handle = handle
 
-    def lookup_on_device(self, d_queries):
-        out = _lib.DeviceArray(d_queries.n, np.int64)
-        _lib.check(_lib.load().gki_counter_lookup(self.handle, d_queries.ptr, d_queries.n, out.ptr))
+    @classmethod
+    def from_host(cls, kmers, counts):
+        """The counter of sorted distinct host k-mers and their counts; both uploads are its own."""
+        kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
+        with _lib.DeviceScope() as s:
+            d_kmers, d_counts = s.on_device(kmers, np.uint64), s.on_device(counts, np.int64)
+            out = cls(d_kmers, d_counts, _bits_of(kmers))
+            s.release(d_kmers), s.release(d_counts)
         return out
+
+    def lookup_on_device(self, d_queries):
+        with _lib.DeviceScope() as s:
+            out = s.array(d_queries.n, np.int64)
+            _lib.check(_lib.load().gki_counter_lookup(self.handle, d_queries.ptr, d_queries.n, out.ptr))
+            return s.release(out)
+
+    def lookup(self, queries):
+        """The counts of host k-mers as a NumPy array (int64, 0 when absent)."""
+        q = np.ascontiguousarray(queries, dtype=np.uint64)
+        if len(q) == 0:
+            return np.zeros(0, np.int64)
+        with _lib.DeviceScope() as s:
+            return s.keep(self.lookup_on_device(s.on_device(q, np.uint64))).to_host()
 
     def free(self):
         if self.handle is not None and self.handle.value:
@@ -149,10 +164,7 @@ class KmerCounter:
     def _device_counter(self):
         if self._device is None:
             _lib.require_device()
-            h = _lib.DeviceArray.from_host
-            n = len(self._kmers)
-            self._device = DeviceCounter(h(self._kmers) if n else _lib.DeviceArray(0, np.uint64),
-                                         h(self._counts) if n else _lib.DeviceArray(0, np.int64), _bits_of(self._kmers))
+            self._device = DeviceCounter.from_host(self._kmers, self._counts)
         return self._device
 
     def get_frequency(self, kmer):
@@ -168,15 +180,7 @@ class KmerCounter:
         counter = self._device_counter()
         if isinstance(kmers, _lib.DeviceArray):
             return counter.lookup_on_device(kmers)
-        q = np.ascontiguousarray(kmers, dtype=np.uint64)
-        if len(q) == 0:
-            return np.zeros(0, np.int64)
-        d_q = _lib.DeviceArray.from_host(q)
-        d_out = counter.lookup_on_device(d_q)
-        out = d_out.to_host()
-        d_q.free()
-        d_out.free()
-        return out
+        return counter.lookup(kmers)
 
     def score_kmers(self, kmers):
         """A scorer for a set of k-mers, low is bad: minus the largest count among those present, 1 when none is

@@ -322,23 +322,22 @@ class DenseKmerFinder:
         if n == 0:
             cols = [np.zeros(0, dtype=d) for d in dt]
         else:
-            bufs = [_lib.DeviceArray(n, d) for d in dt]
-            _lib.check(lib.gki_finder_emit_v2(self._finder_handle(), *[b.ptr for b in bufs]))
-            _lib.check(lib.gki_finder_synchronize(self._finder_handle()))
-            cols = [b.to_host() for b in bufs]
-            for b in bufs:
-                b.free()
+            with _lib.DeviceScope() as s:
+                bufs = [s.array(n, d) for d in dt]
+                _lib.check(lib.gki_finder_emit_v2(self._finder_handle(), *[b.ptr for b in bufs]))
+                _lib.check(lib.gki_finder_synchronize(self._finder_handle()))
+                cols = [b.to_host() for b in bufs]
         kmers, start_nodes, start_offsets, nodes, af = cols
         # The int16 column holds the end offset modulo 2^16 (the reference's dtype).  The positions
         # get_flat_kmers(v="0"/"1") hands out need the true offset: the same run's 64-bit position column (by-node layout,
         # the v2 order) minus the end node's base.
         offsets = start_offsets.astype(np.int64)
         if n and int(self._arrays.node_size.max()) > 32768:
-            pos = _lib.DeviceArray(n, np.uint64)
-            _lib.check(lib.gki_finder_emit_flat(self._finder_handle(), None, None, pos.ptr, None))
-            _lib.check(lib.gki_finder_synchronize(self._finder_handle()))
-            offsets = pos.to_host().view(np.int64) - self._position_base[start_nodes]
-            pos.free()
+            with _lib.DeviceScope() as s:
+                pos = s.array(n, np.uint64)
+                _lib.check(lib.gki_finder_emit_flat(self._finder_handle(), None, None, pos.ptr, None))
+                _lib.check(lib.gki_finder_synchronize(self._finder_handle()))
+                offsets = pos.to_host().view(np.int64) - self._position_base[start_nodes]
         keep = None
         if self._whitelist is not None:                                # kmer_finder.py:130-132, 362-365
             keep = self._in_whitelist(kmers)
@@ -354,32 +353,30 @@ class DenseKmerFinder:
         split_layout: records whose window lies inside one node first, then the others (GKI_LAYOUT_SPLIT) -- the
         same multiset, written as two dense streams; False gives find()'s by-node order."""
         n = self._count(layout=1 if split_layout else 0)
-        if out is None or out.hashes.n < n:
-            out = DeviceFlatKmers.allocate(n)
-        out.n = n
-        if n:
-            _lib.check(_lib.load().gki_finder_emit_flat(self._finder_handle(), out.hashes.ptr, out.nodes.ptr,
-                                                        out.ref_offsets.ptr, out.allele_frequencies.ptr))
-        if self._whitelist is not None and n:
-            # kmer_finder.py:130-132, 362-365: keep a record iff `kmer in whitelist`; on the device: membership probe of
-            # every hash against the whitelist index, then a stable compaction of the four columns
-            self.synchronize()
-            flags = self._whitelist_index().contains(out.hashes.view(0, n))
-            kept = out.compacted(flags)
-            flags.free()
-            out.free()
-            out = kept
-        return out
+        with _lib.DeviceScope() as s:
+            if out is None or out.hashes.n < n:
+                out = s.keep(DeviceFlatKmers.allocate(n))
+            out.n = n
+            if n:
+                _lib.check(_lib.load().gki_finder_emit_flat(self._finder_handle(), out.hashes.ptr, out.nodes.ptr,
+                                                            out.ref_offsets.ptr, out.allele_frequencies.ptr))
+            if self._whitelist is not None and n:
+                # kmer_finder.py:130-132, 362-365: keep a record iff `kmer in whitelist`; on the device: membership probe
+                # of every hash against the whitelist index, then a stable compaction of the four columns
+                self.synchronize()
+                flags = s.keep(self._whitelist_index().contains(out.hashes.view(0, n)))
+                found, out = out, out.compacted(flags)
+                s.keep(found)
+            return s.release(out)
 
     def _in_whitelist(self, kmers):
         """bool per k-mer: `kmer in whitelist`, probed on the device."""
         kmers = np.ascontiguousarray(kmers)
         if len(kmers) == 0:
             return np.zeros(0, dtype=bool)
-        flags = self._whitelist_index().contains(kmers.astype(np.int64).view(np.uint64))
-        keep = flags.to_host(len(kmers)).astype(bool)
-        flags.free()
-        return keep
+        with _lib.DeviceScope() as s:
+            flags = s.keep(self._whitelist_index().contains(kmers.astype(np.int64).view(np.uint64)))
+            return flags.to_host(len(kmers)).astype(bool)
 
     def _whitelist_index(self):
         """The whitelist as a DeviceIndex: a CollisionFreeKmerIndex (what the reference's CLI passes,
@@ -396,9 +393,10 @@ class DenseKmerFinder:
                 kmers = np.unique(np.fromiter((int(x) for x in wl), dtype=np.int64)).astype(np.uint64)
                 z = np.zeros(len(kmers), np.uint32)
                 modulo = max(2 * len(kmers) + 1, 1009)
-                self._whitelist_device = DeviceIndex.build(
-                    DeviceFlatKmers.from_flat_kmers(FlatKmers(kmers, z, z.astype(np.uint64), z.astype(np.float32))),
-                    modulo, skip_frequencies=True)
+                with _lib.DeviceScope() as s:
+                    dflat = s.keep(DeviceFlatKmers.from_flat_kmers(FlatKmers(kmers, z, z.astype(np.uint64),
+                                                                             z.astype(np.float32))))
+                    self._whitelist_device = DeviceIndex.build(dflat, modulo, skip_frequencies=True)
         return self._whitelist_device
 
     def synchronize(self):
@@ -425,30 +423,26 @@ class DenseKmerFinder:
         g = self._arrays
         graph = self._device_graph()
         n_pos = len(nodes)
-        d_nodes = _lib.DeviceArray.from_host(np.ascontiguousarray(nodes, dtype=np.int32))
-        d_offs = _lib.DeviceArray.from_host(np.ascontiguousarray(offsets, dtype=np.int32))
-        d_start = _lib.DeviceArray(n_pos + 1, np.int64)
         n = C.c_int64(0)
-        d_follow = None
-        if self._only_follow_nodes is not None:
-            mask = np.zeros(g.n_nodes, dtype=np.uint8)
-            mask[np.fromiter((int(x) for x in self._only_follow_nodes), dtype=np.int64)] = 1
-            d_follow = _lib.DeviceArray.from_host(mask)
-        args = (graph.handle, self._k, self._max_variant_nodes, int(self._only_save_one_node_per_kmer),
-                None if d_follow is None else d_follow.ptr, d_nodes.ptr, d_offs.ptr, n_pos)
-        _lib.check(lib.gki_forward_count(*args, d_start.ptr, C.byref(n)))
-        dt = [np.int64, np.int32, np.int16, np.int32, np.float64]
-        if n.value:
-            bufs = [_lib.DeviceArray(n.value, d) for d in dt]
-            _lib.check(lib.gki_forward_emit(*args, d_start.ptr, *[b.ptr for b in bufs]))
-            cols = [b.to_host() for b in bufs]
-            for b in bufs:
-                b.free()
-        else:
-            cols = [np.zeros(0, dtype=d) for d in dt]
-        per_start = np.diff(d_start.to_host())
-        for b in (d_nodes, d_offs, d_start) + (() if d_follow is None else (d_follow,)):
-            b.free()
+        with _lib.DeviceScope() as s:
+            d_nodes, d_offs = s.on_device(nodes, np.int32), s.on_device(offsets, np.int32)
+            d_start = s.array(n_pos + 1, np.int64)
+            d_follow = None
+            if self._only_follow_nodes is not None:
+                mask = np.zeros(g.n_nodes, dtype=np.uint8)
+                mask[np.fromiter((int(x) for x in self._only_follow_nodes), dtype=np.int64)] = 1
+                d_follow = s.on_device(mask, np.uint8)
+            args = (graph.handle, self._k, self._max_variant_nodes, int(self._only_save_one_node_per_kmer),
+                    None if d_follow is None else d_follow.ptr, d_nodes.ptr, d_offs.ptr, n_pos)
+            _lib.check(lib.gki_forward_count(*args, d_start.ptr, C.byref(n)))
+            dt = [np.int64, np.int32, np.int16, np.int32, np.float64]
+            if n.value:
+                bufs = [s.array(n.value, d) for d in dt]
+                _lib.check(lib.gki_forward_emit(*args, d_start.ptr, *[b.ptr for b in bufs]))
+                cols = [b.to_host() for b in bufs]
+            else:
+                cols = [np.zeros(0, dtype=d) for d in dt]
+            per_start = np.diff(d_start.to_host())
         kmers, start_nodes, start_offsets, out_nodes, af = cols
         # True end offsets beside the int16 column.  The search stops at the first k-mer of every
         # path, k bases from its start: a window that ends in the node it started in ends at start offset + k - 1, every

@@ -12,7 +12,7 @@ import logging
 import numpy as np
 
 from . import _lib
-from .kmer_counter import DeviceCounter, _bits_of, unique_counts
+from .kmer_counter import DeviceCounter, unique_counts
 
 
 class KmerFrequencyIndex:
@@ -31,21 +31,12 @@ class KmerFrequencyIndex:
 
     def get_frequencies(self, kmers):
         """True counts of a batch of k-mers on the device (int64, 0 when absent)."""
-        q = np.ascontiguousarray(kmers, dtype=np.uint64)
-        if len(q) == 0:
+        if len(kmers) == 0:
             return np.zeros(0, np.int64)
         if self._device is None:
             _lib.require_device()
-            keys = np.ascontiguousarray(self._kmers, dtype=np.uint64)
-            self._device = DeviceCounter(_lib.DeviceArray.from_host(keys) if len(keys) else _lib.DeviceArray(0, np.uint64),
-                                         _lib.DeviceArray.from_host(np.ascontiguousarray(self._frequencies, dtype=np.int64))
-                                         if len(keys) else _lib.DeviceArray(0, np.int64), _bits_of(keys))
-        d_q = _lib.DeviceArray.from_host(q)
-        d_out = self._device.lookup_on_device(d_q)
-        out = d_out.to_host()
-        d_q.free()
-        d_out.free()
-        return out
+            self._device = DeviceCounter.from_host(self._kmers, self._frequencies)
+        return self._device.lookup(kmers)
 
     @classmethod
     def from_kmers(cls, kmers):

@@ -23,11 +23,10 @@ def _device_unary(fn_name, hashes, k):
     if h.size == 0:
         return h
     _lib.require_device()
-    d = _lib.DeviceArray.from_host(h)
-    _lib.check(getattr(_lib.load(), fn_name)(d.ptr, h.size, int(k), d.ptr))
-    out = d.to_host()
-    d.free()
-    return out
+    with _lib.DeviceScope() as s:
+        d = s.on_device(h, np.uint64)
+        _lib.check(getattr(_lib.load(), fn_name)(d.ptr, h.size, int(k), d.ptr))
+        return d.to_host()
 
 
 def kmer_hashes_to_reverse_complement_hash(hashes, k):

@@ -542,12 +542,13 @@ def build_index_sharded(graph_arrays, k, critical_graph_paths, comm, modulo=4529
     """find (sharded) -> all-gather over RCCL -> CollisionFreeKmerIndex build on every rank (replicated index, as
     KAGE's lookup side wants it).  Returns (DeviceIndex, per-rank record counts)."""
     from .collision_free_kmer_index import DeviceIndex
-    mine = find_sharded(graph_arrays, k, critical_graph_paths, comm.control.rank, comm.control.world, **finder_kwargs)
-    everything, counts = comm.allgather_flat(mine)
-    mine.free()
-    index = DeviceIndex.build(everything, modulo, skip_frequencies)
-    everything.free()
-    return index, counts
+    with _lib.DeviceScope() as s:
+        mine = s.keep(find_sharded(graph_arrays, k, critical_graph_paths, comm.control.rank, comm.control.world,
+                                   **finder_kwargs))
+        everything, counts = comm.allgather_flat(mine)
+        s.keep(everything)
+        mine.free()                                  # early: only the gathered records are needed for the build
+        return DeviceIndex.build(everything, modulo, skip_frequencies), counts
 
 
 def build_index_partitioned(graph_arrays, k, critical_graph_paths, comm, modulo=452930477, skip_frequencies=False,
@@ -557,15 +558,15 @@ def build_index_partitioned(graph_arrays, k, critical_graph_paths, comm, modulo=
     1/world of the directory.  Returns this rank's slice as a DeviceIndex (bucket_begin / n_buckets set)."""
     from .collision_free_kmer_index import DeviceIndex, bucket_range, partition_by_bucket_range
     rank, world = comm.control.rank, comm.control.world
-    mine = find_sharded(graph_arrays, k, critical_graph_paths, rank, world, **finder_kwargs)
-    by_dest, send_start = partition_by_bucket_range(mine, modulo, world)
-    mine.free()
-    received, _ = comm.alltoall_flat(by_dest, send_start)
-    by_dest.free()
-    lo, hi = bucket_range(modulo, world, rank)
-    index = DeviceIndex.build(received, modulo, skip_frequencies, bucket_begin=lo, n_buckets=hi - lo)
-    received.free()
-    return index
+    with _lib.DeviceScope() as s:
+        mine = s.keep(find_sharded(graph_arrays, k, critical_graph_paths, rank, world, **finder_kwargs))
+        by_dest, send_start = partition_by_bucket_range(mine, modulo, world)
+        s.keep(by_dest)
+        mine.free()                                  # early, like by_dest below: one copy of the records at a time
+        received = s.keep(comm.alltoall_flat(by_dest, send_start)[0])
+        by_dest.free()
+        lo, hi = bucket_range(modulo, world, rank)
+        return DeviceIndex.build(received, modulo, skip_frequencies, bucket_begin=lo, n_buckets=hi - lo)
 
 
 def map_reads_partitioned(index_slice, comm, letters, read_start, k, n_nodes, strands=3, max_hits=10):

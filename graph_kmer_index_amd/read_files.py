@@ -10,12 +10,19 @@ first member -- is uploaded compressed in pieces cut at member boundaries and in
 csrc/gki_inflate.hip), and the inflated text goes to the same parse and probe kernels without a host pass.  Any other
 gzip file is one serial DEFLATE stream and is read through Python's gzip module: that route is bound by the host's
 inflate, not by the device.
+
+Every route is the one loop of `count_nodes_from_file` over a source of pieces: `host_text_pieces` (raw and host gzip) or
+`bgzf_text_pieces`, generators of (text on the device, bytes of it that are whole lines) built from the step functions
+`upload_piece`, `inflate_piece` and `cut_at_line_end`; `count_piece` parses and probes one piece.  Device temporaries
+belong to a `_lib.DeviceScope`, so that nothing stays behind on any way out.
 """
+import contextlib
 import ctypes as C
 import gzip
 import numpy as np
 
 from . import _lib, bgzf
+from .collision_free_kmer_index import zeroed_counts
 
 FORMATS = {"fasta": 0, "fastq": 1}            # GKI_READS_FASTA, GKI_READS_FASTQ
 DEFAULT_CHUNK_BYTES = 256 << 20
@@ -92,37 +99,37 @@ def _format_code(fmt):
     return FORMATS[fmt]
 
 
-def _device_bytes(buf):
-    """(DeviceArray of the bytes, number of bytes, whether this call owns it)."""
+def _device_bytes(scope, buf):
+    """The bytes of `buf` on the device: a uint8 DeviceArray as it is, anything else uploaded into `scope`."""
     if isinstance(buf, _lib.DeviceArray):
         if buf.dtype.itemsize != 1:
             raise ValueError("a device buffer of bytes is uint8")
-        return buf, buf.n, False
-    a = np.ascontiguousarray(np.frombuffer(buf, dtype=np.uint8) if isinstance(buf, (bytes, bytearray, memoryview))
-                             else np.asarray(buf, dtype=np.uint8))
-    return _lib.DeviceArray.from_host(a if a.size else np.zeros(1, np.uint8)), a.size, True
+    elif isinstance(buf, (bytes, bytearray, memoryview)):
+        buf = np.frombuffer(buf, dtype=np.uint8)
+    return scope.on_device(buf, np.uint8)
 
 
-def _count(d, n_bytes, code, line_phase):
+def parse_count(text, n_bytes, code, line_phase):
+    """(n_lines, n_reads, n_letters, n_bad_lines) of the device bytes text[:n_bytes] (gki_reads_parse_count)."""
     n_lines, n_reads, n_letters, n_bad = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
-    _lib.check(_lib.load().gki_reads_parse_count(d.ptr, n_bytes, code, int(line_phase), C.byref(n_lines), C.byref(n_reads),
-                                                 C.byref(n_letters), C.byref(n_bad)))
+    _lib.check(_lib.load().gki_reads_parse_count(text.ptr, n_bytes, code, int(line_phase), C.byref(n_lines),
+                                                 C.byref(n_reads), C.byref(n_letters), C.byref(n_bad)))
     return n_lines.value, n_reads.value, n_letters.value, n_bad.value
 
 
-def _parse(d, n_bytes, code, line_phase):
-    """(letters, read_start, n_reads, n_lines, n_bad) of the device bytes d[:n_bytes]."""
-    n_lines, n_reads, n_letters, n_bad = _count(d, n_bytes, code, line_phase)
-    letters = _lib.DeviceArray(max(n_letters, 1), np.uint8)
-    read_start = _lib.DeviceArray(n_reads + 1, np.int64)
-    try:
-        _lib.check(_lib.load().gki_reads_parse_emit(d.ptr, n_bytes, code, int(line_phase), letters.ptr, n_letters,
+def parse_emit(text, n_bytes, code, line_phase, n_reads, n_letters):
+    """(letters, read_start) of the device bytes text[:n_bytes], sized by what `parse_count` said of them."""
+    with _lib.DeviceScope() as s:
+        letters, read_start = s.array(n_letters, np.uint8), s.array(n_reads + 1, np.int64)
+        _lib.check(_lib.load().gki_reads_parse_emit(text.ptr, n_bytes, code, int(line_phase), letters.ptr, n_letters,
                                                     read_start.ptr, n_reads + 1))
-    except Exception:
-        letters.free(); read_start.free()
-        raise
-    letters.n = n_letters
-    return letters, read_start, n_reads, n_lines, n_bad
+        return s.release(letters), s.release(read_start)
+
+
+def parse_piece(text, n_bytes, code, line_phase):
+    """(letters, read_start, n_reads, n_lines, n_bad) of the device bytes text[:n_bytes]."""
+    n_lines, n_reads, n_letters, n_bad = parse_count(text, n_bytes, code, line_phase)
+    return parse_emit(text, n_bytes, code, line_phase, n_reads, n_letters) + (n_reads, n_lines, n_bad)
 
 
 def count_reads_in_buffer(buf, fmt, line_phase=0):
@@ -130,12 +137,9 @@ def count_reads_in_buffer(buf, fmt, line_phase=0):
     `parse_reads_on_device` would lay out, and for FASTQ the lines that are not where a record has them."""
     _lib.require_device()
     code = _format_code(fmt)
-    d, n_bytes, own = _device_bytes(buf)
-    try:
-        return _count(d, n_bytes, code, line_phase)
-    finally:
-        if own:
-            d.free()
+    with _lib.DeviceScope() as s:
+        d = _device_bytes(s, buf)
+        return parse_count(d, d.n, code, line_phase)
 
 
 def parse_reads_on_device(buf, fmt, line_phase=0):
@@ -144,13 +148,9 @@ def parse_reads_on_device(buf, fmt, line_phase=0):
     line_phase: lines of the file before this buffer, mod 4 (FASTQ only)."""
     _lib.require_device()
     code = _format_code(fmt)
-    d, n_bytes, own = _device_bytes(buf)
-    try:
-        letters, read_start, n_reads, n_lines, _ = _parse(d, n_bytes, code, line_phase)
-    finally:
-        if own:
-            d.free()
-    return letters, read_start, n_reads, n_lines
+    with _lib.DeviceScope() as s:
+        d = _device_bytes(s, buf)
+        return parse_piece(d, d.n, code, line_phase)[:4]
 
 
 def iter_bgzf_pieces(f, chunk_bytes, file_name=""):
@@ -198,86 +198,106 @@ def iter_bgzf_pieces(f, chunk_bytes, file_name=""):
         start, base = start + n_comp, base + n_comp
 
 
-def _last_newline(d, n_bytes):
+# ---- the steps of the streamed route; tools/bench_read_files.py puts a clock around each of them
+
+def upload_piece(piece):
+    """The bytes of a piece of the file as a uint8 DeviceArray."""
+    return _lib.DeviceArray.from_host(np.frombuffer(piece, dtype=np.uint8))
+
+
+def inflate_piece(piece, members, base, tail, file_name=""):
+    """The text of one `iter_bgzf_pieces` piece (host bytes or a uint8 DeviceArray of them) behind `tail`, the unfinished
+    line the piece before left on the device (or None): one DeviceArray.  The tail is freed right after its copy.  A
+    member that does not inflate is a ValueError with the member's offset in the file."""
+    prefix = tail.n if tail is not None else 0
+    try:
+        text = bgzf.inflate_on_device(piece, members, prefix)
+    except bgzf.BgzfInflateError as e:
+        e.output.free()
+        at = base + (members[e.block - 1][4] if e.block else 0)     # where the member begins in the file
+        reason = bgzf.STATUS_TEXT.get(e.status, "status %d" % e.status)
+        raise ValueError("%s: BGZF block at offset %d: %s" % (file_name, at, reason)) from None
+    with _lib.DeviceScope() as s:
+        s.keep(text)
+        if prefix:
+            _lib.check(_lib.load().gki_memcpy_d2d(text.ptr, tail.ptr, prefix))
+            tail.free()
+        return s.release(text)
+
+
+def cut_at_line_end(text):
+    """(n_bytes, tail): text[:n_bytes] ends with the text's last line end (0: there is none), and what follows it is
+    copied into `tail`, a DeviceArray of its own (None: nothing follows)."""
     pos = C.c_int64(-1)
-    _lib.check(_lib.load().gki_last_byte_position(d.ptr, n_bytes, 10, C.byref(pos)))
-    return pos.value
+    _lib.check(_lib.load().gki_last_byte_position(text.ptr, text.n, 10, C.byref(pos)))
+    cut = pos.value + 1
+    if cut == text.n:
+        return cut, None
+    with _lib.DeviceScope() as s:
+        tail = s.array(text.n - cut, np.uint8)
+        _lib.check(_lib.load().gki_memcpy_d2d(tail.ptr, text.ptr.value + cut, tail.n))
+        return cut, s.release(tail)
 
 
-def _count_nodes_from_bgzf(device_index, file_name, k, n_nodes, strands, max_hits, counts, code, chunk_bytes):
-    """`count_nodes_from_file` of a BGZF file.  Per piece: upload the compressed bytes, inflate them behind the tail the
-    last piece left (an unfinished line), parse and probe the text up to and including its last line end, and keep what
-    follows on the device as the next tail.  The end of the file flushes the tail as the last line."""
-    lib = _lib.load()
-    line_phase = n_reads = n_kmers = n_hits = n_bad = 0
-    tail = None                                   # DeviceArray of the bytes behind the last line end so far
+def count_piece(device_index, text, n_bytes, code, line_phase, k, n_nodes, strands, max_hits, counts):
+    """One piece into `counts`: text[:n_bytes] is parsed, the text freed, the reads probed and then freed too.
+    Takes `text` over from the caller.  Returns (reads, lines, bad lines, k-mers probed, hits)."""
+    kmers = hits = 0
+    with _lib.DeviceScope() as s:
+        s.keep(text)
+        letters, read_start, reads, lines, bad = parse_piece(text, n_bytes, code, line_phase)
+        s.keep(letters), s.keep(read_start)
+        text.free()                               # early: the file bytes are not held through the probe
+        if reads:
+            _, kmers, hits = device_index.count_nodes_from_reads(letters, read_start, k, n_nodes, strands, max_hits, counts)
+    return reads, lines, bad, kmers, hits
 
-    def parse_and_probe(d, n_bytes):
-        nonlocal line_phase, n_reads, n_kmers, n_hits, n_bad
-        letters = read_start = None
-        try:
-            letters, read_start, reads, lines, bad = _parse(d, n_bytes, code, line_phase)
-            if reads:
-                _, kmers, hits = device_index.count_nodes_from_reads(letters, read_start, k, n_nodes, strands, max_hits, counts)
-                n_kmers += kmers
-                n_hits += hits
-        finally:
-            for a in (letters, read_start):
-                if a is not None:
-                    a.free()
-        n_reads += reads
-        n_bad += bad
-        line_phase = (line_phase + lines) % 4
-        if n_bad:
-            raise ValueError("%s is not a four-line FASTQ: %d record lines do not begin with '@' or '+' where they must"
-                             % (file_name, n_bad))
 
+# ---- the two sources of pieces: generators of (text, n_bytes), text a uint8 DeviceArray that passes to the consumer and
+# whose first n_bytes bytes are whole lines (only the stream's last piece may end unterminated)
+
+def host_text_pieces(file_name, chunk_bytes):
+    """The 'raw' and 'gzip-host' routes: the text read (and inflated) on the host in pieces that end at a line end
+    (`iter_line_chunks`), each uploaded."""
+    with open_reads_file(file_name) as f:
+        for piece in iter_line_chunks(f, chunk_bytes):
+            text = upload_piece(piece)
+            del piece
+            yield text, text.n
+
+
+def bgzf_text_pieces(file_name, chunk_bytes):
+    """The 'bgzf-device' route: the compressed pieces of `iter_bgzf_pieces`, each inflated on the device behind the tail
+    of the piece before, cut at its last line end, and what follows kept on the device as the next tail; the end of the
+    file gives the tail as the last piece.  The tail is this generator's own and goes back when it is closed, so a
+    consumer that may stop early closes it (contextlib.closing)."""
+    tail = None
     try:
         with open(file_name, "rb") as f:
             for piece, members, base in iter_bgzf_pieces(f, chunk_bytes, file_name):
-                prefix = tail.n if tail is not None else 0
-                try:
-                    text = bgzf.inflate_on_device(piece, members, prefix)
-                except bgzf.BgzfInflateError as e:
-                    e.output.free()
-                    at = base + (members[e.block - 1][4] if e.block else 0)     # where the member begins in the file
-                    reason = bgzf.STATUS_TEXT.get(e.status, "status %d" % e.status)
-                    raise ValueError("%s: BGZF block at offset %d: %s" % (file_name, at, reason)) from None
-                del piece
-                try:
-                    if prefix:
-                        _lib.check(lib.gki_memcpy_d2d(text.ptr, tail.ptr, prefix))
-                        tail.free()
-                    tail = None
-                    if text.n == 0:
-                        continue
-                    if code is None:
-                        code = _format_code(detect_format(text.to_host(1)))
-                    cut = _last_newline(text, text.n) + 1
+                with _lib.DeviceScope() as s:
+                    text = s.keep(inflate_piece(piece, members, base, tail, file_name))
+                    del piece
+                    cut, tail = cut_at_line_end(text)
                     if cut:
-                        parse_and_probe(text, cut)
-                    if cut < text.n:
-                        tail = _lib.DeviceArray(text.n - cut, np.uint8)
-                        _lib.check(lib.gki_memcpy_d2d(tail.ptr, text.ptr.value + cut, text.n - cut))
-                finally:
-                    text.free()
+                        yield s.release(text), cut
         if tail is not None:
-            parse_and_probe(tail, tail.n)
+            text, tail = tail, None
+            yield text, text.n
     finally:
         if tail is not None:
             tail.free()
-    return counts, n_reads, n_kmers, n_hits
 
 
 def count_nodes_from_file(device_index, file_name, k, n_nodes, strands=3, max_hits=2 ** 62, counts=None, fmt=None,
                           chunk_bytes=DEFAULT_CHUNK_BYTES, inflate="auto"):
-    """Node hit counts of every k-mer of every read of a FASTA / FASTQ file, streamed: the file is read in pieces of about
-    `chunk_bytes` that end at a line end (`iter_line_chunks`), each piece is parsed on the device and probed with
-    `device_index.count_nodes_from_reads`, all into one `counts`, and its buffers are freed before the next piece is
-    read.  A `.gz` file goes by `reads_file_route`: BGZF is inflated on the device (pieces of whole members,
-    `iter_bgzf_pieces`), any other gzip through Python's gzip on the host.  inflate: 'auto' that rule, 'host' gzip on the
-    host for every `.gz`, 'device' ValueError unless the file is BGZF.  fmt None: by the first byte of the text.  A FASTQ
-    whose records do not have their '@' and '+' lines in place raises ValueError after the piece that shows it.
+    """Node hit counts of every k-mer of every read of a FASTA / FASTQ file, streamed: one loop over the pieces of the
+    text, about `chunk_bytes` each, that the file's route gives (`host_text_pieces`, `bgzf_text_pieces`); each piece is
+    parsed on the device and probed with `device_index.count_nodes_from_reads` (`count_piece`), all into one `counts`,
+    and everything of it is freed before the next piece is made.  A `.gz` file goes by `reads_file_route`: BGZF is inflated
+    on the device, any other gzip through Python's gzip on the host.  inflate: 'auto' that rule, 'host' gzip on the host
+    for every `.gz`, 'device' ValueError unless the file is BGZF.  fmt None: by the first byte of the text.  A FASTQ whose
+    records do not have their '@' and '+' lines in place raises ValueError after the piece that shows it.
     Returns (counts DeviceArray uint32[n_nodes], reads, k-mers probed, hits)."""
     _lib.require_device()
     if inflate not in INFLATE_CHOICES:
@@ -285,36 +305,21 @@ def count_nodes_from_file(device_index, file_name, k, n_nodes, strands=3, max_hi
     route = reads_file_route(file_name)
     if inflate == "device" and route != "bgzf-device":
         raise ValueError("%s is not a BGZF file: only BGZF is inflated on the device" % file_name)
-    if counts is None:
-        counts = _lib.DeviceArray(max(int(n_nodes), 1), np.uint32)
-        counts.zero()
+    source = bgzf_text_pieces if route == "bgzf-device" and inflate != "host" else host_text_pieces
     code = None if fmt is None else _format_code(fmt)
-    if route == "bgzf-device" and inflate != "host":
-        return _count_nodes_from_bgzf(device_index, file_name, k, n_nodes, strands, max_hits, counts, code, chunk_bytes)
     line_phase = n_reads = n_kmers = n_hits = n_bad = 0
-    with open_reads_file(file_name) as f:
-        for piece in iter_line_chunks(f, chunk_bytes):
+    with _lib.DeviceScope() as s, contextlib.closing(source(file_name, chunk_bytes)) as pieces:
+        counts = zeroed_counts(s, n_nodes) if counts is None else counts
+        for text, n_bytes in pieces:
             if code is None:
-                code = _format_code(detect_format(piece))
-            d = _lib.DeviceArray.from_host(np.frombuffer(piece, dtype=np.uint8))
-            del piece
-            letters = read_start = None
-            try:
-                letters, read_start, reads, lines, bad = _parse(d, d.n, code, line_phase)
-                d.free()
-                if reads:
-                    _, kmers, hits = device_index.count_nodes_from_reads(letters, read_start, k, n_nodes, strands, max_hits,
-                                                                         counts)
-                    n_kmers += kmers
-                    n_hits += hits
-            finally:
-                for a in (d, letters, read_start):
-                    if a is not None:
-                        a.free()
-            n_reads += reads
-            n_bad += bad
+                s.keep(text)                      # until count_piece has it
+                code = _format_code(detect_format(text.to_host(1)))
+                s.release(text)
+            reads, lines, bad, kmers, hits = count_piece(device_index, text, n_bytes, code, line_phase, k, n_nodes, strands,
+                                                         max_hits, counts)
+            n_reads, n_kmers, n_hits, n_bad = n_reads + reads, n_kmers + kmers, n_hits + hits, n_bad + bad
             line_phase = (line_phase + lines) % 4
             if n_bad:
                 raise ValueError("%s is not a four-line FASTQ: %d record lines do not begin with '@' or '+' where they must"
                                  % (file_name, n_bad))
-    return counts, n_reads, n_kmers, n_hits
+        return s.release(counts), n_reads, n_kmers, n_hits

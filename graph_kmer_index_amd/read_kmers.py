@@ -27,22 +27,19 @@ def hash_reads(reads, k, strand=0, return_device=False):
         np.cumsum([len(e) for e in enc], out=read_start[1:])
         letters = np.frombuffer(b"".join(enc), dtype=np.uint8)
     n_reads = len(read_start) - 1
-    d_letters = _lib.DeviceArray.from_host(letters if len(letters) else np.zeros(1, np.uint8))
-    d_start = _lib.DeviceArray.from_host(read_start)
-    d_out_start = _lib.DeviceArray(n_reads + 1, np.int64)
     n_out = C.c_int64(0)
-    _lib.check(lib.gki_hash_reads(d_letters.ptr, d_start.ptr, n_reads, int(k), int(strand), d_out_start.ptr, None, 0,
-                                  C.byref(n_out)))
-    d_out = _lib.DeviceArray(max(n_out.value, 1), np.uint64)
-    _lib.check(lib.gki_hash_reads(d_letters.ptr, d_start.ptr, n_reads, int(k), int(strand), d_out_start.ptr, d_out.ptr,
-                                  d_out.n, C.byref(n_out)))
-    out_start = d_out_start.to_host()
-    d_letters.free(); d_start.free(); d_out_start.free()
-    if return_device:
-        return d_out, n_out.value, out_start
-    out = d_out.to_host(n_out.value)
-    d_out.free()
-    return out, out_start
+    with _lib.DeviceScope() as s:
+        d_letters, d_start = s.on_device(letters, np.uint8), s.on_device(read_start, np.int64)
+        d_out_start = s.array(n_reads + 1, np.int64)
+        _lib.check(lib.gki_hash_reads(d_letters.ptr, d_start.ptr, n_reads, int(k), int(strand), d_out_start.ptr, None, 0,
+                                      C.byref(n_out)))
+        d_out = s.array(n_out.value, np.uint64)
+        _lib.check(lib.gki_hash_reads(d_letters.ptr, d_start.ptr, n_reads, int(k), int(strand), d_out_start.ptr, d_out.ptr,
+                                      d_out.n, C.byref(n_out)))
+        out_start = d_out_start.to_host()
+        if return_device:
+            return s.release(d_out), n_out.value, out_start
+        return d_out.to_host(), out_start
 
 
 class ReadKmers:

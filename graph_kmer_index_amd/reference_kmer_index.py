@@ -51,13 +51,12 @@ class ReferenceKmerIndex:
         host = reference_to_letters(genome_sequence)
         if len(host) < k:
             raise NoReferenceSequence("the sequence has %d letters, fewer than k=%d" % (len(host), k))
-        letters = _lib.DeviceArray.from_host(host)
-        try:
+        with _lib.DeviceScope() as s:
+            letters = s.on_device(host, np.uint8)
             hashes, n = linear_kmers_on_device(letters, k, 1, [0], [len(host) - k + 1], hashes_only=True)
-        finally:
-            letters.free()
-        kmers = hashes.to_host(n)
-        hashes.free()
+            s.keep(hashes)
+            letters.free()                  # early: the letters are not needed while the hashes are copied
+            kmers = hashes.to_host(n)
         ref_position_to_index = None
         if not only_store_kmers:
             ref_position_to_index = np.arange(0, len(host), dtype=np.uint32)

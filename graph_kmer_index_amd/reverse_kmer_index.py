@@ -68,10 +68,9 @@ class ReverseKmerIndex:
             n = flat_kmers.n
             if n == 0:
                 raise ValueError("zero-size array to reduction operation maximum which has no identity")
-            d_nodes, d_kmers, d_refs = flat_kmers.nodes, flat_kmers.hashes, flat_kmers.ref_offsets
-            max_node = int(d_nodes.to_host(n).max())
+            nodes, kmers, refs = flat_kmers.nodes, flat_kmers.hashes, flat_kmers.ref_offsets
+            max_node = int(nodes.to_host(n).max())
             kmer_dtype = ref_dtype = np.dtype(np.uint64)
-            owned = []
         else:
             nodes = np.asarray(flat_kmers._nodes)
             max_node = int(np.max(nodes))                   # raises on an empty input like the reference (:55)
@@ -79,15 +78,13 @@ class ReverseKmerIndex:
                 raise ValueError("node ids must be in 0..2^32-1")
             kmer_dtype, ref_dtype = np.asarray(flat_kmers._hashes).dtype, np.asarray(flat_kmers._ref_offsets).dtype
             n = len(nodes)
-            d_nodes = _lib.DeviceArray.from_host(np.ascontiguousarray(nodes).astype(np.uint32))
-            d_kmers = _lib.DeviceArray.from_host(_as_u64(flat_kmers._hashes, "hashes"))
-            d_refs = _lib.DeviceArray.from_host(_as_u64(flat_kmers._ref_offsets, "ref_offsets"))
-            owned = [d_nodes, d_kmers, d_refs]
+            kmers, refs = _as_u64(flat_kmers._hashes, "hashes"), _as_u64(flat_kmers._ref_offsets, "ref_offsets")
         logging.info("Max node: %d" % max_node)
         n_nodes = max_node + 1
-        index_pos, n_hashes = _lib.DeviceArray(n_nodes, np.uint32), _lib.DeviceArray(n_nodes, np.uint16)
-        out_kmers, out_refs = _lib.DeviceArray(n, np.uint64), _lib.DeviceArray(n, np.uint64)
-        try:
+        with _lib.DeviceScope() as s:
+            d_nodes, d_kmers, d_refs = s.on_device(nodes, np.uint32), s.on_device(kmers, np.uint64), s.on_device(refs, np.uint64)
+            index_pos, n_hashes = s.array(n_nodes, np.uint32), s.array(n_nodes, np.uint16)
+            out_kmers, out_refs = s.array(n, np.uint64), s.array(n, np.uint64)
             _lib.check(_lib.load().gki_reverse_index_build(d_nodes.ptr, d_kmers.ptr, d_refs.ptr, n, n_nodes, index_pos.ptr,
                                                            n_hashes.ptr, out_kmers.ptr, out_refs.ptr))
             cols = []
@@ -95,6 +92,3 @@ class ReverseKmerIndex:
                 h = d.to_host(n)
                 cols.append(h.view(dt) if dt.itemsize == 8 else h.astype(dt))
             return cls(index_pos.to_host(), n_hashes.to_host(), cols[0], cols[1])
-        finally:
-            for a in owned + [index_pos, n_hashes, out_kmers, out_refs]:
-                a.free()

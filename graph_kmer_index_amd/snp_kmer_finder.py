@@ -92,18 +92,16 @@ def linear_kmers_on_device(letters, k, spacing, seg_first, seg_count, with_rever
     _lib.check(lib.gki_linear_kmers(*args, None, None, None, None, 0, C.byref(n_out), None))
     n = n_out.value
     ms = (C.c_float * 2)() if kernel_ms is not None else None
-    if hashes_only:
-        out = _lib.DeviceArray(max(n, 1), np.uint64)
-        cols = (out.ptr, None, None, None)
-    else:
-        out = DeviceFlatKmers.allocate(n)
-        cols = (out.hashes.ptr, out.nodes.ptr, out.ref_offsets.ptr, out.allele_frequencies.ptr)
-    try:
+    with _lib.DeviceScope() as s:
+        if hashes_only:
+            out = s.array(n, np.uint64)
+            cols = (out.ptr, None, None, None)
+        else:
+            out = s.keep(DeviceFlatKmers.allocate(n))
+            cols = (out.hashes.ptr, out.nodes.ptr, out.ref_offsets.ptr, out.allele_frequencies.ptr)
         _lib.check(lib.gki_linear_kmers(*args, *cols, max(n, 1), C.byref(n_out), ms))
-    except Exception:
-        out.free()
-        raise
-    assert n_out.value == n
+        assert n_out.value == n
+        s.release(out)
     if kernel_ms is not None:
         kernel_ms[:] = [ms[0], ms[1]]
     return (out, n) if hashes_only else out
@@ -113,19 +111,15 @@ def make_linear_reference_flat_on_device(reference, k, spacing, genome_size, thr
                                          kernel_ms=None):
     """`make -R` (command_line_interface.py:105-153) as one device call: the reference's 10 * threads chunks in order, each
     followed by its own reverse complements when asked for."""
-    letters = reference if isinstance(reference, _lib.DeviceArray) else None
-    if letters is None:
+    if not isinstance(reference, _lib.DeviceArray):
         _lib.require_device()
-        host = reference_to_letters(reference)
-        if host.size == 0:
+        reference = reference_to_letters(reference)
+        if reference.size == 0:
             raise NoReferenceSequence("the reference sequence is empty")
-        letters = _lib.DeviceArray.from_host(host)
-    try:
+    with _lib.DeviceScope() as s:
+        letters = s.on_device(reference, np.uint8)
         first, count = segments_of_intervals(chunk_intervals(genome_size, spacing, max(1, int(threads))), letters.n, k, spacing)
         return linear_kmers_on_device(letters, k, spacing, first, count, include_reverse_complement, kernel_ms=kernel_ms)
-    finally:
-        if letters is not reference:
-            letters.free()
 
 
 class SnpKmerFinder:
@@ -166,25 +160,19 @@ class SnpKmerFinder:
             # the reference adds k to None here (snp_kmer_finder.py:301)
             raise TypeError("SnpKmerFinder on a linear reference needs end_position")
         _lib.require_device()
-        if isinstance(self.reference, _lib.DeviceArray):
-            letters, own = self.reference, False
-        else:
-            host = reference_to_letters(self.reference)
-            if host.size == 0:
+        reference = self.reference
+        if not isinstance(reference, _lib.DeviceArray):
+            reference = reference_to_letters(reference)
+            if reference.size == 0:
                 raise NoReferenceSequence("No reference sequence between positions %d and %d: the sequence is empty"
                                           % (self._start_position, self._end_position + self.k))
-            letters, own = _lib.DeviceArray.from_host(host), True
-        try:
+        with _lib.DeviceScope() as s:
+            letters = s.on_device(reference, np.uint8)
             first, count = segments_of_intervals([(self._start_position, self._end_position)], letters.n, self.k, self.spacing)
             return linear_kmers_on_device(letters, self.k, self.spacing, first, count)
-        finally:
-            if own:
-                letters.free()
 
     def find_kmers(self):
         if self.reference is not None:
             logging.warning("Will find kmers on linear reference and not graph")
-        dflat = self.find_kmers_on_device()
-        flat = dflat.to_flat_kmers()
-        dflat.free()
-        return flat
+        with _lib.DeviceScope() as s:
+            return s.keep(self.find_kmers_on_device()).to_flat_kmers()

@@ -69,26 +69,27 @@ def sample_kmers_from_structural_variants_on_device(graph, variant_to_nodes, kme
         counter, view = None, kmer_index_with_frequencies._device_index().view()
     t["host_prepare"] = time.perf_counter() - t0
     t1 = time.perf_counter()
-    d_cand = _lib.DeviceArray.from_host(cand) if len(cand) else _lib.DeviceArray(1, np.int32)
     n_rec, plan = _lib._I64(0), _lib.C.c_void_p()
     ms, ms_emit = (_lib.C.c_float * 2)(), (_lib.C.c_float * 1)()
-    try:
-        if counter is not None:
-            _lib.check(lib.gki_sv_sample_count_counter(dg.handle, counter.handle, d_cand.ptr, len(cand), k, max_frequency,
-                                                       None, _lib.C.byref(n_rec), _lib.C.byref(plan), ms))
-        else:
-            _lib.check(lib.gki_sv_sample_count(dg.handle, _lib.C.byref(view), d_cand.ptr, len(cand), k, max_frequency, None,
-                                               _lib.C.byref(n_rec), _lib.C.byref(plan), ms))
-        t["count"] = time.perf_counter() - t1
-        t2 = time.perf_counter()
-        out = DeviceFlatKmers.allocate(n_rec.value)
-        _lib.check(lib.gki_sv_sample_emit(plan, out.hashes.ptr, out.nodes.ptr, out.ref_offsets.ptr,
-                                          out.allele_frequencies.ptr, ms_emit))
-        t["emit"] = time.perf_counter() - t2
-    finally:
-        if plan.value:
-            lib.gki_sv_sample_destroy(plan)
-        d_cand.free()
+    with _lib.DeviceScope() as s:
+        d_cand = s.on_device(cand, np.int32)
+        try:
+            if counter is not None:
+                _lib.check(lib.gki_sv_sample_count_counter(dg.handle, counter.handle, d_cand.ptr, len(cand), k, max_frequency,
+                                                           None, _lib.C.byref(n_rec), _lib.C.byref(plan), ms))
+            else:
+                _lib.check(lib.gki_sv_sample_count(dg.handle, _lib.C.byref(view), d_cand.ptr, len(cand), k, max_frequency,
+                                                   None, _lib.C.byref(n_rec), _lib.C.byref(plan), ms))
+            t["count"] = time.perf_counter() - t1
+            t2 = time.perf_counter()
+            out = s.keep(DeviceFlatKmers.allocate(n_rec.value))
+            _lib.check(lib.gki_sv_sample_emit(plan, out.hashes.ptr, out.nodes.ptr, out.ref_offsets.ptr,
+                                              out.allele_frequencies.ptr, ms_emit))
+            t["emit"] = time.perf_counter() - t2
+        finally:
+            if plan.value:
+                lib.gki_sv_sample_destroy(plan)
+        s.release(out)
     t["kernel_ms"] = {"probe": float(ms[0]), "greedy_count": float(ms[1]), "greedy_emit_and_records": float(ms_emit[0])}
     last_timings = t
     last_counts = dict(pairs=len(nodes) // 2, candidates=int(len(cand)), records=int(n_rec.value),
@@ -99,9 +100,9 @@ def sample_kmers_from_structural_variants_on_device(graph, variant_to_nodes, kme
 def sample_kmers_from_structural_variants(graph, variant_to_nodes, kmer_index_with_frequencies, k, max_frequency=2):
     """structural_variants.py:6-43: FlatKmers(hashes uint64, nodes uint32, ref_offsets uint32 all 0)."""
     t0 = time.perf_counter()
-    d = sample_kmers_from_structural_variants_on_device(graph, variant_to_nodes, kmer_index_with_frequencies, k,
-                                                        max_frequency)
-    flat = FlatKmers(d.hashes.to_host(d.n), d.nodes.to_host(d.n), np.zeros(d.n, dtype=np.uint32))
-    d.free()
+    with _lib.DeviceScope() as s:
+        d = s.keep(sample_kmers_from_structural_variants_on_device(graph, variant_to_nodes, kmer_index_with_frequencies, k,
+                                                                   max_frequency))
+        flat = FlatKmers(d.hashes.to_host(d.n), d.nodes.to_host(d.n), np.zeros(d.n, dtype=np.uint32))
     last_timings["end_to_end"] = time.perf_counter() - t0
     return flat

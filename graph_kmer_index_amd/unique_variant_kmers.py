@@ -260,7 +260,7 @@ class UniqueVariantKmersFinder:
 
     def _device_graph(self, arrays):
         """The graph in HBM with the position ids of `position_id_index`: the package's cached upload when they are the
-        default ones, otherwise an upload owned by this finder."""
+        default ones, otherwise an upload of this finder's own."""
         if self._dg is not None and self._dg[0] is arrays:
             return self._dg[1]
         dg = _graph_on_device(arrays, self._position_id_index)
@@ -326,67 +326,66 @@ class UniqueVariantKmersFinder:
             _lib.check(lib.gki_device_synchronize())
             t[name] = time.perf_counter() - t_start
 
-        # 1. start positions
-        t1 = time.perf_counter()
-        h = _lib.DeviceArray.from_host
-        d_lin_start, d_lin_node, d_ro = h(lin.starts), h(lin.nodes), h(ref_offsets)
-        n_pos = n_var * P
-        d_nodes, d_offs, d_var = (_lib.DeviceArray(n_pos, np.int32) for _ in range(3))
-        bad = _lib._I64(-1)
-        _lib.check(lib.gki_uvk_starts(dg.handle, d_lin_start.ptr, d_lin_node.ptr, len(lin.nodes), d_ro.ptr, n_var, P,
-                                      d_nodes.ptr, d_offs.ptr, d_var.ptr, _lib.C.byref(bad)))
-        sync_time("starts", t1)
-        if bad.value >= 0:
-            raise _outside_linear_reference(va, int(active[bad.value]))
-        self._check_against_obgraph(lin, va, active, ref_offsets, d_nodes, d_offs, P)
-        # 2. the forward search over all starts, no store filter
-        t2 = time.perf_counter()
-        d_rec = _lib.DeviceArray(n_pos + 1, np.int64)
-        n_rec = _lib._I64(0)
-        args = (dg.handle, self.k, self._max_variant_nodes, 0, None, d_nodes.ptr, d_offs.ptr, n_pos)
-        _lib.check(lib.gki_forward_count(*args, d_rec.ptr, _lib.C.byref(n_rec)))
-        cols = [_lib.DeviceArray(max(n_rec.value, 1), d) for d in (np.int64, np.int32, np.int16, np.int32, np.float64)]
-        if n_rec.value:
-            _lib.check(lib.gki_forward_emit(*args, d_rec.ptr, *[c.ptr for c in cols]))
-        sync_time("search", t2)
-        d_hashes, d_snodes, d_soffs, d_rnodes, d_af = cols
-        # 3. summaries with the fused frequency probe
-        t3 = time.perf_counter()
-        d_ref, d_alt = h(ref), h(alt)
-        d_summ = _lib.DeviceArray(n_pos * SUMMARY_DTYPE.itemsize, np.uint8)
-        source = self._kmer_index_with_frequencies
-        cols_and_nodes = (d_rec.ptr, n_var, P, d_hashes.ptr, d_snodes.ptr, d_soffs.ptr, d_rnodes.ptr, d_ref.ptr, d_alt.ptr,
-                          d_summ.ptr)
-        if isinstance(source, KmerCounter):              # the count of the hash alone: no reverse complement added
-            _lib.check(lib.gki_uvk_summarize_counter(dg.handle, source._device_counter().handle, *cols_and_nodes))
-        else:
-            view = source._device_index().view()
-            _lib.check(lib.gki_uvk_summarize(dg.handle, _lib.C.byref(view), *cols_and_nodes))
-        t["summarize"] = time.perf_counter() - t3
-        # 4. selection; variants sharing a node with another variant of their chunk resolved in order on the host
-        t4 = time.perf_counter()
-        mask = self._store_masks(active, ref, alt, d_summ, n_var, P)
-        d_mask = None if mask is None else h(mask)
-        d_choice = _lib.DeviceArray(n_var, np.int32)
-        d_out_start = _lib.DeviceArray(n_var + 1, np.int64)
-        n_out = _lib._I64(0)
-        _lib.check(lib.gki_uvk_select(d_summ.ptr, n_var, P, int(self._choose_kmers_with_lowest_frequencies),
-                                      None if d_mask is None else d_mask.ptr, d_choice.ptr, d_out_start.ptr,
-                                      _lib.C.byref(n_out)))
-        t["select"] = time.perf_counter() - t4
-        # 5. gather
-        t5 = time.perf_counter()
-        out = DeviceFlatKmers.allocate(n_out.value)
-        out.n = n_out.value
-        if n_out.value:
-            _lib.check(lib.gki_uvk_emit(dg.handle, d_rec.ptr, n_var, P, d_choice.ptr,
-                                        None if d_mask is None else d_mask.ptr, d_ref.ptr, d_alt.ptr, d_out_start.ptr,
-                                        d_hashes.ptr, d_snodes.ptr, d_soffs.ptr, d_rnodes.ptr, d_af.ptr, out.hashes.ptr,
-                                        out.nodes.ptr, out.ref_offsets.ptr, out.allele_frequencies.ptr))
-        t["emit"] = time.perf_counter() - t5
-        for b in [d_lin_start, d_lin_node, d_ro, d_nodes, d_offs, d_var, d_rec, d_ref, d_alt, d_summ, d_choice,
-                  d_out_start] + cols + ([] if d_mask is None else [d_mask]):
-            b.free()
+        with _lib.DeviceScope() as s:
+            # 1. start positions
+            t1 = time.perf_counter()
+            h = lambda a: s.on_device(a, a.dtype)
+            d_lin_start, d_lin_node, d_ro = h(lin.starts), h(lin.nodes), h(ref_offsets)
+            n_pos = n_var * P
+            d_nodes, d_offs, d_var = (s.array(n_pos, np.int32) for _ in range(3))
+            bad = _lib._I64(-1)
+            _lib.check(lib.gki_uvk_starts(dg.handle, d_lin_start.ptr, d_lin_node.ptr, len(lin.nodes), d_ro.ptr, n_var, P,
+                                          d_nodes.ptr, d_offs.ptr, d_var.ptr, _lib.C.byref(bad)))
+            sync_time("starts", t1)
+            if bad.value >= 0:
+                raise _outside_linear_reference(va, int(active[bad.value]))
+            self._check_against_obgraph(lin, va, active, ref_offsets, d_nodes, d_offs, P)
+            # 2. the forward search over all starts, no store filter
+            t2 = time.perf_counter()
+            d_rec = s.array(n_pos + 1, np.int64)
+            n_rec = _lib._I64(0)
+            args = (dg.handle, self.k, self._max_variant_nodes, 0, None, d_nodes.ptr, d_offs.ptr, n_pos)
+            _lib.check(lib.gki_forward_count(*args, d_rec.ptr, _lib.C.byref(n_rec)))
+            cols = [s.array(n_rec.value, d) for d in (np.int64, np.int32, np.int16, np.int32, np.float64)]
+            if n_rec.value:
+                _lib.check(lib.gki_forward_emit(*args, d_rec.ptr, *[c.ptr for c in cols]))
+            sync_time("search", t2)
+            d_hashes, d_snodes, d_soffs, d_rnodes, d_af = cols
+            # 3. summaries with the fused frequency probe
+            t3 = time.perf_counter()
+            d_ref, d_alt = h(ref), h(alt)
+            d_summ = s.array(n_pos * SUMMARY_DTYPE.itemsize, np.uint8)
+            source = self._kmer_index_with_frequencies
+            cols_and_nodes = (d_rec.ptr, n_var, P, d_hashes.ptr, d_snodes.ptr, d_soffs.ptr, d_rnodes.ptr, d_ref.ptr, d_alt.ptr,
+                              d_summ.ptr)
+            if isinstance(source, KmerCounter):              # the count of the hash alone: no reverse complement added
+                _lib.check(lib.gki_uvk_summarize_counter(dg.handle, source._device_counter().handle, *cols_and_nodes))
+            else:
+                view = source._device_index().view()
+                _lib.check(lib.gki_uvk_summarize(dg.handle, _lib.C.byref(view), *cols_and_nodes))
+            t["summarize"] = time.perf_counter() - t3
+            # 4. selection; variants sharing a node with another variant of their chunk resolved in order on the host
+            t4 = time.perf_counter()
+            mask = self._store_masks(active, ref, alt, d_summ, n_var, P)
+            d_mask = None if mask is None else h(mask)
+            d_choice = s.array(n_var, np.int32)
+            d_out_start = s.array(n_var + 1, np.int64)
+            n_out = _lib._I64(0)
+            _lib.check(lib.gki_uvk_select(d_summ.ptr, n_var, P, int(self._choose_kmers_with_lowest_frequencies),
+                                          None if d_mask is None else d_mask.ptr, d_choice.ptr, d_out_start.ptr,
+                                          _lib.C.byref(n_out)))
+            t["select"] = time.perf_counter() - t4
+            # 5. gather
+            t5 = time.perf_counter()
+            out = s.keep(DeviceFlatKmers.allocate(n_out.value))
+            out.n = n_out.value
+            if n_out.value:
+                _lib.check(lib.gki_uvk_emit(dg.handle, d_rec.ptr, n_var, P, d_choice.ptr,
+                                            None if d_mask is None else d_mask.ptr, d_ref.ptr, d_alt.ptr, d_out_start.ptr,
+                                            d_hashes.ptr, d_snodes.ptr, d_soffs.ptr, d_rnodes.ptr, d_af.ptr, out.hashes.ptr,
+                                            out.nodes.ptr, out.ref_offsets.ptr, out.allele_frequencies.ptr))
+            t["emit"] = time.perf_counter() - t5
+            s.release(out)
         self.last_timings = t
         self.last_counts = dict(variants=len(va), active=n_var, starts=n_pos, search_records=int(n_rec.value),
                                 chosen=int(n_out.value), serial=self.last_serial_variants)
@@ -426,9 +425,8 @@ class UniqueVariantKmersFinder:
     def find_unique_kmers(self):
         """unique_variant_kmers.py:243-270: the chosen k-mers of every variant, in variant order (FlatKmers)."""
         t0 = time.perf_counter()
-        d = self.find_unique_kmers_on_device()
-        flat = d.to_flat_kmers()
-        d.free()
+        with _lib.DeviceScope() as s:
+            flat = s.keep(self.find_unique_kmers_on_device()).to_flat_kmers()
         self.last_timings["end_to_end"] = time.perf_counter() - t0
         logging.info("N variants with kmers found: %d" % self.last_counts.get("active", 0))
         return flat
@@ -444,12 +442,11 @@ class UniqueVariantKmersFinder:
         va = VariantArrays([variant.position], np.array([variant.chromosome], dtype=object), [0],
                            [-1 if getattr(variant, "type", None) is None else int(variant.type == "SNP")])
         one = variant_node is None
-        d, _ = _simple_selection(self.graph, va, np.array([ref_node], np.int64),
-                                 np.array([ref_node if one else variant_node], np.int64), self.k, self._max_variant_nodes,
-                                 self._position_id_index, n_searches=1 if one else 2, skip_zero_nodes=False)
-        flat = d.to_flat_kmers()
-        d.free()
-        return flat
+        with _lib.DeviceScope() as s:
+            return s.keep(_simple_selection(
+                self.graph, va, np.array([ref_node], np.int64), np.array([ref_node if one else variant_node], np.int64),
+                self.k, self._max_variant_nodes, self._position_id_index, n_searches=1 if one else 2,
+                skip_zero_nodes=False)[0]).to_flat_kmers()
 
 
 def _simple_selection(graph, va, ref_all, alt_all, k, max_variant_nodes, position_id_index, n_searches=None,
@@ -479,20 +476,14 @@ def _simple_selection(graph, va, ref_all, alt_all, k, max_variant_nodes, positio
     ref_offsets = _graph_ref_offsets(lin, va, active)
     dg = _graph_on_device(arrays, position_id_index)
     t["host_prepare"] = time.perf_counter() - t0
-    buffers = []
-
-    def keep(b):
-        buffers.append(b)
-        return b
-
-    try:
+    with _lib.DeviceScope() as s:
         # 1. the start and the target of both searches of every variant
         t1 = time.perf_counter()
-        h = _lib.DeviceArray.from_host
-        d_lin_start, d_lin_node, d_ro = keep(h(lin.starts)), keep(h(lin.nodes)), keep(h(ref_offsets))
-        d_snp, d_ref, d_alt = keep(h(is_snp)), keep(h(ref)), keep(h(alt))
+        h = lambda a: s.on_device(a, a.dtype)
+        d_lin_start, d_lin_node, d_ro = h(lin.starts), h(lin.nodes), h(ref_offsets)
+        d_snp, d_ref, d_alt = h(is_snp), h(ref), h(alt)
         n_pos = 2 * n_var
-        d_nodes, d_offs, d_targets = (keep(_lib.DeviceArray(n_pos, np.int32)) for _ in range(3))
+        d_nodes, d_offs, d_targets = (s.array(n_pos, np.int32) for _ in range(3))
         bad = _lib._I64(-1)
         _lib.check(lib.gki_uvk_simple_starts(dg.handle, d_lin_start.ptr, d_lin_node.ptr, len(lin.nodes), d_ro.ptr, d_snp.ptr,
                                              d_ref.ptr, d_alt.ptr, n_var, d_nodes.ptr, d_offs.ptr, d_targets.ptr,
@@ -504,24 +495,18 @@ def _simple_selection(graph, va, ref_all, alt_all, k, max_variant_nodes, positio
             n_pos = min(n_pos, int(n_searches))
         # 2. the per-node search: count, then the FlatKmers columns straight from the walk
         t2 = time.perf_counter()
-        d_rec = keep(_lib.DeviceArray(n_pos + 1, np.int64))
+        d_rec = s.array(n_pos + 1, np.int64)
         n_rec = _lib._I64(0)
         args = (dg.handle, int(k), int(max_variant_nodes), d_targets.ptr, d_nodes.ptr, d_offs.ptr, n_pos, d_rec.ptr)
         _lib.check(lib.gki_forward_node_count(*args, _lib.C.byref(n_rec)))
         t["count"] = time.perf_counter() - t2
         t3 = time.perf_counter()
-        out = DeviceFlatKmers.allocate(n_rec.value)
+        out = s.keep(DeviceFlatKmers.allocate(n_rec.value))
         if n_rec.value:
-            try:
-                _lib.check(lib.gki_forward_node_emit(*args, out.hashes.ptr, out.nodes.ptr, out.ref_offsets.ptr,
-                                                     out.allele_frequencies.ptr))
-            except Exception:
-                out.free()
-                raise
+            _lib.check(lib.gki_forward_node_emit(*args, out.hashes.ptr, out.nodes.ptr, out.ref_offsets.ptr,
+                                                 out.allele_frequencies.ptr))
         t["emit"] = time.perf_counter() - t3
-    finally:
-        for b in buffers:
-            b.free()
+        s.release(out)
     facts.update(searches=n_pos, records=int(n_rec.value))
     return out, facts
 
@@ -542,7 +527,6 @@ def find_kmers_over_variants(graph, variant_to_nodes, variants, k=31, max_varian
     k-mers of the search for its ref node, then of the search for its alt node -- FlatKmers, hash / node / position id of
     the k-mer's end / minimum allele frequency of its path.  position_id_index None: the graph's default position ids
     (PositionId.from_graph).  One device batch; no frequency source."""
-    d = find_kmers_over_variants_on_device(graph, variant_to_nodes, variants, k, max_variant_nodes, position_id_index)
-    flat = d.to_flat_kmers()
-    d.free()
-    return flat
+    with _lib.DeviceScope() as s:
+        return s.keep(find_kmers_over_variants_on_device(graph, variant_to_nodes, variants, k, max_variant_nodes,
+                                                         position_id_index)).to_flat_kmers()

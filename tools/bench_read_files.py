@@ -16,7 +16,7 @@ temporary directory as a FASTA and as a FASTQ file (fixed-width names, constant 
                                   host route (Python's gzip, which reads BGZF as multi-member gzip: what a .gz file took
                                   before the device inflate) and the device route end to end, and the device route with a
                                   clock around each stage: file read with the member scan (and, beside it, the scan alone over
-                                  the same pieces), upload, inflate (the whole inflate_on_device call, and the inflate
+                                  the same pieces), upload, inflate (the whole read_files.inflate_piece call, and the inflate
                                   kernel's own device time from gki_bgzf_inflate_kernel_ms with GB/s of its output), line
                                   cut, parse, probe.
 All routes' counts are checked equal.  Prints one JSON object and a few summary lines."""
@@ -26,7 +26,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 from graph_kmer_index_amd import _lib, DenseKmerFinder, CriticalGraphPaths, bgzf, read_files
 from graph_kmer_index_amd.flat_kmers import DeviceFlatKmers
-from graph_kmer_index_amd.collision_free_kmer_index import DeviceIndex
+from graph_kmer_index_amd.collision_free_kmer_index import DeviceIndex, zeroed_counts
 from graph_kmer_index_amd.graph import synthetic_snp_graph, synthetic_haplotype_sequence
 
 READ_LEN = 150
@@ -75,14 +75,15 @@ def host_lines_then_map_reads(idx, path, k, n_nodes, max_hits):
 
 
 def staged_file_route(idx, path, k, n_nodes, max_hits, chunk_bytes):
-    """read_files.count_nodes_from_file's loop with a clock around each stage, and the device copy of every piece."""
+    """read_files.count_nodes_from_file's steps on the pieces of `iter_line_chunks`, with a clock around each stage, and
+    the device copy of every piece."""
     lib = _lib.load()
     sync = lambda: _lib.check(lib.gki_device_synchronize())
     st = dict(file_read_s=0.0, upload_s=0.0, parse_count_s=0.0, parse_emit_s=0.0, probe_s=0.0, device_copy_s=0.0)
-    counts = _lib.DeviceArray(n_nodes, np.uint32); counts.zero()
     code, phase, n_reads, n_bytes = None, 0, 0, 0
     t_all = time.perf_counter()
-    with read_files.open_reads_file(path) as f:
+    with _lib.DeviceScope() as run, read_files.open_reads_file(path) as f:
+        counts = zeroed_counts(run, n_nodes)
         pieces = read_files.iter_line_chunks(f, chunk_bytes)
         while True:
             t = time.perf_counter()
@@ -92,62 +93,62 @@ def staged_file_route(idx, path, k, n_nodes, max_hits, chunk_bytes):
                 break
             if code is None:
                 code = read_files.FORMATS[read_files.detect_format(piece)]
-            t = time.perf_counter()
-            d = _lib.DeviceArray.from_host(np.frombuffer(piece, dtype=np.uint8)); sync()
-            st["upload_s"] += time.perf_counter() - t
-            n_bytes += d.n
-            t = time.perf_counter()
-            lines, reads, n_letters, bad = read_files._count(d, d.n, code, phase)
-            st["parse_count_s"] += time.perf_counter() - t
-            assert bad == 0
-            t = time.perf_counter()
-            letters = _lib.DeviceArray(max(n_letters, 1), np.uint8)
-            read_start = _lib.DeviceArray(reads + 1, np.int64)
-            _lib.check(lib.gki_reads_parse_emit(d.ptr, d.n, code, phase, letters.ptr, n_letters, read_start.ptr, reads + 1)); sync()
-            st["parse_emit_s"] += time.perf_counter() - t
-            t = time.perf_counter()
-            idx.count_nodes_from_reads(letters, read_start, k, n_nodes, 3, max_hits, counts); sync()
-            st["probe_s"] += time.perf_counter() - t
-            letters.free(); read_start.free()
-            other = _lib.DeviceArray(d.n, np.uint8); sync()
-            t = time.perf_counter()
-            _lib.check(lib.gki_memcpy_d2d(other.ptr, d.ptr, d.n)); sync()
-            st["device_copy_s"] += time.perf_counter() - t
-            other.free(); d.free()
+            with _lib.DeviceScope() as s:
+                t = time.perf_counter()
+                d = s.keep(read_files.upload_piece(piece)); sync()
+                st["upload_s"] += time.perf_counter() - t
+                n_bytes += d.n
+                t = time.perf_counter()
+                lines, reads, n_letters, bad = read_files.parse_count(d, d.n, code, phase)
+                st["parse_count_s"] += time.perf_counter() - t
+                assert bad == 0
+                t = time.perf_counter()
+                letters, read_start = map(s.keep, read_files.parse_emit(d, d.n, code, phase, reads, n_letters)); sync()
+                st["parse_emit_s"] += time.perf_counter() - t
+                t = time.perf_counter()
+                idx.count_nodes_from_reads(letters, read_start, k, n_nodes, 3, max_hits, counts); sync()
+                st["probe_s"] += time.perf_counter() - t
+                letters.free(); read_start.free()
+                other = s.array(d.n, np.uint8); sync()
+                t = time.perf_counter()
+                _lib.check(lib.gki_memcpy_d2d(other.ptr, d.ptr, d.n)); sync()
+                st["device_copy_s"] += time.perf_counter() - t
             n_reads += reads
             phase = (phase + lines) % 4
-    st["s"] = time.perf_counter() - t_all - st["device_copy_s"]
-    st["reads"], st["file_bytes"] = n_reads, n_bytes
-    out = counts.to_host(n_nodes)
-    counts.free()
-    return out, st
+        st["s"] = time.perf_counter() - t_all - st["device_copy_s"]
+        st["reads"], st["file_bytes"] = n_reads, n_bytes
+        return counts.to_host(n_nodes), st
 
 
 def staged_bgzf_route(idx, path, k, n_nodes, max_hits, chunk_bytes):
-    """read_files._count_nodes_from_bgzf's loop with a clock around each stage."""
+    """read_files.bgzf_text_pieces' steps and count_nodes_from_file's with a clock around each stage.  inflate_s is the
+    whole `inflate_piece` call (inflate_on_device and the copy of the tail, less than one line, to its front), line_cut_s
+    the whole `cut_at_line_end` call (the search for the last line end and the copy of what follows it, less than one
+    line, into the next tail)."""
     lib = _lib.load()
     sync = lambda: _lib.check(lib.gki_device_synchronize())
     st = dict(file_read_s=0.0, member_scan_s=0.0, upload_s=0.0, inflate_s=0.0, inflate_kernel_s=0.0, line_cut_s=0.0, parse_s=0.0,
               probe_s=0.0)
-    counts = _lib.DeviceArray(n_nodes, np.uint32); counts.zero()
     code, phase, n_reads, n_out, tail = None, 0, 0, 0, None
     kernel_ms = C.c_float(0)
 
     def parse_and_probe(d, n):
         nonlocal phase, n_reads
-        t = time.perf_counter()
-        letters, read_start, reads, lines, bad = read_files._parse(d, n, code, phase); sync()
-        st["parse_s"] += time.perf_counter() - t
-        assert bad == 0
-        t = time.perf_counter()
-        idx.count_nodes_from_reads(letters, read_start, k, n_nodes, 3, max_hits, counts); sync()
-        st["probe_s"] += time.perf_counter() - t
-        letters.free(); read_start.free()
+        with _lib.DeviceScope() as s:
+            t = time.perf_counter()
+            letters, read_start, reads, lines, bad = read_files.parse_piece(d, n, code, phase); sync()
+            s.keep(letters), s.keep(read_start)
+            st["parse_s"] += time.perf_counter() - t
+            assert bad == 0
+            t = time.perf_counter()
+            idx.count_nodes_from_reads(letters, read_start, k, n_nodes, 3, max_hits, counts); sync()
+            st["probe_s"] += time.perf_counter() - t
         n_reads += reads
         phase = (phase + lines) % 4
 
     t_all = time.perf_counter()
-    with open(path, "rb") as f:
+    with _lib.DeviceScope() as run, open(path, "rb") as f:
+        counts = zeroed_counts(run, n_nodes)
         pieces = read_files.iter_bgzf_pieces(f, chunk_bytes, path)
         while True:
             t = time.perf_counter()
@@ -155,42 +156,36 @@ def staged_bgzf_route(idx, path, k, n_nodes, max_hits, chunk_bytes):
             st["file_read_s"] += time.perf_counter() - t
             if item is None:
                 break
-            piece, members, _ = item
+            piece, members, base = item
             t = time.perf_counter()
             assert len(bgzf.scan_all(piece)[0]) == len(members)                # the scan again, alone: its share of file_read_s
             st["member_scan_s"] += time.perf_counter() - t
-            t = time.perf_counter()
-            d = _lib.DeviceArray.from_host(np.frombuffer(piece, dtype=np.uint8)); sync()
-            st["upload_s"] += time.perf_counter() - t
-            prefix = tail.n if tail is not None else 0
-            t = time.perf_counter()
-            text = bgzf.inflate_on_device(d, members, prefix); sync()
-            st["inflate_s"] += time.perf_counter() - t
-            _lib.check(lib.gki_bgzf_inflate_kernel_ms(C.byref(kernel_ms)))
-            st["inflate_kernel_s"] += kernel_ms.value * 1e-3
-            d.free()
-            n_out += text.n - prefix
-            if prefix:
-                _lib.check(lib.gki_memcpy_d2d(text.ptr, tail.ptr, prefix)); tail.free()
-            tail = None
-            if code is None:
-                code = read_files.FORMATS[read_files.detect_format(text.to_host(1))]
-            t = time.perf_counter()
-            cut = read_files._last_newline(text, text.n) + 1
-            st["line_cut_s"] += time.perf_counter() - t
-            if cut:
-                parse_and_probe(text, cut)
-            if cut < text.n:
-                tail = _lib.DeviceArray(text.n - cut, np.uint8)
-                _lib.check(lib.gki_memcpy_d2d(tail.ptr, text.ptr.value + cut, text.n - cut))
-            text.free()
-    if tail is not None:
-        parse_and_probe(tail, tail.n); tail.free()
-    st["s"] = time.perf_counter() - t_all - st["member_scan_s"]
-    st["reads"], st["inflated_bytes"] = n_reads, n_out
-    out = counts.to_host(n_nodes)
-    counts.free()
-    return out, st
+            with _lib.DeviceScope() as s:
+                t = time.perf_counter()
+                d = s.keep(read_files.upload_piece(piece)); sync()
+                st["upload_s"] += time.perf_counter() - t
+                prefix = tail.n if tail is not None else 0
+                t = time.perf_counter()
+                text = s.keep(read_files.inflate_piece(d, members, base, tail, path)); sync()
+                st["inflate_s"] += time.perf_counter() - t
+                _lib.check(lib.gki_bgzf_inflate_kernel_ms(C.byref(kernel_ms)))
+                st["inflate_kernel_s"] += kernel_ms.value * 1e-3
+                d.free()
+                n_out += text.n - prefix
+                if code is None:
+                    code = read_files.FORMATS[read_files.detect_format(text.to_host(1))]
+                t = time.perf_counter()
+                cut, tail = read_files.cut_at_line_end(text)
+                st["line_cut_s"] += time.perf_counter() - t
+                if tail is not None:
+                    run.keep(tail)
+                if cut:
+                    parse_and_probe(text, cut)
+        if tail is not None:
+            parse_and_probe(tail, tail.n)
+        st["s"] = time.perf_counter() - t_all - st["member_scan_s"]
+        st["reads"], st["inflated_bytes"] = n_reads, n_out
+        return counts.to_host(n_nodes), st
 
 
 def median_of(runs):
