@@ -13,13 +13,14 @@ __device__ __forceinline__ uint32_t pack4(uint32_t x) {
     return (x | (x >> 12)) & 0xFFu;
 }
 
-__global__ __launch_bounds__(256) void k_pack_2bit(const uint8_t *__restrict__ seq, int64_t n_bases,
+// aligned16: seq is 16-byte aligned (uniform, from gki_launch_pack); any other pointer takes the byte loads throughout
+__global__ __launch_bounds__(256) void k_pack_2bit(const uint8_t *__restrict__ seq, int64_t n_bases, int aligned16,
                                                    uint32_t *__restrict__ seq2_u32, int64_t n_u32) {
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_u32; i += stride) {
         int64_t b = i * 16;
         uint32_t r;
-        if (b + 16 <= n_bases) {
+        if (aligned16 && b + 16 <= n_bases) {
             uint4 v = *reinterpret_cast<const uint4 *>(seq + b);     // 16 B per lane, coalesced
             r = pack4(v.x & 0x03030303u) | (pack4(v.y & 0x03030303u) << 8) |
                 (pack4(v.z & 0x03030303u) << 16) | (pack4(v.w & 0x03030303u) << 24);
@@ -71,7 +72,8 @@ __global__ __launch_bounds__(256) void k_popcount(const uint64_t *__restrict__ m
 int gki_launch_pack(const uint8_t *d_seq, int64_t n_bases, uint32_t *d_out, hipStream_t s) {
     int64_t n_u32 = ceil_div(n_bases, 16);
     if (n_u32 <= 0) return GKI_OK;
-    hipLaunchKernelGGL(k_pack_2bit, dim3(stream_grid(n_u32, 256)), dim3(256), 0, s, d_seq, n_bases, d_out, n_u32);
+    const int aligned16 = (reinterpret_cast<uintptr_t>(d_seq) & 15) == 0;
+    hipLaunchKernelGGL(k_pack_2bit, dim3(stream_grid(n_u32, 256)), dim3(256), 0, s, d_seq, n_bases, aligned16, d_out, n_u32);
     HIP_TRY(hipGetLastError());
     return GKI_OK;
 }

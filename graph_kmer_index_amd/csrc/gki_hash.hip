@@ -29,12 +29,16 @@ __global__ __launch_bounds__(256) void k_complement(const uint64_t *__restrict__
     }
 }
 
+// cnt is 32 bits wide: a read with more k-mers than that is flagged (as k_parse_classify flags a line of 2^32 letters)
+// and the call refused, instead of its count stored modulo 2^32
 __global__ __launch_bounds__(256) void k_read_counts(const int64_t *__restrict__ read_start, int64_t n_reads, int k,
-                                                     uint32_t *__restrict__ cnt) {
+                                                     uint32_t *__restrict__ cnt, unsigned int *__restrict__ too_long) {
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_reads; r += stride) {
         int64_t len = read_start[r + 1] - read_start[r];
-        cnt[r] = len >= k ? (uint32_t)(len - k + 1) : 0u;
+        int64_t c = len >= k ? len - k + 1 : 0;
+        if (c > 0xFFFFFFFFll) { atomicOr(too_long, 1u); c = 0; }
+        cnt[r] = (uint32_t)c;
     }
 }
 
@@ -123,14 +127,20 @@ int gki_hash_reads(const void *d_reads, const void *d_read_start, int64_t n_read
     if (n_reads <= 0) { HIP_TRY(hipMemset(d_out_start, 0, 8)); return GKI_OK; }
     int64_t total = 0;
     {
-        DevBuf cnt, tmp;                               // freed before the hashing pass
+        DevBuf cnt, tmp, flag;                         // freed before the hashing pass
         int64_t tmp_bytes = gki_scan_tmp_bytes(n_reads);
+        unsigned int too_long = 0;
         HIP_TRY(cnt.alloc((size_t)n_reads * 4));
         HIP_TRY(tmp.alloc((size_t)tmp_bytes));
+        HIP_TRY(flag.alloc(4));
+        HIP_TRY(hipMemsetAsync(flag.get(), 0, 4, 0));
         hipLaunchKernelGGL(k_read_counts, dim3(stream_grid(n_reads, 256)), dim3(256), 0, 0, (const int64_t *)d_read_start,
-                           n_reads, k, cnt.get<uint32_t>());
+                           n_reads, k, cnt.get<uint32_t>(), flag.get<unsigned int>());
+        HIP_TRY(hipGetLastError());
         GKI_TRY(gki_scan_u32_to_i64(cnt.get<const uint32_t>(), n_reads, (int64_t *)d_out_start, tmp.get(), tmp_bytes, 0));
         HIP_TRY(hipMemcpy(&total, (const int64_t *)d_out_start + n_reads, 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&too_long, flag.get(), 4, hipMemcpyDeviceToHost));
+        if (too_long) return gki_set_error(GKI_ERR_BAD_ARG, "hash_reads: a read of more than 2^32 - 1 k-mers");
     }
     *n_out = total;
     if (d_out == nullptr) return GKI_OK;               // count only

@@ -407,3 +407,21 @@ int gki_scan_i32_to_i64(const int32_t *d_in, int64_t n, int64_t *d_out, void *d_
 int gki_scan_u32_to_u32(const uint32_t *d_in, int64_t n, uint32_t *d_out, void *d_tmp, int64_t tmp_bytes, hipStream_t s) {
     return scan_impl<uint32_t, int64_t, uint32_t>(d_in, n, d_out, d_tmp, tmp_bytes, s);
 }
+
+extern "C" {
+
+// Checking aid: the scans above are internal, this is the one way to run them alone (tests/test_gpu_runtime_primitives.py)
+int gki_exclusive_scan(const void *d_in, int64_t n, int kind, void *d_out) {
+    if (kind < 0 || kind > 2) return gki_set_error(GKI_ERR_BAD_ARG, "exclusive_scan: kind must be 0, 1 or 2");
+    if (n < 0) return gki_set_error(GKI_ERR_BAD_ARG, "exclusive_scan: negative n");
+    const int64_t tmp_bytes = gki_scan_tmp_bytes(n);
+    DevBuf tmp;
+    HIP_TRY(tmp.alloc((size_t)tmp_bytes));
+    if (kind == 0) GKI_TRY(gki_scan_u32_to_i64((const uint32_t *)d_in, n, (int64_t *)d_out, tmp.get(), tmp_bytes, 0));
+    else if (kind == 1) GKI_TRY(gki_scan_i32_to_i64((const int32_t *)d_in, n, (int64_t *)d_out, tmp.get(), tmp_bytes, 0));
+    else GKI_TRY(gki_scan_u32_to_u32((const uint32_t *)d_in, n, (uint32_t *)d_out, tmp.get(), tmp_bytes, 0));
+    HIP_TRY(hipStreamSynchronize(0));
+    return GKI_OK;
+}
+
+}  // extern "C"

@@ -71,6 +71,12 @@ int gki_mem_info(int64_t *free_bytes, int64_t *total_bytes);
 /* Order-independent checksums of a device column of n elements of 1, 2, 4 or 8 bytes (zero-extended): sum mod 2^64 and
  * xor.  Lets a caller check that two layouts / a set of shards hold the same multiset without copying it back. */
 int gki_column_checksum(const void *d_column, int64_t n, int elem_bytes, uint64_t *sum, uint64_t *xor_fold);
+/* Checking aid: the library's internal exclusive scan run alone, for tests that compare it with a host prefix sum (no
+ * feature needs the call).  d_out[i] = d_in[0] + .. + d_in[i - 1] for i = 0..n, so d_out has n + 1 entries and
+ * d_out[n] is the total.  kind 0: uint32 -> int64, 1: int32 -> int64, 2: uint32 -> uint32 (modulo 2^32).  Allocates its
+ * own temporary, runs on stream 0 and returns when the result is there; n == 0 writes d_out[0] = 0.
+ * GKI_ERR_BAD_ARG for another kind or a negative n. */
+int gki_exclusive_scan(const void *d_in, int64_t n, int kind, void *d_out);
 /* FlatKmers.get_new_without_singletons (flat_kmers.py:98-125): d_flags uint8[n] = 1 for every record whose hash also
  * occurs at an earlier position (the first occurrence of each hash gets 0); follow with gki_compact_flat. */
 int gki_flag_repeated_kmers(const void *d_kmers, int64_t n, void *d_flags);
@@ -93,7 +99,10 @@ int gki_hash_sequence(const void *d_codes, int64_t n, int k, void *d_out);
  * max(0, len-k+1) of earlier reads (computed by the call, also returned in d_out_start).
  * strand 0: forward (read_kmers.py:21-22); strand 1: reverse complement of the read
  * (read_kmers.py:23-26, Bio.Seq.reverse_complement then the same hash).
- * d_reads uint8[], d_read_start int64[n_reads+1], d_out_start int64[n_reads+1], d_out uint64[]. */
+ * d_reads uint8[], d_read_start int64[n_reads+1], d_out_start int64[n_reads+1], d_out uint64[].
+ * d_out NULL: count only -- d_out_start and *n_out are filled and d_reads is not read.
+ * A read's k-mer count is kept in 32 bits: a read of more than 2^32 - 1 k-mers (2^32 + k - 1 letters or more) makes the
+ * call return GKI_ERR_BAD_ARG with *n_out = 0, in count-only mode too, as gki_reads_parse_* refuses such a line. */
 int gki_hash_reads(const void *d_reads, const void *d_read_start, int64_t n_reads, int k, int strand,
                    void *d_out_start, void *d_out, int64_t out_capacity, int64_t *n_out);
 

@@ -21,7 +21,7 @@ GRID_ITEMS = 2048 * 256      # csrc/gki_common.h:66-71 stream_grid: at most 256 
 PROBE_UNROLL = 4             # csrc/gki_probe.hip:128 k_probe_kmers loads i0 + u * stride for u = 0..3
 WAVE = 64                    # csrc/gki_common.h:12
 CAND_QUEUE = 64 + 4 * 64     # csrc/gki_probe.hip:76 CQ = 320 entries of the per-wave LDS candidate queue
-READ_WAVES = 2048 * 4        # csrc/gki_probe.hip:421-422, csrc/gki_hash.hip:139-140: at most 256 * 8 blocks of 4 waves = 8 192
+READ_WAVES = 2048 * 4        # csrc/gki_probe.hip:421-422, csrc/gki_hash.hip:149-150: at most 256 * 8 blocks of 4 waves = 8 192
 FP_SCAN_MAX = 64             # csrc/gki_probe.hip:28 longer buckets get an all-ones fingerprint set
 CNT_SAT = 0xFFFF             # csrc/gki_probe.hip:27 directory count saturates at 65 535, the length then comes from n_kmers
 SMALL_Q = 64                 # csrc/gki_index.hip:907 queries per gki_index_get_small call
@@ -286,7 +286,7 @@ def boundary_reads(k, rng):
 @pytest.mark.parametrize("k", [1, 2, 16, 31])
 def test_reads_later_reads_of_a_wave_and_step_boundaries(k):
     """Issue item 3.  k_probe_reads (csrc/gki_probe.hip:286-342) prefetches the next read's first 64 letters in the
-    `len < k` branch (:293-294) and in the last step of a read (:304-306); k_hash_reads (csrc/gki_hash.hip:65-68) skips
+    `len < k` branch (:293-294) and in the last step of a read (:304-306); k_hash_reads (csrc/gki_hash.hip:69-72) skips
     a short read and goes on.  Neither is reached before a wave has a second read, i.e. below READ_WAVES + 1 reads;
     (long, empty, short, long) in one wave needs 3 * READ_WAVES + 1, and five more make the last grid row ragged.  The
     lengths put n_out = len - k + 1 at 64, 65, 128 and 129 (the last step has 64, 1, 64, 1 windows) and the read's end
@@ -330,7 +330,7 @@ def test_reads_later_reads_of_a_wave_and_step_boundaries(k):
 
 
 def test_hash_reads_past_one_grid_pass_of_reads():
-    """Issue item 1.  k_read_counts (csrc/gki_hash.hip:35) and the scan of its counts are grid-stride over GRID_ITEMS
+    """Issue item 1.  k_read_counts (csrc/gki_hash.hip:37) and the scan of its counts are grid-stride over GRID_ITEMS
     threads, one read each: 600 000 reads take the second trip.  Reads of 20..60 letters at k = 31 keep the output at a
     few million hashes, and a quarter of the reads (len < k) give none."""
     rng = np.random.default_rng(77)
