@@ -147,6 +147,9 @@ SYMBOLS = {
     "gki_probe_reads_count_nodes": (_I32, [_P, _P, _P, _I64, _I32, _I32, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(_I64)]),
     "gki_reads_parse_count": (_I32, [_P, _I64, _I32, _I32, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
     "gki_reads_parse_emit": (_I32, [_P, _I64, _I32, _I32, _P, _I64, _P, _I64]),
+    "gki_vcf_parse_count": (_I32, [_P, _I64, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64),
+                                   C.POINTER(C.c_int)]),
+    "gki_vcf_parse_emit": (_I32, [_P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _I64]),
     "gki_bgzf_inflate": (_I32, [_P, _I64, _P, _P, _P, _P, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(C.c_int)]),
     "gki_bgzf_inflate_kernel_ms": (_I32, [C.POINTER(C.c_float)]),
     "gki_last_byte_position": (_I32, [_P, _I64, _I32, C.POINTER(_I64)]),

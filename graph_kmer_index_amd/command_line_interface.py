@@ -214,21 +214,30 @@ def make_kmer_frequencies(args):
     logging.info("Wrote to file %s" % args.out_file_name)
 
 
+def load_variants(args):
+    """The VCF of `-v` as VariantArrays: `--vcf-parse host` reads the lines in Python (VariantArrays.from_vcf), `device`
+    and `auto` parse them on the device, a `.gz` file inflated as `--inflate` says."""
+    from .unique_variant_kmers import VariantArrays
+    if args.vcf_parse == "host":
+        return VariantArrays.from_vcf(args.vcf)
+    return VariantArrays.from_vcf_on_device(args.vcf, inflate=args.inflate)
+
+
 def make_unique_variant_kmers(args):
     """command_line_interface.py:299-389, dense path: one finder per `-c` chunk of VCF data lines (`_nodes_found` starts
     empty at every chunk), run here as one device batch.  `-t` is accepted; the chunks' outputs do not depend on it.
     `-S True` (simple selection, find_kmers_over_variant): one batch of per-node searches, no frequency source; -D is not
     consulted, -i / -I are not needed, -N and -H are ignored as in the reference, and -c / -t do not change the output
-    (this mode keeps no state from variant to variant)."""
-    from .unique_variant_kmers import (UniqueVariantKmersFinder, VariantArrays, find_kmers_over_variants,
-                                       load_variant_to_nodes)
+    (this mode keeps no state from variant to variant).
+    Both routes read the VCF through `load_variants` (`--vcf-parse`, `--inflate`)."""
+    from .unique_variant_kmers import UniqueVariantKmersFinder, find_kmers_over_variants, load_variant_to_nodes
     if _bool(args.simple):
         if args.vcf is None:
             raise ValueError("make_unique_variant_kmers: -v (the VCF) is required")
         graph = load_graph(args.graph)
         position_id = None if args.position_id_index is None else load_position_id(args.position_id_index, graph)
         flat = find_kmers_over_variants(graph, load_variant_to_nodes(args.variant_to_nodes),
-                                        VariantArrays.from_vcf(args.vcf), args.kmer_size, args.max_variant_nodes,
+                                        load_variants(args), args.kmer_size, args.max_variant_nodes,
                                         position_id_index=position_id)
         flat.to_file(args.out_file_name)
         logging.info("Wrote %d k-mers (simple selection) to %s" % (len(flat._hashes), args.out_file_name))
@@ -244,7 +253,7 @@ def make_unique_variant_kmers(args):
     if args.vcf is None:
         raise ValueError("make_unique_variant_kmers: -v (the VCF) is required")
     graph = load_graph(args.graph)
-    finder = UniqueVariantKmersFinder(graph, load_variant_to_nodes(args.variant_to_nodes), VariantArrays.from_vcf(args.vcf),
+    finder = UniqueVariantKmersFinder(graph, load_variant_to_nodes(args.variant_to_nodes), load_variants(args),
                                       args.kmer_size, args.max_variant_nodes,
                                       kmer_index_with_frequencies=frequencies,
                                       do_not_choose_lowest_frequency_kmers=_bool(args.do_not_choose_lowest_frequency_kmers),
@@ -411,6 +420,11 @@ def build_parser():
     p.add_argument("-m", "--max-variant-nodes", required=False, default=6, type=int)
     p.add_argument("-d", "--do-not-choose-lowest-frequency-kmers", required=False, type=_bool, default=False)
     p.add_argument("-S", "--simple", type=_bool, default=False)
+    p.add_argument("--vcf-parse", required=False, choices=("auto", "host", "device"), default="auto",
+                   help="where the VCF's lines are parsed: auto = device; host = line by line in Python")
+    p.add_argument("--inflate", required=False, choices=("auto", "host", "device"), default="auto",
+                   help="where a .gz VCF is inflated when it is parsed on the device: auto = BGZF on the device, other gzip "
+                        "on the host; device refuses a file that is not BGZF")
     p.set_defaults(func=make_unique_variant_kmers)
     p = sub.add_parser("sample_kmers_from_structural_variants")
     p.add_argument("-g", "--graph", required=True)

@@ -15,13 +15,9 @@
 //
 // A line may be of any length: nothing here holds a line in a workgroup.  Lines of 2^32 letters or more after the strip
 // are refused (GKI_ERR_BAD_ARG): a read's length passes through the 32-bit input of the scan.
-#include "gki_common.h"
+#include "gki_text_lines.h"
 
 namespace {
-
-constexpr int PARSE_BLOCK = 256;                          // threads per workgroup
-constexpr int PARSE_LANE_BYTES = 16;                      // one 16-byte load per lane
-constexpr int PARSE_TILE = PARSE_BLOCK * PARSE_LANE_BYTES; // 4096 bytes per workgroup
 
 // bit j set where byte j of the word is '\n': x = w ^ 0x0A.. has a zero byte there; (x & 0x7F) + 0x7F carries into bit 7
 // of a byte exactly when its low seven bits are not all zero, and never beyond the byte, so the test is exact per byte
@@ -44,22 +40,6 @@ __device__ __forceinline__ uint32_t newline_mask16(const uint8_t *__restrict__ b
     for (int j = 0; j < PARSE_LANE_BYTES; j++)
         if (pos + j < n && bytes[pos + j] == (uint8_t)'\n') m |= 1u << j;
     return m;
-}
-
-// the lanes' values summed over the workgroup's four waves: (sum of the waves before this one, sum of all)
-__device__ __forceinline__ void block_wave_offsets(int wave_total, int *lds, int *before, int *total) {
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 63) lds[wave] = wave_total;
-    __syncthreads();
-    int b = 0, t = 0;
-#pragma unroll
-    for (int w = 0; w < PARSE_BLOCK / 64; w++) {
-        const int v = lds[w];
-        if (w < wave) b += v;
-        t += v;
-    }
-    *before = b;
-    *total = t;
 }
 
 __global__ __launch_bounds__(PARSE_BLOCK) void k_parse_count_newlines(const uint8_t *__restrict__ bytes, int64_t n,
@@ -93,10 +73,36 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_parse_line_ends(const uint8_t *
     }
 }
 
-// str.strip() of ASCII text removes 0x09-0x0D, 0x1C-0x1F and the blank
-__device__ __forceinline__ bool is_strip_byte(uint8_t c) {
-    return c == 0x20 || (c >= 0x09 && c <= 0x0D) || (c >= 0x1C && c <= 0x1F);
+}  // namespace
+
+int gki_text_line_ends(const uint8_t *bytes, int64_t n, const char *who, DevBuf &line_end, int64_t *n_lines) {
+    const int64_t n_tiles = ceil_div(n, PARSE_TILE);
+    if (n_tiles > 0x7FFFFFFFll) return gki_set_error(GKI_ERR_BAD_ARG, "%s: buffer of %lld bytes is too large", who, (long long)n);
+    DevBuf tile_newlines, tile_first_line, tmp;
+    const int64_t tile_tmp_bytes = gki_scan_tmp_bytes(n_tiles);
+    HIP_TRY(tile_newlines.alloc((size_t)n_tiles * 4));
+    HIP_TRY(tile_first_line.alloc((size_t)(n_tiles + 1) * 8));
+    HIP_TRY(tmp.alloc((size_t)tile_tmp_bytes));
+    hipLaunchKernelGGL(k_parse_count_newlines, dim3((unsigned)n_tiles), dim3(PARSE_BLOCK), 0, 0, bytes, n,
+                       tile_newlines.get<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    GKI_TRY(gki_scan_u32_to_i64(tile_newlines.get<const uint32_t>(), n_tiles, tile_first_line.get<int64_t>(), tmp.get(),
+                                tile_tmp_bytes, 0));
+    int64_t n_newlines = 0;
+    uint8_t last = 0;
+    HIP_TRY(hipMemcpy(&n_newlines, tile_first_line.get<const int64_t>() + n_tiles, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&last, bytes + n - 1, 1, hipMemcpyDeviceToHost));
+    const bool open_end = last != (uint8_t)'\n';           // the last line has no terminator
+    *n_lines = n_newlines + (open_end ? 1 : 0);
+    HIP_TRY(line_end.alloc((size_t)*n_lines * 8));
+    hipLaunchKernelGGL(k_parse_line_ends, dim3((unsigned)n_tiles), dim3(PARSE_BLOCK), 0, 0, bytes, n,
+                       tile_first_line.get<const int64_t>(), n_newlines, line_end.get<int64_t>());
+    HIP_TRY(hipGetLastError());
+    if (open_end) HIP_TRY(hipMemcpy(line_end.get<int64_t>() + n_newlines, &n, 8, hipMemcpyHostToDevice));
+    return GKI_OK;
 }
+
+namespace {
 
 struct ParseTotals { unsigned long long n_bad; unsigned int too_long; unsigned int pad; };
 
@@ -162,7 +168,7 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_parse_emit(const uint8_t *__res
 
 // What one parse of a buffer leaves on the device, and its totals.  Both entry points build it; neither keeps it.
 struct ParsePlan {
-    DevBuf tile_newlines, tile_first_line, line_end, is_read, read_len, letters_begin, read_index, letter_offset, tmp, totals;
+    DevBuf line_end, is_read, read_len, letters_begin, read_index, letter_offset, tmp, totals;
     int64_t n_lines = 0, n_reads = 0, n_letters = 0, n_bad = 0;
 };
 
@@ -173,32 +179,8 @@ int parse_lines(const uint8_t *bytes, int64_t n, int format, int line_phase, Par
     if (line_phase < 0 || line_phase > 3) return gki_set_error(GKI_ERR_BAD_ARG, "reads_parse: line_phase must be in 0..3");
     if (n == 0) return GKI_OK;
     if (bytes == nullptr) return gki_set_error(GKI_ERR_BAD_ARG, "reads_parse: d_bytes is NULL");
-    const int64_t n_tiles = ceil_div(n, PARSE_TILE);
-    if (n_tiles > 0x7FFFFFFFll) return gki_set_error(GKI_ERR_BAD_ARG, "reads_parse: buffer of %lld bytes is too large", (long long)n);
-
-    // line ends
-    const int64_t tile_tmp_bytes = gki_scan_tmp_bytes(n_tiles);
-    HIP_TRY(p.tile_newlines.alloc((size_t)n_tiles * 4));
-    HIP_TRY(p.tile_first_line.alloc((size_t)(n_tiles + 1) * 8));
-    HIP_TRY(p.tmp.alloc((size_t)tile_tmp_bytes));
-    hipLaunchKernelGGL(k_parse_count_newlines, dim3((unsigned)n_tiles), dim3(PARSE_BLOCK), 0, 0, bytes, n,
-                       p.tile_newlines.get<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    GKI_TRY(gki_scan_u32_to_i64(p.tile_newlines.get<const uint32_t>(), n_tiles, p.tile_first_line.get<int64_t>(), p.tmp.get(),
-                                tile_tmp_bytes, 0));
-    int64_t n_newlines = 0;
-    uint8_t last = 0;
-    HIP_TRY(hipMemcpy(&n_newlines, p.tile_first_line.get<const int64_t>() + n_tiles, 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&last, bytes + n - 1, 1, hipMemcpyDeviceToHost));
-    const bool open_end = last != (uint8_t)'\n';           // the last line has no terminator
-    const int64_t n_lines = n_newlines + (open_end ? 1 : 0);
-    HIP_TRY(p.line_end.alloc((size_t)n_lines * 8));
-    hipLaunchKernelGGL(k_parse_line_ends, dim3((unsigned)n_tiles), dim3(PARSE_BLOCK), 0, 0, bytes, n,
-                       p.tile_first_line.get<const int64_t>(), n_newlines, p.line_end.get<int64_t>());
-    HIP_TRY(hipGetLastError());
-    if (open_end) HIP_TRY(hipMemcpy(p.line_end.get<int64_t>() + n_newlines, &n, 8, hipMemcpyHostToDevice));
-    p.tile_newlines.reset();
-    p.tile_first_line.reset();
+    int64_t n_lines = 0;
+    GKI_TRY(gki_text_line_ends(bytes, n, "reads_parse", p.line_end, &n_lines));
 
     // lines -> reads
     const int64_t line_tmp_bytes = gki_scan_tmp_bytes(n_lines);

@@ -289,6 +289,19 @@ def bgzf_text_pieces(file_name, chunk_bytes):
             tail.free()
 
 
+def text_pieces(file_name, chunk_bytes=DEFAULT_CHUNK_BYTES, inflate="auto"):
+    """The source of pieces of a text file by its route (`reads_file_route`).  inflate: 'auto' BGZF is inflated on the
+    device and any other gzip on the host, 'host' gzip on the host for every `.gz`, 'device' ValueError unless the file is
+    BGZF.  The consumer closes it (contextlib.closing)."""
+    if inflate not in INFLATE_CHOICES:
+        raise ValueError("inflate must be one of %s, not %r" % (", ".join(INFLATE_CHOICES), inflate))
+    route = reads_file_route(file_name)
+    if inflate == "device" and route != "bgzf-device":
+        raise ValueError("%s is not a BGZF file: only BGZF is inflated on the device" % file_name)
+    source = bgzf_text_pieces if route == "bgzf-device" and inflate != "host" else host_text_pieces
+    return source(file_name, chunk_bytes)
+
+
 def count_nodes_from_file(device_index, file_name, k, n_nodes, strands=3, max_hits=2 ** 62, counts=None, fmt=None,
                           chunk_bytes=DEFAULT_CHUNK_BYTES, inflate="auto"):
     """Node hit counts of every k-mer of every read of a FASTA / FASTQ file, streamed: one loop over the pieces of the
@@ -300,15 +313,10 @@ def count_nodes_from_file(device_index, file_name, k, n_nodes, strands=3, max_hi
     records do not have their '@' and '+' lines in place raises ValueError after the piece that shows it.
     Returns (counts DeviceArray uint32[n_nodes], reads, k-mers probed, hits)."""
     _lib.require_device()
-    if inflate not in INFLATE_CHOICES:
-        raise ValueError("inflate must be one of %s, not %r" % (", ".join(INFLATE_CHOICES), inflate))
-    route = reads_file_route(file_name)
-    if inflate == "device" and route != "bgzf-device":
-        raise ValueError("%s is not a BGZF file: only BGZF is inflated on the device" % file_name)
-    source = bgzf_text_pieces if route == "bgzf-device" and inflate != "host" else host_text_pieces
+    source = text_pieces(file_name, chunk_bytes, inflate)
     code = None if fmt is None else _format_code(fmt)
     line_phase = n_reads = n_kmers = n_hits = n_bad = 0
-    with _lib.DeviceScope() as s, contextlib.closing(source(file_name, chunk_bytes)) as pieces:
+    with _lib.DeviceScope() as s, contextlib.closing(source) as pieces:
         counts = zeroed_counts(s, n_nodes) if counts is None else counts
         for text, n_bytes in pieces:
             if code is None:

@@ -93,6 +93,13 @@ class VariantArrays:
                 is_snp.append(-1 if len(fields) < 5 else int(len(fields[3]) == 1 and len(fields[4]) == 1))
         return cls(positions, np.array(chroms, dtype=object), np.arange(len(positions)), is_snp)
 
+    @classmethod
+    def from_vcf_on_device(cls, file_name, chunk_bytes=None, inflate="auto"):
+        """What `from_vcf` returns, with the lines parsed on the device (vcf_files.py): a .vcf, a BGZF .vcf.gz inflated on
+        the device, any other .gz through Python's gzip.  POS must be plain digits there."""
+        from .vcf_files import variant_arrays_from_file
+        return variant_arrays_from_file(file_name, chunk_bytes=chunk_bytes, inflate=inflate)
+
 
 def load_variant_to_nodes(file_name):
     """(ref_nodes, var_nodes) of a VariantToNodes file: an .npz with `ref_nodes` and `var_nodes`, or obgraph's own

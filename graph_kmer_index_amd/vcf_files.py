@@ -1,0 +1,122 @@
+"""VCF files on the device: .vcf and BGZF .vcf.gz text -> VariantArrays, without a host pass over the lines.
+
+The text reaches HBM as the reads files' does -- `read_files.text_pieces`: `host_text_pieces` or `bgzf_text_pieces`, pieces
+that end at a line end, a BGZF file inflated on the device -- and gki_vcf_parse_count / _emit (csrc/gki_vcf_parse.hip) turn each piece
+into POS, is_snp and the chromosome of every data line, the chromosomes as runs of equal names.  The rules are stated in
+include/gki.h ("VCF files") and DESIGN.md 4.14; they give what `VariantArrays.from_vcf` gives wherever that returns, except
+that POS must be plain digits.
+
+`variant_arrays_from_file` is one loop over the pieces; `VariantPieces` joins them on the host: data-line numbers go on
+across pieces, and a piece's first run continues the last run of the piece before when the names are equal.
+"""
+import contextlib
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .read_files import DEFAULT_CHUNK_BYTES, _device_bytes, text_pieces
+
+BAD_TEXT = {1: "VCF data line %d has fewer than two columns",          # VariantArrays.from_vcf's own message
+            2: "VCF data line %d: POS must be 1 to 18 plain digits (no sign, blank or underscore) for the device parser"}
+
+
+def bad_line_error(data_line, kind):
+    """The ValueError for bad data line `data_line` (numbered from 0 in the file) of `kind` (include/gki.h)."""
+    return ValueError(BAD_TEXT[kind] % data_line)
+
+
+def vcf_count(text, n_bytes):
+    """(n_lines, n_variants, n_runs, n_name_bytes, first_bad_variant, first_bad_kind) of the device bytes text[:n_bytes]."""
+    n_lines, n_variants, n_runs, n_names, bad = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(-1)
+    kind = C.c_int(0)
+    _lib.check(_lib.load().gki_vcf_parse_count(text.ptr, n_bytes, C.byref(n_lines), C.byref(n_variants), C.byref(n_runs),
+                                               C.byref(n_names), C.byref(bad), C.byref(kind)))
+    return n_lines.value, n_variants.value, n_runs.value, n_names.value, bad.value, kind.value
+
+
+def vcf_emit(scope, text, n_bytes, n_variants, n_runs, n_name_bytes):
+    """(positions int64, is_snp int8, chrom_run int32, run_name_start int64[n_runs + 1], run_names uint8) of the device
+    bytes text[:n_bytes], DeviceArrays of `scope` sized by what `vcf_count` said of them."""
+    out = (scope.array(n_variants, np.int64), scope.array(n_variants, np.int8), scope.array(n_variants, np.int32),
+           scope.array(n_runs + 1, np.int64), scope.array(n_name_bytes, np.uint8))
+    _lib.check(_lib.load().gki_vcf_parse_emit(text.ptr, n_bytes, out[0].ptr, out[1].ptr, out[2].ptr, n_variants, out[3].ptr,
+                                              n_runs, out[4].ptr, n_name_bytes))
+    return out
+
+
+def copy_back(positions, is_snp, chrom_run, run_name_start, run_names):
+    """`vcf_emit`'s arrays on the host: (positions, is_snp, chrom_run, run_names list[str]); names are UTF-8."""
+    start, raw = run_name_start.to_host(), run_names.to_host().tobytes()
+    names = [raw[a:b].decode("utf-8") for a, b in zip(start[:-1], start[1:])]
+    return positions.to_host(), is_snp.to_host(), chrom_run.to_host(), names
+
+
+def parse_piece(scope, text, n_bytes):
+    """One piece: ((positions, is_snp, chrom_run, run_names, n_lines), None), or (None, (first bad data line of the piece,
+    its kind)) when the piece has a bad line.  Host arrays; what the device holds for them on the way belongs to `scope`."""
+    n_lines, n_variants, n_runs, n_name_bytes, bad, kind = vcf_count(text, n_bytes)
+    if bad >= 0:
+        return None, (bad, kind)
+    return copy_back(*vcf_emit(scope, text, n_bytes, n_variants, n_runs, n_name_bytes)) + (n_lines,), None
+
+
+def parse_vcf_on_device(buf):
+    """VCF bytes (bytes, NumPy uint8 or a DeviceArray; whole lines, the last one terminated or not) -> (positions int64,
+    is_snp int8, chrom_run int32, run_names list[str], n_lines), host arrays: chrom_run[v] is the number of the run of
+    equal CHROM data line v belongs to, run_names[r] that run's name.  ValueError for a bad data line."""
+    _lib.require_device()
+    with _lib.DeviceScope() as s:
+        d = _device_bytes(s, buf)
+        out, bad = parse_piece(s, d, d.n)
+    if bad is not None:
+        raise bad_line_error(*bad)
+    return out
+
+
+class VariantPieces:
+    """The pieces of one file joined on the host (no device work here)."""
+
+    def __init__(self):
+        self.positions, self.is_snp, self.run_of_variant, self.run_names = [], [], [], []
+        self.n_variants = self.n_lines = 0
+
+    def add(self, positions, is_snp, chrom_run, run_names, n_lines):
+        joined = bool(run_names) and bool(self.run_names) and run_names[0] == self.run_names[-1]
+        shift = len(self.run_names) - (1 if joined else 0)
+        self.run_names.extend(run_names[1:] if joined else run_names)
+        self.positions.append(positions)
+        self.is_snp.append(is_snp)
+        self.run_of_variant.append(chrom_run.astype(np.int64) + shift)
+        self.n_variants += len(positions)
+        self.n_lines += n_lines
+
+    def variant_arrays(self):
+        from .unique_variant_kmers import VariantArrays
+
+        def cat(parts, dtype):
+            return np.concatenate(parts) if parts else np.zeros(0, dtype)
+        run_of_variant = cat(self.run_of_variant, np.int64)
+        chromosomes = np.array(self.run_names, dtype=object)[run_of_variant]
+        return VariantArrays(cat(self.positions, np.int64), chromosomes, np.arange(self.n_variants),
+                             cat(self.is_snp, np.int8))
+
+
+def variant_arrays_from_file(file_name, chunk_bytes=DEFAULT_CHUNK_BYTES, inflate="auto"):
+    """`VariantArrays.from_vcf(file_name)` with the lines parsed on the device, streamed: one loop over the pieces of the
+    text, about `chunk_bytes` each, that the file's route gives.  A `.gz` file goes by `reads_file_route`: BGZF is inflated
+    on the device, any other gzip through Python's gzip on the host.  inflate: 'auto' that rule, 'host' gzip on the host
+    for every `.gz`, 'device' ValueError unless the file is BGZF.  A bad data line raises ValueError after the piece that
+    shows it, with its number in the file."""
+    _lib.require_device()
+    joined = VariantPieces()
+    source = text_pieces(file_name, DEFAULT_CHUNK_BYTES if chunk_bytes is None else chunk_bytes, inflate)
+    with contextlib.closing(source) as pieces:
+        for text, n_bytes in pieces:
+            with _lib.DeviceScope() as s:
+                s.keep(text)
+                out, bad = parse_piece(s, text, n_bytes)
+            if bad is not None:
+                raise bad_line_error(joined.n_variants + bad[0], bad[1])
+            joined.add(*out)
+    return joined.variant_arrays()

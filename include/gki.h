@@ -619,6 +619,40 @@ int gki_reads_parse_count(const void *d_bytes, int64_t n_bytes, int format, int 
 int gki_reads_parse_emit(const void *d_bytes, int64_t n_bytes, int format, int line_phase, void *d_letters,
                          int64_t letters_capacity, void *d_read_start, int64_t read_start_capacity);
 
+/* ---------------------------------------------------------------- VCF files (VCF text -> POS, is_snp, chromosome runs)
+ * The raw bytes of a VCF file in HBM, or of a piece of one that ends at a line end, become what VariantArrays holds
+ * (unique_variant_kmers.py): POS and is_snp of every data line, and its chromosome as the number of a run of equal names.
+ * Count, allocate, emit, as above; both calls parse the buffer themselves and nothing is kept between them.  The rules
+ * give VariantArrays.from_vcf's result on every input where that function returns:
+ *   line       ends at '\n'; the last one may lack it.  Every '\r' at its end is then dropped (rstrip("\r\n"), so CRLF files
+ *              work; a lone '\r' inside a line is unsupported input).
+ *   skipped    a line whose first raw byte is '#', and a line that str.strip() empties (the ASCII strip set of the reads
+ *              files: 0x09-0x0D, 0x1C-0x1F, 0x20), so a line of blanks and tabs too.
+ *   data line  every other line; data lines are numbered from 0 in the buffer, in file order.
+ *   fields     separated by '\t'.  CHROM is the bytes before the first tab; it may be empty and is copied unchanged.  POS is
+ *              field 1, ending at the second tab or the line's end.
+ *   POS        1 to 18 ASCII digits, leading zeros allowed; anything else (a sign, a blank, an underscore, a 19th digit) is
+ *              bad kind 2.  A data line without any tab is bad kind 1 (fewer than two columns).
+ *   is_snp     -1 when the line has fewer than five fields; otherwise 1 exactly when field 3 (REF) and field 4 (ALT, ending
+ *              at the fifth tab or the line's end) are one byte long each, else 0 (an empty ALT, "C,G" and "<DEL>" give 0).
+ *              Nothing behind the fifth tab is read.
+ *   runs       a data line begins a chromosome run when it is the buffer's first data line or its CHROM differs from the
+ *              previous data line's in length or bytes; an unsorted file simply has more runs.
+ * gki_vcf_parse_count: the totals; *first_bad_variant is the number of the lowest bad data line and *first_bad_kind its
+ * kind, -1 and 0 when there is none.  A bad line is reported, not refused: the call still returns 0.
+ * gki_vcf_parse_emit: d_positions int64, d_is_snp int8, d_chrom_run int32 (the run variant v belongs to), each
+ * [variant_capacity]; d_run_name_start int64[run_capacity + 1] and d_run_names uint8[name_capacity]: run r's name is
+ * d_run_names[run_name_start[r], run_name_start[r + 1]).  It writes *n_variants entries, *n_chrom_runs + 1 offsets and
+ * *n_chrom_bytes name bytes, and returns GKI_ERR_BAD_ARG, writing nothing, when a capacity is too small or the buffer has a
+ * bad line.  n_bytes == 0 and a buffer of headers only give zero variants and zero runs (run_name_start = [0]).
+ * d_bytes uint8[n_bytes], any alignment.  Every total is 64-bit and a line may be of any length; a CHROM of 2^32 bytes or
+ * more and more than 2^31 - 1 runs in one buffer are GKI_ERR_BAD_ARG. */
+int gki_vcf_parse_count(const void *d_bytes, int64_t n_bytes, int64_t *n_lines, int64_t *n_variants, int64_t *n_chrom_runs,
+                        int64_t *n_chrom_bytes, int64_t *first_bad_variant, int *first_bad_kind);
+int gki_vcf_parse_emit(const void *d_bytes, int64_t n_bytes, void *d_positions, void *d_is_snp, void *d_chrom_run,
+                       int64_t variant_capacity, void *d_run_name_start, int64_t run_capacity, void *d_run_names,
+                       int64_t name_capacity);
+
 /* ---------------------------------------------------------------- BGZF (blocked gzip: the .gz reads files of bgzip / htslib)
  * A BGZF file is a chain of gzip members of at most 64 KiB, each with its compressed size in a 'BC' extra subfield, so
  * every member's raw DEFLATE payload, CRC-32 and ISIZE are found without inflating anything (graph_kmer_index_amd/bgzf.py
