@@ -16,6 +16,7 @@ collision_free_kmer_index.py:393-402).
     python -m graph_kmer_index_amd.command_line_interface make_reverse -f variant_kmers.npz -o reverse
     python -m graph_kmer_index_amd.command_line_interface make -t 16 -s 1 -k 31 -r True -R ref.fa -n chr1 -G <size> -o linear_kmers
     python -m graph_kmer_index_amd.command_line_interface map -i index.npz -f reads.fq.gz -k 31 -o node_counts
+    python -m graph_kmer_index_amd.command_line_interface make_graph -r ref.fa -v variants.vcf.gz -o graph -n chr1,chr2
 
 `-g` takes an obgraph file when obgraph is installed, else a GraphArrays .npz (GraphArrays.to_file).  `index -t N` runs
 one process per GPU (at most N, at most the visible devices), each on its own range of critical-path numbers, and
@@ -329,6 +330,24 @@ def map_reads_file(args):
     logging.info("Wrote %d node counts (%d hits) to %s" % (len(counts), int(counts.sum(dtype=np.int64)), out))
 
 
+def make_graph(args):
+    """Reference FASTA + VCF -> the graph (GraphArrays.to_file) and its variant-to-nodes table, built on the device
+    (graph_files.py).  What it writes is what `-g` and `-V` of the other commands read."""
+    from .graph_files import STATUS_TEXT, build_graph_from_files
+    chromosomes = None if args.chromosomes is None else [c for c in args.chromosomes.split(",") if c]
+    built = build_graph_from_files(args.reference_fasta, args.vcf, chromosomes, chunk_bytes=args.chunk_bytes,
+                                   inflate=args.inflate)
+    v2n = args.variant_to_nodes if args.variant_to_nodes is not None else args.out_file_name + ".variant_to_nodes"
+    built.graph.to_file(args.out_file_name)
+    built.variant_to_nodes.to_file(v2n)
+    counts = np.bincount(built.line_status, minlength=len(STATUS_TEXT))
+    for code, text in STATUS_TEXT.items():
+        logging.info("%d data lines: %s" % (counts[code], text))
+    logging.info("Wrote %d nodes, %d edges and %d bases to %s, variant-to-nodes of %d lines to %s"
+                 % (built.graph.n_nodes, len(built.graph.edges), len(built.graph.seq), args.out_file_name,
+                    len(built.line_status), v2n))
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description="graph_kmer_index on MI355X (in-scope sub-commands)")
     sub = parser.add_subparsers()
@@ -446,6 +465,17 @@ def build_parser():
     p.add_argument("-r", "--reference-kmers", required=True)
     p.add_argument("-o", "--out-file-name", required=True)
     p.set_defaults(func=make_kmer_frequencies)
+    p = sub.add_parser("make_graph")
+    p.add_argument("-r", "--reference-fasta", required=True)
+    p.add_argument("-v", "--vcf", required=True, help="VCF, optionally .gz (BGZF or gzip)")
+    p.add_argument("-o", "--out-file-name", required=True, help="the graph, as GraphArrays.to_file writes it")
+    p.add_argument("-n", "--chromosomes", required=False, default=None,
+                   help="comma-separated FASTA record names in graph order (default: every record, in file order)")
+    p.add_argument("-V", "--variant-to-nodes", required=False, default=None, help="default: <out>.variant_to_nodes")
+    p.add_argument("--inflate", required=False, choices=("auto", "host", "device"), default="auto",
+                   help="where a .gz VCF is inflated: auto = BGZF on the device, other gzip on the host")
+    p.add_argument("--chunk-bytes", required=False, type=int, default=None)
+    p.set_defaults(func=make_graph)
     p = sub.add_parser("map")
     p.add_argument("-i", "--kmer-index", required=True)
     p.add_argument("-f", "--reads", required=True, help="FASTA or FASTQ, optionally .gz (gzip or BGZF)")

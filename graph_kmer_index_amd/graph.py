@@ -179,6 +179,13 @@ class GraphArrays:
         return cls(node_size, seq, edge_start, flat_edges, is_ref, af, exists, first, chrom, ntro)
 
     @classmethod
+    def from_reference_and_vcf(cls, fasta, vcf, chromosomes=None, allele_frequencies=None, chunk_bytes=None, inflate="auto"):
+        """The graph of a reference FASTA and a VCF, built on the device: `graph_files.build_graph_from_files(...).graph`
+        (its variant-to-nodes table and line statuses are on the GraphBuild that function returns)."""
+        from .graph_files import build_graph_from_files
+        return build_graph_from_files(fasta, vcf, chromosomes, allele_frequencies, chunk_bytes, inflate).graph
+
+    @classmethod
     def from_obgraph(cls, graph, check_nodes=2000):
         """The flat arrays of an obgraph `Graph`.
 

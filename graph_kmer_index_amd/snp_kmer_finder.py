@@ -36,23 +36,34 @@ def reference_to_letters(reference):
     return reference_to_letters(str(reference[:]))               # a FASTA record object (pyfaidx-like)
 
 
-def read_fasta_record(file_name, name):
-    """The bases of record `name` (the first word of its `>` line) as one uint8 array, line ends stripped.  No .fai."""
+def read_fasta_records(file_name, names=None):
+    """(names, bases): the records `names` of a FASTA file (None: every record, in file order), each as one uint8 array
+    with line ends stripped, from ONE read of the file.  A record's name is the first word of its `>` line.  No .fai."""
     with open(file_name, "rb") as f:
         data = f.read()
     buf = np.frombuffer(data, dtype=np.uint8)
     gt = np.flatnonzero(buf == ord(">"))
     gt = gt[(gt == 0) | (buf[gt - 1] == 10)]                     # a `>` that begins a line
-    names = []
+    found, bodies = [], {}
     for i, g in enumerate(gt.tolist()):
         eol = data.find(b"\n", g)
         eol = len(data) if eol < 0 else eol
         words = data[g + 1:eol].split()
-        names.append(words[0].decode("ascii", "replace") if words else "")
-        if names[-1] == name:
-            body = buf[min(eol + 1, len(data)):int(gt[i + 1]) if i + 1 < len(gt) else len(data)]
-            return np.ascontiguousarray(body[(body != 10) & (body != 13)])
-    raise KeyError("no record %r in %s (records: %s)" % (name, file_name, ", ".join(names)))
+        found.append(words[0].decode("ascii", "replace") if words else "")
+        bodies.setdefault(found[-1], (min(eol + 1, len(data)), int(gt[i + 1]) if i + 1 < len(gt) else len(data)))
+    names = found if names is None else list(names)
+    out = []
+    for name in names:
+        if name not in bodies:
+            raise KeyError("no record %r in %s (records: %s)" % (name, file_name, ", ".join(found)))
+        body = buf[bodies[name][0]:bodies[name][1]]
+        out.append(np.ascontiguousarray(body[(body != 10) & (body != 13)]))
+    return names, out
+
+
+def read_fasta_record(file_name, name):
+    """The bases of record `name` (the first word of its `>` line) as one uint8 array, line ends stripped.  No .fai."""
+    return read_fasta_records(file_name, [name])[1][0]
 
 
 def chunk_intervals(genome_size, spacing, threads):

@@ -653,6 +653,78 @@ int gki_vcf_parse_emit(const void *d_bytes, int64_t n_bytes, void *d_positions, 
                        int64_t variant_capacity, void *d_run_name_start, int64_t run_capacity, void *d_run_names,
                        int64_t name_capacity);
 
+/* ---------------------------------------------------------------- graph build (reference letters + VCF text -> graph arrays)
+ * The flat arrays of graph.py and a variant-to-nodes table from the letters of the chosen chromosomes, concatenated in
+ * graph order in HBM, and the VCF text that gki_vcf_parse_* has already split into chromosome runs.
+ * Coordinates are global and 0-based: chromosome c occupies [C0_c, C1_c) of the concatenated letters.
+ *   lines      data lines, skipped lines and fields are those of "VCF files".  A data line with fewer than five fields
+ *              is at fault (kind 1).  The CHROM runs must name chosen chromosomes, each in at most one run, the runs in
+ *              graph order (the host checks the few run names), POS must be 1 .. length (kind 2) and must not decrease
+ *              inside a run (first_unordered_line).
+ *   plain      an allele is plain when it is non-empty and every byte is one of ACGTNacgtn.  A line whose REF or ALT is
+ *              not plain ("C,G", "<DEL>", "*", ".", IUPAC letters) gets status 1.
+ *   site       when REF and ALT differ in length and their first bytes are equal ignoring case, that byte is stripped
+ *              from both and lo = C0 + POS; otherwise the alleles are taken whole and lo = C0 + POS - 1.  Either allele
+ *              may be empty after the strip.  hi = lo + length of the ref allele.
+ *   REF check  a plain REF, padding base included, must equal the reference letters ignoring case (kind 3) and end
+ *              inside its chromosome (kind 4), whatever the ALT is.
+ *   before     a plain line with lo == C0 gets status 2: there is no base before the site.
+ *   overlap    with reach_i the largest hi of the lines j < i whose status is neither 1 nor 2 (0 when there are none),
+ *              such a line is kept, status 0, exactly when lo_i >= reach_i, and gets status 3 otherwise.  Dropped lines
+ *              still count in reach: one prefix maximum, narrower than a greedy choice.  Two insertions at one point and
+ *              an insertion followed by a SNP at its lo are all kept; of two SNPs at one POS the first is.
+ *   nodes      id 0 is unused (exists 0, size 0).  Then per chromosome in order and per kept site in order: the gap
+ *              [previous hi or C0, lo) as one node when it is non-empty, the ref allele, the alt allele; behind the last
+ *              site the gap to C1 when it is non-empty.  A gap is never split, so it must be shorter than 2^31.  is_ref is
+ *              1 for gaps and ref alleles (an empty ref allele is a linear-ref dummy), 0 for alt alleles.
+ *              node_to_ref_offset[n_nodes + 1]: a gap its start, a ref allele its lo, every other entry 0.  seq holds
+ *              codes (c 1, g 2, t 3 in either case, anything else 0) in node order: gaps and ref alleles from the
+ *              reference, alt alleles from ALT.  Allele frequencies: the line's (ref_af, alt_af) on its two allele
+ *              nodes when given, 1.0 everywhere else.
+ *   edges      every node of an element (a gap: itself; a site: both alleles) has the entry nodes of its chromosome's
+ *              next element as successors: [gap], or [ref, alt] in that order.  The last element has none and nothing
+ *              connects chromosomes.  rev_edges ascend by source id.  chromosome_start_nodes[c] is chromosome c's first
+ *              node, always a gap; a chromosome without kept sites is a single node.
+ *   variant-to-nodes   ref_nodes[v], var_nodes[v]: the two allele nodes of kept line v, 0 and 0 for every other line.
+ * gki_graph_sites_count / _emit work on one piece of text, d_text[n_bytes] of whole lines with n_variants data lines:
+ * d_chrom_run int32[n_variants] is gki_vcf_parse_emit's for the same bytes, d_run_c0 / d_run_c1 int64[n_runs] each run's
+ * C0 / C1, d_reference the concatenated letters.  Both calls do the whole pass; nothing is kept between them.  count:
+ * *n_alt_bytes letters the emit call puts into the alt pool (the alt alleles of the lines with status 0 here, back to
+ * back in line order), *first_bad_variant / *first_bad_kind the lowest data line at fault and why (-1 and 0: none); a line
+ * at fault is reported, not refused.  emit: d_gpos int64 (C0 + POS - 1), d_lo int64, d_ref_len int32, d_alt_len int32,
+ * d_status uint8 (0, 1 or 2; lengths are 0 where the status is 1), each [n_variants], and d_alt_pool uint8[alt_capacity];
+ * GKI_ERR_BAD_ARG when a line is at fault or the pool is too small (the five site arrays may have been written by then).  An allele of 2^31 letters or more is GKI_ERR_BAD_ARG.
+ * gki_graph_build_count takes those arrays of all pieces appended ([n_lines], d_status is updated in place to the final
+ * 0 .. 3) and h_chromosome_bounds int64[n_chromosomes + 1] (C0 of every chromosome and the total; no chromosome is
+ * empty, and a gap or a chromosome without a kept site is one node and must be shorter than 2^31), applies the order
+ * check and the overlap rule and sizes the graph.  When POS decreases,
+ * *first_unordered_line is the first line whose gpos is below its predecessor's, *plan is NULL and the call returns 0.
+ * Otherwise -1 and *plan holds what the emit call needs; the per-line arrays must stay as they are until then.
+ * *n_alt_bytes: the letters the appended alt pools must hold.
+ * gki_graph_build_emit writes d_node_size int32[n_nodes], d_edge_start / d_rev_start / d_node_to_ref_offset
+ * int64[n_nodes + 1] (seq_start is the prefix sum of node_size and is left to the caller), d_seq uint8[n_bases] (16-byte aligned), d_edges / d_rev_edges int32[n_edges],
+ * d_is_ref / d_exists uint8[n_nodes], d_allele_freq float64[n_nodes], d_chromosome_start_nodes int64[n_chromosomes],
+ * d_ref_nodes / d_var_nodes uint32[n_lines].  d_ref_af / d_alt_af float64[n_lines] or both NULL.  *sequence_ms (may be
+ * NULL): the device time of the kernel that writes d_seq.  gki_graph_build_destroy frees the plan (NULL is allowed). */
+typedef struct gki_graph_build gki_graph_build;
+int gki_graph_sites_count(const void *d_text, int64_t n_bytes, const void *d_chrom_run, int64_t n_variants,
+                          const void *d_run_c0, const void *d_run_c1, int64_t n_runs, const void *d_reference,
+                          int64_t *n_alt_bytes, int64_t *first_bad_variant, int *first_bad_kind);
+int gki_graph_sites_emit(const void *d_text, int64_t n_bytes, const void *d_chrom_run, int64_t n_variants,
+                         const void *d_run_c0, const void *d_run_c1, int64_t n_runs, const void *d_reference,
+                         void *d_gpos, void *d_lo, void *d_ref_len, void *d_alt_len, void *d_status, void *d_alt_pool,
+                         int64_t alt_capacity);
+int gki_graph_build_count(const void *d_gpos, const void *d_lo, const void *d_ref_len, const void *d_alt_len, void *d_status,
+                          int64_t n_lines, const int64_t *h_chromosome_bounds, int64_t n_chromosomes, int64_t *n_nodes,
+                          int64_t *n_edges, int64_t *n_bases, int64_t *n_alt_bytes, int64_t *first_unordered_line,
+                          gki_graph_build **plan);
+int gki_graph_build_emit(gki_graph_build *plan, const void *d_reference, const void *d_alt_pool, const void *d_ref_af,
+                         const void *d_alt_af, void *d_node_size, void *d_seq, void *d_edge_start,
+                         void *d_edges, void *d_rev_start, void *d_rev_edges, void *d_is_ref, void *d_allele_freq,
+                         void *d_exists, void *d_node_to_ref_offset, void *d_chromosome_start_nodes, void *d_ref_nodes,
+                         void *d_var_nodes, float *sequence_ms);
+int gki_graph_build_destroy(gki_graph_build *plan);
+
 /* ---------------------------------------------------------------- BGZF (blocked gzip: the .gz reads files of bgzip / htslib)
  * A BGZF file is a chain of gzip members of at most 64 KiB, each with its compressed size in a 'BC' extra subfield, so
  * every member's raw DEFLATE payload, CRC-32 and ISIZE are found without inflating anything (graph_kmer_index_amd/bgzf.py
