@@ -150,6 +150,9 @@ SYMBOLS = {
     "gki_vcf_parse_count": (_I32, [_P, _I64, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64),
                                    C.POINTER(C.c_int)]),
     "gki_vcf_parse_emit": (_I32, [_P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _I64]),
+    "gki_fasta_parse_count": (_I32, [_P, _I64, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(C.c_float)]),
+    "gki_fasta_parse_names": (_I32, [_P, _I64, _P, _P, _I64, _P, _I64, C.POINTER(C.c_float)]),
+    "gki_fasta_parse_emit": (_I32, [_P, _I64, _I32, _P, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(C.c_float)]),
     "gki_graph_sites_count": (_I32, [_P, _I64, _P, _I64, _P, _P, _I64, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(C.c_int)]),
     "gki_graph_sites_emit": (_I32, [_P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I64]),
     "gki_graph_build_count": (_I32, [_P, _P, _P, _P, _P, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64),

@@ -284,15 +284,19 @@ def create_index(args):
     intervals, each ending on the position the next one starts with, each followed by its own reverse complements with
     -r -- as one device call.  The reference's `-t 1` path fails on a linear reference (it adds k to None), so the
     chunked form is used for every -t."""
+    from .fasta_files import reference_from_file, resolve_fasta_parse
     from .snp_kmer_finder import make_linear_reference_flat_on_device, read_fasta_record
     if args.graph_file_name is not None:
         raise NotImplementedError("make -g: SnpKmerFinder over a graph is not ported (use `index`); "
                                   "make builds from a linear reference, -R and -n")
     assert args.reference_fasta is not None
     assert args.reference_name is not None, "Reference name must be specified"
-    letters = read_fasta_record(args.reference_fasta, args.reference_name)
-    assert len(letters) > 0, "Length of ref sequennce is 0. Seomthing is wrong"
     with _lib.DeviceScope() as s:
+        if resolve_fasta_parse(args.fasta_parse) == "device":
+            letters = s.keep(reference_from_file(args.reference_fasta, [args.reference_name]).letters)
+        else:
+            letters = read_fasta_record(args.reference_fasta, args.reference_name)
+        assert len(letters) > 0, "Length of ref sequennce is 0. Seomthing is wrong"
         flat = s.keep(make_linear_reference_flat_on_device(letters, args.kmer_size, args.spacing, args.genome_size,
                                                            args.threads, _bool(args.include_reverse_complement))).to_flat_kmers()
     logging.info("N kmers in flat kmers: %d" % len(flat._hashes))
@@ -304,7 +308,7 @@ def make_reference_kmer_index(args):
     from .reference_kmer_index import ReferenceKmerIndex
     if args.reference_fasta is not None:
         index = ReferenceKmerIndex.from_linear_reference(args.reference_fasta, args.reference_name, args.kmer_size,
-                                                         _bool(args.only_store_kmers))
+                                                         _bool(args.only_store_kmers), args.fasta_parse)
     else:
         index = ReferenceKmerIndex.from_flat_kmers(FlatKmers.from_file(args.flat_index))
     index.to_file(args.out_file_name)
@@ -336,7 +340,7 @@ def make_graph(args):
     from .graph_files import STATUS_TEXT, build_graph_from_files
     chromosomes = None if args.chromosomes is None else [c for c in args.chromosomes.split(",") if c]
     built = build_graph_from_files(args.reference_fasta, args.vcf, chromosomes, chunk_bytes=args.chunk_bytes,
-                                   inflate=args.inflate)
+                                   inflate=args.inflate, fasta_parse=args.fasta_parse)
     v2n = args.variant_to_nodes if args.variant_to_nodes is not None else args.out_file_name + ".variant_to_nodes"
     built.graph.to_file(args.out_file_name)
     built.variant_to_nodes.to_file(v2n)
@@ -385,6 +389,9 @@ def build_parser():
     p.add_argument("-G", "--genome-size", required=False, default=3000000000, type=int)
     p.add_argument("-R", "--reference-fasta", required=False)
     p.add_argument("-n", "--reference-name", required=False)
+    p.add_argument("--fasta-parse", required=False, choices=("auto", "host", "device"), default="auto",
+                   help="where the reference FASTA (.fa, or .fa.gz as BGZF or gzip) is parsed: auto = device; host = on "
+                        "the host with NumPy")
     p.set_defaults(func=create_index)
     p = sub.add_parser("make_reference_kmer_index")
     p.add_argument("-f", "--flat-index", required=False)
@@ -393,6 +400,9 @@ def build_parser():
     p.add_argument("-k", "--kmer-size", required=False, type=int, default=16)
     p.add_argument("-o", "--out-file-name", required=True)
     p.add_argument("-O", "--only-store-kmers", required=False, default=False, type=_bool)
+    p.add_argument("--fasta-parse", required=False, choices=("auto", "host", "device"), default="auto",
+                   help="where the reference FASTA (.fa, or .fa.gz as BGZF or gzip) is parsed: auto = device; host = on "
+                        "the host with NumPy")
     p.set_defaults(func=make_reference_kmer_index)
     p = sub.add_parser("merge_flat_kmers")
     p.add_argument("-f", "--flat-kmers", required=True)
@@ -475,6 +485,9 @@ def build_parser():
     p.add_argument("--inflate", required=False, choices=("auto", "host", "device"), default="auto",
                    help="where a .gz VCF is inflated: auto = BGZF on the device, other gzip on the host")
     p.add_argument("--chunk-bytes", required=False, type=int, default=None)
+    p.add_argument("--fasta-parse", required=False, choices=("auto", "host", "device"), default="auto",
+                   help="where the reference FASTA (.fa, or .fa.gz as BGZF or gzip) is parsed: auto = device; host = on "
+                        "the host with NumPy")
     p.set_defaults(func=make_graph)
     p = sub.add_parser("map")
     p.add_argument("-i", "--kmer-index", required=True)

@@ -64,23 +64,37 @@ def _array(scope, n, dtype):
 
 class _Builder:
     """One build: the reference on the device, the pieces' sites appended, then the assembly.  Everything on the device
-    belongs to `scope`."""
+    belongs to `scope`.  `records` is one array of letters per name, uploaded here, or a reference that is on the device
+    already (`.letters` one uint8 DeviceArray, `.bounds` int64[len(names) + 1], as `fasta_files.DeviceReference` has
+    them), which the scope takes over and uses in place."""
 
     def __init__(self, scope, names, records):
         self.scope, self.names, self.timings = scope, list(names), {}
+        t0 = time.perf_counter()
+        on_device = hasattr(records, "letters") and hasattr(records, "bounds")
+        if on_device:
+            scope.keep(records.letters)
         if not self.names or len(set(self.names)) != len(self.names):
             raise ValueError("the chromosomes must be at least one and distinct: %r" % (self.names,))
-        t0 = time.perf_counter()
-        self.bounds = np.zeros(len(self.names) + 1, dtype=np.int64)
-        records = [_letters(r) for r in records]
-        for c, r in enumerate(records):
-            if len(r) < 1:
+        if on_device:
+            self.bounds = np.ascontiguousarray(records.bounds, dtype=np.int64)
+            if len(self.bounds) != len(self.names) + 1 or int(self.bounds[-1]) != records.letters.n:
+                raise ValueError("the device reference's bounds do not fit its %d names and %d letters"
+                                 % (len(self.names), records.letters.n))
+            for c in np.flatnonzero(np.diff(self.bounds) < 1)[:1]:
                 raise ValueError("chromosome %r has no letters" % (self.names[c],))
-            self.bounds[c + 1] = self.bounds[c] + len(r)
-        self.reference = scope.array(int(self.bounds[-1]), np.uint8)
-        for c, r in enumerate(records):                   # one upload per chromosome, concatenated on the device
-            _lib.check(_lib.load().gki_memcpy_h2d(C.c_void_p(self.reference.ptr.value + int(self.bounds[c])), _lib.hptr(r),
-                                                  len(r)))
+            self.reference = records.letters
+        else:
+            self.bounds = np.zeros(len(self.names) + 1, dtype=np.int64)
+            records = [_letters(r) for r in records]
+            for c, r in enumerate(records):
+                if len(r) < 1:
+                    raise ValueError("chromosome %r has no letters" % (self.names[c],))
+                self.bounds[c + 1] = self.bounds[c] + len(r)
+            self.reference = scope.array(int(self.bounds[-1]), np.uint8)
+            for c, r in enumerate(records):               # one upload per chromosome, concatenated on the device
+                _lib.check(_lib.load().gki_memcpy_h2d(C.c_void_p(self.reference.ptr.value + int(self.bounds[c])),
+                                                      _lib.hptr(r), len(r)))
         self.timings["upload_reference"] = time.perf_counter() - t0
         self.timings["site_pass"] = 0.0
         self.index_of = {n: c for c, n in enumerate(self.names)}
@@ -222,20 +236,32 @@ def build_graph(reference, text, chromosomes=None, allele_frequencies=None):
         return builder.finish(allele_frequencies)
 
 
-def build_graph_from_files(fasta, vcf, chromosomes=None, allele_frequencies=None, chunk_bytes=None, inflate="auto"):
+def build_graph_from_files(fasta, vcf, chromosomes=None, allele_frequencies=None, chunk_bytes=None, inflate="auto",
+                           fasta_parse="auto"):
     """The graph of the FASTA records `chromosomes` (None: every record, in file order) with the variants of `vcf`: a
     .vcf, a BGZF .vcf.gz inflated on the device, any other .gz through Python's gzip (`inflate` as in `vcf_files`).  The
-    VCF is streamed in pieces of about `chunk_bytes`; line numbers and the order check carry across pieces."""
+    VCF is streamed in pieces of about `chunk_bytes`; line numbers and the order check carry across pieces.
+    fasta_parse: 'device' the FASTA (plain, BGZF or gzip) is parsed on the device (`fasta_files.reference_from_file`) and
+    its letters stay there; 'host' `read_fasta_records` and one upload per chromosome; 'auto' the faster of the two."""
+    from .fasta_files import reference_from_file, resolve_fasta_parse
     from .snp_kmer_finder import read_fasta_records
     _lib.require_device()
-    t0 = time.perf_counter()
-    names, records = read_fasta_records(fasta, chromosomes)      # one read of the file for every record
-    read_seconds = time.perf_counter() - t0
+    device = resolve_fasta_parse(fasta_parse) == "device"
     source = text_pieces(vcf, DEFAULT_CHUNK_BYTES if chunk_bytes is None else chunk_bytes, inflate)
     with _lib.DeviceScope() as s, contextlib.closing(source) as pieces:
+        t0 = time.perf_counter()
+        if device:                                        # `chunk_bytes` is the VCF's: the FASTA's pieces keep their size
+            records = reference_from_file(fasta, chromosomes)
+            s.keep(records.letters)
+            names, parse_ms = records.names, records.timings["parse_kernel_ms"]
+        else:
+            names, records = read_fasta_records(fasta, chromosomes)  # one read of the file for every record
+            parse_ms = 0.0
+        read_seconds = time.perf_counter() - t0
         builder = _Builder(s, names, records)
         del records
         builder.timings["read_reference"] = read_seconds
+        builder.timings["parse_reference_kernel_ms"] = parse_ms
         t0 = time.perf_counter()
         for text, n_bytes in pieces:
             with _lib.DeviceScope() as t:

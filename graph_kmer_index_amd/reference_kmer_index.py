@@ -46,28 +46,47 @@ class ReferenceKmerIndex:
     @classmethod
     def from_sequence(cls, genome_sequence, k, only_store_kmers=False):
         """reference_kmer_index.py:50-67: the hash of every k-window, uint32 for k <= 16 else uint64."""
-        from .snp_kmer_finder import NoReferenceSequence, linear_kmers_on_device, reference_to_letters
+        from .snp_kmer_finder import reference_to_letters
         _lib.require_device()
         host = reference_to_letters(genome_sequence)
-        if len(host) < k:
-            raise NoReferenceSequence("the sequence has %d letters, fewer than k=%d" % (len(host), k))
+        cls._check_length(len(host), k)
+        return cls.from_device_letters(_lib.DeviceArray.from_host(host), k, only_store_kmers)
+
+    @staticmethod
+    def _check_length(n_letters, k):
+        from .snp_kmer_finder import NoReferenceSequence
+        if n_letters < k:
+            raise NoReferenceSequence("the sequence has %d letters, fewer than k=%d" % (n_letters, k))
+
+    @classmethod
+    def from_device_letters(cls, letters, k, only_store_kmers=False):
+        """The hashing step of `from_sequence`, from letters that are on the device already: a uint8 DeviceArray, which
+        is taken over and freed here."""
+        from .snp_kmer_finder import linear_kmers_on_device
         with _lib.DeviceScope() as s:
-            letters = s.on_device(host, np.uint8)
-            hashes, n = linear_kmers_on_device(letters, k, 1, [0], [len(host) - k + 1], hashes_only=True)
+            s.keep(letters)
+            n_letters = letters.n
+            cls._check_length(n_letters, k)
+            hashes, n = linear_kmers_on_device(letters, k, 1, [0], [n_letters - k + 1], hashes_only=True)
             s.keep(hashes)
             letters.free()                  # early: the letters are not needed while the hashes are copied
             kmers = hashes.to_host(n)
         ref_position_to_index = None
         if not only_store_kmers:
-            ref_position_to_index = np.arange(0, len(host), dtype=np.uint32)
+            ref_position_to_index = np.arange(0, n_letters, dtype=np.uint32)
         if k <= 16:
             kmers = kmers.astype(np.uint32)
         return cls(ref_position_to_index, kmers)
 
     @classmethod
-    def from_linear_reference(cls, fasta_file_name, reference_name="ref", k=15, only_store_kmers=False):
+    def from_linear_reference(cls, fasta_file_name, reference_name="ref", k=15, only_store_kmers=False, fasta_parse="auto"):
+        """fasta_parse: 'device' the FASTA (plain, BGZF or gzip) is parsed on the device and hashed where it lies; 'host'
+        `read_fasta_record` and an upload; 'auto' the faster of the two (`fasta_files.resolve_fasta_parse`)."""
+        from .fasta_files import reference_from_file, resolve_fasta_parse
         from .snp_kmer_finder import read_fasta_record
-        return cls.from_sequence(read_fasta_record(fasta_file_name, reference_name), k, only_store_kmers)
+        if resolve_fasta_parse(fasta_parse) == "host":
+            return cls.from_sequence(read_fasta_record(fasta_file_name, reference_name), k, only_store_kmers)
+        return cls.from_device_letters(reference_from_file(fasta_file_name, [reference_name]).letters, k, only_store_kmers)
 
     @classmethod
     def from_flat_kmers(cls, flat_kmers):

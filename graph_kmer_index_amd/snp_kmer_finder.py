@@ -38,8 +38,11 @@ def reference_to_letters(reference):
 
 def read_fasta_records(file_name, names=None):
     """(names, bases): the records `names` of a FASTA file (None: every record, in file order), each as one uint8 array
-    with line ends stripped, from ONE read of the file.  A record's name is the first word of its `>` line.  No .fai."""
-    with open(file_name, "rb") as f:
+    with line ends stripped, from ONE read of the file.  A record's name is the first word of its `>` line.  No .fai.
+    A name ending in .gz (gzip or BGZF) is inflated by Python's gzip.  This is the host route; `fasta_files` has the
+    device's."""
+    from .read_files import open_reads_file
+    with open_reads_file(file_name) as f:
         data = f.read()
     buf = np.frombuffer(data, dtype=np.uint8)
     gt = np.flatnonzero(buf == ord(">"))

@@ -653,6 +653,36 @@ int gki_vcf_parse_emit(const void *d_bytes, int64_t n_bytes, void *d_positions, 
                        int64_t variant_capacity, void *d_run_name_start, int64_t run_capacity, void *d_run_names,
                        int64_t name_capacity);
 
+/* ---------------------------------------------------------------- FASTA files (reference FASTA text -> record names and letters)
+ * The raw bytes of a reference FASTA in HBM, or of a piece of one that ends at a line end (only the stream's last piece may
+ * be unterminated), become the names of its records and the letters of the records the caller wants.  Every call parses
+ * the buffer itself and nothing is kept between them.  The rules are those of snp_kmer_finder.read_fasta_records:
+ *   header   a '>' at byte 0 of the buffer or right behind a '\n'; any other '>' is a letter.  Its line ends at the next
+ *            '\n' or at the buffer's end, so a header line never spans two buffers.
+ *   name     the first word of the header line behind the '>', words separated as by bytes.split(): blank, '\t', '\n',
+ *            '\v', '\f', '\r'; empty when the line has no word.  The bytes are copied unchanged.
+ *   body     every byte from behind the header line's '\n' up to the next header or the buffer's end, the bytes 10 and 13
+ *            removed and nothing else: a blank stays, a lone '\r' goes.
+ *   lead     the bytes before the buffer's first header continue the record the buffer before ended in (the carried
+ *            record); in the stream's first buffer they belong to no record.
+ * gki_fasta_parse_count: the number of headers, the bytes of their names together, and the letters of the lead.
+ * gki_fasta_parse_names: d_name_start int64[header_capacity + 1] and d_names uint8[name_capacity]: header h's name is
+ * d_names[name_start[h], name_start[h + 1]); d_body_letters int64[header_capacity]: the letters of header h's body in this
+ * buffer.  No header gives name_start = [0].  GKI_ERR_BAD_ARG, writing nothing, when a capacity is too small.
+ * gki_fasta_parse_emit: d_wanted uint8[n_wanted], one flag per header of the buffer (n_wanted must be their number), and
+ * carry_wanted the flag of the carried record; the letters of the wanted records go to d_letters back to back in file
+ * order, *n_letters of them: the sum of the wanted d_body_letters, plus the lead when carry_wanted.  GKI_ERR_BAD_ARG,
+ * writing nothing, when letters_capacity is smaller.
+ * d_bytes uint8[n_bytes], any alignment (16-byte aligned buffers take the fast loads).  Every offset and total is 64-bit
+ * and a line may be of any length; a name of 2^32 bytes or more is GKI_ERR_BAD_ARG.  kernel_ms (may be NULL): the device
+ * time of the call, from its first kernel to its last. */
+int gki_fasta_parse_count(const void *d_bytes, int64_t n_bytes, int64_t *n_headers, int64_t *n_name_bytes,
+                          int64_t *n_lead_letters, float *kernel_ms);
+int gki_fasta_parse_names(const void *d_bytes, int64_t n_bytes, void *d_name_start, void *d_body_letters,
+                          int64_t header_capacity, void *d_names, int64_t name_capacity, float *kernel_ms);
+int gki_fasta_parse_emit(const void *d_bytes, int64_t n_bytes, int carry_wanted, const void *d_wanted, int64_t n_wanted,
+                         void *d_letters, int64_t letters_capacity, int64_t *n_letters, float *kernel_ms);
+
 /* ---------------------------------------------------------------- graph build (reference letters + VCF text -> graph arrays)
  * The flat arrays of graph.py and a variant-to-nodes table from the letters of the chosen chromosomes, concatenated in
  * graph order in HBM, and the VCF text that gki_vcf_parse_* has already split into chromosome runs.

@@ -130,6 +130,8 @@ def main():
     ap.add_argument("--bases", type=float, default=3e9)
     ap.add_argument("--sites", type=float, default=5e6)
     ap.add_argument("--runs", type=int, default=3, help="timed runs per encoding after the checked one")
+    ap.add_argument("--fasta-parse", default="auto", choices=("auto", "host", "device"),
+                    help="where the reference FASTA is parsed (build_graph_from_files' fasta_parse)")
     ap.add_argument("--dir", default=None, help="where the input files go (default: a temporary directory)")
     args = ap.parse_args()
     _lib.require_device()
@@ -140,21 +142,23 @@ def main():
     with tempfile.TemporaryDirectory(prefix="gki_graph_build_", dir=args.dir) as d:
         paths, ref_af, alt_af = write_inputs(g, d)
         print("wrote the input files", flush=True)
-        result = {"bases": int(args.bases), "sites": int(np.sum(g.is_ref == 0)), "nodes": g.n_nodes + 1,
+        result = {"fasta_parse": args.fasta_parse, "bases": int(args.bases), "sites": int(np.sum(g.is_ref == 0)),
+                  "nodes": g.n_nodes + 1,
                   "synthetic_snp_graph_numpy_s": round(numpy_seconds, 3),
                   "file_bytes": {k: os.path.getsize(p) for k, p in paths.items()}}
         for encoding in ("plain", "bgzf"):
             runs = []
             for i in range(args.runs + 1):
                 t0 = time.perf_counter()
-                built = build_graph_from_files(paths["fasta"], paths[encoding], allele_frequencies=(ref_af, alt_af))
+                built = build_graph_from_files(paths["fasta"], paths[encoding], allele_frequencies=(ref_af, alt_af),
+                                               fasta_parse=args.fasta_parse)
                 whole = time.perf_counter() - t0
                 if i == 0:
                     assert_equals_generator(built, g)
                     print("%s: equals the generator's graph (ids + 1)" % encoding, flush=True)
                 else:
                     stages = dict(built.timings, whole_call=whole, **vcf_text_stages(paths[encoding]))
-                    stages["unattributed"] = whole - sum(v for k, v in built.timings.items() if k != "sequence_kernel_ms")
+                    stages["unattributed"] = whole - sum(v for k, v in built.timings.items() if not k.endswith("_ms"))
                     runs.append(stages)
                 del built
             result[encoding] = {k: round(statistics.median(r[k] for r in runs), 4) for k in runs[0]} if runs else {}
