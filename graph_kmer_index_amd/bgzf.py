@@ -3,9 +3,9 @@ size in a 'BC' extra subfield.  The host walks the member headers (a few bytes p
 the device inflates all members of a piece side by side (gki_bgzf_inflate, csrc/gki_inflate.hip).
 
 A plain gzip file -- one member, or several without the 'BC' subfield -- is one serial DEFLATE stream per member and is
-not BGZF: `is_bgzf` says no and the reads-file route keeps it on the host (read_files.py).
+not BGZF: `is_bgzf` says no and the reads-file route keeps it on the host (text_files.py).
 
-`inflate_on_device` is one piece's inflate; read_files.bgzf_text_pieces streams a file through it."""
+`inflate_on_device` is one piece's inflate; text_files.bgzf_text_pieces streams a file through it."""
 import ctypes as C
 import struct
 import zlib

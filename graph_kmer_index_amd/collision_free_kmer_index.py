@@ -560,7 +560,7 @@ class CollisionFreeKmerIndex:
         with _lib.DeviceScope() as s:
             counts = s.keep(read_files.count_nodes_from_file(
                 self._device_index(), file_name, k, n_nodes, 3 if include_reverse_complement else 1, max_hits, fmt=fmt,
-                chunk_bytes=read_files.DEFAULT_CHUNK_BYTES if chunk_bytes is None else chunk_bytes, inflate=inflate)[0])
+                chunk_bytes=chunk_bytes, inflate=inflate)[0])
             return counts.to_host(n_nodes)
 
     # ------------------------------------------------------------------ probes

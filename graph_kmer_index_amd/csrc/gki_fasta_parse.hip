@@ -27,18 +27,8 @@ namespace {
 
 constexpr int FASTA_STAGE_CHUNKS = PARSE_BLOCK + 1;       // 16-byte chunks of the emit kernel's LDS stage: a tile + the shift
 
-// bit j set where byte j of the word equals C (the exact per-byte zero test of gki_reads_parse.hip's newline_bits4)
-template <uint32_t C> __device__ __forceinline__ uint32_t equal_bits4(uint32_t w) {
-    const uint32_t x = w ^ (C * 0x01010101u);
-    const uint32_t t = (x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;
-    const uint32_t z = ~(t | x | 0x7F7F7F7Fu) >> 7;
-    return (z * 0x01020408u) >> 24;
-}
-template <uint32_t C> __device__ __forceinline__ uint32_t equal_mask16(const uint4 &v) {
-    return equal_bits4<C>(v.x) | equal_bits4<C>(v.y) << 4 | equal_bits4<C>(v.z) << 8 | equal_bits4<C>(v.w) << 12;
-}
-
 // bytes [pos, pos + 16) of the buffer in *v, zero where there are none; returns the 16-bit mask of the bytes that exist
+// (the line-end pass of gki_text_lines.hip needs a mask only and has a leaner loader of its own)
 __device__ __forceinline__ uint32_t load_lane16(const uint8_t *__restrict__ bytes, int64_t pos, int64_t n, uint4 *v) {
     *v = make_uint4(0u, 0u, 0u, 0u);
     if (pos >= n) return 0u;
@@ -80,9 +70,8 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_fasta_count_tiles(const uint8_t
     __shared__ int lds[PARSE_BLOCK / 64];
     const int64_t pos = (int64_t)blockIdx.x * PARSE_TILE + (int64_t)threadIdx.x * PARSE_LANE_BYTES;
     const FastaLane m = fasta_lane(bytes, pos, n);
-    const int incl = gki_wave_incl_sum(packed_counts(m));  // every lane is active here
-    int before, total;
-    block_wave_offsets(incl, lds, &before, &total);
+    int total;
+    block_excl_sum(packed_counts(m), lds, &total);         // every lane is active here
     if (threadIdx.x == 0) {
         tile_headers[blockIdx.x] = (uint32_t)total >> 16;
         tile_plain[blockIdx.x] = (uint32_t)total & 0xFFFFu;
@@ -98,11 +87,8 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_fasta_header_positions(const ui
     __shared__ int lds[PARSE_BLOCK / 64];
     const int64_t pos = (int64_t)blockIdx.x * PARSE_TILE + (int64_t)threadIdx.x * PARSE_LANE_BYTES;
     const FastaLane m = fasta_lane(bytes, pos, n);
-    const int cnt = packed_counts(m);
-    const int incl = gki_wave_incl_sum(cnt);
-    int before, total;
-    block_wave_offsets(incl, lds, &before, &total);
-    const int excl = before + incl - cnt;                  // no field borrows: each is a count of what lies before the lane
+    int total;
+    const int excl = (int)block_excl_sum(packed_counts(m), lds, &total);   // no field borrows: each counts what lies before the lane
     int64_t h = tile_first_header[blockIdx.x] + (excl >> 16);
     const int64_t plain = tile_plain_before[blockIdx.x] + (excl & 0xFFFF);
     uint32_t hm = m.header;
@@ -181,7 +167,7 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_fasta_names(const uint8_t *__re
         const int64_t off = name_offset[h], src = name_begin[h], len = name_len[h];
         if (off + len > n_name_bytes) continue;
         if (lane == 0) name_start[h] = off;
-        for (int64_t j = lane; j < len; j += 64) names[off + j] = bytes[src + j];
+        wave_copy(names + off, bytes + src, len, lane);
     }
 }
 
@@ -209,24 +195,31 @@ __device__ __forceinline__ uint32_t fasta_keep_mask(const FastaLane &m, int64_t 
     return keep & m.plain;
 }
 
+// The two passes over the kept bytes: the lane's 16 bytes and their keep mask, *at = the tile's kept bytes before the lane's,
+// *total = the tile's kept bytes.  Every lane of the workgroup calls it, once.
+__device__ __forceinline__ uint32_t fasta_lane_keep(const uint8_t *__restrict__ bytes, int64_t n, int64_t pos,
+                                                    const int64_t *__restrict__ tile_first_header, int64_t n_headers,
+                                                    const uint8_t *__restrict__ wanted, int carry_wanted,
+                                                    const int64_t *__restrict__ body_begin, FastaLane *m, int *at,
+                                                    int *total) {
+    __shared__ int lds[2][PARSE_BLOCK / 64];
+    *m = fasta_lane(bytes, pos, n);
+    int htotal;
+    const int64_t before = tile_first_header[blockIdx.x] + block_excl_sum(__popc(m->header), lds[0], &htotal);
+    const uint32_t keep = fasta_keep_mask(*m, pos, before, n_headers, wanted, carry_wanted, body_begin);
+    *at = (int)block_excl_sum(__popc(keep), lds[1], total);
+    return keep;
+}
+
 __global__ __launch_bounds__(PARSE_BLOCK) void k_fasta_keep_tiles(const uint8_t *__restrict__ bytes, int64_t n,
                                                                   const int64_t *__restrict__ tile_first_header,
                                                                   int64_t n_headers, const uint8_t *__restrict__ wanted,
                                                                   int carry_wanted, const int64_t *__restrict__ body_begin,
                                                                   uint32_t *__restrict__ tile_kept) {
-    __shared__ int lds[PARSE_BLOCK / 64];
-    __shared__ int lds2[PARSE_BLOCK / 64];
     const int64_t pos = (int64_t)blockIdx.x * PARSE_TILE + (int64_t)threadIdx.x * PARSE_LANE_BYTES;
-    const FastaLane m = fasta_lane(bytes, pos, n);
-    const int hcnt = __popc(m.header);
-    const int hincl = gki_wave_incl_sum(hcnt);
-    int hbefore, htotal;
-    block_wave_offsets(hincl, lds, &hbefore, &htotal);
-    const int64_t before = tile_first_header[blockIdx.x] + hbefore + (hincl - hcnt);
-    const int cnt = __popc(fasta_keep_mask(m, pos, before, n_headers, wanted, carry_wanted, body_begin));
-    const int incl = gki_wave_incl_sum(cnt);
-    int kbefore, total;
-    block_wave_offsets(incl, lds2, &kbefore, &total);
+    FastaLane m;
+    int at, total;
+    fasta_lane_keep(bytes, n, pos, tile_first_header, n_headers, wanted, carry_wanted, body_begin, &m, &at, &total);
     if (threadIdx.x == 0) tile_kept[blockIdx.x] = (uint32_t)total;
 }
 
@@ -239,26 +232,17 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_fasta_emit(const uint8_t *__res
                                                             int carry_wanted, const int64_t *__restrict__ body_begin,
                                                             const int64_t *__restrict__ tile_out, int64_t n_kept,
                                                             uint8_t *__restrict__ letters) {
-    __shared__ int lds[PARSE_BLOCK / 64];
-    __shared__ int lds2[PARSE_BLOCK / 64];
     __shared__ uint4 stage4[FASTA_STAGE_CHUNKS];
     uint8_t *stage = reinterpret_cast<uint8_t *>(stage4);
     const int64_t pos = (int64_t)blockIdx.x * PARSE_TILE + (int64_t)threadIdx.x * PARSE_LANE_BYTES;
-    const FastaLane m = fasta_lane(bytes, pos, n);
-    const int hcnt = __popc(m.header);
-    const int hincl = gki_wave_incl_sum(hcnt);
-    int hbefore, htotal;
-    block_wave_offsets(hincl, lds, &hbefore, &htotal);
-    const int64_t before = tile_first_header[blockIdx.x] + hbefore + (hincl - hcnt);
-    const uint32_t keep = fasta_keep_mask(m, pos, before, n_headers, wanted, carry_wanted, body_begin);
-    const int cnt = __popc(keep);
-    const int incl = gki_wave_incl_sum(cnt);
-    int kbefore, total;
-    block_wave_offsets(incl, lds2, &kbefore, &total);
+    FastaLane m;
+    int at, total;
+    const uint32_t keep = fasta_lane_keep(bytes, n, pos, tile_first_header, n_headers, wanted, carry_wanted, body_begin, &m,
+                                          &at, &total);
     const int64_t out = tile_out[blockIdx.x];
     if (total == 0 || out + total > n_kept) return;        // the same in every lane; totals of another run: write nothing
     const int shift = (int)((reinterpret_cast<uintptr_t>(letters) + (uint64_t)out) & 15);
-    int at = shift + kbefore + (incl - cnt);
+    at += shift;
     const uint32_t w[4] = {m.v.x, m.v.y, m.v.z, m.v.w};
 #pragma unroll
     for (int j = 0; j < PARSE_LANE_BYTES; j++)
@@ -325,8 +309,8 @@ int fasta_plan(const uint8_t *bytes, int64_t n, FastaPlan &p, FastaClock &clock)
                                 p.tmp.get(), tile_tmp_bytes, 0));
     GKI_TRY(gki_scan_u32_to_i64(p.tile_plain.get<const uint32_t>(), n_tiles, p.tile_plain_before.get<int64_t>(),
                                 p.tmp.get(), tile_tmp_bytes, 0));
-    HIP_TRY(hipMemcpy(&p.n_headers, p.tile_first_header.get<const int64_t>() + n_tiles, 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&p.n_plain, p.tile_plain_before.get<const int64_t>() + n_tiles, 8, hipMemcpyDeviceToHost));
+    GKI_TRY(gki_scan_total(p.tile_first_header, n_tiles, &p.n_headers));
+    GKI_TRY(gki_scan_total(p.tile_plain_before, n_tiles, &p.n_plain));
     p.tile_headers.reset();
     p.tile_plain.reset();
     p.n_lead = p.n_plain;
@@ -355,7 +339,7 @@ int fasta_plan(const uint8_t *bytes, int64_t n, FastaPlan &p, FastaClock &clock)
     GKI_TRY(gki_scan_u32_to_i64(p.name_len.get<const uint32_t>(), nh, p.name_offset.get<int64_t>(), p.tmp.get(),
                                 header_tmp_bytes, 0));
     uint32_t too_long = 0;
-    HIP_TRY(hipMemcpy(&p.n_name_bytes, p.name_offset.get<const int64_t>() + nh, 8, hipMemcpyDeviceToHost));
+    GKI_TRY(gki_scan_total(p.name_offset, nh, &p.n_name_bytes));
     HIP_TRY(hipMemcpy(&p.n_lead, p.plain_before.get<const int64_t>(), 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(&too_long, p.too_long.get(), 4, hipMemcpyDeviceToHost));
     p.tile_plain_before.reset();
@@ -437,7 +421,7 @@ int gki_fasta_parse_emit(const void *d_bytes, int64_t n_bytes, int carry_wanted,
     GKI_TRY(gki_scan_u32_to_i64(tile_kept.get<const uint32_t>(), p.n_tiles, tile_out.get<int64_t>(), p.tmp.get(),
                                 tile_tmp_bytes, 0));
     int64_t n_kept = 0;
-    HIP_TRY(hipMemcpy(&n_kept, tile_out.get<const int64_t>() + p.n_tiles, 8, hipMemcpyDeviceToHost));
+    GKI_TRY(gki_scan_total(tile_out, p.n_tiles, &n_kept));
     if (n_kept > letters_capacity)
         return gki_set_error(GKI_ERR_BAD_ARG, "fasta_parse_emit: %lld letters, capacity %lld", (long long)n_kept,
                              (long long)letters_capacity);

@@ -2,8 +2,9 @@
 // The rules are those of include/gki.h ("graph build") and DESIGN.md 4.15.
 //
 // 1. per piece of text (gki_graph_sites_count / _emit), beside the unchanged gki_vcf_parse_*:
-//   (line ends)              gki_text_line_ends
-//   k_gb_is_data             one lane per line: header / blank / data
+//   (line ends)              gki_text_line_ends (kernels in gki_text_lines.hip)
+//   k_gb_is_data             one lane per line: header / blank / data -- gki_text_lines.h's vcf_line, the rule k_vcf_classify
+//                            applies, so both number the data lines alike; vcf_fields and vcf_pos_value are shared too
 //   (exclusive scan)         line -> data lines before it
 //   k_gb_sites               one lane per data line: fields, POS against its chromosome, plain or not, the strip rule, REF
 //                            against the reference; writes the line's site and how many alt letters it has for the pool
@@ -41,18 +42,8 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_gb_is_data(const uint8_t *__res
                                                             const int64_t *__restrict__ line_end, int64_t n_lines,
                                                             uint32_t *__restrict__ is_data) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_lines; i += stride) {
-        const int64_t b = i ? line_end[i - 1] + 1 : 0;
-        int64_t e = line_end[i];
-        while (e > b && bytes[e - 1] == (uint8_t)'\r') e--;
-        bool data = b < e && bytes[b] != (uint8_t)'#';
-        if (data) {
-            int64_t p = b;
-            while (p < e && is_strip_byte(bytes[p])) p++;
-            data = p < e;
-        }
-        is_data[i] = data ? 1u : 0u;
-    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_lines; i += stride)
+        is_data[i] = vcf_line(bytes, line_end, i).data ? 1u : 0u;
 }
 
 // Data line v of the piece: gpos = C0 + POS - 1, the site (lo, ref_len, alt_len), status 0 / 1 / 2, where its alt allele
@@ -75,38 +66,19 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_gb_sites(const uint8_t *__restr
         if (!is_data[i]) continue;
         const int64_t v = variant_index[i];
         if (v >= n_variants) { atomicOr(&totals->flags, 2u); continue; }
-        const int64_t b = i ? line_end[i - 1] + 1 : 0;
-        int64_t e = line_end[i];
-        while (e > b && bytes[e - 1] == (uint8_t)'\r') e--;
-        // fields 0..4; field f is closed by tab number f + 1, or by the line's end
-        int tabs = 0, closed = 0;
-        int64_t field_begin = b, pos_b = 0, pos_e = 0, ref_b = 0, ref_e = 0, alt_b = 0, alt_e = 0;
-        for (int64_t p = b; p <= e && tabs < 5; p++) {
-            if (p != e && bytes[p] != (uint8_t)'\t') continue;
-            if (tabs == 1) { pos_b = field_begin; pos_e = p; }
-            else if (tabs == 3) { ref_b = field_begin; ref_e = p; }
-            else if (tabs == 4) { alt_b = field_begin; alt_e = p; }
-            closed++;
-            if (p == e) break;
-            tabs++;
-            field_begin = p + 1;
-        }
+        const VcfLine l = vcf_line(bytes, line_end, i);
+        const VcfFields f = vcf_fields(bytes, l.b, l.e);
         int kind = 0, st = 0;
         int64_t g = 0, site_lo = 0, rl = 0, al = 0, ab = 0;
         const int32_t r = chrom_run[v];
         if (r < 0 || r >= n_runs) { atomicOr(&totals->flags, 2u); kind = 7; }
-        else if (closed < 5) kind = 1;
+        else if (f.n < VCF_FIELDS) kind = 1;
         else {
             const int64_t c0 = run_c0[r], c1 = run_c1[r];
-            int64_t value = 0;
-            bool pos_ok = pos_e > pos_b && pos_e - pos_b <= 18;
-            for (int64_t p = pos_b; pos_ok && p < pos_e; p++) {
-                const uint8_t c = bytes[p];
-                if (c < (uint8_t)'0' || c > (uint8_t)'9') pos_ok = false;
-                else value = value * 10 + (c - (uint8_t)'0');
-            }
-            if (!pos_ok || value < 1 || value > c1 - c0) kind = 2;
+            int64_t value;
+            if (!vcf_pos_value(bytes, f.begin(1), f.end[1], &value) || value < 1 || value > c1 - c0) kind = 2;
             else {
+                const int64_t ref_b = f.begin(3), ref_e = f.end[3], alt_b = f.begin(4), alt_e = f.end[4];
                 g = c0 + value - 1;
                 rl = ref_e - ref_b;
                 al = alt_e - alt_b;
@@ -188,7 +160,7 @@ int site_pass(const uint8_t *bytes, int64_t n, const int32_t *chrom_run, int64_t
     GKI_TRY(gki_scan_u32_to_i64(p.is_data.get<const uint32_t>(), n_lines, p.variant_index.get<int64_t>(), p.tmp.get(),
                                 tmp_bytes, 0));
     int64_t found = 0;
-    HIP_TRY(hipMemcpy(&found, p.variant_index.get<const int64_t>() + n_lines, 8, hipMemcpyDeviceToHost));
+    GKI_TRY(gki_scan_total(p.variant_index, n_lines, &found));
     if (found != nv)
         return gki_set_error(GKI_ERR_BAD_ARG, "graph_sites: the text has %lld data lines, chrom_run %lld", (long long)found,
                              (long long)nv);
@@ -200,7 +172,7 @@ int site_pass(const uint8_t *bytes, int64_t n, const int32_t *chrom_run, int64_t
     HIP_TRY(hipGetLastError());
     GKI_TRY(gki_scan_u32_to_i64(p.pool_len.get<const uint32_t>(), nv, p.pool_off.get<int64_t>(), p.tmp.get(), tmp_bytes, 0));
     SiteTotals totals;
-    HIP_TRY(hipMemcpy(&p.n_alt_bytes, p.pool_off.get<const int64_t>() + nv, 8, hipMemcpyDeviceToHost));
+    GKI_TRY(gki_scan_total(p.pool_off, nv, &p.n_alt_bytes));
     HIP_TRY(hipMemcpy(&totals, p.totals.get(), sizeof(SiteTotals), hipMemcpyDeviceToHost));
     if (totals.flags & 2u) return gki_set_error(GKI_ERR_BAD_ARG, "graph_sites: chrom_run does not belong to this text");
     if (totals.flags & 1u) return gki_set_error(GKI_ERR_BAD_ARG, "graph_sites: an allele of 2^31 letters or more");

@@ -3,12 +3,8 @@
 // (gki_hash_reads, gki_probe_reads_count_nodes).  The rules are those of include/gki.h ("reads files"); the FASTA one is
 // the reference's (read_kmers.py:18-25: every line that does not start with '>' is one read, stripped).
 //
-//   k_parse_count_newlines   a workgroup counts the '\n' of its PARSE_TILE bytes: one 16-byte load per lane, a SWAR
-//                            compare per word, popcounts, a wave and a workgroup sum
-//   (exclusive scan)         tile -> number of line ends before it
-//   k_parse_line_ends        the same loads again; a wave prefix sum of the lanes' popcounts numbers every '\n', and its
-//                            byte position goes to line_end[its number]
-//   k_parse_classify         one lane per line: header / read / FASTQ role by position, the record-shape check, the strip;
+//   (line ends)              gki_text_line_ends: the coalesced 16-byte pass of gki_text_lines.hip, the only whole-buffer work
+//   k_parse_classify        one lane per line: header / read / FASTQ role by position, the record-shape check, the strip;
 //                            writes whether the line is a read, where its letters begin and how many there are
 //   (two exclusive scans)    line -> number of reads before it, line -> letters before it
 //   k_parse_emit             one wave per line: read_start[read] and the letters, copied 64 bytes per step
@@ -16,91 +12,6 @@
 // A line may be of any length: nothing here holds a line in a workgroup.  Lines of 2^32 letters or more after the strip
 // are refused (GKI_ERR_BAD_ARG): a read's length passes through the 32-bit input of the scan.
 #include "gki_text_lines.h"
-
-namespace {
-
-// bit j set where byte j of the word is '\n': x = w ^ 0x0A.. has a zero byte there; (x & 0x7F) + 0x7F carries into bit 7
-// of a byte exactly when its low seven bits are not all zero, and never beyond the byte, so the test is exact per byte
-__device__ __forceinline__ uint32_t newline_bits4(uint32_t w) {
-    const uint32_t x = w ^ 0x0A0A0A0Au;
-    const uint32_t t = (x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;
-    const uint32_t z = ~(t | x | 0x7F7F7F7Fu) >> 7;       // bit 0, 8, 16, 24 = byte 0..3 is '\n'
-    return (z * 0x01020408u) >> 24;                       // gathered into bits 0..3 (no two partial products meet)
-}
-
-// 16-bit mask of the '\n' among bytes [pos, pos + 16) of the buffer; bytes at or past n are not read and are no line ends
-__device__ __forceinline__ uint32_t newline_mask16(const uint8_t *__restrict__ bytes, int64_t pos, int64_t n) {
-    if (pos >= n) return 0u;
-    if (pos + PARSE_LANE_BYTES <= n && (reinterpret_cast<uintptr_t>(bytes + pos) & 15) == 0) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(bytes + pos);
-        return newline_bits4(v.x) | newline_bits4(v.y) << 4 | newline_bits4(v.z) << 8 | newline_bits4(v.w) << 12;
-    }
-    uint32_t m = 0;                                        // the buffer's last bytes, or a buffer that is not 16-byte aligned
-#pragma unroll
-    for (int j = 0; j < PARSE_LANE_BYTES; j++)
-        if (pos + j < n && bytes[pos + j] == (uint8_t)'\n') m |= 1u << j;
-    return m;
-}
-
-__global__ __launch_bounds__(PARSE_BLOCK) void k_parse_count_newlines(const uint8_t *__restrict__ bytes, int64_t n,
-                                                                      uint32_t *__restrict__ tile_newlines) {
-    __shared__ int lds[PARSE_BLOCK / 64];
-    const int64_t pos = (int64_t)blockIdx.x * PARSE_TILE + (int64_t)threadIdx.x * PARSE_LANE_BYTES;
-    const int cnt = __popc(newline_mask16(bytes, pos, n));
-    const int incl = gki_wave_incl_sum(cnt);               // every lane is active here
-    int before, total;
-    block_wave_offsets(incl, lds, &before, &total);        // lane 63's inclusive sum is its wave's total
-    if (threadIdx.x == 0) tile_newlines[blockIdx.x] = (uint32_t)total;
-}
-
-// line_end[i] = the byte position of the i-th '\n' (i < n_newlines: the count the first kernel made over the same bytes)
-__global__ __launch_bounds__(PARSE_BLOCK) void k_parse_line_ends(const uint8_t *__restrict__ bytes, int64_t n,
-                                                                 const int64_t *__restrict__ tile_first_line,
-                                                                 int64_t n_newlines, int64_t *__restrict__ line_end) {
-    __shared__ int lds[PARSE_BLOCK / 64];
-    const int64_t pos = (int64_t)blockIdx.x * PARSE_TILE + (int64_t)threadIdx.x * PARSE_LANE_BYTES;
-    uint32_t m = newline_mask16(bytes, pos, n);
-    const int cnt = __popc(m);
-    const int incl = gki_wave_incl_sum(cnt);
-    int before, total;
-    block_wave_offsets(incl, lds, &before, &total);
-    int64_t line = tile_first_line[blockIdx.x] + before + (incl - cnt);
-    while (m) {
-        const int j = __ffs(m) - 1;
-        m &= m - 1u;
-        if (line < n_newlines) line_end[line] = pos + j;
-        line++;
-    }
-}
-
-}  // namespace
-
-int gki_text_line_ends(const uint8_t *bytes, int64_t n, const char *who, DevBuf &line_end, int64_t *n_lines) {
-    const int64_t n_tiles = ceil_div(n, PARSE_TILE);
-    if (n_tiles > 0x7FFFFFFFll) return gki_set_error(GKI_ERR_BAD_ARG, "%s: buffer of %lld bytes is too large", who, (long long)n);
-    DevBuf tile_newlines, tile_first_line, tmp;
-    const int64_t tile_tmp_bytes = gki_scan_tmp_bytes(n_tiles);
-    HIP_TRY(tile_newlines.alloc((size_t)n_tiles * 4));
-    HIP_TRY(tile_first_line.alloc((size_t)(n_tiles + 1) * 8));
-    HIP_TRY(tmp.alloc((size_t)tile_tmp_bytes));
-    hipLaunchKernelGGL(k_parse_count_newlines, dim3((unsigned)n_tiles), dim3(PARSE_BLOCK), 0, 0, bytes, n,
-                       tile_newlines.get<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    GKI_TRY(gki_scan_u32_to_i64(tile_newlines.get<const uint32_t>(), n_tiles, tile_first_line.get<int64_t>(), tmp.get(),
-                                tile_tmp_bytes, 0));
-    int64_t n_newlines = 0;
-    uint8_t last = 0;
-    HIP_TRY(hipMemcpy(&n_newlines, tile_first_line.get<const int64_t>() + n_tiles, 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&last, bytes + n - 1, 1, hipMemcpyDeviceToHost));
-    const bool open_end = last != (uint8_t)'\n';           // the last line has no terminator
-    *n_lines = n_newlines + (open_end ? 1 : 0);
-    HIP_TRY(line_end.alloc((size_t)*n_lines * 8));
-    hipLaunchKernelGGL(k_parse_line_ends, dim3((unsigned)n_tiles), dim3(PARSE_BLOCK), 0, 0, bytes, n,
-                       tile_first_line.get<const int64_t>(), n_newlines, line_end.get<int64_t>());
-    HIP_TRY(hipGetLastError());
-    if (open_end) HIP_TRY(hipMemcpy(line_end.get<int64_t>() + n_newlines, &n, 8, hipMemcpyHostToDevice));
-    return GKI_OK;
-}
 
 namespace {
 
@@ -119,8 +30,7 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_parse_classify(const uint8_t *_
                                                                 ParseTotals *__restrict__ totals) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_lines; i += stride) {
-        int64_t b = i ? line_end[i - 1] + 1 : 0;
-        int64_t e = line_end[i];
+        auto [b, e] = text_line(line_end, i);
         const uint8_t first = b < e ? bytes[b] : (uint8_t)'\n';
         bool read;
         if (fastq) {
@@ -162,7 +72,7 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_parse_emit(const uint8_t *__res
         const int64_t len = read_len[i];
         if (r >= n_reads || off + len > n_letters) continue;   // totals of another run of the same buffer: write nothing
         if (lane == 0) read_start[r] = off;
-        for (int64_t j = lane; j < len; j += 64) letters[off + j] = bytes[src + j];
+        wave_copy(letters + off, bytes + src, len, lane);
     }
 }
 
@@ -202,8 +112,8 @@ int parse_lines(const uint8_t *bytes, int64_t n, int format, int line_phase, Par
     GKI_TRY(gki_scan_u32_to_i64(p.read_len.get<const uint32_t>(), n_lines, p.letter_offset.get<int64_t>(), p.tmp.get(),
                                 line_tmp_bytes, 0));
     ParseTotals totals;
-    HIP_TRY(hipMemcpy(&p.n_reads, p.read_index.get<const int64_t>() + n_lines, 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&p.n_letters, p.letter_offset.get<const int64_t>() + n_lines, 8, hipMemcpyDeviceToHost));
+    GKI_TRY(gki_scan_total(p.read_index, n_lines, &p.n_reads));
+    GKI_TRY(gki_scan_total(p.letter_offset, n_lines, &p.n_letters));
     HIP_TRY(hipMemcpy(&totals, p.totals.get(), sizeof(ParseTotals), hipMemcpyDeviceToHost));
     if (totals.too_long) return gki_set_error(GKI_ERR_BAD_ARG, "reads_parse: a read of 2^32 letters or more");
     p.n_lines = n_lines;

@@ -1,5 +1,8 @@
-// Lines of ASCII text in HBM, shared by the parsers of text files (gki_reads_parse.hip, gki_vcf_parse.hip): the tile
-// geometry of the line-end pass, its host-side driver, and the small device helpers both parsers use.
+// Lines of ASCII text in HBM: what the four parsers of text files share -- reads (gki_reads_parse.hip), VCF
+// (gki_vcf_parse.hip), the graph build's site pass (gki_graph_build.hip) and the reference FASTA (gki_fasta_parse.hip).
+// The tile geometry, the SWAR byte test, the block prefix and the wave copy serve the dense kernels of all four; the
+// line-end pass (kernels in gki_text_lines.hip) serves all but the FASTA parser; the VCF line rules serve the VCF parser
+// and the site pass, which must number the data lines alike (gki_graph_sites_* checks the count).
 #pragma once
 #include "gki_common.h"
 
@@ -12,10 +15,26 @@ __device__ __forceinline__ bool is_strip_byte(uint8_t c) {
     return c == 0x20 || (c >= 0x09 && c <= 0x0D) || (c >= 0x1C && c <= 0x1F);
 }
 
-// the lanes' values summed over the workgroup's four waves: (sum of the waves before this one, sum of all)
-__device__ __forceinline__ void block_wave_offsets(int wave_total, int *lds, int *before, int *total) {
+// bit j set where byte j of the word equals C: x = w ^ CCCCCCCC has a zero byte there; (x & 0x7F) + 0x7F carries into
+// bit 7 of a byte exactly when its low seven bits are not all zero, and never beyond the byte, so the test is exact per byte
+template <uint32_t C> __device__ __forceinline__ uint32_t equal_bits4(uint32_t w) {
+    const uint32_t x = w ^ (C * 0x01010101u);
+    const uint32_t t = (x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;
+    const uint32_t z = ~(t | x | 0x7F7F7F7Fu) >> 7;       // bit 0, 8, 16, 24 = byte 0..3 equals C
+    return (z * 0x01020408u) >> 24;                       // gathered into bits 0..3 (no two partial products meet)
+}
+template <uint32_t C> __device__ __forceinline__ uint32_t equal_mask16(const uint4 &v) {
+    return equal_bits4<C>(v.x) | equal_bits4<C>(v.y) << 4 | equal_bits4<C>(v.z) << 8 | equal_bits4<C>(v.w) << 12;
+}
+
+// The lanes' counts summed over the workgroup's four waves, in lane order: returns the sum of the lanes before this one,
+// *total = the sum of all.  Every lane calls it; lds holds one int per wave and serves one call.  A count may pack two
+// fields (high and low half) that do not overflow over the workgroup.  64 bits wide as its users add it to a tile's 64-bit
+// offset: formed in 32 bits, `incl - cnt` is folded back into the scan's six partial sums, all live across the barrier.
+__device__ __forceinline__ int64_t block_excl_sum(int cnt, int *lds, int *total) {
+    const int incl = gki_wave_incl_sum(cnt);
     const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 63) lds[wave] = wave_total;
+    if ((threadIdx.x & 63) == 63) lds[wave] = incl;       // lane 63's inclusive sum is its wave's total
     __syncthreads();
     int b = 0, t = 0;
 #pragma unroll
@@ -24,11 +43,85 @@ __device__ __forceinline__ void block_wave_offsets(int wave_total, int *lds, int
         if (w < wave) b += v;
         t += v;
     }
-    *before = b;
     *total = t;
+    return (int64_t)b + (incl - cnt);
+}
+
+// one wave copies len bytes, 64 a step
+__device__ __forceinline__ void wave_copy(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, int64_t len, int lane) {
+    for (int64_t j = lane; j < len; j += 64) dst[j] = src[j];
+}
+
+// Line i is bytes [b, e) = [line_end[i - 1] + 1, line_end[i]), its '\n' excluded
+struct TextLine { int64_t b, e; };
+__device__ __forceinline__ TextLine text_line(const int64_t *line_end, int64_t i) {
+    return {i ? line_end[i - 1] + 1 : 0, line_end[i]};
+}
+
+constexpr int VCF_MAX_POS_DIGITS = 18;                     // 10^18 - 1 fits int64
+constexpr int VCF_FIELDS = 5;                              // CHROM POS ID REF ALT: no kernel walks beyond them
+
+// Line i of VCF text: every '\r' at its end is dropped; a data line is not empty, does not begin with '#' and is not blank
+// (nothing but strip bytes).  One function: a kernel drops what it does not use, two helpers cost k_gb_is_data a register.
+struct VcfLine { int64_t b, e; bool data; };
+__device__ __forceinline__ VcfLine vcf_line(const uint8_t *bytes, const int64_t *line_end, int64_t i) {
+    auto [b, e] = text_line(line_end, i);
+    while (e > b && bytes[e - 1] == (uint8_t)'\r') e--;
+    bool data = b < e && bytes[b] != (uint8_t)'#';
+    if (data) {                                            // ends at the first byte that is no strip byte
+        int64_t p = b;
+        while (p < e && is_strip_byte(bytes[p])) p++;
+        data = p < e;
+    }
+    return {b, e, data};
+}
+
+// Fields 0..4 of the data line [b, e): field f is closed by tab number f + 1, or by the line's end.  n = how many of them
+// the line has (1..5); field f < n is bytes [begin(f), end[f]).  The walk never goes beyond the fifth tab.
+struct VcfFields {
+    int64_t b, end[VCF_FIELDS];
+    int n;
+    __device__ __forceinline__ int64_t begin(int f) const { return f ? end[f - 1] + 1 : b; }
+    __device__ __forceinline__ int64_t len(int f) const { return end[f] - begin(f); }
+};
+__device__ __forceinline__ VcfFields vcf_fields(const uint8_t *__restrict__ bytes, int64_t b, int64_t e) {
+    VcfFields f;
+    f.b = b;
+    f.n = 0;
+#pragma unroll
+    for (int k = 0; k < VCF_FIELDS; k++) f.end[k] = e;
+    for (int64_t p = b; f.n < VCF_FIELDS; p++) {
+        const bool last = p == e;
+        if (last || bytes[p] == (uint8_t)'\t') {
+#pragma unroll
+            for (int k = 0; k < VCF_FIELDS; k++) f.end[k] = k == f.n ? p : f.end[k];
+            f.n++;
+            if (last) break;
+        }
+    }
+    return f;
+}
+
+// POS is 1 to 18 plain digits: bytes [b, e) -> *value; false otherwise, and *value is then of no meaning
+__device__ __forceinline__ bool vcf_pos_value(const uint8_t *__restrict__ bytes, int64_t b, int64_t e, int64_t *value) {
+    int64_t v = 0;
+    bool ok = e > b && e - b <= VCF_MAX_POS_DIGITS;
+    for (int64_t p = b; ok && p < e; p++) {
+        const uint8_t c = bytes[p];
+        ok = c >= (uint8_t)'0' && c <= (uint8_t)'9';
+        v = v * 10 + (c - (uint8_t)'0');
+    }
+    *value = v;
+    return ok;
 }
 
 // bytes[0, n) on the device (n > 0) -> line_end, int64[*n_lines]: line i is bytes [line_end[i - 1] + 1, line_end[i]),
 // its '\n' excluded; a last line without '\n' ends at n.  *n_lines = number of '\n' + (the last byte is not '\n').
-// The kernels are k_parse_count_newlines and k_parse_line_ends of gki_reads_parse.hip; `who` begins the error messages.
+// The kernels are k_parse_count_newlines and k_parse_line_ends of gki_text_lines.hip; `who` begins the error messages.
 int gki_text_line_ends(const uint8_t *bytes, int64_t n, const char *who, DevBuf &line_end, int64_t *n_lines);
+
+// the total of an exclusive scan of n inputs (gki_scan_u32_to_i64): its entry n, read back; waits for the scan
+static inline int gki_scan_total(const DevBuf &scan, int64_t n, int64_t *total) {
+    HIP_TRY(hipMemcpy(total, scan.get<const int64_t>() + n, 8, hipMemcpyDeviceToHost));
+    return GKI_OK;
+}

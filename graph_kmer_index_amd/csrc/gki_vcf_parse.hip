@@ -3,9 +3,10 @@
 // rules are those of include/gki.h ("VCF files"), chosen so that the result equals VariantArrays.from_vcf
 // (unique_variant_kmers.py) wherever that function returns.
 //
-//   (line ends)              gki_text_line_ends: the coalesced 16-byte pass of gki_reads_parse.hip, the only whole-line work
+//   (line ends)              gki_text_line_ends: the coalesced 16-byte pass of gki_text_lines.hip, the only whole-line work
 //   k_vcf_classify           one lane per line: header / blank / data; a data line is walked to its fifth tab at the most
 //                            (never into the genotype columns) for POS, is_snp, where CHROM lies and whether the line is bad
+//                            (the line, field and POS rules are gki_text_lines.h's, shared with the graph build's site pass)
 //   (exclusive scan)         line -> number of data lines (variants) before it
 //   k_vcf_compact            line_of_variant[v]
 //   k_vcf_run_flags          one lane per variant: its CHROM against the previous variant's, in length and bytes
@@ -18,13 +19,11 @@
 
 namespace {
 
-constexpr int VCF_MAX_POS_DIGITS = 18;                     // 10^18 - 1 fits int64
-
 // first_bad: (line << 2 | kind) of the lowest bad line, all ones when there is none (atomicMin)
 struct VcfTotals { unsigned long long first_bad; unsigned int too_long; unsigned int pad; };
 
-// Line i is bytes [line_end[i - 1] + 1, line_end[i]), and every '\r' at its end is dropped.  is_data[i]; for a data line
-// pos[i], snp[i], and CHROM as bytes [chrom_begin[i], chrom_begin[i] + chrom_len[i]).
+// One lane per line, by the rules of gki_text_lines.h (vcf_line, vcf_fields, vcf_pos_value).  is_data[i];
+// for a data line pos[i], snp[i], and CHROM as bytes [chrom_begin[i], chrom_begin[i] + chrom_len[i]).
 __global__ __launch_bounds__(PARSE_BLOCK) void k_vcf_classify(const uint8_t *__restrict__ bytes,
                                                               const int64_t *__restrict__ line_end, int64_t n_lines,
                                                               uint32_t *__restrict__ is_data, int64_t *__restrict__ pos,
@@ -33,43 +32,17 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_vcf_classify(const uint8_t *__r
                                                               VcfTotals *__restrict__ totals) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_lines; i += stride) {
-        const int64_t b = i ? line_end[i - 1] + 1 : 0;
-        int64_t e = line_end[i];
-        while (e > b && bytes[e - 1] == (uint8_t)'\r') e--;
-        bool data = b < e && bytes[b] != (uint8_t)'#';
-        if (data) {                                        // blank when nothing but strip bytes: ends at the first other byte
-            int64_t p = b;
-            while (p < e && is_strip_byte(bytes[p])) p++;
-            data = p < e;
-        }
-        is_data[i] = data ? 1u : 0u;
-        if (!data) continue;
-        // fields 0..4; field f is closed by tab number f + 1, or by the line's end when the line has only f tabs
-        int tabs = 0, digits = 0;
-        bool pos_ok = true;
-        int64_t value = 0, field_begin = b, len0 = 0, len3 = 0, len4 = 0, p = b;
-        for (; p <= e && tabs < 5; p++) {
-            const bool close = p == e || bytes[p] == (uint8_t)'\t';
-            if (close) {
-                const int64_t len = p - field_begin;
-                if (tabs == 0) len0 = len;
-                else if (tabs == 3) len3 = len;
-                else if (tabs == 4) len4 = len;
-                if (p == e) break;
-                tabs++;
-                field_begin = p + 1;
-            } else if (tabs == 1) {
-                const uint8_t c = bytes[p];
-                if (c < (uint8_t)'0' || c > (uint8_t)'9' || digits == VCF_MAX_POS_DIGITS) pos_ok = false;
-                else { value = value * 10 + (c - (uint8_t)'0'); digits++; }
-            }
-        }
-        const int kind = tabs == 0 ? 1 : (!pos_ok || digits == 0) ? 2 : 0;
+        const VcfLine l = vcf_line(bytes, line_end, i);
+        is_data[i] = l.data ? 1u : 0u;
+        if (!l.data) continue;
+        const VcfFields f = vcf_fields(bytes, l.b, l.e);
+        int64_t value = 0, len0 = f.len(0);
+        const int kind = f.n < 2 ? 1 : !vcf_pos_value(bytes, f.begin(1), f.end[1], &value) ? 2 : 0;
         if (kind) atomicMin(&totals->first_bad, (unsigned long long)i << 2 | (unsigned long long)kind);
         if (len0 > 0xFFFFFFFFll) { atomicOr(&totals->too_long, 1u); len0 = 0; }
         pos[i] = value;
-        snp[i] = tabs < 4 ? (int8_t)-1 : (int8_t)(len3 == 1 && len4 == 1);
-        chrom_begin[i] = b;
+        snp[i] = f.n < VCF_FIELDS ? (int8_t)-1 : (int8_t)(f.len(3) == 1 && f.len(4) == 1);
+        chrom_begin[i] = l.b;
         chrom_len[i] = (uint32_t)len0;
     }
 }
@@ -174,14 +147,13 @@ int vcf_parse(const uint8_t *bytes, int64_t n, VcfPlan &p) {
     GKI_TRY(gki_scan_u32_to_i64(p.is_data.get<const uint32_t>(), n_lines, p.variant_index.get<int64_t>(), p.tmp.get(),
                                 gki_scan_tmp_bytes(n_lines), 0));
     VcfTotals totals;
-    HIP_TRY(hipMemcpy(&p.n_variants, p.variant_index.get<const int64_t>() + n_lines, 8, hipMemcpyDeviceToHost));
+    GKI_TRY(gki_scan_total(p.variant_index, n_lines, &p.n_variants));
     HIP_TRY(hipMemcpy(&totals, p.totals.get(), sizeof(VcfTotals), hipMemcpyDeviceToHost));
     p.line_end.reset();
     if (totals.too_long) return gki_set_error(GKI_ERR_BAD_ARG, "vcf_parse: a CHROM of 2^32 bytes or more");
     p.n_lines = n_lines;
     if (totals.first_bad != ~0ull) {
-        HIP_TRY(hipMemcpy(&p.first_bad_variant, p.variant_index.get<const int64_t>() + (totals.first_bad >> 2), 8,
-                          hipMemcpyDeviceToHost));
+        GKI_TRY(gki_scan_total(p.variant_index, (int64_t)(totals.first_bad >> 2), &p.first_bad_variant));
         p.first_bad_kind = (int)(totals.first_bad & 3);
     }
     if (p.n_variants == 0) return GKI_OK;
@@ -206,8 +178,8 @@ int vcf_parse(const uint8_t *bytes, int64_t n, VcfPlan &p) {
                                 run_tmp_bytes, 0));
     GKI_TRY(gki_scan_u32_to_i64(p.name_len.get<const uint32_t>(), nv, p.name_bytes_before.get<int64_t>(), p.tmp.get(),
                                 run_tmp_bytes, 0));
-    HIP_TRY(hipMemcpy(&p.n_runs, p.runs_before.get<const int64_t>() + nv, 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&p.n_name_bytes, p.name_bytes_before.get<const int64_t>() + nv, 8, hipMemcpyDeviceToHost));
+    GKI_TRY(gki_scan_total(p.runs_before, nv, &p.n_runs));
+    GKI_TRY(gki_scan_total(p.name_bytes_before, nv, &p.n_name_bytes));
     if (p.n_runs > 0x7FFFFFFFll) return gki_set_error(GKI_ERR_BAD_ARG, "vcf_parse: %lld chromosome runs do not fit int32", (long long)p.n_runs);
     return GKI_OK;
 }

@@ -1,7 +1,7 @@
 """Reference FASTA files on the device: .fa and BGZF .fa.gz text -> the letters of the chosen records in HBM, without a
 host pass over the text.
 
-The text reaches HBM as the reads files' and the VCF's do -- `read_files.text_pieces`: pieces that end at a line end, a
+The text reaches HBM as the reads files' and the VCF's do -- `text_files.text_pieces`: pieces that end at a line end, a
 BGZF file inflated on the device, any other gzip through Python's gzip -- and gki_fasta_parse_count / _names / _emit
 (csrc/gki_fasta_parse.hip) give, per piece, the headers' names and letter counts and then the letters of the records the
 host wants, line ends removed.  The rules are `snp_kmer_finder.read_fasta_records`' own, stated in include/gki.h ("FASTA
@@ -19,7 +19,7 @@ import time
 import numpy as np
 
 from . import _lib
-from .read_files import DEFAULT_CHUNK_BYTES, _device_bytes, text_pieces
+from .text_files import DEFAULT_CHUNK_BYTES, device_bytes, names_from, text_pieces
 
 PARSE_CHOICES = ("auto", "host", "device")
 
@@ -75,7 +75,7 @@ def fasta_names(text, n_bytes, n_headers, n_name_bytes, kernel_ms):
                                                      n_name_bytes, C.byref(ms)))
         start, raw, body = name_start.to_host(), raw.to_host(n_name_bytes).tobytes(), body.to_host()
     kernel_ms[0] += ms.value
-    return [raw[a:b].decode("ascii", "replace") for a, b in zip(start[:-1], start[1:])], body
+    return names_from(start, raw, "ascii", "replace"), body
 
 
 def fasta_emit(scope, text, n_bytes, carry_wanted, wanted, n_letters, kernel_ms):
@@ -169,13 +169,12 @@ def _reference_from_pieces(pieces, names, file_name):
 
 def reference_from_file(file_name, names=None, chunk_bytes=DEFAULT_CHUNK_BYTES, inflate="auto"):
     """`read_fasta_records(file_name, names)` with the text parsed on the device, streamed: one loop over the pieces of
-    the text, about `chunk_bytes` each, that the file's route gives.  A `.gz` file goes by `reads_file_route`: BGZF is
-    inflated on the device, any other gzip through Python's gzip on the host.  inflate: 'auto' that rule, 'host' gzip on
-    the host for every `.gz`, 'device' ValueError unless the file is BGZF.  names None: every distinct name in file order;
+    the text, about `chunk_bytes` each, that the file's route gives (`chunk_bytes` and `inflate` as in
+    `text_files.text_pieces`).  names None: every distinct name in file order;
     of records that share a name the first is the one meant.  A name that is not in the file is read_fasta_records'
     KeyError.  Returns a DeviceReference; the caller frees its letters."""
     _lib.require_device()
-    source = text_pieces(file_name, DEFAULT_CHUNK_BYTES if chunk_bytes is None else chunk_bytes, inflate)
+    source = text_pieces(file_name, chunk_bytes, inflate)
     with contextlib.closing(source) as pieces:
         return _reference_from_pieces(pieces, names, file_name)
 
@@ -185,6 +184,6 @@ def parse_fasta_on_device(buf, names=None):
     piece.  A DeviceArray stays its owner's."""
     _lib.require_device()
     with _lib.DeviceScope() as s:
-        d = _device_bytes(s, buf)
+        d = device_bytes(s, buf)
         pieces = [(d.view(0, d.n), d.n)] if d.n else []   # a window: the loop frees what it is handed, `d` stays
         return _reference_from_pieces(iter(pieces), names, "<buffer>")

@@ -1,7 +1,7 @@
 """The graph and its variant-to-nodes table from a reference FASTA and a VCF, built on the device.
 
 The chosen chromosomes' letters go to HBM one record at a time and lie there concatenated; the VCF text reaches HBM as it
-does for `vcf_files` (`read_files.text_pieces`: plain, BGZF inflated on the device, other gzip on the host).  Per piece the
+does for `vcf_files` (`text_files.text_pieces`: plain, BGZF inflated on the device, other gzip on the host).  Per piece the
 existing parse gives the chromosome runs, the host maps the few run names to their chromosomes' bounds, and
 gki_graph_sites_count / _emit (csrc/gki_graph_build.hip) turn every data line into a site.  Over all lines
 gki_graph_build_count / _emit decide which sites are kept and write the arrays of graph.py, `ref_nodes` / `var_nodes`
@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib
 from .graph import GraphArrays
-from .read_files import DEFAULT_CHUNK_BYTES, _device_bytes, text_pieces
+from .text_files import device_bytes, names_from, text_pieces
 from .vcf_files import vcf_count, vcf_emit
 
 STATUS_TEXT = {0: "kept", 1: "REF or ALT is not plain letters", 2: "no base before the site", 3: "overlaps an earlier site"}
@@ -130,8 +130,7 @@ class _Builder:
         s = self.scope
         with _lib.DeviceScope() as t:
             _, _, chrom_run, run_name_start, run_names = vcf_emit(t, text, n_bytes, nv, n_runs, n_name_bytes)
-            start, raw = run_name_start.to_host(), run_names.to_host().tobytes()
-            names = [raw[a:b].decode("utf-8", "replace") for a, b in zip(start[:-1], start[1:])]
+            names = names_from(run_name_start.to_host(), run_names.to_host().tobytes(), errors="replace")
             c0, c1 = self._run_bounds(
                 names, lambda r: self.n_lines + int(np.searchsorted(chrom_run.to_host(), r, side="left")))
             run_c0, run_c1 = t.on_device(c0, np.int64), t.on_device(c1, np.int64)
@@ -231,7 +230,7 @@ def build_graph(reference, text, chromosomes=None, allele_frequencies=None):
     names = list(reference) if chromosomes is None else list(chromosomes)
     with _lib.DeviceScope() as s:
         builder = _Builder(s, names, [reference[n] for n in names])
-        d = _device_bytes(s, text)
+        d = device_bytes(s, text)
         builder.add_piece(d, d.n)
         return builder.finish(allele_frequencies)
 
@@ -239,15 +238,16 @@ def build_graph(reference, text, chromosomes=None, allele_frequencies=None):
 def build_graph_from_files(fasta, vcf, chromosomes=None, allele_frequencies=None, chunk_bytes=None, inflate="auto",
                            fasta_parse="auto"):
     """The graph of the FASTA records `chromosomes` (None: every record, in file order) with the variants of `vcf`: a
-    .vcf, a BGZF .vcf.gz inflated on the device, any other .gz through Python's gzip (`inflate` as in `vcf_files`).  The
-    VCF is streamed in pieces of about `chunk_bytes`; line numbers and the order check carry across pieces.
+    .vcf, a BGZF .vcf.gz inflated on the device, any other .gz through Python's gzip (`inflate` and `chunk_bytes` as in
+    `text_files.text_pieces`).  The VCF is streamed in pieces of about `chunk_bytes`; line numbers and the order check
+    carry across pieces.
     fasta_parse: 'device' the FASTA (plain, BGZF or gzip) is parsed on the device (`fasta_files.reference_from_file`) and
     its letters stay there; 'host' `read_fasta_records` and one upload per chromosome; 'auto' the faster of the two."""
     from .fasta_files import reference_from_file, resolve_fasta_parse
     from .snp_kmer_finder import read_fasta_records
     _lib.require_device()
     device = resolve_fasta_parse(fasta_parse) == "device"
-    source = text_pieces(vcf, DEFAULT_CHUNK_BYTES if chunk_bytes is None else chunk_bytes, inflate)
+    source = text_pieces(vcf, chunk_bytes, inflate)
     with _lib.DeviceScope() as s, contextlib.closing(source) as pieces:
         t0 = time.perf_counter()
         if device:                                        # `chunk_bytes` is the VCF's: the FASTA's pieces keep their size

@@ -41,7 +41,7 @@ def read_fasta_records(file_name, names=None):
     with line ends stripped, from ONE read of the file.  A record's name is the first word of its `>` line.  No .fai.
     A name ending in .gz (gzip or BGZF) is inflated by Python's gzip.  This is the host route; `fasta_files` has the
     device's."""
-    from .read_files import open_reads_file
+    from .text_files import open_reads_file
     with open_reads_file(file_name) as f:
         data = f.read()
     buf = np.frombuffer(data, dtype=np.uint8)

@@ -1,10 +1,10 @@
 """VCF files on the device: .vcf and BGZF .vcf.gz text -> VariantArrays, without a host pass over the lines.
 
-The text reaches HBM as the reads files' does -- `read_files.text_pieces`: `host_text_pieces` or `bgzf_text_pieces`, pieces
-that end at a line end, a BGZF file inflated on the device -- and gki_vcf_parse_count / _emit (csrc/gki_vcf_parse.hip) turn each piece
-into POS, is_snp and the chromosome of every data line, the chromosomes as runs of equal names.  The rules are stated in
-include/gki.h ("VCF files") and DESIGN.md 4.14; they give what `VariantArrays.from_vcf` gives wherever that returns, except
-that POS must be plain digits.
+The text reaches HBM as the reads files' does -- `text_files.text_pieces`: pieces that end at a line end, a BGZF file
+inflated on the device -- and gki_vcf_parse_count / _emit (csrc/gki_vcf_parse.hip) turn each piece into POS, is_snp and
+the chromosome of every data line, the chromosomes as runs of equal names.  The rules are stated in include/gki.h ("VCF
+files") and DESIGN.md 4.14; they give what `VariantArrays.from_vcf` gives wherever that returns, except that POS must be
+plain digits.
 
 `variant_arrays_from_file` is one loop over the pieces; `VariantPieces` joins them on the host: data-line numbers go on
 across pieces, and a piece's first run continues the last run of the piece before when the names are equal.
@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .read_files import DEFAULT_CHUNK_BYTES, _device_bytes, text_pieces
+from .text_files import DEFAULT_CHUNK_BYTES, device_bytes, names_from, text_pieces
 
 BAD_TEXT = {1: "VCF data line %d has fewer than two columns",          # VariantArrays.from_vcf's own message
             2: "VCF data line %d: POS must be 1 to 18 plain digits (no sign, blank or underscore) for the device parser"}
@@ -47,8 +47,7 @@ def vcf_emit(scope, text, n_bytes, n_variants, n_runs, n_name_bytes):
 
 def copy_back(positions, is_snp, chrom_run, run_name_start, run_names):
     """`vcf_emit`'s arrays on the host: (positions, is_snp, chrom_run, run_names list[str]); names are UTF-8."""
-    start, raw = run_name_start.to_host(), run_names.to_host().tobytes()
-    names = [raw[a:b].decode("utf-8") for a, b in zip(start[:-1], start[1:])]
+    names = names_from(run_name_start.to_host(), run_names.to_host().tobytes())
     return positions.to_host(), is_snp.to_host(), chrom_run.to_host(), names
 
 
@@ -67,7 +66,7 @@ def parse_vcf_on_device(buf):
     equal CHROM data line v belongs to, run_names[r] that run's name.  ValueError for a bad data line."""
     _lib.require_device()
     with _lib.DeviceScope() as s:
-        d = _device_bytes(s, buf)
+        d = device_bytes(s, buf)
         out, bad = parse_piece(s, d, d.n)
     if bad is not None:
         raise bad_line_error(*bad)
@@ -104,13 +103,12 @@ class VariantPieces:
 
 def variant_arrays_from_file(file_name, chunk_bytes=DEFAULT_CHUNK_BYTES, inflate="auto"):
     """`VariantArrays.from_vcf(file_name)` with the lines parsed on the device, streamed: one loop over the pieces of the
-    text, about `chunk_bytes` each, that the file's route gives.  A `.gz` file goes by `reads_file_route`: BGZF is inflated
-    on the device, any other gzip through Python's gzip on the host.  inflate: 'auto' that rule, 'host' gzip on the host
-    for every `.gz`, 'device' ValueError unless the file is BGZF.  A bad data line raises ValueError after the piece that
-    shows it, with its number in the file."""
+    text, about `chunk_bytes` each, that the file's route gives (`chunk_bytes` and `inflate` as in
+    `text_files.text_pieces`).  A bad data line raises ValueError after the piece that shows it, with its number in the
+    file."""
     _lib.require_device()
     joined = VariantPieces()
-    source = text_pieces(file_name, DEFAULT_CHUNK_BYTES if chunk_bytes is None else chunk_bytes, inflate)
+    source = text_pieces(file_name, chunk_bytes, inflate)
     with contextlib.closing(source) as pieces:
         for text, n_bytes in pieces:
             with _lib.DeviceScope() as s:

@@ -20,7 +20,7 @@ from read_side_ref import build_index_ref, count_nodes_ref
 
 pytestmark = pytest.mark.gpu
 
-T = 4096            # csrc/gki_reads_parse.hip:24 PARSE_TILE = 256 lanes * 16 bytes: the bytes one workgroup scans
+T = 4096            # csrc/gki_text_lines.h PARSE_TILE = 256 lanes * 16 bytes: the bytes one workgroup scans
 S = 2048            # csrc/gki_runtime.hip:276 STILE = 256 * 8: the items one block of the exclusive scans covers
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAX = 2 ** 62

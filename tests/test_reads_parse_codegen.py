@@ -1,41 +1,14 @@
 """The reads-file parse kernels (csrc/gki_reads_parse.hip) compiled for gfx950: every kernel present, no scratch, no FLAT
-memory instruction, and the register and LDS footprints at what the build gives, as upper bounds.  CPU only: hipcc
-cross-compiles."""
-import os
+memory instruction, and the register and LDS footprints at what the build gives, as upper bounds.  The line-end pass the
+parser begins with is csrc/gki_text_lines.hip's (test_text_lines_codegen.py).  CPU only: hipcc cross-compiles."""
 import re
-import subprocess
 
-import pytest
+from codegen_asm import _bodies, _metadata, _of, asm_of, needs_hipcc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "graph_kmer_index_amd", "csrc", "gki_reads_parse.hip")
-HIPCC = "/opt/rocm/bin/hipcc"
-
-pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-# kernel -> (VGPRs, LDS bytes) of the build this was written against: the two tile kernels keep one int per wave in LDS
-FOOTPRINT = {"k_parse_count_newlines": (14, 16), "k_parse_line_ends": (14, 16), "k_parse_classify": (14, 0),
-             "k_parse_emit": (15, 0)}
-
-
-@pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("codegen_reads_parse") / "gki_reads_parse.s")
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function", "--cuda-device-only", "-S",
-                    SRC, "-o", out], check=True, stderr=subprocess.DEVNULL)
-    return open(out).read()
-
-
-def _bodies(txt):
-    return {m.group(1): m.group(2) for m in re.finditer(r"\n(_Z\w+):[^\n]*\n(.*?)\n\.Lfunc_end\d+:", txt, re.S)}
-
-
-def _metadata(txt):
-    out = {}
-    for blk in re.split(r"\n  - \.agpr_count:", txt)[1:]:
-        name = re.search(r"\.name:\s*(\S+)", blk).group(1)
-        out[name] = {key: int(re.search(r"\.%s:\s*(\d+)" % key, blk).group(1))
-                     for key in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_count")}
-    return out
+pytestmark = needs_hipcc
+# kernel -> (VGPRs, LDS bytes) of the build this was written against: neither uses LDS
+FOOTPRINT = {"k_parse_classify": (14, 0), "k_parse_emit": (15, 0)}
+asm = asm_of("gki_reads_parse")
 
 
 def test_every_kernel_is_present(asm):
@@ -58,5 +31,5 @@ def test_no_scratch(asm):
 def test_footprints(asm):
     md = _metadata(asm)
     for k, (vgprs, lds) in FOOTPRINT.items():
-        m = md[next(n for n in md if ("%d%s" % (len(k), k)) in n)]
+        m = _of(md, k)
         assert m["vgpr_count"] <= vgprs and m["group_segment_fixed_size"] <= lds, (k, m)

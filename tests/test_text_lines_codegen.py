@@ -1,14 +1,14 @@
-"""The VCF parse kernels (csrc/gki_vcf_parse.hip) compiled for gfx950: every kernel present, no scratch, no FLAT
-memory instruction, and the register and LDS footprints at what the build gives, as upper bounds.  CPU only: hipcc
+"""The line-end kernels of the text parsers (csrc/gki_text_lines.hip) compiled for gfx950: every kernel present, no scratch,
+no FLAT memory instruction, and the register and LDS footprints at what the build gives, as upper bounds.  CPU only: hipcc
 cross-compiles."""
 import re
 
 from codegen_asm import _bodies, _metadata, _of, asm_of, needs_hipcc
 
 pytestmark = needs_hipcc
-# kernel -> (VGPRs, LDS bytes) of the build this was written against: none of them uses LDS
-FOOTPRINT = {"k_vcf_classify": (30, 0), "k_vcf_compact": (9, 0), "k_vcf_run_flags": (13, 0), "k_vcf_emit": (21, 0)}
-asm = asm_of("gki_vcf_parse")
+# kernel -> (VGPRs, LDS bytes) of the build this was written against: the two tile kernels keep one int per wave in LDS
+FOOTPRINT = {"k_parse_count_newlines": (14, 16), "k_parse_line_ends": (14, 16)}
+asm = asm_of("gki_text_lines")
 
 
 def test_every_kernel_is_present(asm):
