@@ -16,7 +16,7 @@ collision_free_kmer_index.py:393-402).
     python -m graph_kmer_index_amd.command_line_interface make_reverse -f variant_kmers.npz -o reverse
     python -m graph_kmer_index_amd.command_line_interface make -t 16 -s 1 -k 31 -r True -R ref.fa -n chr1 -G <size> -o linear_kmers
     python -m graph_kmer_index_amd.command_line_interface map -i index.npz -f reads.fq.gz -k 31 -o node_counts
-    python -m graph_kmer_index_amd.command_line_interface make_graph -r ref.fa -v variants.vcf.gz -o graph -n chr1,chr2
+    python -m graph_kmer_index_amd.command_line_interface make_graph -r ref.fa -v variants.vcf.gz -o graph -n chr1,chr2 -a genotypes
 
 `-g` takes an obgraph file when obgraph is installed, else a GraphArrays .npz (GraphArrays.to_file).  `index -t N` runs
 one process per GPU (at most N, at most the visible devices), each on its own range of critical-path numbers, and
@@ -339,14 +339,18 @@ def make_graph(args):
     (graph_files.py).  What it writes is what `-g` and `-V` of the other commands read."""
     from .graph_files import STATUS_TEXT, build_graph_from_files
     chromosomes = None if args.chromosomes is None else [c for c in args.chromosomes.split(",") if c]
-    built = build_graph_from_files(args.reference_fasta, args.vcf, chromosomes, chunk_bytes=args.chunk_bytes,
-                                   inflate=args.inflate, fasta_parse=args.fasta_parse)
+    source = None if args.allele_frequencies == "none" else args.allele_frequencies
+    built = build_graph_from_files(args.reference_fasta, args.vcf, chromosomes, allele_frequencies=source,
+                                   chunk_bytes=args.chunk_bytes, inflate=args.inflate, fasta_parse=args.fasta_parse)
     v2n = args.variant_to_nodes if args.variant_to_nodes is not None else args.out_file_name + ".variant_to_nodes"
     built.graph.to_file(args.out_file_name)
     built.variant_to_nodes.to_file(v2n)
     counts = np.bincount(built.line_status, minlength=len(STATUS_TEXT))
     for code, text in STATUS_TEXT.items():
         logging.info("%d data lines: %s" % (counts[code], text))
+    if built.route is not None:
+        logging.info("allele frequencies from %s: %d data lines without a value keep 1.0, %d values parsed by the host"
+                     % (source, int(np.count_nonzero(built.route == 1)), int(np.count_nonzero(built.route == 2))))
     logging.info("Wrote %d nodes, %d edges and %d bases to %s, variant-to-nodes of %d lines to %s"
                  % (built.graph.n_nodes, len(built.graph.edges), len(built.graph.seq), args.out_file_name,
                     len(built.line_status), v2n))
@@ -482,6 +486,9 @@ def build_parser():
     p.add_argument("-n", "--chromosomes", required=False, default=None,
                    help="comma-separated FASTA record names in graph order (default: every record, in file order)")
     p.add_argument("-V", "--variant-to-nodes", required=False, default=None, help="default: <out>.variant_to_nodes")
+    p.add_argument("-a", "--allele-frequencies", required=False, choices=("none", "info", "genotypes"), default="none",
+                   help="where the allele nodes' frequencies come from: none = 1.0 on every node; info = the AF= entry of "
+                        "INFO; genotypes = the GT columns, counted on the device.  A line without a value keeps 1.0")
     p.add_argument("--inflate", required=False, choices=("auto", "host", "device"), default="auto",
                    help="where a .gz VCF is inflated: auto = BGZF on the device, other gzip on the host")
     p.add_argument("--chunk-bytes", required=False, type=int, default=None)

@@ -1,8 +1,10 @@
-// Lines of ASCII text in HBM: what the four parsers of text files share -- reads (gki_reads_parse.hip), VCF
-// (gki_vcf_parse.hip), the graph build's site pass (gki_graph_build.hip) and the reference FASTA (gki_fasta_parse.hip).
-// The tile geometry, the SWAR byte test, the block prefix and the wave copy serve the dense kernels of all four; the
-// line-end pass (kernels in gki_text_lines.hip) serves all but the FASTA parser; the VCF line rules serve the VCF parser
-// and the site pass, which must number the data lines alike (gki_graph_sites_* checks the count).
+// Lines of ASCII text in HBM: what the five parsers of text files share -- reads (gki_reads_parse.hip), VCF
+// (gki_vcf_parse.hip), the graph build's site pass (gki_graph_build.hip), the VCF's allele frequencies (gki_vcf_af.hip) and
+// the reference FASTA (gki_fasta_parse.hip).
+// The tile geometry, the SWAR byte test, the block prefix and the wave copy serve the dense kernels; the line-end pass
+// (kernels in gki_text_lines.hip) serves all but the FASTA parser; the VCF line rules serve the VCF parser, the site pass
+// and the allele-frequency pass, which must number the data lines alike (gki_graph_sites_* and
+// gki_vcf_allele_frequencies check the count).
 #pragma once
 #include "gki_common.h"
 

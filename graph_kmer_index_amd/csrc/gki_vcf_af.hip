@@ -1,0 +1,309 @@
+// Allele frequencies of VCF text in HBM: per data line (ref_af, alt_af) from INFO's AF= entry or from the GT columns.
+// The rules are those of include/gki.h ("VCF allele frequencies") and DESIGN.md 4.17.
+//
+// per piece of text (gki_vcf_allele_frequencies), beside the unchanged gki_vcf_parse_* and gki_graph_sites_*:
+//   (line ends)      gki_text_line_ends (kernels in gki_text_lines.hip)
+//   k_af_is_data     one lane per line: header / blank / data -- gki_text_lines.h's vcf_line, so the data lines are numbered
+//                    as the two other passes number them; the host checks the count
+//   (exclusive scan) line -> data lines before it
+//   k_af_info        source info: one lane per data line walks to the seventh tab and through INFO, which lies before the
+//                    sample columns, finds the AF= entry and turns its value text into a double by one exact operation
+//   k_af_genotypes   source genotypes: one wave per data line, dense in the bytes.  Each step the 64 lanes take 16
+//                    consecutive bytes each (AF_STEP = 1024 bytes a step), find the tabs with equal_mask16 and number them
+//                    with a wave prefix sum on top of the line's running count, which the wave carries in a scalar.  A
+//                    lane whose bytes hold tab number 9 or higher parses the GT behind it straight from memory, eight bytes
+//                    in one load (a GT is a few bytes; they may lie in the next lane's or the next step's bytes).  Tab number 8 opens FORMAT,
+//                    which its lane checks.  One wave reduction per line gives the three counts; lane 0 divides and stores.
+//                    A wave owns its line: no atomics but the atomicMin of the lowest line at fault.
+#include "gki_text_lines.h"
+
+namespace {
+
+constexpr int AF_STEP = 64 * PARSE_LANE_BYTES;            // bytes a wave takes per step
+constexpr int AF_MAX_MANTISSA_DIGITS = 15, AF_MAX_EXPONENT_DIGITS = 3, AF_MAX_POWER = 22, AF_MAX_ALLELE_DIGITS = 9;
+constexpr uint8_t ROUTE_DEVICE = 0, ROUTE_ABSENT = 1, ROUTE_HOST = 2;
+
+// first_bad: (data line << 3 | kind) of the lowest line at fault, all ones when there is none (atomicMin)
+struct AfTotals { unsigned long long first_bad; };
+
+// the powers of ten a double holds exactly
+__device__ const double AF_POW10[AF_MAX_POWER + 1] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
+                                                      1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
+
+__device__ __forceinline__ bool is_digit(uint8_t c) { return c >= (uint8_t)'0' && c <= (uint8_t)'9'; }
+
+__global__ __launch_bounds__(PARSE_BLOCK) void k_af_is_data(const uint8_t *__restrict__ bytes,
+                                                            const int64_t *__restrict__ line_end, int64_t n_lines,
+                                                            uint32_t *__restrict__ is_data) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_lines; i += stride)
+        is_data[i] = vcf_line(bytes, line_end, i).data ? 1u : 0u;
+}
+
+// The value text bytes [b, e) under the device grammar  D* [ . D* ] [ (e|E) [+|-] D+ ]: true and *value when the mantissa
+// has 1 to 15 digits, the exponent at most 3 and |q| <= 22, q = exponent - fraction digits.  m (below 10^15) and 10^|q| are
+// exact doubles, so the one multiplication or division is the correctly rounded value of the text.
+__device__ __forceinline__ bool af_value(const uint8_t *__restrict__ bytes, int64_t b, int64_t e, double *value) {
+    uint64_t m = 0;
+    int digits = 0, fraction = 0, exponent = 0, exponent_digits = 0;
+    bool negative = false, ok = true;
+    int64_t p = b;
+    for (; p < e && is_digit(bytes[p]); p++, digits++)
+        if (digits < AF_MAX_MANTISSA_DIGITS) m = m * 10 + (bytes[p] - (uint8_t)'0');
+    if (p < e && bytes[p] == (uint8_t)'.') {
+        for (p++; p < e && is_digit(bytes[p]); p++, digits++, fraction++)
+            if (digits < AF_MAX_MANTISSA_DIGITS) m = m * 10 + (bytes[p] - (uint8_t)'0');
+    }
+    ok = digits >= 1 && digits <= AF_MAX_MANTISSA_DIGITS;
+    if (ok && p < e && (bytes[p] | 0x20) == (uint8_t)'e') {
+        p++;
+        if (p < e && (bytes[p] == (uint8_t)'+' || bytes[p] == (uint8_t)'-')) { negative = bytes[p] == (uint8_t)'-'; p++; }
+        for (; p < e && is_digit(bytes[p]) && exponent_digits <= AF_MAX_EXPONENT_DIGITS; p++, exponent_digits++)
+            exponent = exponent * 10 + (bytes[p] - (uint8_t)'0');
+        ok = exponent_digits >= 1 && exponent_digits <= AF_MAX_EXPONENT_DIGITS;
+    }
+    ok = ok && p == e;                                     // a stray byte, a sign, nan, inf: the host's
+    const int q = (negative ? -exponent : exponent) - fraction;
+    ok = ok && q >= -AF_MAX_POWER && q <= AF_MAX_POWER;
+    const double power = AF_POW10[ok ? (q < 0 ? -q : q) : 0];
+    *value = q < 0 ? (double)m / power : (double)m * power;
+    return ok;
+}
+
+// Data line v: INFO is field 7.  route 0 with the value, 1 absent, 2 with the value text's place for the host.
+__global__ __launch_bounds__(PARSE_BLOCK) void k_af_info(const uint8_t *__restrict__ bytes,
+                                                         const int64_t *__restrict__ line_end, int64_t n_lines,
+                                                         const uint32_t *__restrict__ is_data,
+                                                         const int64_t *__restrict__ variant_index, int64_t n_variants,
+                                                         double *__restrict__ ref_af, double *__restrict__ alt_af,
+                                                         uint8_t *__restrict__ route, int64_t *__restrict__ span_begin,
+                                                         int32_t *__restrict__ span_len, AfTotals *__restrict__ totals) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_lines; i += stride) {
+        if (!is_data[i]) continue;
+        const int64_t v = variant_index[i];
+        if (v >= n_variants) continue;
+        const VcfLine l = vcf_line(bytes, line_end, i);
+        int64_t p = l.b;
+        int tabs = 0;
+        for (; p < l.e && tabs < 7; p++) tabs += bytes[p] == (uint8_t)'\t';
+        int64_t value_b = -1, value_e = -1;
+        if (tabs == 7) {                                   // p is INFO's first byte; its entries end at ';', the field at a tab
+            bool entry_begins = true;
+            for (; p < l.e && bytes[p] != (uint8_t)'\t'; p++) {
+                const uint8_t c = bytes[p];
+                if (entry_begins && c == (uint8_t)'A' && p + 2 < l.e && bytes[p + 1] == (uint8_t)'F' && bytes[p + 2] == (uint8_t)'=') {
+                    value_b = value_e = p + 3;
+                    while (value_e < l.e && bytes[value_e] != (uint8_t)';' && bytes[value_e] != (uint8_t)',' &&
+                           bytes[value_e] != (uint8_t)'\t')
+                        value_e++;
+                    break;
+                }
+                entry_begins = c == (uint8_t)';';
+            }
+        }
+        const int64_t len = value_e - value_b;
+        double value = 0.0;
+        uint8_t r = ROUTE_ABSENT;
+        if (value_b >= 0 && len > 0 && !(len == 1 && bytes[value_b] == (uint8_t)'.'))
+            r = af_value(bytes, value_b, value_e, &value) ? ROUTE_DEVICE : ROUTE_HOST;
+        const bool at_fault = r == ROUTE_DEVICE && !(value <= 1.0);   // the grammar has no sign: never negative, never NaN
+        if (at_fault) atomicMin(&totals->first_bad, (unsigned long long)v << 3 | 1ull);
+        const bool parsed = r == ROUTE_DEVICE && !at_fault;
+        ref_af[v] = parsed ? 1.0 - value : 1.0;
+        alt_af[v] = parsed ? value : 1.0;
+        route[v] = r;
+        span_begin[v] = r == ROUTE_HOST ? value_b : 0;
+        span_len[v] = r == ROUTE_HOST ? (int32_t)(len < 0x7FFFFFFFll ? len : 0x7FFFFFFFll) : 0;
+    }
+}
+
+struct alignas(4) Bytes16 { uint32_t w[4]; };
+
+__device__ __forceinline__ int64_t wave_uniform(int64_t x) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)x >> 32));
+    return (int64_t)((uint64_t)hi << 32 | lo);
+}
+__device__ __forceinline__ int wave_sum(int x) { return gki_lane_value(gki_wave_incl_sum(x), 63); }
+
+// A GT of `len` bytes at most, byte i of it at(i): alleles separated by '/' or '|', each '.' or 1 to 9 digits, closed by
+// ':', a tab, or the end of the bytes when they reach the line's end (`whole`).  1: closed, the three counts in *c; 0: an
+// empty GT, an empty allele or any other byte; 2: the bytes ended first (never when `whole`).
+struct GtCounts { int called, n_ref, n_alt; };
+template <class At> __device__ __forceinline__ int gt_parse(At at, int64_t len, bool whole, GtCounts *c) {
+    *c = {0, 0, 0};
+    for (int64_t i = 0;;) {
+        if (i < len && at(i) == (uint8_t)'.') i++;
+        else {
+            int value = 0, digits = 0;
+            for (; i < len && is_digit(at(i)) && digits <= AF_MAX_ALLELE_DIGITS; i++, digits++)
+                value = value * 10 + (at(i) - (uint8_t)'0');
+            if (i >= len && !whole) return 2;
+            if (digits < 1 || digits > AF_MAX_ALLELE_DIGITS) return 0;
+            c->called += 1;
+            c->n_ref += value == 0;
+            c->n_alt += value == 1;
+        }
+        if (i >= len) return whole ? 1 : 2;
+        const uint8_t sep = at(i);
+        if (sep == (uint8_t)':' || sep == (uint8_t)'\t') return 1;
+        if (sep != (uint8_t)'/' && sep != (uint8_t)'|') return 0;
+        i++;
+    }
+}
+
+// The GT at bytes[p ..] of the line that ends at e, added to the three counts; false when it is at fault.  Eight bytes in
+// one load hold a GT and what closes it in all but rare lines ("0|1" and a tab are four), so the parse reads registers:
+// one load per GT instead of one per byte, which is what the kernel's rate hangs on.  A GT that is
+// longer, and one within eight bytes of the piece's end, goes byte by byte from memory.
+struct alignas(4) Bytes8 { uint32_t w[2]; };
+__device__ __forceinline__ bool gt_counts(const uint8_t *__restrict__ bytes, int64_t n_bytes, int64_t p, int64_t e,
+                                          int *called, int *n_ref, int *n_alt) {
+    GtCounts c;
+    int state = 2;
+    if (p + 8 <= n_bytes) {
+        Bytes8 raw;
+        __builtin_memcpy(&raw, bytes + p, 8);
+        const uint64_t window = (uint64_t)raw.w[1] << 32 | raw.w[0];
+        state = gt_parse([window](int64_t i) { return (uint8_t)(window >> (8 * (int)i)); }, e - p < 8 ? e - p : 8, e - p <= 8, &c);
+    }
+    if (state == 2) state = gt_parse([bytes, p](int64_t i) { return bytes[p + i]; }, e - p, true, &c);
+    *called += c.called;
+    *n_ref += c.n_ref;
+    *n_alt += c.n_alt;
+    return state == 1;
+}
+
+// One wave per data line.  FORMAT is field 8 (opened by tab number 8), the samples are fields 9 and up.
+__global__ __launch_bounds__(PARSE_BLOCK) void k_af_genotypes(const uint8_t *__restrict__ bytes, int64_t n_bytes,
+                                                              const int64_t *__restrict__ line_end, int64_t n_lines,
+                                                              const uint32_t *__restrict__ is_data,
+                                                              const int64_t *__restrict__ variant_index, int64_t n_variants,
+                                                              double *__restrict__ ref_af, double *__restrict__ alt_af,
+                                                              uint8_t *__restrict__ route, AfTotals *__restrict__ totals) {
+    const int lane = threadIdx.x & 63;
+    const int64_t first = wave_uniform((int64_t)blockIdx.x * (PARSE_BLOCK / 64) + (threadIdx.x >> 6));
+    const int64_t stride = (int64_t)gridDim.x * (PARSE_BLOCK / 64);
+    for (int64_t i = first; i < n_lines; i += stride) {
+        if (!is_data[i]) continue;
+        const int64_t v = variant_index[i];
+        if (v >= n_variants) continue;
+        const VcfLine l = vcf_line(bytes, line_end, i);
+        const int64_t b = wave_uniform(l.b), e = wave_uniform(l.e);
+        int tabs_before = 0, called = 0, n_ref = 0, n_alt = 0, bad_format = 0, bad_gt = 0;
+        for (int64_t base = b; base < e; base += AF_STEP) {
+            const int64_t p0 = base + (int64_t)lane * PARSE_LANE_BYTES;
+            uint4 in = {0u, 0u, 0u, 0u};
+            if (p0 + PARSE_LANE_BYTES <= n_bytes) {        // 16 bytes at any alignment; bytes behind e are masked below
+                if (p0 < e) {
+                    Bytes16 raw;
+                    __builtin_memcpy(&raw, bytes + p0, PARSE_LANE_BYTES);
+                    in = {raw.w[0], raw.w[1], raw.w[2], raw.w[3]};
+                }
+            } else {                                       // the piece's last bytes: one by one, none behind n_bytes
+                uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                for (int j = 0; j < PARSE_LANE_BYTES; j++)
+                    if (p0 + j < e) w[j >> 2] |= (uint32_t)bytes[p0 + j] << (8 * (j & 3));
+                in = {w[0], w[1], w[2], w[3]};
+            }
+            const int64_t left = e - p0;                   // bytes of the line from p0 on
+            const uint32_t inside = left >= PARSE_LANE_BYTES ? 0xFFFFu : left > 0 ? (1u << (int)left) - 1u : 0u;
+            uint32_t tabs = equal_mask16<'\t'>(in) & inside;
+            const int mine = __popc(tabs);
+            const int incl = gki_wave_incl_sum(mine);
+            int number = tabs_before + incl - mine;        // tabs of the line before this lane's first
+            tabs_before += gki_lane_value(incl, 63);
+            while (tabs) {
+                const int j = __ffs(tabs) - 1;
+                tabs &= tabs - 1;
+                number++;
+                const int64_t p = p0 + j + 1;              // the field tab `number` opens
+                if (number == 8)
+                    bad_format |= !(p + 2 <= e && bytes[p] == (uint8_t)'G' && bytes[p + 1] == (uint8_t)'T' &&
+                                    (p + 2 == e || bytes[p + 2] == (uint8_t)':' || bytes[p + 2] == (uint8_t)'\t'));
+                else if (number >= 9)
+                    bad_gt |= !gt_counts(bytes, n_bytes, p, e, &called, &n_ref, &n_alt);
+            }
+        }
+        called = wave_sum(called);
+        n_ref = wave_sum(n_ref);
+        n_alt = wave_sum(n_alt);
+        const int kind = tabs_before < 9 ? 0 : wave_sum(bad_format) ? 2 : wave_sum(bad_gt) ? 3 : 0;
+        if (lane == 0) {
+            const bool counted = tabs_before >= 9 && kind == 0 && called > 0;
+            if (kind) atomicMin(&totals->first_bad, (unsigned long long)v << 3 | (unsigned long long)kind);
+            ref_af[v] = counted ? (double)n_ref / (double)called : 1.0;
+            alt_af[v] = counted ? (double)n_alt / (double)called : 1.0;
+            route[v] = counted ? ROUTE_DEVICE : ROUTE_ABSENT;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int gki_vcf_allele_frequencies(const void *d_text, int64_t n_bytes, int source, int64_t n_variants, void *d_ref_af,
+                                          void *d_alt_af, void *d_route, void *d_span_begin, void *d_span_len,
+                                          int64_t *n_data_lines, int64_t *first_bad_variant, int *first_bad_kind,
+                                          float *kernel_ms) {
+    if (n_data_lines) *n_data_lines = 0;
+    if (first_bad_variant) *first_bad_variant = -1;
+    if (first_bad_kind) *first_bad_kind = 0;
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (n_bytes < 0 || n_variants < 0) return gki_set_error(GKI_ERR_BAD_ARG, "vcf_allele_frequencies: a negative size");
+    if (source != GKI_AF_SOURCE_INFO && source != GKI_AF_SOURCE_GENOTYPES)
+        return gki_set_error(GKI_ERR_BAD_ARG, "vcf_allele_frequencies: source %d is neither INFO nor genotypes", source);
+    if (n_bytes > 0 && d_text == nullptr) return gki_set_error(GKI_ERR_BAD_ARG, "vcf_allele_frequencies: the text is NULL");
+    if (n_variants > 0 && (d_ref_af == nullptr || d_alt_af == nullptr || d_route == nullptr ||
+                           (source == GKI_AF_SOURCE_INFO && (d_span_begin == nullptr || d_span_len == nullptr))))
+        return gki_set_error(GKI_ERR_BAD_ARG, "vcf_allele_frequencies: an output buffer is NULL");
+    const uint8_t *bytes = (const uint8_t *)d_text;
+    TimerEvents ev;
+    DevBuf line_end, is_data, variant_index, tmp, totals;
+    int64_t n_lines = 0, found = 0;
+    if (n_bytes > 0) {
+        GKI_TRY(gki_text_line_ends(bytes, n_bytes, "vcf_allele_frequencies", line_end, &n_lines));
+        const int64_t tmp_bytes = gki_scan_tmp_bytes(n_lines);
+        HIP_TRY(is_data.alloc((size_t)n_lines * 4));
+        HIP_TRY(variant_index.alloc((size_t)(n_lines + 1) * 8));
+        HIP_TRY(tmp.alloc((size_t)tmp_bytes));
+        hipLaunchKernelGGL(k_af_is_data, dim3(stream_grid(n_lines, PARSE_BLOCK)), dim3(PARSE_BLOCK), 0, 0, bytes,
+                           line_end.get<const int64_t>(), n_lines, is_data.get<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        GKI_TRY(gki_scan_u32_to_i64(is_data.get<const uint32_t>(), n_lines, variant_index.get<int64_t>(), tmp.get(), tmp_bytes, 0));
+        GKI_TRY(gki_scan_total(variant_index, n_lines, &found));
+    }
+    if (n_data_lines) *n_data_lines = found;
+    if (found != n_variants)
+        return gki_set_error(GKI_ERR_BAD_ARG, "vcf_allele_frequencies: the text has %lld data lines, the caller expects %lld",
+                             (long long)found, (long long)n_variants);
+    if (found == 0) return GKI_OK;
+    HIP_TRY(totals.alloc(sizeof(AfTotals)));
+    const AfTotals none = {~0ull};
+    HIP_TRY(hipMemcpy(totals.get(), &none, sizeof(AfTotals), hipMemcpyHostToDevice));
+    HIP_TRY(hipEventCreate(&ev.e0));
+    HIP_TRY(hipEventCreate(&ev.e1));
+    HIP_TRY(hipEventRecord(ev.e0, 0));
+    if (source == GKI_AF_SOURCE_INFO)
+        hipLaunchKernelGGL(k_af_info, dim3(stream_grid(n_lines, PARSE_BLOCK)), dim3(PARSE_BLOCK), 0, 0, bytes,
+                           line_end.get<const int64_t>(), n_lines, is_data.get<const uint32_t>(),
+                           variant_index.get<const int64_t>(), n_variants, (double *)d_ref_af, (double *)d_alt_af,
+                           (uint8_t *)d_route, (int64_t *)d_span_begin, (int32_t *)d_span_len, totals.get<AfTotals>());
+    else
+        hipLaunchKernelGGL(k_af_genotypes, dim3(stream_grid(n_lines, PARSE_BLOCK / 64)), dim3(PARSE_BLOCK), 0, 0, bytes, n_bytes,
+                           line_end.get<const int64_t>(), n_lines, is_data.get<const uint32_t>(),
+                           variant_index.get<const int64_t>(), n_variants, (double *)d_ref_af, (double *)d_alt_af,
+                           (uint8_t *)d_route, totals.get<AfTotals>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev.e1, 0));
+    HIP_TRY(hipStreamSynchronize(0));
+    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, ev.e0, ev.e1));
+    AfTotals t;
+    HIP_TRY(hipMemcpy(&t, totals.get(), sizeof(AfTotals), hipMemcpyDeviceToHost));
+    if (t.first_bad != ~0ull) {
+        if (first_bad_variant) *first_bad_variant = (int64_t)(t.first_bad >> 3);
+        if (first_bad_kind) *first_bad_kind = (int)(t.first_bad & 7);
+    }
+    return GKI_OK;
+}

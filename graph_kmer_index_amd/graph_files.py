@@ -5,7 +5,9 @@ does for `vcf_files` (`text_files.text_pieces`: plain, BGZF inflated on the devi
 existing parse gives the chromosome runs, the host maps the few run names to their chromosomes' bounds, and
 gki_graph_sites_count / _emit (csrc/gki_graph_build.hip) turn every data line into a site.  Over all lines
 gki_graph_build_count / _emit decide which sites are kept and write the arrays of graph.py, `ref_nodes` / `var_nodes`
-and the sequence.  The rules are stated in include/gki.h ("graph build") and DESIGN.md 4.15.
+and the sequence.  The rules are stated in include/gki.h ("graph build") and DESIGN.md 4.15.  With a source of allele
+frequencies ('info' or 'genotypes') `vcf_files.allele_frequencies_piece` runs on every piece while it is on the device, and
+its two arrays go to the emit call as device pointers.
 
 The layout is the bubble chain of `graph.synthetic_snp_graph` / `synthetic_indel_graph` with every id shifted by one; it
 is this package's own construction and not claimed equal to obgraph's node numbering, so a
@@ -20,7 +22,7 @@ import numpy as np
 from . import _lib
 from .graph import GraphArrays
 from .text_files import device_bytes, names_from, text_pieces
-from .vcf_files import vcf_count, vcf_emit
+from .vcf_files import AlleleFrequencyError, af_source_code, allele_frequencies_piece, vcf_count, vcf_emit
 
 STATUS_TEXT = {0: "kept", 1: "REF or ALT is not plain letters", 2: "no base before the site", 3: "overlaps an earlier site"}
 # kinds 1 to 4 are those of gki_graph_sites_count (include/gki.h)
@@ -41,10 +43,13 @@ class GraphBuildError(ValueError):
 
 class GraphBuild:
     """`.graph` GraphArrays, `.variant_to_nodes` VariantToNodesArrays, `.line_status` uint8 per data line (STATUS_TEXT);
+    `.route` uint8 per data line when the allele frequencies came from the VCF (vcf_files.ROUTE_*: 0 parsed on the device,
+    1 absent, 2 parsed by the host), else None;
     `.timings`: seconds per stage of the call that made it, `sequence_kernel_ms` the device time of the sequence kernel."""
 
-    def __init__(self, graph, variant_to_nodes, line_status, timings):
+    def __init__(self, graph, variant_to_nodes, line_status, timings, route=None):
         self.graph, self.variant_to_nodes, self.line_status, self.timings = graph, variant_to_nodes, line_status, timings
+        self.route = route
 
 
 def _letters(x):
@@ -66,10 +71,16 @@ class _Builder:
     """One build: the reference on the device, the pieces' sites appended, then the assembly.  Everything on the device
     belongs to `scope`.  `records` is one array of letters per name, uploaded here, or a reference that is on the device
     already (`.letters` one uint8 DeviceArray, `.bounds` int64[len(names) + 1], as `fasta_files.DeviceReference` has
-    them), which the scope takes over and uses in place."""
+    them), which the scope takes over and uses in place.  `af_source`: None, or where the pieces' allele frequencies come
+    from ('info' or 'genotypes')."""
 
-    def __init__(self, scope, names, records):
+    def __init__(self, scope, names, records, af_source=None):
         self.scope, self.names, self.timings = scope, list(names), {}
+        self.af_source = af_source
+        if af_source is not None:
+            af_source_code(af_source)
+            self.timings["allele_frequencies"] = self.timings["allele_frequencies_kernel_ms"] = 0.0
+        self.af_pieces, self.routes = [], []              # (ref_af, alt_af, n_variants) on the device; route on the host
         t0 = time.perf_counter()
         on_device = hasattr(records, "letters") and hasattr(records, "bounds")
         if on_device:
@@ -121,13 +132,34 @@ class _Builder:
     def add_piece(self, text, n_bytes):
         """The data lines of the device bytes text[:n_bytes] (whole lines) as sites, appended."""
         t0 = time.perf_counter()
-        lib = _lib.load()
         _, nv, n_runs, n_name_bytes, bad, kind = vcf_count(text, n_bytes)
-        if bad >= 0:                                      # kind 1: no tab at all; kind 2: POS is not plain digits
-            raise GraphBuildError(self.n_lines + bad, 1 if kind == 1 else "digits")
-        if nv == 0:
-            return
-        s = self.scope
+        t1 = time.perf_counter()
+        af_error = self._allele_frequencies(text, n_bytes, nv) if self.af_source is not None and nv else None
+        t0 += time.perf_counter() - t1                    # the site pass's clock leaves the allele frequencies out
+        try:
+            if bad >= 0:                                  # kind 1: no tab at all; kind 2: POS is not plain digits
+                raise GraphBuildError(self.n_lines + bad, 1 if kind == 1 else "digits")
+            if nv:
+                self._sites(text, n_bytes, nv, n_runs, n_name_bytes)
+        except GraphBuildError as e:                      # of two lines at fault the lowest is reported
+            raise (af_error if af_error is not None and af_error.line < e.line else e) from None
+        if af_error is not None:
+            raise af_error
+        self.n_lines += nv
+        self.timings["site_pass"] += time.perf_counter() - t0
+
+    def _allele_frequencies(self, text, n_bytes, nv):
+        """The piece's allele frequencies, appended; returns the error of its lowest line at fault, or None."""
+        t0 = time.perf_counter()
+        ref_af, alt_af, route, ms, fault = allele_frequencies_piece(self.scope, text, n_bytes, self.af_source, nv)
+        self.af_pieces.append((ref_af, alt_af, nv))
+        self.routes.append(route)
+        self.timings["allele_frequencies"] += time.perf_counter() - t0
+        self.timings["allele_frequencies_kernel_ms"] += ms
+        return None if fault is None else AlleleFrequencyError(self.n_lines + fault[0], fault[1])
+
+    def _sites(self, text, n_bytes, nv, n_runs, n_name_bytes):
+        s, lib = self.scope, _lib.load()
         with _lib.DeviceScope() as t:
             _, _, chrom_run, run_name_start, run_names = vcf_emit(t, text, n_bytes, nv, n_runs, n_name_bytes)
             names = names_from(run_name_start.to_host(), run_names.to_host().tobytes(), errors="replace")
@@ -143,34 +175,35 @@ class _Builder:
                    s.array(nv, np.uint8), _array(s, n_alt.value, np.uint8))
             _lib.check(lib.gki_graph_sites_emit(*args, *(a.ptr for a in out), n_alt.value))
         self.pieces.append(out + (nv, n_alt.value))
-        self.n_lines += nv
-        self.timings["site_pass"] += time.perf_counter() - t0
+
+    def _joined(self, parts, dtype):
+        """The pieces' arrays [(DeviceArray, entries)] as one on the device, the pieces freed; a single piece as it is."""
+        if len(parts) == 1:
+            return parts[0][0]
+        out, at = _array(self.scope, sum(n for _, n in parts), dtype), 0
+        size = out.dtype.itemsize
+        for a, n in parts:
+            if n:
+                _lib.check(_lib.load().gki_memcpy_d2d(C.c_void_p(out.ptr.value + at * size), a.ptr, n * size))
+            a.free()
+            at += n
+        return out
 
     def _appended(self):
         """The pieces' arrays as one set: (gpos, lo, ref_len, alt_len, status, pool)."""
-        s, lib = self.scope, _lib.load()
-        if len(self.pieces) == 1:
-            return self.pieces[0][:6]
-        n_alt = sum(p[7] for p in self.pieces)
         dtypes = (np.int64, np.int64, np.int32, np.int32, np.uint8, np.uint8)
-        out = tuple(_array(s, n_alt if j == 5 else self.n_lines, dt) for j, dt in enumerate(dtypes))
-        at, alt_at = 0, 0
-        for p in self.pieces:
-            for j in range(6):
-                n, off = (p[7], alt_at) if j == 5 else (p[6], at)
-                size = out[j].dtype.itemsize
-                if n:
-                    _lib.check(lib.gki_memcpy_d2d(C.c_void_p(out[j].ptr.value + off * size), p[j].ptr, n * size))
-                p[j].free()
-            at, alt_at = at + p[6], alt_at + p[7]
-        return out
+        return tuple(self._joined([(p[j], p[7] if j == 5 else p[6]) for p in self.pieces], dt)
+                     for j, dt in enumerate(dtypes))
 
     def finish(self, allele_frequencies=None):
         from .unique_variant_kmers import VariantToNodesArrays
         s, lib, n = self.scope, _lib.load(), self.n_lines
         t0 = time.perf_counter()
-        ref_af = alt_af = None
-        if allele_frequencies is not None:
+        ref_af = alt_af = route = None
+        if self.af_source is not None:                    # on the device already, one value per data line
+            ref_af, alt_af = (self._joined([(p[j], p[2]) for p in self.af_pieces], np.float64) for j in (0, 1))
+            route = np.concatenate(self.routes) if self.routes else np.zeros(0, np.uint8)
+        elif allele_frequencies is not None:
             ref_af, alt_af = (np.ascontiguousarray(a, dtype=np.float64) for a in allele_frequencies)
             if len(ref_af) != n or len(alt_af) != n:
                 raise ValueError("allele_frequencies: %d and %d values for %d data lines" % (len(ref_af), len(alt_af), n))
@@ -218,21 +251,33 @@ class _Builder:
                             first_node=1, chromosome_start_nodes=h["chromosome_start_nodes"].tolist(),
                             node_to_ref_offset=h["node_to_ref_offset"], rev_start=h["rev_start"], rev_edges=h["rev_edges"])
         self.timings["graph_arrays"] = time.perf_counter() - t0
-        return GraphBuild(graph, VariantToNodesArrays(h["ref_nodes"], h["var_nodes"]), line_status, self.timings)
+        return GraphBuild(graph, VariantToNodesArrays(h["ref_nodes"], h["var_nodes"]), line_status, self.timings, route)
+
+
+def _af_argument(allele_frequencies):
+    """(source, values) of the `allele_frequencies` argument: a source's name, or None / the two host arrays."""
+    if isinstance(allele_frequencies, str):
+        af_source_code(allele_frequencies)
+        return allele_frequencies, None
+    return None, allele_frequencies
 
 
 def build_graph(reference, text, chromosomes=None, allele_frequencies=None):
     """The build from in-memory inputs: `reference` a {name: letters} mapping (bytes or uint8), `text` the VCF as bytes
     (or NumPy uint8, or a uint8 DeviceArray).  `chromosomes`: the names in graph order, None = the mapping's order.
-    `allele_frequencies`: None (every node 1.0) or (ref_af, alt_af), float64 with one value per data line.
-    Returns a GraphBuild; GraphBuildError (a ValueError) names the data line a faulty VCF is refused at."""
+    `allele_frequencies`: None (every node 1.0), (ref_af, alt_af), float64 with one value per data line, or the source
+    they are read from on the device: 'info' (INFO's AF= entry) or 'genotypes' (the GT columns); a line without a value
+    keeps 1.0 on both nodes.
+    Returns a GraphBuild; GraphBuildError and vcf_files.AlleleFrequencyError (both ValueError) name the data line a faulty
+    VCF is refused at."""
     _lib.require_device()
     names = list(reference) if chromosomes is None else list(chromosomes)
+    source, values = _af_argument(allele_frequencies)
     with _lib.DeviceScope() as s:
-        builder = _Builder(s, names, [reference[n] for n in names])
+        builder = _Builder(s, names, [reference[n] for n in names], source)
         d = device_bytes(s, text)
         builder.add_piece(d, d.n)
-        return builder.finish(allele_frequencies)
+        return builder.finish(values)
 
 
 def build_graph_from_files(fasta, vcf, chromosomes=None, allele_frequencies=None, chunk_bytes=None, inflate="auto",
@@ -240,13 +285,15 @@ def build_graph_from_files(fasta, vcf, chromosomes=None, allele_frequencies=None
     """The graph of the FASTA records `chromosomes` (None: every record, in file order) with the variants of `vcf`: a
     .vcf, a BGZF .vcf.gz inflated on the device, any other .gz through Python's gzip (`inflate` and `chunk_bytes` as in
     `text_files.text_pieces`).  The VCF is streamed in pieces of about `chunk_bytes`; line numbers and the order check
-    carry across pieces.
+    carry across pieces.  `allele_frequencies` as in `build_graph`; a source is read from every piece while it is on the
+    device.
     fasta_parse: 'device' the FASTA (plain, BGZF or gzip) is parsed on the device (`fasta_files.reference_from_file`) and
     its letters stay there; 'host' `read_fasta_records` and one upload per chromosome; 'auto' the faster of the two."""
     from .fasta_files import reference_from_file, resolve_fasta_parse
     from .snp_kmer_finder import read_fasta_records
     _lib.require_device()
     device = resolve_fasta_parse(fasta_parse) == "device"
+    af_source, af_values = _af_argument(allele_frequencies)
     source = text_pieces(vcf, chunk_bytes, inflate)
     with _lib.DeviceScope() as s, contextlib.closing(source) as pieces:
         t0 = time.perf_counter()
@@ -258,7 +305,7 @@ def build_graph_from_files(fasta, vcf, chromosomes=None, allele_frequencies=None
             names, records = read_fasta_records(fasta, chromosomes)  # one read of the file for every record
             parse_ms = 0.0
         read_seconds = time.perf_counter() - t0
-        builder = _Builder(s, names, records)
+        builder = _Builder(s, names, records, af_source)
         del records
         builder.timings["read_reference"] = read_seconds
         builder.timings["parse_reference_kernel_ms"] = parse_ms
@@ -268,5 +315,6 @@ def build_graph_from_files(fasta, vcf, chromosomes=None, allele_frequencies=None
                 t.keep(text)
                 builder.add_piece(text, n_bytes)
         # reading, uploading and inflating the VCF happen inside the loop, between the site passes
-        builder.timings["vcf_text"] = time.perf_counter() - t0 - builder.timings["site_pass"]
-        return builder.finish(allele_frequencies)
+        builder.timings["vcf_text"] = (time.perf_counter() - t0 - builder.timings["site_pass"]
+                                       - builder.timings.get("allele_frequencies", 0.0))
+        return builder.finish(af_values)

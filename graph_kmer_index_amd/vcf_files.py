@@ -8,6 +8,11 @@ plain digits.
 
 `variant_arrays_from_file` is one loop over the pieces; `VariantPieces` joins them on the host: data-line numbers go on
 across pieces, and a piece's first run continues the last run of the piece before when the names are equal.
+
+`allele_frequencies_from_file` / `allele_frequencies_on_device` give (ref_af, alt_af, route) per data line from INFO's AF=
+entry or from the GT columns (gki_vcf_allele_frequencies, csrc/gki_vcf_af.hip; include/gki.h "VCF allele frequencies",
+DESIGN.md 4.17).  `allele_frequencies_piece` is the step both and `graph_files` share: the kernel, then the host's
+float() on the few value texts the device's grammar leaves out.
 """
 import contextlib
 import ctypes as C
@@ -19,6 +24,23 @@ from .text_files import DEFAULT_CHUNK_BYTES, device_bytes, names_from, text_piec
 
 BAD_TEXT = {1: "VCF data line %d has fewer than two columns",          # VariantArrays.from_vcf's own message
             2: "VCF data line %d: POS must be 1 to 18 plain digits (no sign, blank or underscore) for the device parser"}
+
+
+AF_SOURCES = {"info": 0, "genotypes": 1}                  # GKI_AF_SOURCE_* of include/gki.h
+ROUTE_DEVICE, ROUTE_ABSENT, ROUTE_HOST = 0, 1, 2
+AF_KINDS = {1: "value", 2: "format", 3: "genotype"}       # first_bad_kind of gki_vcf_allele_frequencies
+AF_KIND_TEXT = {"value": "INFO's AF is not a finite number in [0, 1]", "text": "INFO's AF is not a number",
+                "format": "FORMAT does not begin with GT",
+                "genotype": "a GT is not alleles ('.' or 1 to 9 digits) separated by '/' or '|'"}
+
+
+class AlleleFrequencyError(ValueError):
+    """A VCF whose allele frequencies cannot be read; `line` is the data line at fault, numbered from 0 in the file, `kind`
+    a key of AF_KIND_TEXT."""
+
+    def __init__(self, line, kind):
+        super().__init__("VCF data line %d: %s" % (line, AF_KIND_TEXT[kind]))
+        self.line, self.kind = int(line), kind
 
 
 def bad_line_error(data_line, kind):
@@ -118,3 +140,100 @@ def variant_arrays_from_file(file_name, chunk_bytes=DEFAULT_CHUNK_BYTES, inflate
                 raise bad_line_error(joined.n_variants + bad[0], bad[1])
             joined.add(*out)
     return joined.variant_arrays()
+
+
+def af_source_code(source):
+    if source not in AF_SOURCES:
+        raise ValueError("the allele frequencies' source must be one of %s, not %r" % (", ".join(AF_SOURCES), source))
+    return AF_SOURCES[source]
+
+
+def allele_frequencies_piece(scope, text, n_bytes, source, n_variants):
+    """One piece, the device bytes text[:n_bytes] with `n_variants` data lines (`vcf_count`'s): (ref_af, alt_af) float64
+    DeviceArrays of `scope`, route as a host uint8 array, the device time of the kernel in ms, and the lowest line at
+    fault as (data line of the piece, kind) or None.  The value texts of route 2 alone come back to the host; float()
+    turns them into values that are written into the two device arrays."""
+    lib, nv = _lib.load(), int(n_variants)
+    ref_af, alt_af = scope.array(max(nv, 1), np.float64), scope.array(max(nv, 1), np.float64)
+    with _lib.DeviceScope() as t:
+        route, begin, length = t.array(max(nv, 1), np.uint8), t.array(max(nv, 1), np.int64), t.array(max(nv, 1), np.int32)
+        found, bad, kind, ms = C.c_int64(0), C.c_int64(-1), C.c_int(0), C.c_float(0)
+        _lib.check(lib.gki_vcf_allele_frequencies(text.ptr, n_bytes, af_source_code(source), nv, ref_af.ptr, alt_af.ptr,
+                                                  route.ptr, begin.ptr, length.ptr, C.byref(found), C.byref(bad),
+                                                  C.byref(kind), C.byref(ms)))
+        fault = (bad.value, AF_KINDS[kind.value]) if bad.value >= 0 else None
+        h_route = route.to_host(nv)
+        host_lines = np.flatnonzero(h_route == ROUTE_HOST)
+        if len(host_lines):
+            h_begin, h_length = begin.to_host(nv), length.to_host(nv)
+        for v in host_lines.tolist():                     # ascending: the first text at fault is the lowest
+            if fault is not None and fault[0] < v:
+                break
+            raw = np.empty(int(h_length[v]), dtype=np.uint8)
+            _lib.check(lib.gki_memcpy_d2h(_lib.hptr(raw), C.c_void_p(text.ptr.value + int(h_begin[v])), raw.nbytes))
+            try:
+                value = float(raw.tobytes())
+            except ValueError:
+                fault = (v, "text")
+                break
+            if not (np.isfinite(value) and 0.0 <= value <= 1.0):
+                fault = (v, "value")
+                break
+            pair = np.array([1.0 - value, value], dtype=np.float64)
+            for a, x in zip((ref_af, alt_af), (pair[0:1], pair[1:2])):
+                _lib.check(lib.gki_memcpy_h2d(C.c_void_p(a.ptr.value + 8 * v), _lib.hptr(x), 8))
+    return ref_af, alt_af, h_route, float(ms.value), fault
+
+
+class _AfPieces:
+    """The pieces' results joined on the host."""
+
+    def __init__(self):
+        self.ref_af, self.alt_af, self.route, self.n_variants = [], [], [], 0
+
+    def add_piece(self, text, n_bytes, source):
+        nv = vcf_count(text, n_bytes)[1]
+        if nv == 0:
+            return
+        with _lib.DeviceScope() as s:
+            ref_af, alt_af, route, _, fault = allele_frequencies_piece(s, text, n_bytes, source, nv)
+            if fault is not None:
+                raise AlleleFrequencyError(self.n_variants + fault[0], fault[1])
+            self.ref_af.append(ref_af.to_host(nv))
+            self.alt_af.append(alt_af.to_host(nv))
+        self.route.append(route)
+        self.n_variants += nv
+
+    def arrays(self):
+        def cat(parts, dtype):
+            return np.concatenate(parts) if parts else np.zeros(0, dtype)
+        return cat(self.ref_af, np.float64), cat(self.alt_af, np.float64), cat(self.route, np.uint8)
+
+
+def allele_frequencies_on_device(buf, source):
+    """VCF bytes (bytes, NumPy uint8 or a DeviceArray; whole lines, the last one terminated or not) -> (ref_af float64,
+    alt_af float64, route uint8), one entry per data line, host arrays.  source: 'info' (INFO's AF= entry) or 'genotypes'
+    (the GT columns).  route: 0 parsed on the device, 1 absent (both values 1.0), 2 the value text went through float()
+    on the host.  AlleleFrequencyError (a ValueError) names the lowest data line at fault."""
+    _lib.require_device()
+    af_source_code(source)
+    joined = _AfPieces()
+    with _lib.DeviceScope() as s:
+        d = device_bytes(s, buf)
+        joined.add_piece(d, d.n, source)
+    return joined.arrays()
+
+
+def allele_frequencies_from_file(file_name, source, chunk_bytes=DEFAULT_CHUNK_BYTES, inflate="auto"):
+    """`allele_frequencies_on_device` for every data line of a .vcf, a BGZF .vcf.gz (inflated on the device) or another
+    gzip file, streamed in pieces of about `chunk_bytes` (`chunk_bytes` and `inflate` as in `text_files.text_pieces`);
+    line numbers go on across pieces.  No reference and no graph is needed."""
+    _lib.require_device()
+    af_source_code(source)
+    joined = _AfPieces()
+    with contextlib.closing(text_pieces(file_name, chunk_bytes, inflate)) as pieces:
+        for text, n_bytes in pieces:
+            with _lib.DeviceScope() as s:
+                s.keep(text)
+                joined.add_piece(text, n_bytes, source)
+    return joined.arrays()

@@ -755,6 +755,44 @@ int gki_graph_build_emit(gki_graph_build *plan, const void *d_reference, const v
                          void *d_var_nodes, float *sequence_ms);
 int gki_graph_build_destroy(gki_graph_build *plan);
 
+/* ---------------------------------------------------------------- VCF allele frequencies (VCF text -> ref_af, alt_af per data line)
+ * The allele frequencies gki_graph_build_emit puts on a kept line's two allele nodes, read from the VCF text itself
+ * (DESIGN.md 4.17).  Lines, '\r' at line ends, data lines and their numbers are those of "VCF files"; field f is closed by
+ * tab f + 1 or by the line's end.  Per data line the result is ref_af, alt_af (float64) and a route (uint8): 0 parsed on
+ * the device, 1 absent (ref_af = alt_af = 1.0, what every node has without a source), 2 the value text is outside the
+ * device's grammar and the host parses it (ref_af = alt_af = 1.0 until then).
+ *   source GKI_AF_SOURCE_INFO        INFO is field 7; a line with fewer than 8 fields is absent.  INFO's entries are separated
+ *              by ';'.  The first entry whose bytes begin with "AF=" gives the value text: the bytes behind '=' up to the next
+ *              ';', the next ',' or the field's end ("XAF=", "MAF=" and "AF_EUR=" do not match; of "AF=0.1,0.2" the first
+ *              value counts).  No such entry, an empty value text and "." are absent.
+ *              Device grammar: D* [ . D* ] [ (e|E) [+|-] D+ ] with at least one mantissa digit.  m = the mantissa's digits
+ *              without the dot as an integer, q = the exponent minus the number of fraction digits.  The device parses the
+ *              text when the mantissa has at most 15 digits in all, the exponent at most 3 and |q| <= 22; the value is then
+ *              m / 10^-q or m * 10^q, one IEEE double operation on exact operands (a table of the 23 powers, no pow, no
+ *              fast-math), hence correctly rounded and bit-equal to strtod.  Everything else -- more digits, a larger
+ *              exponent, nan, inf, a sign, stray bytes -- is route 2: d_span_begin[v] / d_span_len[v] give the value text's
+ *              place in d_text and the host applies its own conversion to those bytes alone.
+ *              alt_af = value, ref_af = 1.0 - value.  A device value above 1 is at fault, kind 1 (the grammar has no sign
+ *              and |q| <= 22 keeps it finite).
+ *   source GKI_AF_SOURCE_GENOTYPES   FORMAT is field 8, the samples are fields 9 and up; a line with fewer than 10 fields is
+ *              absent.  FORMAT must begin with "GT" followed by ':' or its end, else the line is at fault, kind 2.  A
+ *              sample's GT is its bytes up to the first ':' or the field's end: one or more alleles separated by '/' or '|',
+ *              an allele '.' (missing, not counted) or 1 to 9 digits taken as a decimal number ("10" is allele ten, "01"
+ *              allele one).  An empty GT, an empty allele and any other byte are at fault, kind 3.  n_called = the numeric
+ *              alleles of all samples, n_ref those equal to 0, n_alt those equal to 1; n_called == 0 is absent, otherwise
+ *              ref_af = n_ref / n_called and alt_af = n_alt / n_called, double divisions of exact integers.  Ploidy is free.
+ * gki_vcf_allele_frequencies works on one piece of text, d_text[n_bytes] of whole lines (any alignment; no byte behind
+ * n_bytes is read) with n_variants data lines: *n_data_lines is what the pass itself counted, and GKI_ERR_BAD_ARG when the
+ * two differ.  d_ref_af / d_alt_af float64, d_route uint8, d_span_begin int64, d_span_len int32, each [n_variants]; the two
+ * span arrays are written by source INFO only (0 where the route is not 2) and may be NULL for genotypes.
+ * *first_bad_variant / *first_bad_kind: the lowest data line at fault and why (-1 and 0: none); a line at fault is reported,
+ * not refused, and holds the absent values.  *kernel_ms (may be NULL): the device time of the source's kernel. */
+#define GKI_AF_SOURCE_INFO 0
+#define GKI_AF_SOURCE_GENOTYPES 1
+int gki_vcf_allele_frequencies(const void *d_text, int64_t n_bytes, int source, int64_t n_variants, void *d_ref_af,
+                               void *d_alt_af, void *d_route, void *d_span_begin, void *d_span_len, int64_t *n_data_lines,
+                               int64_t *first_bad_variant, int *first_bad_kind, float *kernel_ms);
+
 /* ---------------------------------------------------------------- BGZF (blocked gzip: the .gz reads files of bgzip / htslib)
  * A BGZF file is a chain of gzip members of at most 64 KiB, each with its compressed size in a 'BC' extra subfield, so
  * every member's raw DEFLATE payload, CRC-32 and ISIZE are found without inflating anything (graph_kmer_index_amd/bgzf.py
