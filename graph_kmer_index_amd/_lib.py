@@ -161,6 +161,9 @@ SYMBOLS = {
     "gki_graph_build_destroy": (_I32, [_P]),
     "gki_vcf_allele_frequencies": (_I32, [_P, _I64, _I32, _I64, _P, _P, _P, _P, _P, C.POINTER(_I64), C.POINTER(_I64),
                                           C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    "gki_vcf_haplotype_matrix": (_I32, [_P, _I64, _I64, _I64, _I32, _P, _P, C.POINTER(_I64), C.POINTER(_I64),
+                                        C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    "gki_haplotype_planes": (_I32, [_P, _I64, _I64, _P, _P, C.POINTER(C.c_float)]),
     "gki_bgzf_inflate": (_I32, [_P, _I64, _P, _P, _P, _P, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(C.c_int)]),
     "gki_bgzf_inflate_kernel_ms": (_I32, [C.POINTER(C.c_float)]),
     "gki_last_byte_position": (_I32, [_P, _I64, _I32, C.POINTER(_I64)]),

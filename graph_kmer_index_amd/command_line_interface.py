@@ -17,6 +17,7 @@ collision_free_kmer_index.py:393-402).
     python -m graph_kmer_index_amd.command_line_interface make -t 16 -s 1 -k 31 -r True -R ref.fa -n chr1 -G <size> -o linear_kmers
     python -m graph_kmer_index_amd.command_line_interface map -i index.npz -f reads.fq.gz -k 31 -o node_counts
     python -m graph_kmer_index_amd.command_line_interface make_graph -r ref.fa -v variants.vcf.gz -o graph -n chr1,chr2 -a genotypes
+    python -m graph_kmer_index_amd.command_line_interface make_haplotype_matrix -v variants.vcf.gz -o haplotypes --planes True
 
 `-g` takes an obgraph file when obgraph is installed, else a GraphArrays .npz (GraphArrays.to_file).  `index -t N` runs
 one process per GPU (at most N, at most the visible devices), each on its own range of critical-path numbers, and
@@ -356,6 +357,20 @@ def make_graph(args):
                     len(built.line_status), v2n))
 
 
+def make_haplotype_matrix(args):
+    """VCF -> the haplotype matrix of its GT columns (HaplotypeMatrix.to_file), parsed on the device (vcf_files.py)."""
+    from .vcf_files import DEFAULT_CHUNK_BYTES, haplotype_matrix_from_file
+    matrix = haplotype_matrix_from_file(args.vcf, ploidy=args.ploidy, n_samples=args.n_samples,
+                                        chunk_bytes=DEFAULT_CHUNK_BYTES if args.chunk_bytes is None else args.chunk_bytes,
+                                        inflate=args.inflate)
+    matrix.to_file(args.out_file_name, planes=args.planes)
+    counts = np.bincount(matrix.codes.reshape(-1), minlength=4)
+    logging.info("%d data lines x %d samples of ploidy %d: %d lines hold an unphased GT"
+                 % (matrix.n_variants, matrix.n_samples, matrix.ploidy, int(np.count_nonzero(matrix.phased == 0))))
+    logging.info("slots: %d allele 0, %d allele 1, %d another allele, %d no allele" % tuple(int(c) for c in counts[:4]))
+    logging.info("Wrote the haplotype matrix%s to %s" % (" and its bit planes" if args.planes else "", args.out_file_name))
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description="graph_kmer_index on MI355X (in-scope sub-commands)")
     sub = parser.add_subparsers()
@@ -496,6 +511,18 @@ def build_parser():
                    help="where the reference FASTA (.fa, or .fa.gz as BGZF or gzip) is parsed: auto = device; host = on "
                         "the host with NumPy")
     p.set_defaults(func=make_graph)
+    p = sub.add_parser("make_haplotype_matrix")
+    p.add_argument("-v", "--vcf", required=True, help="VCF with GT columns, optionally .gz (BGZF or gzip)")
+    p.add_argument("-o", "--out-file-name", required=True, help="the matrix, as HaplotypeMatrix.to_file writes it (.npz)")
+    p.add_argument("-p", "--ploidy", required=False, type=int, default=2, help="slots per sample, 1 to 8")
+    p.add_argument("-s", "--n-samples", required=False, type=int, default=None,
+                   help="default: the sample columns of the #CHROM header line, else of the first data line")
+    p.add_argument("--planes", required=False, type=_bool, default=False,
+                   help="also write ref_bits and alt_bits, one bit per slot and line")
+    p.add_argument("--inflate", required=False, choices=("auto", "host", "device"), default="auto",
+                   help="where a .gz VCF is inflated: auto = BGZF on the device, other gzip on the host")
+    p.add_argument("--chunk-bytes", required=False, type=int, default=None)
+    p.set_defaults(func=make_haplotype_matrix)
     p = sub.add_parser("map")
     p.add_argument("-i", "--kmer-index", required=True)
     p.add_argument("-f", "--reads", required=True, help="FASTA or FASTQ, optionally .gz (gzip or BGZF)")

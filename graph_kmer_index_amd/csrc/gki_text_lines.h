@@ -1,6 +1,6 @@
-// Lines of ASCII text in HBM: what the five parsers of text files share -- reads (gki_reads_parse.hip), VCF
-// (gki_vcf_parse.hip), the graph build's site pass (gki_graph_build.hip), the VCF's allele frequencies (gki_vcf_af.hip) and
-// the reference FASTA (gki_fasta_parse.hip).
+// Lines of ASCII text in HBM: what the six parsers of text files share -- reads (gki_reads_parse.hip), VCF
+// (gki_vcf_parse.hip), the graph build's site pass (gki_graph_build.hip), the VCF's allele frequencies (gki_vcf_af.hip), its
+// haplotype matrix (gki_vcf_gt.hip) and the reference FASTA (gki_fasta_parse.hip).
 // The tile geometry, the SWAR byte test, the block prefix and the wave copy serve the dense kernels; the line-end pass
 // (kernels in gki_text_lines.hip) serves all but the FASTA parser; the VCF line rules serve the VCF parser, the site pass
 // and the allele-frequency pass, which must number the data lines alike (gki_graph_sites_* and

@@ -9,18 +9,18 @@
 //   k_af_info        source info: one lane per data line walks to the seventh tab and through INFO, which lies before the
 //                    sample columns, finds the AF= entry and turns its value text into a double by one exact operation
 //   k_af_genotypes   source genotypes: one wave per data line, dense in the bytes.  Each step the 64 lanes take 16
-//                    consecutive bytes each (AF_STEP = 1024 bytes a step), find the tabs with equal_mask16 and number them
+//                    consecutive bytes each (GT_STEP = 1024 bytes a step), find the tabs with equal_mask16 and number them
 //                    with a wave prefix sum on top of the line's running count, which the wave carries in a scalar.  A
 //                    lane whose bytes hold tab number 9 or higher parses the GT behind it straight from memory, eight bytes
 //                    in one load (a GT is a few bytes; they may lie in the next lane's or the next step's bytes).  Tab number 8 opens FORMAT,
 //                    which its lane checks.  One wave reduction per line gives the three counts; lane 0 divides and stores.
 //                    A wave owns its line: no atomics but the atomicMin of the lowest line at fault.
-#include "gki_text_lines.h"
+// The walk's loads and the GT grammar are gki_vcf_gt.h's, shared with the haplotype matrix (gki_vcf_gt.hip).
+#include "gki_vcf_gt.h"
 
 namespace {
 
-constexpr int AF_STEP = 64 * PARSE_LANE_BYTES;            // bytes a wave takes per step
-constexpr int AF_MAX_MANTISSA_DIGITS = 15, AF_MAX_EXPONENT_DIGITS = 3, AF_MAX_POWER = 22, AF_MAX_ALLELE_DIGITS = 9;
+constexpr int AF_MAX_MANTISSA_DIGITS = 15, AF_MAX_EXPONENT_DIGITS = 3, AF_MAX_POWER = 22;
 constexpr uint8_t ROUTE_DEVICE = 0, ROUTE_ABSENT = 1, ROUTE_HOST = 2;
 
 // first_bad: (data line << 3 | kind) of the lowest line at fault, all ones when there is none (atomicMin)
@@ -29,8 +29,6 @@ struct AfTotals { unsigned long long first_bad; };
 // the powers of ten a double holds exactly
 __device__ const double AF_POW10[AF_MAX_POWER + 1] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
                                                       1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
-
-__device__ __forceinline__ bool is_digit(uint8_t c) { return c >= (uint8_t)'0' && c <= (uint8_t)'9'; }
 
 __global__ __launch_bounds__(PARSE_BLOCK) void k_af_is_data(const uint8_t *__restrict__ bytes,
                                                             const int64_t *__restrict__ line_end, int64_t n_lines,
@@ -118,62 +116,13 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_af_info(const uint8_t *__restri
     }
 }
 
-struct alignas(4) Bytes16 { uint32_t w[4]; };
-
-__device__ __forceinline__ int64_t wave_uniform(int64_t x) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)x >> 32));
-    return (int64_t)((uint64_t)hi << 32 | lo);
-}
-__device__ __forceinline__ int wave_sum(int x) { return gki_lane_value(gki_wave_incl_sum(x), 63); }
-
-// A GT of `len` bytes at most, byte i of it at(i): alleles separated by '/' or '|', each '.' or 1 to 9 digits, closed by
-// ':', a tab, or the end of the bytes when they reach the line's end (`whole`).  1: closed, the three counts in *c; 0: an
-// empty GT, an empty allele or any other byte; 2: the bytes ended first (never when `whole`).
-struct GtCounts { int called, n_ref, n_alt; };
-template <class At> __device__ __forceinline__ int gt_parse(At at, int64_t len, bool whole, GtCounts *c) {
-    *c = {0, 0, 0};
-    for (int64_t i = 0;;) {
-        if (i < len && at(i) == (uint8_t)'.') i++;
-        else {
-            int value = 0, digits = 0;
-            for (; i < len && is_digit(at(i)) && digits <= AF_MAX_ALLELE_DIGITS; i++, digits++)
-                value = value * 10 + (at(i) - (uint8_t)'0');
-            if (i >= len && !whole) return 2;
-            if (digits < 1 || digits > AF_MAX_ALLELE_DIGITS) return 0;
-            c->called += 1;
-            c->n_ref += value == 0;
-            c->n_alt += value == 1;
-        }
-        if (i >= len) return whole ? 1 : 2;
-        const uint8_t sep = at(i);
-        if (sep == (uint8_t)':' || sep == (uint8_t)'\t') return 1;
-        if (sep != (uint8_t)'/' && sep != (uint8_t)'|') return 0;
-        i++;
-    }
-}
-
-// The GT at bytes[p ..] of the line that ends at e, added to the three counts; false when it is at fault.  Eight bytes in
-// one load hold a GT and what closes it in all but rare lines ("0|1" and a tab are four), so the parse reads registers:
-// one load per GT instead of one per byte, which is what the kernel's rate hangs on.  A GT that is
-// longer, and one within eight bytes of the piece's end, goes byte by byte from memory.
-struct alignas(4) Bytes8 { uint32_t w[2]; };
-__device__ __forceinline__ bool gt_counts(const uint8_t *__restrict__ bytes, int64_t n_bytes, int64_t p, int64_t e,
-                                          int *called, int *n_ref, int *n_alt) {
-    GtCounts c;
-    int state = 2;
-    if (p + 8 <= n_bytes) {
-        Bytes8 raw;
-        __builtin_memcpy(&raw, bytes + p, 8);
-        const uint64_t window = (uint64_t)raw.w[1] << 32 | raw.w[0];
-        state = gt_parse([window](int64_t i) { return (uint8_t)(window >> (8 * (int)i)); }, e - p < 8 ? e - p : 8, e - p <= 8, &c);
-    }
-    if (state == 2) state = gt_parse([bytes, p](int64_t i) { return bytes[p + i]; }, e - p, true, &c);
-    *called += c.called;
-    *n_ref += c.n_ref;
-    *n_alt += c.n_alt;
-    return state == 1;
-}
+// what k_af_genotypes takes from a GT: the numeric alleles, those equal to 0 and those equal to 1
+struct GtCounts {
+    int called = 0, n_ref = 0, n_alt = 0;
+    __device__ __forceinline__ void number(int value) { called += 1; n_ref += value == 0; n_alt += value == 1; }
+    __device__ __forceinline__ void missing() {}
+    __device__ __forceinline__ void slash() {}
+};
 
 // One wave per data line.  FORMAT is field 8 (opened by tab number 8), the samples are fields 9 and up.
 __global__ __launch_bounds__(PARSE_BLOCK) void k_af_genotypes(const uint8_t *__restrict__ bytes, int64_t n_bytes,
@@ -192,25 +141,10 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_af_genotypes(const uint8_t *__r
         const VcfLine l = vcf_line(bytes, line_end, i);
         const int64_t b = wave_uniform(l.b), e = wave_uniform(l.e);
         int tabs_before = 0, called = 0, n_ref = 0, n_alt = 0, bad_format = 0, bad_gt = 0;
-        for (int64_t base = b; base < e; base += AF_STEP) {
+        for (int64_t base = b; base < e; base += GT_STEP) {
             const int64_t p0 = base + (int64_t)lane * PARSE_LANE_BYTES;
-            uint4 in = {0u, 0u, 0u, 0u};
-            if (p0 + PARSE_LANE_BYTES <= n_bytes) {        // 16 bytes at any alignment; bytes behind e are masked below
-                if (p0 < e) {
-                    Bytes16 raw;
-                    __builtin_memcpy(&raw, bytes + p0, PARSE_LANE_BYTES);
-                    in = {raw.w[0], raw.w[1], raw.w[2], raw.w[3]};
-                }
-            } else {                                       // the piece's last bytes: one by one, none behind n_bytes
-                uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-                for (int j = 0; j < PARSE_LANE_BYTES; j++)
-                    if (p0 + j < e) w[j >> 2] |= (uint32_t)bytes[p0 + j] << (8 * (j & 3));
-                in = {w[0], w[1], w[2], w[3]};
-            }
-            const int64_t left = e - p0;                   // bytes of the line from p0 on
-            const uint32_t inside = left >= PARSE_LANE_BYTES ? 0xFFFFu : left > 0 ? (1u << (int)left) - 1u : 0u;
-            uint32_t tabs = equal_mask16<'\t'>(in) & inside;
+            const uint4 in = line_bytes16(bytes, n_bytes, p0, e);
+            uint32_t tabs = line_tabs16(in, p0, e);
             const int mine = __popc(tabs);
             const int incl = gki_wave_incl_sum(mine);
             int number = tabs_before + incl - mine;        // tabs of the line before this lane's first
@@ -221,10 +155,14 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_af_genotypes(const uint8_t *__r
                 number++;
                 const int64_t p = p0 + j + 1;              // the field tab `number` opens
                 if (number == 8)
-                    bad_format |= !(p + 2 <= e && bytes[p] == (uint8_t)'G' && bytes[p + 1] == (uint8_t)'T' &&
-                                    (p + 2 == e || bytes[p + 2] == (uint8_t)':' || bytes[p + 2] == (uint8_t)'\t'));
-                else if (number >= 9)
-                    bad_gt |= !gt_counts(bytes, n_bytes, p, e, &called, &n_ref, &n_alt);
+                    bad_format |= !format_begins_with_gt(bytes, p, e);
+                else if (number >= 9) {
+                    GtCounts c;
+                    bad_gt |= !gt_at(bytes, n_bytes, p, e, &c);
+                    called += c.called;
+                    n_ref += c.n_ref;
+                    n_alt += c.n_alt;
+                }
             }
         }
         called = wave_sum(called);

@@ -793,6 +793,41 @@ int gki_vcf_allele_frequencies(const void *d_text, int64_t n_bytes, int source, 
                                void *d_alt_af, void *d_route, void *d_span_begin, void *d_span_len, int64_t *n_data_lines,
                                int64_t *first_bad_variant, int *first_bad_kind, float *kernel_ms);
 
+/* ---------------------------------------------------------------- VCF haplotype matrix (VCF text -> one code per sample haplotype and data line)
+ * Which allele every sample haplotype carries at every data line, read from the GT columns.  Lines, '\r'
+ * at line ends, data lines and their numbers are those of "VCF files"; fields, FORMAT and the GT grammar are those of
+ * "VCF allele frequencies", source genotypes, unchanged: FORMAT is field 8 and must begin with "GT" followed by ':' or its
+ * end; sample s is field 9 + s and its GT its bytes up to the first ':'; alleles are separated by '/' or '|'; an allele is
+ * '.' or 1 to 9 digits.
+ *   parameters   ploidy P, 1 <= P <= 8; n_samples S >= 0; H = S * P slots per line.
+ *   slot codes   (uint8) 0: allele number 0; 1: allele number 1; 2: any other number; 3: no allele -- the allele '.', and a
+ *                slot the GT does not fill (a GT of fewer than P alleles).  A GT's alleles fill its sample's slots in text
+ *                order, whatever the separators.
+ *   output       per data line v: codes[v][s * P + j], row-major, H bytes a row; phased[v] (uint8) 1 when no GT of the line
+ *                holds a '/', else 0.
+ *   faults       a line of 10 fields or more is at fault when FORMAT does not begin with GT (kind 2), when one of its sample
+ *                fields holds a GT outside the grammar (kind 3), when it does not have exactly S sample fields (kind 4) or
+ *                when a GT has more than P alleles (kind 5); of several the lowest kind is reported.  A line of fewer than
+ *                10 fields has no sample field and its FORMAT is not looked at: kind 4 when S > 0, and with S = 0 it is fine
+ *                and its row is empty.  A line at fault is reported, not refused: its row is all 3 and its phased is 0.
+ * gki_vcf_haplotype_matrix works on one piece of text, d_text[n_bytes] of whole lines (any alignment; no byte behind n_bytes
+ * is read) with n_variants data lines: *n_data_lines is what the pass itself counted, and GKI_ERR_BAD_ARG when the two
+ * differ.  d_codes uint8[n_variants * H] (offsets are formed in 64 bits; may be NULL when H is 0), d_phased
+ * uint8[n_variants]; the kernel writes every byte of both, whatever they held.  *first_bad_variant / *first_bad_kind: the
+ * lowest data line at fault and why (-1 and 0: none).  *kernel_ms (may be NULL): the device time of the matrix kernel.
+ * GKI_ERR_BAD_ARG for a negative size, a ploidy outside 1..8 and a NULL buffer where its size is positive; zero sizes do
+ * nothing and succeed.
+ * gki_haplotype_planes turns d_codes uint8[n_variants][n_slots] into two bit planes, the form whole-genome data is kept
+ * in: d_ref_bits and d_alt_bits uint64[n_slots][W], W = ceil(n_variants / 64).  Bit v mod 64 (least significant first) of
+ * word [h][v / 64] is set in ref_bits when codes[v][h] == 0 and in alt_bits when it is 1; any other byte value sets neither;
+ * bits at and beyond n_variants in the last word are 0.  The kernel writes every word of both planes.  It runs once, over
+ * the rows of all pieces: a piece's first line is no multiple of 64.  *kernel_ms (may be NULL): its device time. */
+int gki_vcf_haplotype_matrix(const void *d_text, int64_t n_bytes, int64_t n_variants, int64_t n_samples, int ploidy,
+                             void *d_codes, void *d_phased, int64_t *n_data_lines, int64_t *first_bad_variant,
+                             int *first_bad_kind, float *kernel_ms);
+int gki_haplotype_planes(const void *d_codes, int64_t n_variants, int64_t n_slots, void *d_ref_bits, void *d_alt_bits,
+                         float *kernel_ms);
+
 /* ---------------------------------------------------------------- BGZF (blocked gzip: the .gz reads files of bgzip / htslib)
  * A BGZF file is a chain of gzip members of at most 64 KiB, each with its compressed size in a 'BC' extra subfield, so
  * every member's raw DEFLATE payload, CRC-32 and ISIZE are found without inflating anything (graph_kmer_index_amd/bgzf.py
