@@ -52,13 +52,13 @@ class DevBuf {
     void *p_ = nullptr;
 };
 
-// The two events of a timed launch (host only), destroyed when it goes out of scope
+// The two events of a timed launch (host only), destroyed when it goes out of scope; start and stop are defined below
 struct TimerEvents {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     TimerEvents() = default;
-    TimerEvents(const TimerEvents &) = delete;
-    TimerEvents &operator=(const TimerEvents &) = delete;
+    TimerEvents(const TimerEvents &) = delete; TimerEvents &operator=(const TimerEvents &) = delete;
     ~TimerEvents() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    int start(hipStream_t s), stop(hipStream_t s, float *ms);
 };
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -69,6 +69,22 @@ static inline int stream_grid(int64_t work_items, int block) {
     if (g > 256 * 8) g = 256 * 8;
     if (g < 1) g = 1;
     return (int)g;
+}
+
+// A timed launch is start(s), the launches, stop(s, ms): start creates the events when they are not there yet and records
+// the first; stop records the second, waits for the stream and writes the device time between the two into *ms unless ms
+// is NULL.
+inline int TimerEvents::start(hipStream_t s) {
+    if (!e0) HIP_TRY(hipEventCreate(&e0));
+    if (!e1) HIP_TRY(hipEventCreate(&e1));
+    HIP_TRY(hipEventRecord(e0, s));
+    return GKI_OK;
+}
+inline int TimerEvents::stop(hipStream_t s, float *ms) {
+    HIP_TRY(hipEventRecord(e1, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (ms) HIP_TRY(hipEventElapsedTime(ms, e0, e1));
+    return GKI_OK;
 }
 
 // ---------------------------------------------------------------------------------- 2-bit sequence

@@ -2,10 +2,9 @@
 // The rules are those of include/gki.h ("graph build") and DESIGN.md 4.15.
 //
 // 1. per piece of text (gki_graph_sites_count / _emit), beside the unchanged gki_vcf_parse_*:
-//   (line ends)              gki_text_line_ends (kernels in gki_text_lines.hip)
-//   k_gb_is_data             one lane per line: header / blank / data -- gki_text_lines.h's vcf_line, the rule k_vcf_classify
-//                            applies, so both number the data lines alike; vcf_fields and vcf_pos_value are shared too
-//   (exclusive scan)         line -> data lines before it
+//   (data lines)             gki_vcf_data_lines (gki_text_lines.hip): line ends, header / blank / data by vcf_line -- the
+//                            rule k_vcf_classify applies, so both number the data lines alike --, line -> data lines before
+//                            it; vcf_fields and vcf_pos_value are shared too
 //   k_gb_sites               one lane per data line: fields, POS against its chromosome, plain or not, the strip rule, REF
 //                            against the reference; writes the line's site and how many alt letters it has for the pool
 //   (exclusive scan)         data line -> alt letters before it
@@ -29,21 +28,12 @@ constexpr int GB_ITEMS = 8;                                // lines per lane in 
 constexpr int GB_TILE = PARSE_BLOCK * GB_ITEMS;            // 2048 lines per workgroup
 constexpr int SEQ_TILE = PARSE_BLOCK * 16;                 // 4096 codes per workgroup
 
-// first_bad: (data line << 3 | kind) of the lowest line at fault, all ones when there is none (atomicMin).
-// flags: bit 0 an allele of 2^31 letters or more, bit 1 the text and chrom_run disagree
-struct SiteTotals { unsigned long long first_bad; unsigned int flags; unsigned int pad; };
+// beside the lowest data line at fault, flags: bit 0 an allele of 2^31 letters or more, bit 1 the text and chrom_run disagree
+struct SiteTotals : LineFault { unsigned int flags = 0, pad = 0; };
 
 __device__ __forceinline__ bool plain_letter(uint8_t c) {  // ACGTN in either case: none of them has bit 5 set
     const uint8_t u = c & 0xDF;
     return u == (uint8_t)'A' || u == (uint8_t)'C' || u == (uint8_t)'G' || u == (uint8_t)'T' || u == (uint8_t)'N';
-}
-
-__global__ __launch_bounds__(PARSE_BLOCK) void k_gb_is_data(const uint8_t *__restrict__ bytes,
-                                                            const int64_t *__restrict__ line_end, int64_t n_lines,
-                                                            uint32_t *__restrict__ is_data) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_lines; i += stride)
-        is_data[i] = vcf_line(bytes, line_end, i).data ? 1u : 0u;
 }
 
 // Data line v of the piece: gpos = C0 + POS - 1, the site (lo, ref_len, alt_len), status 0 / 1 / 2, where its alt allele
@@ -101,7 +91,7 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_gb_sites(const uint8_t *__restr
                 }
             }
         }
-        if (kind && kind != 7) atomicMin(&totals->first_bad, (unsigned long long)v << 3 | (unsigned long long)kind);
+        if (kind && kind != 7) line_fault(&totals->first_bad, v, kind);
         if (kind) { g = site_lo = rl = al = 0; st = 1; }
         gpos[v] = g;
         lo[v] = site_lo;
@@ -128,7 +118,7 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_gb_copy_alt(const uint8_t *__re
 
 // What the site pass of one piece leaves on the device.  Both entry points build it; neither keeps it.
 struct SitePlan {
-    DevBuf line_end, is_data, variant_index, alt_begin, pool_len, pool_off, tmp, totals;
+    DevBuf alt_begin, pool_len, pool_off;
     int64_t n_alt_bytes = 0, first_bad = -1;
     int first_bad_kind = 0;
 };
@@ -141,45 +131,31 @@ int site_pass(const uint8_t *bytes, int64_t n, const int32_t *chrom_run, int64_t
     if (n == 0 || bytes == nullptr || chrom_run == nullptr || run_c0 == nullptr || run_c1 == nullptr || reference == nullptr)
         return gki_set_error(GKI_ERR_BAD_ARG, "graph_sites: %lld data lines need the text, their runs and the reference",
                              (long long)nv);
-    int64_t n_lines = 0;
-    GKI_TRY(gki_text_line_ends(bytes, n, "graph_sites", p.line_end, &n_lines));
-    HIP_TRY(p.is_data.alloc((size_t)n_lines * 4));
-    HIP_TRY(p.variant_index.alloc((size_t)(n_lines + 1) * 8));
-    const int64_t tmp_bytes = gki_scan_tmp_bytes(n_lines > nv ? n_lines : nv);
-    HIP_TRY(p.tmp.alloc((size_t)tmp_bytes));
+    VcfDataLines d;                                        // of the pass alone: both waits below come before it is freed
+    GKI_TRY(gki_vcf_data_lines(bytes, n, "graph_sites", d));
+    GKI_TRY(gki_vcf_expect_data_lines("graph_sites", d.n_data, nv, "chrom_run"));
+    DevBuf tmp, d_totals;
+    const int64_t tmp_bytes = gki_scan_tmp_bytes(nv);
+    HIP_TRY(tmp.alloc((size_t)tmp_bytes));
     HIP_TRY(p.alt_begin.alloc((size_t)nv * 8));
     HIP_TRY(p.pool_len.alloc((size_t)nv * 4));
     HIP_TRY(p.pool_off.alloc((size_t)(nv + 1) * 8));
-    HIP_TRY(p.totals.alloc(sizeof(SiteTotals)));
-    const SiteTotals none = {~0ull, 0u, 0u};
-    HIP_TRY(hipMemcpy(p.totals.get(), &none, sizeof(SiteTotals), hipMemcpyHostToDevice));
+    GKI_TRY(line_fault_init<SiteTotals>(d_totals));
     HIP_TRY(hipMemset(p.pool_len.get(), 0, (size_t)nv * 4));      // a data line the text does not have stays without letters
-    hipLaunchKernelGGL(k_gb_is_data, dim3(stream_grid(n_lines, PARSE_BLOCK)), dim3(PARSE_BLOCK), 0, 0, bytes,
-                       p.line_end.get<const int64_t>(), n_lines, p.is_data.get<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    GKI_TRY(gki_scan_u32_to_i64(p.is_data.get<const uint32_t>(), n_lines, p.variant_index.get<int64_t>(), p.tmp.get(),
-                                tmp_bytes, 0));
-    int64_t found = 0;
-    GKI_TRY(gki_scan_total(p.variant_index, n_lines, &found));
-    if (found != nv)
-        return gki_set_error(GKI_ERR_BAD_ARG, "graph_sites: the text has %lld data lines, chrom_run %lld", (long long)found,
-                             (long long)nv);
-    hipLaunchKernelGGL(k_gb_sites, dim3(stream_grid(n_lines, PARSE_BLOCK)), dim3(PARSE_BLOCK), 0, 0, bytes,
-                       p.line_end.get<const int64_t>(), n_lines, p.is_data.get<const uint32_t>(),
-                       p.variant_index.get<const int64_t>(), chrom_run, nv, run_c0, run_c1, n_runs, reference,
+    hipLaunchKernelGGL(k_gb_sites, dim3(stream_grid(d.n_lines, PARSE_BLOCK)), dim3(PARSE_BLOCK), 0, 0, bytes,
+                       d.line_end.get<const int64_t>(), d.n_lines, d.is_data.get<const uint32_t>(),
+                       d.variant_index.get<const int64_t>(), chrom_run, nv, run_c0, run_c1, n_runs, reference,
                        gpos, lo, ref_len, alt_len, status, p.alt_begin.get<int64_t>(), p.pool_len.get<uint32_t>(),
-                       p.totals.get<SiteTotals>());
+                       d_totals.get<SiteTotals>());
     HIP_TRY(hipGetLastError());
-    GKI_TRY(gki_scan_u32_to_i64(p.pool_len.get<const uint32_t>(), nv, p.pool_off.get<int64_t>(), p.tmp.get(), tmp_bytes, 0));
+    GKI_TRY(gki_scan_u32_to_i64(p.pool_len.get<const uint32_t>(), nv, p.pool_off.get<int64_t>(), tmp.get(), tmp_bytes, 0));
     SiteTotals totals;
     GKI_TRY(gki_scan_total(p.pool_off, nv, &p.n_alt_bytes));
-    HIP_TRY(hipMemcpy(&totals, p.totals.get(), sizeof(SiteTotals), hipMemcpyDeviceToHost));
+    GKI_TRY(line_fault_read(d_totals, &totals));
     if (totals.flags & 2u) return gki_set_error(GKI_ERR_BAD_ARG, "graph_sites: chrom_run does not belong to this text");
     if (totals.flags & 1u) return gki_set_error(GKI_ERR_BAD_ARG, "graph_sites: an allele of 2^31 letters or more");
-    if (totals.first_bad != ~0ull) {
-        p.first_bad = (int64_t)(totals.first_bad >> 3);
-        p.first_bad_kind = (int)(totals.first_bad & 7);
-    }
+    p.first_bad = totals.line();
+    p.first_bad_kind = totals.kind();
     return GKI_OK;
 }
 
@@ -807,9 +783,7 @@ int gki_graph_build_emit(gki_graph_build *plan, const void *d_reference, const v
     TimerEvents ev;
     DevBuf tile_site;                                      // int64[n_tiles + 1], freed behind the synchronise below
     HIP_TRY(tile_site.alloc((size_t)(ceil_div(g.n_bases, SEQ_TILE) + 1) * 8));
-    HIP_TRY(hipEventCreate(&ev.e0));
-    HIP_TRY(hipEventCreate(&ev.e1));
-    HIP_TRY(hipEventRecord(ev.e0, 0));
+    GKI_TRY(ev.start(0));
     const int64_t n_tiles = ceil_div(g.n_bases, SEQ_TILE);
     hipLaunchKernelGGL(k_gb_tile_sites, dim3(stream_grid(n_tiles + 1, PARSE_BLOCK)), dim3(PARSE_BLOCK), 0, 0,
                        g.alt_end.get<const int64_t>(), g.K, n_tiles, tile_site.get<int64_t>());
@@ -819,10 +793,7 @@ int gki_graph_build_emit(gki_graph_build *plan, const void *d_reference, const v
                        g.alt_before.get<const int64_t>(), g.kpool.get<const int64_t>(), tile_site.get<const int64_t>(),
                        g.n_bases, (uint8_t *)d_seq);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev.e1, 0));
-    HIP_TRY(hipStreamSynchronize(0));
-    if (sequence_ms) HIP_TRY(hipEventElapsedTime(sequence_ms, ev.e0, ev.e1));
-    return GKI_OK;
+    return ev.stop(0, sequence_ms);
 }
 
 }  // extern "C"

@@ -2,9 +2,11 @@
 // (gki_vcf_parse.hip), the graph build's site pass (gki_graph_build.hip), the VCF's allele frequencies (gki_vcf_af.hip), its
 // haplotype matrix (gki_vcf_gt.hip) and the reference FASTA (gki_fasta_parse.hip).
 // The tile geometry, the SWAR byte test, the block prefix and the wave copy serve the dense kernels; the line-end pass
-// (kernels in gki_text_lines.hip) serves all but the FASTA parser; the VCF line rules serve the VCF parser, the site pass
-// and the allele-frequency pass, which must number the data lines alike (gki_graph_sites_* and
-// gki_vcf_allele_frequencies check the count).
+// (kernels in gki_text_lines.hip) serves all but the FASTA parser; the VCF line rules (vcf_line, vcf_fields, vcf_pos_value)
+// and the record of the lowest line at fault (LineFault) serve the four VCF passes.  The site pass, the allele frequencies
+// and the haplotype matrix number the data lines through one front end, gki_vcf_data_lines (k_vcf_is_data, the scan, the
+// total), and check the caller's count with gki_vcf_expect_data_lines; the VCF parser applies the same vcf_line in its
+// fused k_vcf_classify, which makes the fields in the same walk.
 #pragma once
 #include "gki_common.h"
 
@@ -64,7 +66,7 @@ constexpr int VCF_MAX_POS_DIGITS = 18;                     // 10^18 - 1 fits int
 constexpr int VCF_FIELDS = 5;                              // CHROM POS ID REF ALT: no kernel walks beyond them
 
 // Line i of VCF text: every '\r' at its end is dropped; a data line is not empty, does not begin with '#' and is not blank
-// (nothing but strip bytes).  One function: a kernel drops what it does not use, two helpers cost k_gb_is_data a register.
+// (nothing but strip bytes).  One function: a kernel drops what it does not use, two helpers cost k_vcf_is_data a register.
 struct VcfLine { int64_t b, e; bool data; };
 __device__ __forceinline__ VcfLine vcf_line(const uint8_t *bytes, const int64_t *line_end, int64_t i) {
     auto [b, e] = text_line(line_end, i);
@@ -125,5 +127,38 @@ int gki_text_line_ends(const uint8_t *bytes, int64_t n, const char *who, DevBuf 
 // the total of an exclusive scan of n inputs (gki_scan_u32_to_i64): its entry n, read back; waits for the scan
 static inline int gki_scan_total(const DevBuf &scan, int64_t n, int64_t *total) {
     HIP_TRY(hipMemcpy(total, scan.get<const int64_t>() + n, 8, hipMemcpyDeviceToHost));
+    return GKI_OK;
+}
+
+// The data lines of VCF text, numbered: is_data uint32[n_lines] by vcf_line (k_vcf_is_data of gki_text_lines.hip),
+// variant_index int64[n_lines + 1] its exclusive scan -- the data lines before line i -- and n_data the scan's total.
+struct VcfDataLines {
+    DevBuf line_end, is_data, variant_index;
+    int64_t n_lines = 0, n_data = 0;
+};
+// bytes[0, n) on the device (n > 0) -> out; waits for the device (gki_scan_total).  `who` begins the error messages.
+int gki_vcf_data_lines(const uint8_t *bytes, int64_t n, const char *who, VcfDataLines &out);
+// GKI_ERR_BAD_ARG unless the text has the data lines its caller counted before (through `counted_by`)
+int gki_vcf_expect_data_lines(const char *who, int64_t found, int64_t expected, const char *counted_by = "the caller expects");
+
+// The lowest line at fault of a pass and its kind (1..7), in one word for atomicMin: line << 3 | kind, all ones when there
+// is none.  A pass with flag words of its own derives its totals from LineFault, so that one copy brings all of them back.
+struct LineFault {
+    unsigned long long first_bad = ~0ull;
+    int64_t line() const { return first_bad == ~0ull ? -1 : (int64_t)(first_bad >> 3); }
+    int kind() const { return first_bad == ~0ull ? 0 : (int)(first_bad & 7); }
+};
+__device__ __forceinline__ void line_fault(unsigned long long *first_bad, int64_t line, int kind) {
+    atomicMin(first_bad, (unsigned long long)line << 3 | (unsigned long long)kind);
+}
+// host side: a pass's totals T (LineFault or derived from it) in their first state on the device, and read back
+template <class T = LineFault> static inline int line_fault_init(DevBuf &totals) {
+    const T none;
+    HIP_TRY(totals.alloc(sizeof(T)));
+    HIP_TRY(hipMemcpy(totals.get(), &none, sizeof(T), hipMemcpyHostToDevice));
+    return GKI_OK;
+}
+template <class T> static inline int line_fault_read(const DevBuf &totals, T *out) {
+    HIP_TRY(hipMemcpy(out, totals.get(), sizeof(T), hipMemcpyDeviceToHost));
     return GKI_OK;
 }

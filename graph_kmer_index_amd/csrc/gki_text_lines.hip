@@ -1,10 +1,14 @@
-// The line-end pass of gki_text_lines.h: where every line of a buffer ends.  The only whole-buffer work of the reads parser,
-// the VCF parser and the graph build's site pass.
+// The line-end pass of gki_text_lines.h: where every line of a buffer ends.  The only whole-buffer work of the reads parser
+// and the VCF passes.  Behind it the numbering of VCF data lines that the graph build's site pass, the allele frequencies
+// and the haplotype matrix share (gki_vcf_data_lines).
 //   k_parse_count_newlines   a workgroup counts the '\n' of its PARSE_TILE bytes: one 16-byte load per lane, a SWAR
 //                            compare per word, popcounts, a wave and a workgroup sum
 //   (exclusive scan)         tile -> number of line ends before it
 //   k_parse_line_ends        the same loads again; a wave prefix sum of the lanes' popcounts numbers every '\n', and its
 //                            byte position goes to line_end[its number]
+//   k_vcf_is_data            one lane per line: header / blank / data by gki_text_lines.h's vcf_line, the rule k_vcf_classify
+//                            applies too
+//   (exclusive scan)         line -> data lines before it
 #include "gki_text_lines.h"
 
 namespace {
@@ -48,6 +52,14 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_parse_line_ends(const uint8_t *
     }
 }
 
+__global__ __launch_bounds__(PARSE_BLOCK) void k_vcf_is_data(const uint8_t *__restrict__ bytes,
+                                                             const int64_t *__restrict__ line_end, int64_t n_lines,
+                                                             uint32_t *__restrict__ is_data) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_lines; i += stride)
+        is_data[i] = vcf_line(bytes, line_end, i).data ? 1u : 0u;
+}
+
 }  // namespace
 
 int gki_text_line_ends(const uint8_t *bytes, int64_t n, const char *who, DevBuf &line_end, int64_t *n_lines) {
@@ -75,4 +87,25 @@ int gki_text_line_ends(const uint8_t *bytes, int64_t n, const char *who, DevBuf 
     HIP_TRY(hipGetLastError());
     if (open_end) HIP_TRY(hipMemcpy(line_end.get<int64_t>() + n_newlines, &n, 8, hipMemcpyHostToDevice));
     return GKI_OK;
+}
+
+int gki_vcf_data_lines(const uint8_t *bytes, int64_t n, const char *who, VcfDataLines &out) {
+    GKI_TRY(gki_text_line_ends(bytes, n, who, out.line_end, &out.n_lines));
+    const int64_t n_lines = out.n_lines, tmp_bytes = gki_scan_tmp_bytes(n_lines);
+    DevBuf tmp;                                            // the scan's scratch: gki_scan_total has waited when it is freed
+    HIP_TRY(out.is_data.alloc((size_t)n_lines * 4));
+    HIP_TRY(out.variant_index.alloc((size_t)(n_lines + 1) * 8));
+    HIP_TRY(tmp.alloc((size_t)tmp_bytes));
+    hipLaunchKernelGGL(k_vcf_is_data, dim3(stream_grid(n_lines, PARSE_BLOCK)), dim3(PARSE_BLOCK), 0, 0, bytes,
+                       out.line_end.get<const int64_t>(), n_lines, out.is_data.get<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    GKI_TRY(gki_scan_u32_to_i64(out.is_data.get<const uint32_t>(), n_lines, out.variant_index.get<int64_t>(), tmp.get(),
+                                tmp_bytes, 0));
+    return gki_scan_total(out.variant_index, n_lines, &out.n_data);
+}
+
+int gki_vcf_expect_data_lines(const char *who, int64_t found, int64_t expected, const char *counted_by) {
+    if (found == expected) return GKI_OK;
+    return gki_set_error(GKI_ERR_BAD_ARG, "%s: the text has %lld data lines, %s %lld", who, (long long)found, counted_by,
+                         (long long)expected);
 }

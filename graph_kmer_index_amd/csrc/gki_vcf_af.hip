@@ -2,20 +2,17 @@
 // The rules are those of include/gki.h ("VCF allele frequencies") and DESIGN.md 4.17.
 //
 // per piece of text (gki_vcf_allele_frequencies), beside the unchanged gki_vcf_parse_* and gki_graph_sites_*:
-//   (line ends)      gki_text_line_ends (kernels in gki_text_lines.hip)
-//   k_af_is_data     one lane per line: header / blank / data -- gki_text_lines.h's vcf_line, so the data lines are numbered
-//                    as the two other passes number them; the host checks the count
-//   (exclusive scan) line -> data lines before it
+//   (data lines)     gki_vcf_data_lines (gki_text_lines.hip): line ends, header / blank / data, line -> data lines before
+//                    it -- the front end of the site pass and the haplotype matrix, so the three number the data lines
+//                    alike; the host checks the count
 //   k_af_info        source info: one lane per data line walks to the seventh tab and through INFO, which lies before the
 //                    sample columns, finds the AF= entry and turns its value text into a double by one exact operation
-//   k_af_genotypes   source genotypes: one wave per data line, dense in the bytes.  Each step the 64 lanes take 16
-//                    consecutive bytes each (GT_STEP = 1024 bytes a step), find the tabs with equal_mask16 and number them
-//                    with a wave prefix sum on top of the line's running count, which the wave carries in a scalar.  A
+//   k_af_genotypes   source genotypes: one wave per data line, dense in the bytes, by gki_vcf_gt.h's gt_walk_line.  A
 //                    lane whose bytes hold tab number 9 or higher parses the GT behind it straight from memory, eight bytes
-//                    in one load (a GT is a few bytes; they may lie in the next lane's or the next step's bytes).  Tab number 8 opens FORMAT,
-//                    which its lane checks.  One wave reduction per line gives the three counts; lane 0 divides and stores.
-//                    A wave owns its line: no atomics but the atomicMin of the lowest line at fault.
-// The walk's loads and the GT grammar are gki_vcf_gt.h's, shared with the haplotype matrix (gki_vcf_gt.hip).
+//                    in one load (a GT is a few bytes; they may lie in the next lane's or the next step's bytes).  Tab
+//                    number 8 opens FORMAT, which its lane checks.  One wave reduction per line gives the three counts;
+//                    lane 0 divides and stores.  A wave owns its line: no atomics but that of the lowest line at fault.
+// The walk and the GT grammar are gki_vcf_gt.h's, shared with the haplotype matrix (gki_vcf_gt.hip).
 #include "gki_vcf_gt.h"
 
 namespace {
@@ -23,20 +20,9 @@ namespace {
 constexpr int AF_MAX_MANTISSA_DIGITS = 15, AF_MAX_EXPONENT_DIGITS = 3, AF_MAX_POWER = 22;
 constexpr uint8_t ROUTE_DEVICE = 0, ROUTE_ABSENT = 1, ROUTE_HOST = 2;
 
-// first_bad: (data line << 3 | kind) of the lowest line at fault, all ones when there is none (atomicMin)
-struct AfTotals { unsigned long long first_bad; };
-
 // the powers of ten a double holds exactly
 __device__ const double AF_POW10[AF_MAX_POWER + 1] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
                                                       1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
-
-__global__ __launch_bounds__(PARSE_BLOCK) void k_af_is_data(const uint8_t *__restrict__ bytes,
-                                                            const int64_t *__restrict__ line_end, int64_t n_lines,
-                                                            uint32_t *__restrict__ is_data) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_lines; i += stride)
-        is_data[i] = vcf_line(bytes, line_end, i).data ? 1u : 0u;
-}
 
 // The value text bytes [b, e) under the device grammar  D* [ . D* ] [ (e|E) [+|-] D+ ]: true and *value when the mantissa
 // has 1 to 15 digits, the exponent at most 3 and |q| <= 22, q = exponent - fraction digits.  m (below 10^15) and 10^|q| are
@@ -75,7 +61,8 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_af_info(const uint8_t *__restri
                                                          const int64_t *__restrict__ variant_index, int64_t n_variants,
                                                          double *__restrict__ ref_af, double *__restrict__ alt_af,
                                                          uint8_t *__restrict__ route, int64_t *__restrict__ span_begin,
-                                                         int32_t *__restrict__ span_len, AfTotals *__restrict__ totals) {
+                                                         int32_t *__restrict__ span_len,
+                                                         unsigned long long *__restrict__ first_bad) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_lines; i += stride) {
         if (!is_data[i]) continue;
@@ -106,7 +93,7 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_af_info(const uint8_t *__restri
         if (value_b >= 0 && len > 0 && !(len == 1 && bytes[value_b] == (uint8_t)'.'))
             r = af_value(bytes, value_b, value_e, &value) ? ROUTE_DEVICE : ROUTE_HOST;
         const bool at_fault = r == ROUTE_DEVICE && !(value <= 1.0);   // the grammar has no sign: never negative, never NaN
-        if (at_fault) atomicMin(&totals->first_bad, (unsigned long long)v << 3 | 1ull);
+        if (at_fault) line_fault(first_bad, v, 1);
         const bool parsed = r == ROUTE_DEVICE && !at_fault;
         ref_af[v] = parsed ? 1.0 - value : 1.0;
         alt_af[v] = parsed ? value : 1.0;
@@ -124,13 +111,29 @@ struct GtCounts {
     __device__ __forceinline__ void slash() {}
 };
 
-// One wave per data line.  FORMAT is field 8 (opened by tab number 8), the samples are fields 9 and up.
+// what a lane of k_af_genotypes gathers over its line (gt_walk_line's visitor): the counts of its samples, and what it saw
+struct AfLine {
+    const uint8_t *__restrict__ bytes;
+    int64_t n_bytes, e;
+    int &called, &n_ref, &n_alt, &bad_format, &bad_gt;
+    __device__ __forceinline__ void format(bool ok) { bad_format |= !ok; }
+    __device__ __forceinline__ void sample(int64_t, int64_t p) {
+        GtCounts c;
+        bad_gt |= !gt_at(bytes, n_bytes, p, e, &c);
+        called += c.called;
+        n_ref += c.n_ref;
+        n_alt += c.n_alt;
+    }
+};
+
+// One wave per data line.
 __global__ __launch_bounds__(PARSE_BLOCK) void k_af_genotypes(const uint8_t *__restrict__ bytes, int64_t n_bytes,
                                                               const int64_t *__restrict__ line_end, int64_t n_lines,
                                                               const uint32_t *__restrict__ is_data,
                                                               const int64_t *__restrict__ variant_index, int64_t n_variants,
                                                               double *__restrict__ ref_af, double *__restrict__ alt_af,
-                                                              uint8_t *__restrict__ route, AfTotals *__restrict__ totals) {
+                                                              uint8_t *__restrict__ route,
+                                                              unsigned long long *__restrict__ first_bad) {
     const int lane = threadIdx.x & 63;
     const int64_t first = wave_uniform((int64_t)blockIdx.x * (PARSE_BLOCK / 64) + (threadIdx.x >> 6));
     const int64_t stride = (int64_t)gridDim.x * (PARSE_BLOCK / 64);
@@ -140,38 +143,16 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_af_genotypes(const uint8_t *__r
         if (v >= n_variants) continue;
         const VcfLine l = vcf_line(bytes, line_end, i);
         const int64_t b = wave_uniform(l.b), e = wave_uniform(l.e);
-        int tabs_before = 0, called = 0, n_ref = 0, n_alt = 0, bad_format = 0, bad_gt = 0;
-        for (int64_t base = b; base < e; base += GT_STEP) {
-            const int64_t p0 = base + (int64_t)lane * PARSE_LANE_BYTES;
-            const uint4 in = line_bytes16(bytes, n_bytes, p0, e);
-            uint32_t tabs = line_tabs16(in, p0, e);
-            const int mine = __popc(tabs);
-            const int incl = gki_wave_incl_sum(mine);
-            int number = tabs_before + incl - mine;        // tabs of the line before this lane's first
-            tabs_before += gki_lane_value(incl, 63);
-            while (tabs) {
-                const int j = __ffs(tabs) - 1;
-                tabs &= tabs - 1;
-                number++;
-                const int64_t p = p0 + j + 1;              // the field tab `number` opens
-                if (number == 8)
-                    bad_format |= !format_begins_with_gt(bytes, p, e);
-                else if (number >= 9) {
-                    GtCounts c;
-                    bad_gt |= !gt_at(bytes, n_bytes, p, e, &c);
-                    called += c.called;
-                    n_ref += c.n_ref;
-                    n_alt += c.n_alt;
-                }
-            }
-        }
+        int called = 0, n_ref = 0, n_alt = 0, bad_format = 0, bad_gt = 0;
+        const int tabs_before = gt_walk_line(bytes, n_bytes, b, e, lane,
+                                             AfLine{bytes, n_bytes, e, called, n_ref, n_alt, bad_format, bad_gt});
         called = wave_sum(called);
         n_ref = wave_sum(n_ref);
         n_alt = wave_sum(n_alt);
         const int kind = tabs_before < 9 ? 0 : wave_sum(bad_format) ? 2 : wave_sum(bad_gt) ? 3 : 0;
         if (lane == 0) {
             const bool counted = tabs_before >= 9 && kind == 0 && called > 0;
-            if (kind) atomicMin(&totals->first_bad, (unsigned long long)v << 3 | (unsigned long long)kind);
+            if (kind) line_fault(first_bad, v, kind);
             ref_af[v] = counted ? (double)n_ref / (double)called : 1.0;
             alt_af[v] = counted ? (double)n_alt / (double)called : 1.0;
             route[v] = counted ? ROUTE_DEVICE : ROUTE_ABSENT;
@@ -198,50 +179,30 @@ extern "C" int gki_vcf_allele_frequencies(const void *d_text, int64_t n_bytes, i
         return gki_set_error(GKI_ERR_BAD_ARG, "vcf_allele_frequencies: an output buffer is NULL");
     const uint8_t *bytes = (const uint8_t *)d_text;
     TimerEvents ev;
-    DevBuf line_end, is_data, variant_index, tmp, totals;
-    int64_t n_lines = 0, found = 0;
-    if (n_bytes > 0) {
-        GKI_TRY(gki_text_line_ends(bytes, n_bytes, "vcf_allele_frequencies", line_end, &n_lines));
-        const int64_t tmp_bytes = gki_scan_tmp_bytes(n_lines);
-        HIP_TRY(is_data.alloc((size_t)n_lines * 4));
-        HIP_TRY(variant_index.alloc((size_t)(n_lines + 1) * 8));
-        HIP_TRY(tmp.alloc((size_t)tmp_bytes));
-        hipLaunchKernelGGL(k_af_is_data, dim3(stream_grid(n_lines, PARSE_BLOCK)), dim3(PARSE_BLOCK), 0, 0, bytes,
-                           line_end.get<const int64_t>(), n_lines, is_data.get<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        GKI_TRY(gki_scan_u32_to_i64(is_data.get<const uint32_t>(), n_lines, variant_index.get<int64_t>(), tmp.get(), tmp_bytes, 0));
-        GKI_TRY(gki_scan_total(variant_index, n_lines, &found));
-    }
-    if (n_data_lines) *n_data_lines = found;
-    if (found != n_variants)
-        return gki_set_error(GKI_ERR_BAD_ARG, "vcf_allele_frequencies: the text has %lld data lines, the caller expects %lld",
-                             (long long)found, (long long)n_variants);
-    if (found == 0) return GKI_OK;
-    HIP_TRY(totals.alloc(sizeof(AfTotals)));
-    const AfTotals none = {~0ull};
-    HIP_TRY(hipMemcpy(totals.get(), &none, sizeof(AfTotals), hipMemcpyHostToDevice));
-    HIP_TRY(hipEventCreate(&ev.e0));
-    HIP_TRY(hipEventCreate(&ev.e1));
-    HIP_TRY(hipEventRecord(ev.e0, 0));
+    VcfDataLines d;
+    DevBuf totals;
+    if (n_bytes > 0) GKI_TRY(gki_vcf_data_lines(bytes, n_bytes, "vcf_allele_frequencies", d));
+    if (n_data_lines) *n_data_lines = d.n_data;
+    GKI_TRY(gki_vcf_expect_data_lines("vcf_allele_frequencies", d.n_data, n_variants));
+    if (n_variants == 0) return GKI_OK;
+    GKI_TRY(line_fault_init(totals));
+    GKI_TRY(ev.start(0));
     if (source == GKI_AF_SOURCE_INFO)
-        hipLaunchKernelGGL(k_af_info, dim3(stream_grid(n_lines, PARSE_BLOCK)), dim3(PARSE_BLOCK), 0, 0, bytes,
-                           line_end.get<const int64_t>(), n_lines, is_data.get<const uint32_t>(),
-                           variant_index.get<const int64_t>(), n_variants, (double *)d_ref_af, (double *)d_alt_af,
-                           (uint8_t *)d_route, (int64_t *)d_span_begin, (int32_t *)d_span_len, totals.get<AfTotals>());
+        hipLaunchKernelGGL(k_af_info, dim3(stream_grid(d.n_lines, PARSE_BLOCK)), dim3(PARSE_BLOCK), 0, 0, bytes,
+                           d.line_end.get<const int64_t>(), d.n_lines, d.is_data.get<const uint32_t>(),
+                           d.variant_index.get<const int64_t>(), n_variants, (double *)d_ref_af, (double *)d_alt_af,
+                           (uint8_t *)d_route, (int64_t *)d_span_begin, (int32_t *)d_span_len,
+                           totals.get<unsigned long long>());
     else
-        hipLaunchKernelGGL(k_af_genotypes, dim3(stream_grid(n_lines, PARSE_BLOCK / 64)), dim3(PARSE_BLOCK), 0, 0, bytes, n_bytes,
-                           line_end.get<const int64_t>(), n_lines, is_data.get<const uint32_t>(),
-                           variant_index.get<const int64_t>(), n_variants, (double *)d_ref_af, (double *)d_alt_af,
-                           (uint8_t *)d_route, totals.get<AfTotals>());
+        hipLaunchKernelGGL(k_af_genotypes, dim3(stream_grid(d.n_lines, PARSE_BLOCK / 64)), dim3(PARSE_BLOCK), 0, 0, bytes,
+                           n_bytes, d.line_end.get<const int64_t>(), d.n_lines, d.is_data.get<const uint32_t>(),
+                           d.variant_index.get<const int64_t>(), n_variants, (double *)d_ref_af, (double *)d_alt_af,
+                           (uint8_t *)d_route, totals.get<unsigned long long>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev.e1, 0));
-    HIP_TRY(hipStreamSynchronize(0));
-    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, ev.e0, ev.e1));
-    AfTotals t;
-    HIP_TRY(hipMemcpy(&t, totals.get(), sizeof(AfTotals), hipMemcpyDeviceToHost));
-    if (t.first_bad != ~0ull) {
-        if (first_bad_variant) *first_bad_variant = (int64_t)(t.first_bad >> 3);
-        if (first_bad_kind) *first_bad_kind = (int)(t.first_bad & 7);
-    }
+    GKI_TRY(ev.stop(0, kernel_ms));
+    LineFault fault;
+    GKI_TRY(line_fault_read(totals, &fault));
+    if (first_bad_variant) *first_bad_variant = fault.line();
+    if (first_bad_kind) *first_bad_kind = fault.kind();
     return GKI_OK;
 }

@@ -1,7 +1,8 @@
 // The GT columns of VCF text in HBM: what the two kernels that walk them share -- k_af_genotypes (gki_vcf_af.hip, allele
 // frequencies) and k_gt_matrix (gki_vcf_gt.hip, the haplotype matrix).  One wave takes a data line GT_STEP bytes a step,
-// 16 per lane; the lane that holds a sample's tab parses the GT behind it.  The GT grammar of include/gki.h ("VCF allele
-// frequencies") is stated once, in gt_parse; what a kernel does with the alleles is its sink's.
+// 16 per lane; the lane that holds a sample's tab parses the GT behind it.  The walk is stated once, in gt_walk_line, and
+// the GT grammar of include/gki.h ("VCF allele frequencies") once, in gt_parse; what a kernel does with a field is its
+// visitor's, what it does with the alleles its sink's.
 #pragma once
 #include "gki_text_lines.h"
 
@@ -99,4 +100,36 @@ template <class Sink> __device__ __forceinline__ bool gt_at(const uint8_t *__res
         state = gt_parse([bytes, p](int64_t i) { return bytes[p + i]; }, e - p, true, sink);
     }
     return state == 1;
+}
+
+// One wave walks the data line [b, e) (both wave-uniform), GT_STEP bytes a step: the lanes find the tabs of their 16 bytes
+// and number them with a wave prefix sum on top of the line's running count, which the wave carries in a scalar.  FORMAT is
+// field 8 (opened by tab number 8), sample s is field 9 + s.  The lane that holds tab 8 calls visit.format(ok), ok = FORMAT
+// begins with GT; the lane that holds tab 9 + s calls visit.sample(s, p), p the sample field's first byte, where the kernel
+// calls gt_at with its own sink.  Returns the line's tab count, wave-uniform.  Every lane of the wave must be active.
+// The visitor is taken by value and refers to what the lane gathers in the kernel's own locals: with the state inside a
+// visitor passed by reference k_af_genotypes needs a 59th register.
+template <class Visitor> __device__ __forceinline__ int gt_walk_line(const uint8_t *__restrict__ bytes, int64_t n_bytes, int64_t b,
+                                                                     int64_t e, int lane, Visitor visit) {
+    int tabs_before = 0;
+    for (int64_t base = b; base < e; base += GT_STEP) {
+        const int64_t p0 = base + (int64_t)lane * PARSE_LANE_BYTES;
+        const uint4 in = line_bytes16(bytes, n_bytes, p0, e);
+        uint32_t tabs = line_tabs16(in, p0, e);
+        const int mine = __popc(tabs);
+        const int incl = gki_wave_incl_sum(mine);
+        int number = tabs_before + incl - mine;            // tabs of the line before this lane's first
+        tabs_before += gki_lane_value(incl, 63);
+        while (tabs) {
+            const int j = __ffs(tabs) - 1;
+            tabs &= tabs - 1;
+            number++;
+            const int64_t p = p0 + j + 1;                  // the field tab `number` opens
+            if (number == 8)
+                visit.format(format_begins_with_gt(bytes, p, e));
+            else if (number >= 9)
+                visit.sample((int64_t)(number - 9), p);
+        }
+    }
+    return tabs_before;
 }

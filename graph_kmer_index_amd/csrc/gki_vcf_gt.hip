@@ -2,15 +2,14 @@
 // slot, and the same as two bit planes.  The rules are those of include/gki.h ("VCF haplotype matrix") and DESIGN.md 4.18.
 //
 // per piece of text (gki_vcf_haplotype_matrix), beside the unchanged gki_vcf_parse_* and gki_vcf_allele_frequencies:
-//   (line ends)         gki_text_line_ends (kernels in gki_text_lines.hip)
-//   k_gt_is_data        one lane per line: header / blank / data -- gki_text_lines.h's vcf_line; the host checks the count
-//   (exclusive scan)    line -> data lines before it
-//   k_gt_matrix         the walk of k_af_genotypes (gki_vcf_gt.h) with stores in place of counts: one wave per data line,
-//                       GT_STEP bytes a step, tabs numbered on top of the wave's running count.  The lane that holds tab
-//                       9 + s parses sample s and stores its P codes at codes[v][s P ..]; a good line has exactly S samples,
-//                       so its lanes write the whole row between them.  Whether the line is at fault is known after its
-//                       last step: the wave then writes the row again, all 3 (a wave-uniform branch behind a wait for the
-//                       stores above).  Lane 0 stores phased[v].  No atomics but the atomicMin of the lowest line at fault.
+//   (data lines)        gki_vcf_data_lines (gki_text_lines.hip): line ends, header / blank / data, line -> data lines
+//                       before it; the host checks the count
+//   k_gt_matrix         the walk of k_af_genotypes (gki_vcf_gt.h's gt_walk_line) with stores in place of counts: one wave
+//                       per data line.  The lane that holds tab 9 + s parses sample s and stores its P codes at
+//                       codes[v][s P ..]; a good line has exactly S samples, so its lanes write the whole row between
+//                       them.  Whether the line is at fault is known after its last step: the wave then writes the row
+//                       again, all 3 (a wave-uniform branch behind a wait for the stores above).  Lane 0 stores
+//                       phased[v].  No atomics but that of the lowest line at fault.
 // once, over the rows of all pieces (gki_haplotype_planes):
 //   k_haplotype_planes  a workgroup takes a tile of 64 lines x PLANES_T slots: coalesced row reads, 16 bytes a lane, into
 //                       LDS rows padded by one dword (an odd number of dwords, so the 64 lanes that then read one dword
@@ -28,17 +27,6 @@ constexpr int PLANES_T = 256;                              // a tile's slots (vc
 constexpr int PLANES_ROW = PLANES_T + 4;                   // bytes of an LDS row: 65 dwords
 constexpr int PLANES_BLOCK = 256;
 constexpr uint32_t PLANES_NO_BIT = 0xFFFFFFFFu;
-
-// first_bad: (data line << 3 | kind) of the lowest line at fault, all ones when there is none (atomicMin)
-struct GtTotals { unsigned long long first_bad; };
-
-__global__ __launch_bounds__(PARSE_BLOCK) void k_gt_is_data(const uint8_t *__restrict__ bytes,
-                                                            const int64_t *__restrict__ line_end, int64_t n_lines,
-                                                            uint32_t *__restrict__ is_data) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_lines; i += stride)
-        is_data[i] = vcf_line(bytes, line_end, i).data ? 1u : 0u;
-}
 
 // what k_gt_matrix takes from a GT: the codes of its first eight alleles in text order, a byte each (0, 1, 2: any other
 // number, 3: '.'), how many alleles it has and whether a '/' separates two of them
@@ -58,14 +46,42 @@ struct GtCodes {
 
 constexpr int BAD_FORMAT = 1, BAD_GT = 2, TOO_MANY = 4, SLASH = 8;   // what a lane saw in its line, as bits
 
-// One wave per data line.  FORMAT is field 8 (opened by tab number 8), sample s is field 9 + s.  codes: uint8[n_variants][H],
-// H = n_samples * ploidy; the row's offset is formed in 64 bits.
+// what a lane of k_gt_matrix does with its line's fields (gt_walk_line's visitor): sample s goes to row[s P ..], and what
+// the lane saw is kept as bits
+struct MatrixLine {
+    const uint8_t *__restrict__ bytes;
+    int64_t n_bytes, e, n_samples;
+    int ploidy;
+    uint8_t *__restrict__ row;
+    int &seen;
+    __device__ __forceinline__ void format(bool ok) { seen |= ok ? 0 : BAD_FORMAT; }
+    __device__ __forceinline__ void sample(int64_t s, int64_t p) {
+        GtCodes c;
+        seen |= gt_at(bytes, n_bytes, p, e, &c) ? 0 : BAD_GT;
+        seen |= (c.n > ploidy ? TOO_MANY : 0) | (c.slashes ? SLASH : 0);
+        if (s < n_samples) {                               // a sample beyond S stores nothing: the line is at fault, kind 4
+            const uint64_t filled = c.filled();
+            uint8_t *__restrict__ at = row + s * ploidy;
+            switch (ploidy) {                              // one store a sample where P is a power of two, at any alignment
+            case 1: at[0] = (uint8_t)filled; break;
+            case 2: { const uint16_t two = (uint16_t)filled; __builtin_memcpy(at, &two, 2); } break;
+            case 4: { const uint32_t four = (uint32_t)filled; __builtin_memcpy(at, &four, 4); } break;
+            case 8: __builtin_memcpy(at, &filled, 8); break;
+            default:
+                for (int a = 0; a < ploidy; a++) at[a] = (uint8_t)(filled >> (8 * a));
+            }
+        }
+    }
+};
+
+// One wave per data line.  codes: uint8[n_variants][H], H = n_samples * ploidy; the row's offset is formed in 64 bits.
 __global__ __launch_bounds__(PARSE_BLOCK) void k_gt_matrix(const uint8_t *__restrict__ bytes, int64_t n_bytes,
                                                            const int64_t *__restrict__ line_end, int64_t n_lines,
                                                            const uint32_t *__restrict__ is_data,
                                                            const int64_t *__restrict__ variant_index, int64_t n_variants,
                                                            int64_t n_samples, int ploidy, uint8_t *__restrict__ codes,
-                                                           uint8_t *__restrict__ phased, GtTotals *__restrict__ totals) {
+                                                           uint8_t *__restrict__ phased,
+                                                           unsigned long long *__restrict__ first_bad) {
     const int lane = threadIdx.x & 63;
     const int64_t first = wave_uniform((int64_t)blockIdx.x * (PARSE_BLOCK / 64) + (threadIdx.x >> 6));
     const int64_t stride = (int64_t)gridDim.x * (PARSE_BLOCK / 64);
@@ -77,42 +93,8 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_gt_matrix(const uint8_t *__rest
         const VcfLine l = vcf_line(bytes, line_end, i);
         const int64_t b = wave_uniform(l.b), e = wave_uniform(l.e);
         uint8_t *__restrict__ row = codes + v * row_bytes;
-        int tabs_before = 0, seen = 0;
-        for (int64_t base = b; base < e; base += GT_STEP) {
-            const int64_t p0 = base + (int64_t)lane * PARSE_LANE_BYTES;
-            const uint4 in = line_bytes16(bytes, n_bytes, p0, e);
-            uint32_t tabs = line_tabs16(in, p0, e);
-            const int mine = __popc(tabs);
-            const int incl = gki_wave_incl_sum(mine);
-            int number = tabs_before + incl - mine;        // tabs of the line before this lane's first
-            tabs_before += gki_lane_value(incl, 63);
-            while (tabs) {
-                const int j = __ffs(tabs) - 1;
-                tabs &= tabs - 1;
-                number++;
-                const int64_t p = p0 + j + 1;              // the field tab `number` opens
-                if (number == 8)
-                    seen |= format_begins_with_gt(bytes, p, e) ? 0 : BAD_FORMAT;
-                else if (number >= 9) {
-                    GtCodes c;
-                    seen |= gt_at(bytes, n_bytes, p, e, &c) ? 0 : BAD_GT;
-                    seen |= (c.n > ploidy ? TOO_MANY : 0) | (c.slashes ? SLASH : 0);
-                    const int64_t s = number - 9;
-                    if (s < n_samples) {                   // a sample beyond S stores nothing: the line is at fault, kind 4
-                        const uint64_t filled = c.filled();
-                        uint8_t *__restrict__ at = row + s * ploidy;
-                        switch (ploidy) {                  // one store a sample where P is a power of two, at any alignment
-                        case 1: at[0] = (uint8_t)filled; break;
-                        case 2: { const uint16_t two = (uint16_t)filled; __builtin_memcpy(at, &two, 2); } break;
-                        case 4: { const uint32_t four = (uint32_t)filled; __builtin_memcpy(at, &four, 4); } break;
-                        case 8: __builtin_memcpy(at, &filled, 8); break;
-                        default:
-                            for (int a = 0; a < ploidy; a++) at[a] = (uint8_t)(filled >> (8 * a));
-                        }
-                    }
-                }
-            }
-        }
+        int seen = 0;
+        const int tabs_before = gt_walk_line(bytes, n_bytes, b, e, lane, MatrixLine{bytes, n_bytes, e, n_samples, ploidy, row, seen});
         // a line of fewer than 10 fields has no samples: at fault unless none is expected, and its FORMAT is not looked at
         seen = (__ballot(seen & BAD_FORMAT) ? BAD_FORMAT : 0) | (__ballot(seen & BAD_GT) ? BAD_GT : 0) |
                (__ballot(seen & TOO_MANY) ? TOO_MANY : 0) | (__ballot(seen & SLASH) ? SLASH : 0);
@@ -124,7 +106,7 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_gt_matrix(const uint8_t *__rest
             for (int64_t h = lane; h < row_bytes; h += 64) row[h] = 3;
         }
         if (lane == 0) {
-            if (kind) atomicMin(&totals->first_bad, (unsigned long long)v << 3 | (unsigned long long)kind);
+            if (kind) line_fault(first_bad, v, kind);
             phased[v] = kind == 0 && !(seen & SLASH) ? 1 : 0;
         }
     }
@@ -208,45 +190,24 @@ extern "C" int gki_vcf_haplotype_matrix(const void *d_text, int64_t n_bytes, int
         return gki_set_error(GKI_ERR_BAD_ARG, "vcf_haplotype_matrix: an output buffer is NULL");
     const uint8_t *bytes = (const uint8_t *)d_text;
     TimerEvents ev;
-    DevBuf line_end, is_data, variant_index, tmp, totals;
-    int64_t n_lines = 0, found = 0;
-    if (n_bytes > 0) {
-        GKI_TRY(gki_text_line_ends(bytes, n_bytes, "vcf_haplotype_matrix", line_end, &n_lines));
-        const int64_t tmp_bytes = gki_scan_tmp_bytes(n_lines);
-        HIP_TRY(is_data.alloc((size_t)n_lines * 4));
-        HIP_TRY(variant_index.alloc((size_t)(n_lines + 1) * 8));
-        HIP_TRY(tmp.alloc((size_t)tmp_bytes));
-        hipLaunchKernelGGL(k_gt_is_data, dim3(stream_grid(n_lines, PARSE_BLOCK)), dim3(PARSE_BLOCK), 0, 0, bytes,
-                           line_end.get<const int64_t>(), n_lines, is_data.get<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        GKI_TRY(gki_scan_u32_to_i64(is_data.get<const uint32_t>(), n_lines, variant_index.get<int64_t>(), tmp.get(), tmp_bytes, 0));
-        GKI_TRY(gki_scan_total(variant_index, n_lines, &found));
-    }
-    if (n_data_lines) *n_data_lines = found;
-    if (found != n_variants)
-        return gki_set_error(GKI_ERR_BAD_ARG, "vcf_haplotype_matrix: the text has %lld data lines, the caller expects %lld",
-                             (long long)found, (long long)n_variants);
-    if (found == 0) return GKI_OK;
-    HIP_TRY(totals.alloc(sizeof(GtTotals)));
-    const GtTotals none = {~0ull};
-    HIP_TRY(hipMemcpy(totals.get(), &none, sizeof(GtTotals), hipMemcpyHostToDevice));
-    HIP_TRY(hipEventCreate(&ev.e0));
-    HIP_TRY(hipEventCreate(&ev.e1));
-    HIP_TRY(hipEventRecord(ev.e0, 0));
-    hipLaunchKernelGGL(k_gt_matrix, dim3(stream_grid(n_lines, PARSE_BLOCK / 64)), dim3(PARSE_BLOCK), 0, 0, bytes, n_bytes,
-                       line_end.get<const int64_t>(), n_lines, is_data.get<const uint32_t>(),
-                       variant_index.get<const int64_t>(), n_variants, n_samples, ploidy, (uint8_t *)d_codes,
-                       (uint8_t *)d_phased, totals.get<GtTotals>());
+    VcfDataLines d;
+    DevBuf totals;
+    if (n_bytes > 0) GKI_TRY(gki_vcf_data_lines(bytes, n_bytes, "vcf_haplotype_matrix", d));
+    if (n_data_lines) *n_data_lines = d.n_data;
+    GKI_TRY(gki_vcf_expect_data_lines("vcf_haplotype_matrix", d.n_data, n_variants));
+    if (n_variants == 0) return GKI_OK;
+    GKI_TRY(line_fault_init(totals));
+    GKI_TRY(ev.start(0));
+    hipLaunchKernelGGL(k_gt_matrix, dim3(stream_grid(d.n_lines, PARSE_BLOCK / 64)), dim3(PARSE_BLOCK), 0, 0, bytes, n_bytes,
+                       d.line_end.get<const int64_t>(), d.n_lines, d.is_data.get<const uint32_t>(),
+                       d.variant_index.get<const int64_t>(), n_variants, n_samples, ploidy, (uint8_t *)d_codes,
+                       (uint8_t *)d_phased, totals.get<unsigned long long>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev.e1, 0));
-    HIP_TRY(hipStreamSynchronize(0));
-    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, ev.e0, ev.e1));
-    GtTotals t;
-    HIP_TRY(hipMemcpy(&t, totals.get(), sizeof(GtTotals), hipMemcpyDeviceToHost));
-    if (t.first_bad != ~0ull) {
-        if (first_bad_variant) *first_bad_variant = (int64_t)(t.first_bad >> 3);
-        if (first_bad_kind) *first_bad_kind = (int)(t.first_bad & 7);
-    }
+    GKI_TRY(ev.stop(0, kernel_ms));
+    LineFault fault;
+    GKI_TRY(line_fault_read(totals, &fault));
+    if (first_bad_variant) *first_bad_variant = fault.line();
+    if (first_bad_kind) *first_bad_kind = fault.kind();
     return GKI_OK;
 }
 
@@ -261,15 +222,10 @@ extern "C" int gki_haplotype_planes(const void *d_codes, int64_t n_variants, int
         return gki_set_error(GKI_ERR_BAD_ARG, "haplotype_planes: a buffer is NULL");
     const int64_t n_words = ceil_div(n_variants, PLANES_LINES), slot_tiles = ceil_div(n_slots, PLANES_T);
     TimerEvents ev;
-    HIP_TRY(hipEventCreate(&ev.e0));
-    HIP_TRY(hipEventCreate(&ev.e1));
-    HIP_TRY(hipEventRecord(ev.e0, 0));
+    GKI_TRY(ev.start(0));
     hipLaunchKernelGGL(k_haplotype_planes, dim3(stream_grid(n_words * slot_tiles, 1)), dim3(PLANES_BLOCK), 0, 0,
                        (const uint8_t *)d_codes, n_variants, n_slots, n_words, slot_tiles, (uint64_t *)d_ref_bits,
                        (uint64_t *)d_alt_bits);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev.e1, 0));
-    HIP_TRY(hipStreamSynchronize(0));
-    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, ev.e0, ev.e1));
-    return GKI_OK;
+    return ev.stop(0, kernel_ms);
 }

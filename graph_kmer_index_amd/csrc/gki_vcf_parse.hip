@@ -19,8 +19,8 @@
 
 namespace {
 
-// first_bad: (line << 2 | kind) of the lowest bad line, all ones when there is none (atomicMin)
-struct VcfTotals { unsigned long long first_bad; unsigned int too_long; unsigned int pad; };
+// beside the lowest bad line (a line of the text, not a data line; kinds 1 and 2), too_long: a CHROM of 2^32 bytes or more
+struct VcfTotals : LineFault { unsigned int too_long = 0, pad = 0; };
 
 // One lane per line, by the rules of gki_text_lines.h (vcf_line, vcf_fields, vcf_pos_value).  is_data[i];
 // for a data line pos[i], snp[i], and CHROM as bytes [chrom_begin[i], chrom_begin[i] + chrom_len[i]).
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_vcf_classify(const uint8_t *__r
         const VcfFields f = vcf_fields(bytes, l.b, l.e);
         int64_t value = 0, len0 = f.len(0);
         const int kind = f.n < 2 ? 1 : !vcf_pos_value(bytes, f.begin(1), f.end[1], &value) ? 2 : 0;
-        if (kind) atomicMin(&totals->first_bad, (unsigned long long)i << 2 | (unsigned long long)kind);
+        if (kind) line_fault(&totals->first_bad, i, kind);
         if (len0 > 0xFFFFFFFFll) { atomicOr(&totals->too_long, 1u); len0 = 0; }
         pos[i] = value;
         snp[i] = f.n < VCF_FIELDS ? (int8_t)-1 : (int8_t)(f.len(3) == 1 && f.len(4) == 1);
@@ -136,9 +136,7 @@ int vcf_parse(const uint8_t *bytes, int64_t n, VcfPlan &p) {
     HIP_TRY(p.chrom_len.alloc((size_t)n_lines * 4));
     HIP_TRY(p.variant_index.alloc((size_t)(n_lines + 1) * 8));
     HIP_TRY(p.tmp.alloc((size_t)gki_scan_tmp_bytes(n_lines)));
-    HIP_TRY(p.totals.alloc(sizeof(VcfTotals)));
-    const VcfTotals none = {~0ull, 0u, 0u};
-    HIP_TRY(hipMemcpy(p.totals.get(), &none, sizeof(VcfTotals), hipMemcpyHostToDevice));
+    GKI_TRY(line_fault_init<VcfTotals>(p.totals));
     hipLaunchKernelGGL(k_vcf_classify, dim3(stream_grid(n_lines, PARSE_BLOCK)), dim3(PARSE_BLOCK), 0, 0, bytes,
                        p.line_end.get<const int64_t>(), n_lines, p.is_data.get<uint32_t>(), p.pos.get<int64_t>(),
                        p.snp.get<int8_t>(), p.chrom_begin.get<int64_t>(), p.chrom_len.get<uint32_t>(),
@@ -148,13 +146,13 @@ int vcf_parse(const uint8_t *bytes, int64_t n, VcfPlan &p) {
                                 gki_scan_tmp_bytes(n_lines), 0));
     VcfTotals totals;
     GKI_TRY(gki_scan_total(p.variant_index, n_lines, &p.n_variants));
-    HIP_TRY(hipMemcpy(&totals, p.totals.get(), sizeof(VcfTotals), hipMemcpyDeviceToHost));
+    GKI_TRY(line_fault_read(p.totals, &totals));
     p.line_end.reset();
     if (totals.too_long) return gki_set_error(GKI_ERR_BAD_ARG, "vcf_parse: a CHROM of 2^32 bytes or more");
     p.n_lines = n_lines;
-    if (totals.first_bad != ~0ull) {
-        GKI_TRY(gki_scan_total(p.variant_index, (int64_t)(totals.first_bad >> 2), &p.first_bad_variant));
-        p.first_bad_kind = (int)(totals.first_bad & 3);
+    if (totals.line() >= 0) {                              // the data lines before the bad line: its number among them
+        GKI_TRY(gki_scan_total(p.variant_index, totals.line(), &p.first_bad_variant));
+        p.first_bad_kind = totals.kind();
     }
     if (p.n_variants == 0) return GKI_OK;
 

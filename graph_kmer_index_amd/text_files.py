@@ -8,8 +8,10 @@ serial DEFLATE stream and is read through Python's gzip module: that route is bo
 
 `text_pieces` gives a file's source of pieces: `host_text_pieces` (raw and host gzip) or `bgzf_text_pieces`, generators of
 (text on the device, bytes of it that are whole lines) built from the step functions `upload_piece`, `inflate_piece` and
-`cut_at_line_end`.  `device_bytes` takes a buffer that is in memory already; `names_from` decodes the parsers' name lists.
+`cut_at_line_end`; `owned_pieces` is the same source for a consumer that is one loop and leaves the pieces' lifetime to it.
+`device_bytes` takes a buffer that is in memory already; `names_from` decodes the parsers' name lists.
 """
+import contextlib
 import ctypes as C
 import gzip
 import numpy as np
@@ -223,3 +225,14 @@ def text_pieces(file_name, chunk_bytes=None, inflate="auto"):
         raise ValueError("%s is not a BGZF file: only BGZF is inflated on the device" % file_name)
     source = bgzf_text_pieces if route == "bgzf-device" and inflate != "host" else host_text_pieces
     return source(file_name, DEFAULT_CHUNK_BYTES if chunk_bytes is None else chunk_bytes)
+
+
+def owned_pieces(file_name, chunk_bytes=None, inflate="auto"):
+    """`text_pieces` for a consumer that is one loop: yields (text, n_bytes), holds each text in a DeviceScope of its own
+    for the one iteration that uses it, and closes the source when the loop is left, at its end or by an exception (which
+    closes this generator at its yield)."""
+    with contextlib.closing(text_pieces(file_name, chunk_bytes, inflate)) as pieces:
+        for text, n_bytes in pieces:
+            with _lib.DeviceScope() as s:
+                s.keep(text)
+                yield text, n_bytes

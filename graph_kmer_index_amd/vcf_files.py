@@ -1,6 +1,6 @@
 """VCF files on the device: .vcf and BGZF .vcf.gz text -> VariantArrays, without a host pass over the lines.
 
-The text reaches HBM as the reads files' does -- `text_files.text_pieces`: pieces that end at a line end, a BGZF file
+The text reaches HBM as the reads files' does -- `text_files.owned_pieces`: pieces that end at a line end, a BGZF file
 inflated on the device -- and gki_vcf_parse_count / _emit (csrc/gki_vcf_parse.hip) turn each piece into POS, is_snp and
 the chromosome of every data line, the chromosomes as runs of equal names.  The rules are stated in include/gki.h ("VCF
 files") and DESIGN.md 4.14; they give what `VariantArrays.from_vcf` gives wherever that returns, except that POS must be
@@ -19,13 +19,12 @@ per sample haplotype and data line, and on request the same as two bit planes (g
 gki_haplotype_planes, csrc/gki_vcf_gt.hip; include/gki.h "VCF haplotype matrix").  `MatrixPieces` appends
 the pieces' rows on the device; the number of sample columns comes from the text in front of the first data line.
 """
-import contextlib
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
-from .text_files import DEFAULT_CHUNK_BYTES, device_bytes, names_from, text_pieces
+from .text_files import DEFAULT_CHUNK_BYTES, device_bytes, names_from, owned_pieces
 
 BAD_TEXT = {1: "VCF data line %d has fewer than two columns",          # VariantArrays.from_vcf's own message
             2: "VCF data line %d: POS must be 1 to 18 plain digits (no sign, blank or underscore) for the device parser"}
@@ -46,6 +45,11 @@ class AlleleFrequencyError(ValueError):
     def __init__(self, line, kind):
         super().__init__("VCF data line %d: %s" % (line, AF_KIND_TEXT[kind]))
         self.line, self.kind = int(line), kind
+
+
+def cat(parts, dtype):
+    """The pieces' host arrays as one, an empty one of `dtype` when there is no piece."""
+    return np.concatenate(parts) if parts else np.zeros(0, dtype)
 
 
 def bad_line_error(data_line, kind):
@@ -120,8 +124,6 @@ class VariantPieces:
     def variant_arrays(self):
         from .unique_variant_kmers import VariantArrays
 
-        def cat(parts, dtype):
-            return np.concatenate(parts) if parts else np.zeros(0, dtype)
         run_of_variant = cat(self.run_of_variant, np.int64)
         chromosomes = np.array(self.run_names, dtype=object)[run_of_variant]
         return VariantArrays(cat(self.positions, np.int64), chromosomes, np.arange(self.n_variants),
@@ -135,15 +137,12 @@ def variant_arrays_from_file(file_name, chunk_bytes=DEFAULT_CHUNK_BYTES, inflate
     file."""
     _lib.require_device()
     joined = VariantPieces()
-    source = text_pieces(file_name, chunk_bytes, inflate)
-    with contextlib.closing(source) as pieces:
-        for text, n_bytes in pieces:
-            with _lib.DeviceScope() as s:
-                s.keep(text)
-                out, bad = parse_piece(s, text, n_bytes)
-            if bad is not None:
-                raise bad_line_error(joined.n_variants + bad[0], bad[1])
-            joined.add(*out)
+    for text, n_bytes in owned_pieces(file_name, chunk_bytes, inflate):
+        with _lib.DeviceScope() as s:
+            out, bad = parse_piece(s, text, n_bytes)
+        if bad is not None:
+            raise bad_line_error(joined.n_variants + bad[0], bad[1])
+        joined.add(*out)
     return joined.variant_arrays()
 
 
@@ -210,8 +209,6 @@ class _AfPieces:
         self.n_variants += nv
 
     def arrays(self):
-        def cat(parts, dtype):
-            return np.concatenate(parts) if parts else np.zeros(0, dtype)
         return cat(self.ref_af, np.float64), cat(self.alt_af, np.float64), cat(self.route, np.uint8)
 
 
@@ -236,11 +233,8 @@ def allele_frequencies_from_file(file_name, source, chunk_bytes=DEFAULT_CHUNK_BY
     _lib.require_device()
     af_source_code(source)
     joined = _AfPieces()
-    with contextlib.closing(text_pieces(file_name, chunk_bytes, inflate)) as pieces:
-        for text, n_bytes in pieces:
-            with _lib.DeviceScope() as s:
-                s.keep(text)
-                joined.add_piece(text, n_bytes, source)
+    for text, n_bytes in owned_pieces(file_name, chunk_bytes, inflate):
+        joined.add_piece(text, n_bytes, source)
     return joined.arrays()
 
 
@@ -453,9 +447,6 @@ def haplotype_matrix_from_file(file_name, ploidy=2, n_samples=None, chunk_bytes=
     _lib.require_device()
     with _lib.DeviceScope() as s:
         joined = MatrixPieces(s, ploidy, n_samples)
-        with contextlib.closing(text_pieces(file_name, chunk_bytes, inflate)) as pieces:
-            for text, n_bytes in pieces:
-                with _lib.DeviceScope() as t:
-                    t.keep(text)
-                    joined.add_piece(text, n_bytes)
+        for text, n_bytes in owned_pieces(file_name, chunk_bytes, inflate):
+            joined.add_piece(text, n_bytes)
         return joined.finish()

@@ -8,7 +8,7 @@ from codegen_asm import _bodies, _metadata, _of, asm_of, needs_hipcc
 pytestmark = needs_hipcc
 # kernel -> (VGPRs, LDS bytes) of the build this was written against; the three prefix-maximum kernels hold one int64 per
 # lane in LDS
-FOOTPRINT = {"k_gb_is_data": (9, 0), "k_gb_sites": (40, 0), "k_gb_copy_alt": (18, 0), "k_gb_tile_max": (16, 2048),
+FOOTPRINT = {"k_gb_sites": (40, 0), "k_gb_copy_alt": (18, 0), "k_gb_tile_max": (16, 2048),
              "k_gb_scan_tiles": (16, 2048), "k_gb_keep": (16, 2048), "k_gb_compact": (24, 0), "k_gb_site_counts": (23, 0),
              "k_gb_emit_whole": (26, 0), "k_gb_emit_nodes": (56, 0), "k_gb_tile_sites": (14, 0), "k_gb_sequence": (102, 0)}
 asm = asm_of("gki_graph_build")

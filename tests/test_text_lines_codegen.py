@@ -1,4 +1,4 @@
-"""The line-end kernels of the text parsers (csrc/gki_text_lines.hip) compiled for gfx950: every kernel present, no scratch,
+"""The line-end kernels of the text parsers and the VCF passes' data-line kernel (csrc/gki_text_lines.hip) compiled for gfx950: every kernel present, no scratch,
 no FLAT memory instruction, and the register and LDS footprints at what the build gives, as upper bounds.  CPU only: hipcc
 cross-compiles."""
 import re
@@ -7,7 +7,7 @@ from codegen_asm import _bodies, _metadata, _of, asm_of, needs_hipcc
 
 pytestmark = needs_hipcc
 # kernel -> (VGPRs, LDS bytes) of the build this was written against: the two tile kernels keep one int per wave in LDS
-FOOTPRINT = {"k_parse_count_newlines": (14, 16), "k_parse_line_ends": (14, 16)}
+FOOTPRINT = {"k_parse_count_newlines": (14, 16), "k_parse_line_ends": (14, 16), "k_vcf_is_data": (9, 0)}
 asm = asm_of("gki_text_lines")
 
 

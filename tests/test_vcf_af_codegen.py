@@ -7,7 +7,7 @@ from codegen_asm import _bodies, _metadata, _of, asm_of, needs_hipcc
 
 pytestmark = needs_hipcc
 # kernel -> (VGPRs, LDS bytes) of the build this was written against: none of them uses LDS
-FOOTPRINT = {"k_af_is_data": (9, 0), "k_af_info": (36, 0), "k_af_genotypes": (58, 0)}
+FOOTPRINT = {"k_af_info": (36, 0), "k_af_genotypes": (58, 0)}
 asm = asm_of("gki_vcf_af")
 
 

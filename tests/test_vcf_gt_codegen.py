@@ -8,7 +8,7 @@ import re
 from codegen_asm import ROOT, _bodies, _metadata, _of, asm_of, needs_hipcc
 
 pytestmark = needs_hipcc
-KERNELS = ("k_gt_is_data", "k_gt_matrix", "k_haplotype_planes")
+KERNELS = ("k_gt_matrix", "k_haplotype_planes")
 MATRIX_MAX_VGPRS = 64
 PLANES_LINES = 64                                          # a tile's lines; its slots are vcf_files.PLANES_TILE_SLOTS
 asm = asm_of("gki_vcf_gt")
