@@ -7,6 +7,7 @@
 //   k_count_scatter   stable scatter of one tile: ballot ranking per wave, the tile sorted by digit in LDS, then runs of
 //                     equal digits stored to consecutive positions.  Key only; least significant digit first; the first
 //                     pass reads the caller's array at the caller's stride, so the input is read in place and never written
+//                     (both kernels are the pass of gki_radix_tile.h over KeyItems)
 //   k_run_count       per tile of the sorted keys: the number of run heads (key != predecessor); their scan gives n_unique
 //   k_run_emit        per tile: every head's rank from ballots and the tile's scanned start -> its key and its position
 //   k_run_lengths     count of run r = position of head r + 1 (or the number of keys) - position of head r: a run may span
@@ -17,6 +18,7 @@
 //
 // Launches per pass are histogram -> scan -> scatter: no workgroup ever waits for another one.
 #include "gki_frequency.h"
+#include "gki_radix_tile.h"
 #include <memory>
 
 // What the count call leaves for the emit call: the sorted keys and the scanned heads per tile.
@@ -31,105 +33,32 @@ namespace {
 constexpr int CB = 256;              // threads per block
 constexpr int CI = 16;               // keys per thread
 constexpr int CT = CB * CI;          // 4096 keys per tile (graph_kmer_index_amd/kmer_counter.py SORT_TILE)
-constexpr int CBINS = 256;
-static_assert(CB == CBINS, "one thread per digit in the scatter's digit scan");
+constexpr int CBINS = RADIX_BINS;
 static_assert(CI * (CB / 64) == 64, "k_run_emit scans its (round, wave) partial counts with one wave");
+
+// The keys as the items of gki_radix_tile.h's pass: read at a stride (the caller's, in the first pass), written densely;
+// tile offsets are 64 bits wide (up to 2^33 keys)
+struct KeyItems {
+    using Offset = int64_t;
+    const uint64_t *__restrict__ in; int64_t stride; uint64_t *__restrict__ out;
+    __device__ __forceinline__ uint64_t load_key(int64_t i) const { return in[i * stride]; }
+    __device__ __forceinline__ uint64_t load(int64_t i) const { return in[i * stride]; }
+    __device__ __forceinline__ void store(int64_t i, uint64_t key) const { out[i] = key; }
+    static __device__ __forceinline__ uint32_t digit(uint64_t key, int shift) { return (uint32_t)(key >> shift) & 0xFF; }
+};
 
 // `bad` is set when a key has a bit at or above key_bits (checked in the first pass only: key_bits == 0 skips it)
 __global__ __launch_bounds__(CB) void k_count_hist(const uint64_t *__restrict__ keys, int64_t m, int64_t stride, int shift,
                                                    int key_bits, uint32_t *__restrict__ hist, int64_t n_tiles,
                                                    int *__restrict__ bad) {
-    __shared__ uint32_t h[CBINS];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const int64_t base = (int64_t)blockIdx.x * CT;
-    uint64_t acc = 0;
-#pragma unroll
-    for (int r = 0; r < CI; r++) {
-        const int64_t i = base + r * CB + threadIdx.x;
-        if (i < m) {
-            const uint64_t key = keys[i * stride];
-            acc |= key;
-            atomicAdd(&h[(key >> shift) & 0xFF], 1u);
-        }
-    }
+    const uint64_t acc = radix_tile_hist<CB, CI>(KeyItems{keys, stride, nullptr}, m, shift, hist, n_tiles);
     if (key_bits > 0 && key_bits < 64 && (acc >> key_bits) != 0ull) atomicOr(bad, 1);
-    __syncthreads();
-    hist[(int64_t)threadIdx.x * n_tiles + blockIdx.x] = h[threadIdx.x];
 }
 
-// Stable scatter of one tile.  Element order inside a tile is (wave, round, lane): wave w owns the contiguous slice
-// [w * 1024, (w + 1) * 1024) of the tile, round r its r-th group of 64.
 __global__ __launch_bounds__(CB) void k_count_scatter(const uint64_t *__restrict__ keys_in, int64_t m, int64_t stride,
                                                       int shift, const int64_t *__restrict__ offs /* scanned hist */,
                                                       int64_t n_tiles, uint64_t *__restrict__ keys_out) {
-    __shared__ uint32_t wave_cnt[4][CBINS];     // per wave, per digit: running count, then exclusive offset
-    __shared__ uint32_t digit_start[CBINS];     // start of each digit's run in the locally sorted tile
-    __shared__ uint32_t wsum[4];
-    __shared__ uint64_t s_keys[CT];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = threadIdx.x; i < 4 * CBINS; i += CB) (&wave_cnt[0][0])[i] = 0;
-    __syncthreads();
-    const int64_t tile_base = (int64_t)blockIdx.x * CT;
-    const int64_t wave_base = tile_base + (int64_t)wave * (CT / 4);
-    uint64_t key[CI];
-    uint32_t rank[CI];
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int r = 0; r < CI; r++) {
-        const int64_t i = wave_base + r * 64 + lane;
-        const bool valid = i < m;
-        key[r] = valid ? keys_in[i * stride] : ~0ull;
-        const uint32_t d = valid ? (uint32_t)((key[r] >> shift) & 0xFF) : 0x100u;      // 0x100: matches no real digit
-        // lanes of this wave with the same digit (8 ballots) -> rank among them, group size
-        uint64_t same = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            const uint64_t bit = __ballot((d >> b) & 1u);
-            same &= ((d >> b) & 1u) ? bit : ~bit;
-        }
-        const uint32_t before = (uint32_t)__popcll(same & lt_mask);
-        uint32_t prev = 0;
-        if (valid) prev = wave_cnt[wave][d];              // all lanes of the group read the same value ...
-        rank[r] = prev + before;
-        // ... then the group's first lane publishes the new count (rounds are sequential per wave)
-        if (valid && before == 0) wave_cnt[wave][d] = prev + (uint32_t)__popcll(same);
-        __builtin_amdgcn_wave_barrier();
-    }
-    __syncthreads();
-    // per digit: exclusive offsets over waves, and the digit's start in the locally sorted tile
-    {
-        const int d = threadIdx.x;
-        const uint32_t c0 = wave_cnt[0][d], c1 = wave_cnt[1][d], c2 = wave_cnt[2][d], c3 = wave_cnt[3][d];
-        wave_cnt[0][d] = 0; wave_cnt[1][d] = c0; wave_cnt[2][d] = c0 + c1; wave_cnt[3][d] = c0 + c1 + c2;
-        const uint32_t tot = c0 + c1 + c2 + c3;
-        const uint32_t inc = gki_wave_incl_sum(tot);      // exclusive scan of tot over the 256 digits (4 waves of 64)
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        uint32_t woff = 0;
-        for (int w = 0; w < wave; w++) woff += wsum[w];
-        digit_start[d] = woff + inc - tot;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < CI; r++) {
-        const int64_t i = wave_base + r * 64 + lane;
-        if (i < m) {
-            const uint32_t d = (uint32_t)((key[r] >> shift) & 0xFF);
-            s_keys[digit_start[d] + wave_cnt[wave][d] + rank[r]] = key[r];
-        }
-    }
-    __syncthreads();
-    const int64_t n_here = (m - tile_base) < CT ? (m - tile_base) : CT;
-#pragma unroll
-    for (int r = 0; r < CI; r++) {
-        const int p = r * CB + threadIdx.x;
-        if (p < n_here) {
-            const uint64_t k = s_keys[p];
-            const uint32_t d = (uint32_t)((k >> shift) & 0xFF);
-            keys_out[offs[(int64_t)d * n_tiles + blockIdx.x] + (int64_t)(p - digit_start[d])] = k;
-        }
-    }
+    radix_tile_scatter<CB, CI>(KeyItems{keys_in, stride, keys_out}, m, shift, offs, n_tiles);
 }
 
 // heads of a tile of the sorted keys: element order (round, thread), i.e. the keys' own order

@@ -9,14 +9,16 @@
 //                         k_sort_keys (key of every record + the identity permutation), a stable LSD radix sort of the
 //                         (key, index) pairs, 8 bits per pass, only the bits the largest key occupies (per pass: tile
 //                         histograms -> scan -> ranked scatter with an in-LDS reorder so every digit's run leaves the CU as one
-//                         contiguous store), k_pack_rows / k_gather_rows (the payload packed into 16- or 32-byte rows,
-//                         permuted once by the sorted index), k_directory / k_node_directory
+//                         contiguous store: the pass of gki_radix_tile.h over PairItems), k_pack_rows / k_gather_rows (the
+//                         payload packed into 16- or 32-byte rows, permuted once by the sorted index), k_directory /
+//                         k_node_directory
 //   frequencies           k_frequencies_small for the pair-sorting form; k_frequencies_ranges + k_frequencies_large for the
 //                         buckets of more than SMALL_BUCKET records that either form leaves open
 //   the lookups           k_lookup, k_count_nodes, k_get_small
 // Inside a bucket records keep their input order (stable sort), which is also what the oracle's
 // stable restatement produces, so the build is comparable element by element.
 #include "gki_index_internal.h"
+#include "gki_radix_tile.h"
 #include <cstring>
 #include <cstdlib>
 #include <mutex>
@@ -26,7 +28,7 @@ namespace {
 constexpr int RB = 256;             // threads per block in the radix kernels
 constexpr int RI = 16;              // items per thread
 constexpr int RTILE = RB * RI;      // 4096 items per tile
-constexpr int RBINS = 256;
+constexpr int RBINS = RADIX_BINS;
 
 // The sort key of every record and the identity permutation: the bucket relative to the slice (collision_free_kmer_index.py:433)
 // or, BY_NODE, the node id with sl.n_buckets = the number of nodes.  A key outside the slice is flagged and replaced by one
@@ -43,104 +45,31 @@ __global__ __launch_bounds__(256) void k_sort_keys(const void *__restrict__ src,
     }
 }
 
+// The (key, index) pairs as the items of gki_radix_tile.h's pass: two u32 arrays in memory, one 8-byte item (the key in its
+// low half) in registers and LDS; tile offsets are 32 bits wide (fewer than 2^32 records)
+struct PairItems {
+    using Offset = uint32_t;
+    const uint32_t *__restrict__ keys_in, *__restrict__ vals_in;
+    uint32_t *__restrict__ keys_out, *__restrict__ vals_out;
+    __device__ __forceinline__ uint64_t load_key(int64_t i) const { return keys_in[i]; }
+    __device__ __forceinline__ uint64_t load(int64_t i) const { return (uint64_t)keys_in[i] | ((uint64_t)vals_in[i] << 32); }
+    __device__ __forceinline__ void store(int64_t i, uint64_t item) const { keys_out[i] = (uint32_t)item; vals_out[i] = (uint32_t)(item >> 32); }
+    static __device__ __forceinline__ uint32_t digit(uint64_t item, int shift) { return ((uint32_t)item >> shift) & 0xFF; }
+};
+
 // histogram of one 8-bit digit per tile, stored bin-major: hist[bin * n_tiles + tile]
 __global__ __launch_bounds__(RB) void k_radix_hist(const uint32_t *__restrict__ keys, int64_t n, int shift,
                                                    uint32_t *__restrict__ hist, int64_t n_tiles) {
-    __shared__ uint32_t h[RBINS];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const int64_t base = (int64_t)blockIdx.x * RTILE;
-#pragma unroll
-    for (int r = 0; r < RI; r++) {
-        int64_t i = base + r * RB + threadIdx.x;
-        if (i < n) atomicAdd(&h[(keys[i] >> shift) & 0xFF], 1u);
-    }
-    __syncthreads();
-    hist[(int64_t)threadIdx.x * n_tiles + blockIdx.x] = h[threadIdx.x];
+    radix_tile_hist<RB, RI>(PairItems{keys, nullptr, nullptr, nullptr}, n, shift, hist, n_tiles);
 }
 
-// Stable scatter of one tile.  Element order inside a tile is (wave, round, lane): wave w owns the
-// contiguous slice [w*1024, (w+1)*1024) of the tile, round r its r-th group of 64.
+// stable scatter of one tile
 __global__ __launch_bounds__(RB) void k_radix_scatter(const uint32_t *__restrict__ keys_in,
                                                       const uint32_t *__restrict__ vals_in, int64_t n, int shift,
                                                       const uint32_t *__restrict__ offs /* scanned hist */,
                                                       int64_t n_tiles, uint32_t *__restrict__ keys_out,
                                                       uint32_t *__restrict__ vals_out) {
-    __shared__ uint32_t wave_cnt[4][RBINS];     // per wave, per digit: running count, then exclusive offset
-    __shared__ uint32_t digit_start[RBINS];     // start of each digit's run in the locally sorted tile
-    __shared__ uint32_t s_keys[RTILE];
-    __shared__ uint32_t s_vals[RTILE];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = threadIdx.x; i < 4 * RBINS; i += RB) (&wave_cnt[0][0])[i] = 0;
-    __syncthreads();
-    const int64_t tile_base = (int64_t)blockIdx.x * RTILE;
-    const int64_t wave_base = tile_base + (int64_t)wave * (RTILE / 4);
-    uint32_t key[RI], val[RI], rank[RI];
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int r = 0; r < RI; r++) {
-        const int64_t i = wave_base + r * 64 + lane;
-        const bool valid = i < n;
-        key[r] = valid ? keys_in[i] : 0xFFFFFFFFu;
-        val[r] = valid ? vals_in[i] : 0u;
-        const uint32_t d = valid ? ((key[r] >> shift) & 0xFF) : 0x100u;     // 0x100: matches no real digit
-        // lanes of this wave with the same digit (8 ballots) -> rank among them, group size
-        uint64_t same = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            const uint64_t bit = __ballot((d >> b) & 1u);
-            same &= ((d >> b) & 1u) ? bit : ~bit;
-        }
-        const uint32_t before = (uint32_t)__popcll(same & lt_mask);
-        uint32_t prev = 0;
-        if (valid) {
-            prev = wave_cnt[wave][d];                     // all lanes of the group read the same value ...
-        }
-        rank[r] = prev + before;
-        // ... then the group's first lane publishes the new count (rounds are sequential per wave)
-        if (valid && before == 0) wave_cnt[wave][d] = prev + (uint32_t)__popcll(same);
-        __builtin_amdgcn_wave_barrier();
-    }
-    __syncthreads();
-    // per digit: exclusive offsets over waves, and the digit's start in the locally sorted tile
-    {
-        const int d = threadIdx.x;       // RB == RBINS
-        uint32_t c0 = wave_cnt[0][d], c1 = wave_cnt[1][d], c2 = wave_cnt[2][d], c3 = wave_cnt[3][d];
-        wave_cnt[0][d] = 0; wave_cnt[1][d] = c0; wave_cnt[2][d] = c0 + c1; wave_cnt[3][d] = c0 + c1 + c2;
-        const uint32_t tot = c0 + c1 + c2 + c3;
-        // exclusive scan of tot over the 256 digits (4 waves of 64)
-        const uint32_t inc = gki_wave_incl_sum(tot);
-        __shared__ uint32_t wsum[4];
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        uint32_t woff = 0;
-        for (int w = 0; w < wave; w++) woff += wsum[w];
-        digit_start[d] = woff + inc - tot;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RI; r++) {
-        const int64_t i = wave_base + r * 64 + lane;
-        if (i < n) {
-            const uint32_t d = (key[r] >> shift) & 0xFF;
-            const uint32_t pos = digit_start[d] + wave_cnt[wave][d] + rank[r];
-            s_keys[pos] = key[r];
-            s_vals[pos] = val[r];
-        }
-    }
-    __syncthreads();
-    const int64_t n_here = (n - tile_base) < RTILE ? (n - tile_base) : RTILE;
-#pragma unroll
-    for (int r = 0; r < RI; r++) {
-        const int p = r * RB + threadIdx.x;
-        if (p < n_here) {
-            const uint32_t k = s_keys[p];
-            const uint32_t d = (k >> shift) & 0xFF;
-            const int64_t dst = (int64_t)offs[(int64_t)d * n_tiles + blockIdx.x] + (p - digit_start[d]);
-            keys_out[dst] = k;
-            vals_out[dst] = s_vals[p];
-        }
-    }
+    radix_tile_scatter<RB, RI>(PairItems{keys_in, vals_in, keys_out, vals_out}, n, shift, offs, n_tiles);
 }
 
 // Payload permutation.  Gathering four columns by a random index costs four random 64-byte sectors per record

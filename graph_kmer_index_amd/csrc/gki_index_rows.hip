@@ -31,6 +31,7 @@
 // Stability: every pass keeps equal digits in input order and the in-LDS sort ranks equal buckets by row position, so
 // the result equals the first form's (and the oracle's stable build) element by element.
 #include "gki_index_internal.h"
+#include "gki_radix_tile.h"
 #include <math.h>
 #include <vector>
 
@@ -230,45 +231,6 @@ __global__ __launch_bounds__(THREADS) void k_digit_hist(const uint32_t *__restri
     count_digits<THREADS, RI>(sp, shift, bits, h, hist, [&](int r, bool) { return key[r]; });
 }
 
-// Exclusive scan of v over the THREADS threads of the block (lds: THREADS / 64 + 1 words)
-template <int THREADS>
-__device__ __forceinline__ uint32_t block_excl(uint32_t v, uint32_t *lds, uint32_t *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t inc = gki_wave_incl_sum(v);
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < THREADS / 64; w++) { const uint32_t c = lds[w]; if (w < wave) woff += c; tot += c; }
-    __syncthreads();
-    *total = tot;
-    return woff + inc - v;
-}
-
-// Rank of every element among the earlier elements of its wave with the same digit, and the wave's digit counts.
-// Element order inside a tile is (wave, round, lane): wave w owns a contiguous slice, round r its r-th group of 64.
-template <int RI>
-__device__ __forceinline__ void wave_rank(const uint32_t (&dig)[RI], const bool (&valid)[RI], int bits, uint16_t *wcnt /* this wave's [bins] */,
-                                          uint32_t (&rank)[RI]) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int r = 0; r < RI; r++) {
-        const uint32_t d = dig[r];
-        uint64_t same = __ballot(valid[r]);
-        for (int b = 0; b < bits; b++) {
-            const uint64_t bit = __ballot((d >> b) & 1u);
-            same &= ((d >> b) & 1u) ? bit : ~bit;
-        }
-        const uint32_t before = (uint32_t)__popcll(same & lt_mask);
-        uint32_t prev = 0;
-        if (valid[r]) prev = wcnt[d];                       // all lanes of the group read the same value ...
-        rank[r] = prev + before;
-        if (valid[r] && before == 0) wcnt[d] = (uint16_t)(prev + (uint32_t)__popcll(same));   // ... then its first lane publishes
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
 // ------------------------------------------------------------------------------------ the front end of a partition pass
 // What k_partition_rows and k_partition_rows_staged do alike, up to every row's slot in the sorted tile.  The LDS arrays
 // are the kernels' (their sizes and what they lie under differ) and are handed in.
@@ -331,47 +293,9 @@ __device__ __forceinline__ void tile_keys(const PartArgs &a, const uint32_t *s_p
         dig[r] = (sort_key >> a.shift) & mask;
     }
 }
-// (2) ranks inside the wave, digit counts per wave (s_wcnt[W][MAXB], zeroed a barrier ago); (3) per digit: exclusive offsets
-// over the waves (left in s_wcnt), the digit's start in the sorted tile (s_dstart) and, by run_to(digit, that start), where
-// its run goes.  Ends on a barrier.
-template <int THREADS, int RI, class RunTo>
-__device__ __forceinline__ void rank_tile(const uint32_t (&dig)[RI], const bool (&valid)[RI], int bits, uint16_t (*s_wcnt)[MAXB],
-                                          uint32_t *s_dstart, uint32_t *s_scan, uint32_t (&rank)[RI], RunTo run_to) {
-    constexpr int W = THREADS / 64;
-    const int bins = 1 << bits;
-    wave_rank<RI>(dig, valid, bits, s_wcnt[threadIdx.x >> 6], rank);
-    __syncthreads();
-    constexpr int C = MAXB / THREADS > 0 ? MAXB / THREADS : 1;      // digits per thread
-    uint32_t tot[C], sum = 0;
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-        const int d = threadIdx.x * C + c;
-        tot[c] = 0;
-        if (d < bins) {
-            uint32_t run = 0;
-#pragma unroll
-            for (int w = 0; w < W; w++) { const uint32_t x = s_wcnt[w][d]; s_wcnt[w][d] = (uint16_t)run; run += x; }
-            tot[c] = run;
-        }
-        sum += tot[c];
-    }
-    uint32_t total;
-    uint32_t ex = block_excl<THREADS>(sum, s_scan, &total);
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-        const int d = threadIdx.x * C + c;
-        if (d < bins) {
-            s_dstart[d] = ex;
-            run_to(d, ex);
-            ex += tot[c];
-        }
-    }
-    __syncthreads();
-}
-// (4) the slot of a row in the sorted tile: the start of its digit, the rows of the digit in earlier waves, its rank in its own
-__device__ __forceinline__ uint32_t tile_slot(const uint32_t *s_dstart, const uint16_t *wcnt /* this wave's */, uint32_t dig, uint32_t rank) {
-    return s_dstart[dig] + wcnt[dig] + rank;
-}
+// (2) ranks inside the wave, digit counts per wave (s_wcnt[W][MAXB]); (3) per digit: exclusive offsets over the waves, the
+// digit's start in the sorted tile and where its run goes: rank_tile; (4) the slot of a row in the sorted tile: tile_slot
+// (both gki_radix_tile.h).
 
 // One stable partition pass over a tile of THREADS * RI rows, the sorted tile whole in LDS.  Rows + keys in (!SRC_COLS): the
 // payload words are dropped into their rows' slots through a 16-bit destination table.
@@ -888,11 +812,7 @@ __global__ __launch_bounds__(256) void k_group_large(FinishArgs a, const uint32_
             const uint32_t b = valid ? (a.keys[(int64_t)s + e] & lmask) : 0u;
             uint64_t w0 = 0, w1 = 0, w2 = 0;
             if (valid) { const uint64_t *row = a.rows + ((int64_t)s + e) * 3; w0 = row[0]; w1 = row[1]; w2 = row[2]; }
-            uint64_t same = __ballot(valid);
-            for (int t = 0; t < a.L; t++) {
-                const uint64_t bit = __ballot((b >> t) & 1u);
-                same &= ((b >> t) & 1u) ? bit : ~bit;
-            }
+            const uint64_t same = same_digit_lanes(b, a.L, valid);
             const uint32_t before = (uint32_t)__popcll(same & lt_mask);
             for (int w = 0; w < 4; w++) {
                 if (wave == w && valid) {

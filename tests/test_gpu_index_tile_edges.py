@@ -1,7 +1,8 @@
 """The index build at the edges of its tiles (csrc/gki_index_rows.hip): record counts one below, at and one above a tile
 (512 x 8 rows in the build's passes, 256 x 8 in the bucket-range partition into columns), a chunk seam on a tile edge, and
 the segmented tiles of the grouped build with a group of exactly one finish's capacity, an empty group and a group of one
-row.  Every case is a few thousand records and compares element by element with the oracle's stable build or with a NumPy
+row; and the pair-sorting form's 8-bit passes (csrc/gki_radix_tile.h, 256 x 16 pairs a tile) on keys crafted so that a digit's
+run spans all tiles of a pass.  Every case is a few thousand records and compares element by element with the oracle's stable build or with a NumPy
 stable argsort."""
 import numpy as np
 import pytest
@@ -55,6 +56,33 @@ def test_build_from_columns_at_the_tile_edges(n, modulo):
             dev = DeviceIndex.build(d, modulo, want_permutation=want_perm, pairs_form=pairs)
             _check(dev, o, n, order if want_perm else None)
             dev.free()
+    d.free()
+
+
+def _one_run_keys(n, rng):
+    """one low byte, five second bytes: pass 1 of the pair sort is ONE run across all tiles, pass 2 has to keep its order"""
+    return np.uint64(0x5A) | (rng.choice(np.array([0x00, 0x01, 0x7F, 0x80, 0xFF], dtype=np.uint64), size=n) << np.uint64(8))
+
+
+def _digit_255_keys(n, rng):
+    """low byte 0xFF everywhere: in the partial last tile the real digit 255 sits beside the padding lanes"""
+    return np.uint64(0xFF) | (rng.integers(0, 256, size=n).astype(np.uint64) << np.uint64(8))
+
+
+# 4097 = a tile and one record, 3 * 4096 + 3 = three tiles and three records: the last tile is partial in both
+@pytest.mark.parametrize("make_keys", [_one_run_keys, _digit_255_keys])
+@pytest.mark.parametrize("n", [4097, 3 * 4096 + 3])
+def test_pair_sort_is_stable_across_tiles_within_a_pass(n, make_keys):
+    modulo = 65537                                              # every k-mer is below it: bucket = k-mer, three 8-bit passes
+    rng = np.random.default_rng(n)
+    kmers = make_keys(n, rng)
+    assert kmers.max() < modulo
+    nodes, refs, af = _payload(kmers, rng)
+    o = oracle.index_build(kmers, nodes, refs, af, modulo=modulo)
+    d = DeviceFlatKmers.from_flat_kmers(FlatKmers(kmers, nodes, refs, af))
+    dev = DeviceIndex.build(d, modulo, want_permutation=True, pairs_form=True)
+    _check(dev, o, n, np.argsort(kmers, kind="stable").astype(np.uint32))
+    dev.free()
     d.free()
 
 

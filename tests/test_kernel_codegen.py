@@ -181,3 +181,22 @@ def test_index_build_kernels_are_what_they_were_before_the_shared_tile_helpers(i
     blocks_by_lds = lambda b: 163840 // b
     for name in ("k_partition_rows_staged<512, 8, true, 4>", "k_partition_rows_staged<512, 8, false, 4>"):
         assert blocks_by_lds(r[name]["lds"]) >= 2, (name, r[name])
+
+
+@pytest.fixture(scope="module")
+def index_asm(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("codegen_ixp") / "gki_index.s")
+    subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function", "--cuda-device-only", "-S",
+                    os.path.join(CSRC, "gki_index.hip"), "-o", out], check=True, stderr=subprocess.DEVNULL)
+    return open(out).read()
+
+
+def test_footprints_of_the_pair_sort_kernels(index_asm):
+    """The pair-sorting form's pass (csrc/gki_radix_tile.h over PairItems), under the kernel names the tools and profiles know.
+    The bounds are the figures of the kernels before they shared a body with the count sort: 112 VGPRs, 37 904 B of LDS, no
+    scratch for the scatter (four workgroups of 256 threads per CU by LDS and by registers), 8 / 1 024 / 0 for the histogram."""
+    r = _resources(index_asm)
+    assert sorted(k for k in r if k.startswith("k_radix_")) == ["k_radix_hist", "k_radix_scatter"]
+    s, h = r["k_radix_scatter"], r["k_radix_hist"]
+    assert s["vgpr"] <= 112 and s["lds"] <= 37904 and s["scratch"] == 0, s
+    assert h["vgpr"] <= 64 and h["lds"] <= 1024 and h["scratch"] == 0, h
