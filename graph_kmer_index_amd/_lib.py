@@ -164,11 +164,18 @@ SYMBOLS = {
     "gki_vcf_haplotype_matrix": (_I32, [_P, _I64, _I64, _I64, _I32, _P, _P, C.POINTER(_I64), C.POINTER(_I64),
                                         C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "gki_haplotype_planes": (_I32, [_P, _I64, _I64, _P, _P, C.POINTER(C.c_float)]),
+    "gki_haplotype_paths_create": (_I32, [_P, _I64, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _P, _P, C.POINTER(_P)]),
+    "gki_haplotype_spell_count": (_I32, [_P, _P, _I64, _I64, C.POINTER(_I64), _P, C.POINTER(C.c_float)]),
+    "gki_haplotype_spell_emit": (_I32, [_P, _P, C.POINTER(C.c_float)]),
+    "gki_haplotype_alt_nodes_count": (_I32, [_P, _P, _I64, _P, C.POINTER(_I64), C.POINTER(C.c_float)]),
+    "gki_haplotype_alt_nodes_emit": (_I32, [_P, _P, _I64, _P, C.POINTER(C.c_float)]),
+    "gki_haplotype_paths_destroy": (_I32, [_P]),
     "gki_bgzf_inflate": (_I32, [_P, _I64, _P, _P, _P, _P, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(C.c_int)]),
     "gki_bgzf_inflate_kernel_ms": (_I32, [C.POINTER(C.c_float)]),
     "gki_last_byte_position": (_I32, [_P, _I64, _I32, C.POINTER(_I64)]),
     "gki_measure_random_loads": (_I32, [_I64, _I64, C.POINTER(C.c_double)]),
     "gki_measure_store_bw": (_I32, [_P, _P, _P, _P, _I64, C.POINTER(C.c_double)]),
+    "gki_measure_copy_ms": (_I32, [_P, _P, _I64, C.POINTER(C.c_float)]),
     "gki_selftest_wave_scan": (_I32, [C.POINTER(_I64)]),
     "gki_simulate_reads": (_I32, [_P, _I64, _I64, _I32, _U64, C.c_double, C.c_double, _I64, _P]),
     "gki_comm_get_unique_id": (_I32, [_P]),

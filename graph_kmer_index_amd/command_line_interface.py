@@ -18,6 +18,12 @@ collision_free_kmer_index.py:393-402).
     python -m graph_kmer_index_amd.command_line_interface map -i index.npz -f reads.fq.gz -k 31 -o node_counts
     python -m graph_kmer_index_amd.command_line_interface make_graph -r ref.fa -v variants.vcf.gz -o graph -n chr1,chr2 -a genotypes
     python -m graph_kmer_index_amd.command_line_interface make_haplotype_matrix -v variants.vcf.gz -o haplotypes --planes True
+    python -m graph_kmer_index_amd.command_line_interface make_haplotype_to_nodes -g graph.npz -V graph.variant_to_nodes.npz \
+        -m haplotypes.npz -o haplotype_to_nodes
+    python -m graph_kmer_index_amd.command_line_interface spell_haplotype -g graph.npz -V graph.variant_to_nodes.npz \
+        -m haplotypes.npz -s 0 -o haplotype0.fa
+    python -m graph_kmer_index_amd.command_line_interface haplotype_node_counts -g graph.npz -V graph.variant_to_nodes.npz \
+        -m haplotypes.npz -i index.npz -k 31 -s 0,1,5 -o haplotype_counts
 
 `-g` takes an obgraph file when obgraph is installed, else a GraphArrays .npz (GraphArrays.to_file).  `index -t N` runs
 one process per GPU (at most N, at most the visible devices), each on its own range of critical-path numbers, and
@@ -371,6 +377,57 @@ def make_haplotype_matrix(args):
     logging.info("Wrote the haplotype matrix%s to %s" % (" and its bit planes" if args.planes else "", args.out_file_name))
 
 
+def open_haplotype_paths(args):
+    """The HaplotypePaths of `-g`, `-V` and `-m` (a HaplotypeMatrix file)."""
+    from .haplotype_paths import HaplotypePaths
+    from .unique_variant_kmers import load_variant_to_nodes
+    from .vcf_files import HaplotypeMatrix
+    return HaplotypePaths(load_graph(args.graph), load_variant_to_nodes(args.variant_to_nodes),
+                          HaplotypeMatrix.from_file(args.haplotype_matrix))
+
+
+def make_haplotype_to_nodes(args):
+    """Graph + variant-to-nodes + haplotype matrix -> the variant nodes every haplotype slot carries
+    (HaplotypeToNodes.to_file), listed on the device (haplotype_paths.py)."""
+    with open_haplotype_paths(args) as paths:
+        table = paths.alt_nodes()
+    table.to_file(args.out_file_name)
+    logging.info("Wrote %d alt nodes of %d haplotype slots to %s" % (len(table.nodes), table.n_slots, args.out_file_name))
+
+
+def spell_haplotype(args):
+    """One haplotype slot's sequence as a FASTA file with records >1, >2, ... (one per chromosome), lines of 60 letters:
+    spelled on the device (haplotype_paths.py), written by the host."""
+    from .haplotype_paths import write_fasta
+    with open_haplotype_paths(args) as paths, _lib.DeviceScope() as s:
+        reference = s.keep(paths.sequence(args.slot))
+        write_fasta(args.out_file_name, reference.names, reference.to_host())
+        logging.info("Wrote %d letters in %d records of slot %d to %s"
+                     % (reference.letters.n, len(reference.names), args.slot, args.out_file_name))
+
+
+def haplotype_node_counts(args):
+    """Node hit counts of the k-mers of some haplotype slots' sequences, one row per slot in the order of `-s`: np.save of
+    uint32[slots, nodes] (haplotype_paths.py)."""
+    slots = [int(x) for x in args.slots.split(",") if x]
+    index = CollisionFreeKmerIndex.from_file(args.kmer_index)
+    with open_haplotype_paths(args) as paths:
+        counts = paths.node_counts(slots, index, args.kmer_size, args.n_nodes,
+                                   include_reverse_complement=_bool(args.include_reverse_complement))
+    for slot, row in zip(slots, counts):
+        logging.info("slot %d: %d hits on %d nodes" % (slot, int(row.sum(dtype=np.int64)), int(np.count_nonzero(row))))
+    if args.out_file_name is not None:
+        out = args.out_file_name if args.out_file_name.endswith(".npy") else args.out_file_name + ".npy"
+        np.save(out, counts)
+        logging.info("Wrote the node counts of %d slots to %s" % (len(slots), out))
+
+
+def _haplotype_paths_arguments(p):
+    p.add_argument("-g", "--graph", required=True)
+    p.add_argument("-V", "--variant_to_nodes", required=True, help="built with the graph (make_graph writes both)")
+    p.add_argument("-m", "--haplotype-matrix", required=True, help="what make_haplotype_matrix writes, from the same VCF")
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description="graph_kmer_index on MI355X (in-scope sub-commands)")
     sub = parser.add_subparsers()
@@ -523,6 +580,24 @@ def build_parser():
                    help="where a .gz VCF is inflated: auto = BGZF on the device, other gzip on the host")
     p.add_argument("--chunk-bytes", required=False, type=int, default=None)
     p.set_defaults(func=make_haplotype_matrix)
+    p = sub.add_parser("make_haplotype_to_nodes")
+    _haplotype_paths_arguments(p)
+    p.add_argument("-o", "--out-file-name", required=True, help="the table, as HaplotypeToNodes.to_file writes it (.npz)")
+    p.set_defaults(func=make_haplotype_to_nodes)
+    p = sub.add_parser("spell_haplotype")
+    _haplotype_paths_arguments(p)
+    p.add_argument("-s", "--slot", required=True, type=int, help="sample * ploidy + haplotype of the sample")
+    p.add_argument("-o", "--out-file-name", required=True, help="FASTA, a record per chromosome named 1, 2, ...")
+    p.set_defaults(func=spell_haplotype)
+    p = sub.add_parser("haplotype_node_counts")
+    _haplotype_paths_arguments(p)
+    p.add_argument("-i", "--kmer-index", required=True)
+    p.add_argument("-k", "--kmer-size", required=False, type=int, default=31)
+    p.add_argument("-s", "--slots", required=True, help="comma-separated haplotype slots, a row of counts each")
+    p.add_argument("-o", "--out-file-name", required=False, default=None, help="np.save of uint32[slots, nodes]")
+    p.add_argument("-n", "--n-nodes", required=False, type=int, default=None, help="default: the index's max node id + 1")
+    p.add_argument("-r", "--include-reverse-complement", required=False, type=_bool, default=True)
+    p.set_defaults(func=haplotype_node_counts)
     p = sub.add_parser("map")
     p.add_argument("-i", "--kmer-index", required=True)
     p.add_argument("-f", "--reads", required=True, help="FASTA or FASTQ, optionally .gz (gzip or BGZF)")

@@ -20,6 +20,7 @@
 //                            reference with every kept alt allele put in behind its site's ref allele, so a lane's 16
 //                            codes come from 16 consecutive letters of the reference or of the alt pool unless a site's
 //                            boundary falls among them (then byte by byte).
+#include "gki_seq_gather.h"
 #include "gki_text_lines.h"
 
 namespace {
@@ -440,16 +441,7 @@ __device__ __forceinline__ uint32_t encode1(uint8_t c) {
     return u == (uint8_t)'C' ? 1u : u == (uint8_t)'G' ? 2u : u == (uint8_t)'T' ? 3u : 0u;
 }
 
-struct alignas(4) Letters16 { uint32_t w[4]; };
-
-// first k in [a, b) with alt_end[k] > p, b when there is none
-__device__ __forceinline__ int64_t first_site_after(const int64_t *__restrict__ alt_end, int64_t a, int64_t b, int64_t p) {
-    while (a < b) {
-        const int64_t mid = a + ((b - a) >> 1);
-        if (alt_end[mid] > p) b = mid; else a = mid + 1;
-    }
-    return a;
-}
+// Letters16 and first_site_after (the first k in [a, b) with alt_end[k] > p) are gki_seq_gather.h's
 
 // tile_site[t] = the first kept site whose alt allele ends behind output byte t * SEQ_TILE (K when there is none), for
 // t = 0 .. n_tiles: one lane per tile boundary does the search over all K sites, so that k_gb_sequence starts every

@@ -101,6 +101,16 @@ int gki_measure_store_bw(void *d_hashes, void *d_nodes, void *d_ref_offsets, voi
     return GKI_OK;
 }
 
+int gki_measure_copy_ms(void *d_dst, const void *d_src, int64_t bytes, float *ms) {
+    if (ms == nullptr || bytes < 0 || (bytes > 0 && (d_dst == nullptr || d_src == nullptr)))
+        return gki_set_error(GKI_ERR_BAD_ARG, "measure_copy_ms: a pointer is NULL or bytes is negative");
+    *ms = 0.f;
+    TimerEvents ev;
+    GKI_TRY(ev.start(0));
+    if (bytes > 0) HIP_TRY(hipMemcpyAsync(d_dst, d_src, (size_t)bytes, hipMemcpyDeviceToDevice, 0));
+    return ev.stop(0, ms);
+}
+
 int gki_selftest_wave_scan(int64_t *n_bad) {
     DevBuf d_bad;
     int h_bad = -1;

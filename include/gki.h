@@ -828,6 +828,53 @@ int gki_vcf_haplotype_matrix(const void *d_text, int64_t n_bytes, int64_t n_vari
 int gki_haplotype_planes(const void *d_codes, int64_t n_variants, int64_t n_slots, void *d_ref_bits, void *d_alt_bits,
                          float *kernel_ms);
 
+/* ---------------------------------------------------------------- haplotype paths (graph + variant-to-nodes + alt plane -> sequences, alt nodes)
+ * What a sample haplotype of "VCF haplotype matrix" is in the graph of "graph build": its sequence and the variant nodes it
+ * carries.
+ *   inputs        the graph's flat arrays; variant-to-nodes with one entry per VCF data line, V of them -- a line is kept
+ *                 exactly when var_nodes[v] != 0; the codes of V lines x H slots, on the device as the alt plane
+ *                 alt_bits uint64[H][W], W = ceil(V / 64), of gki_haplotype_planes.  A matrix of another number of lines
+ *                 than variant-to-nodes is refused.
+ *   bubble chain  the kept lines' ref_nodes ascend strictly and var_nodes[v] == ref_nodes[v] + 1; every existing node that is
+ *                 not an allele node of a kept line has is_ref 1.  Any other graph is refused, naming the first line or node
+ *                 at fault (the host checks this once per graph; edges are not inspected).  In such a graph node ids ascend
+ *                 along every path.
+ *   choice        slot h takes the alt allele of kept line v exactly when codes[v][h] == 1.  Codes 0, 2 (another allele) and
+ *                 3 (none) take the ref allele.  Lines that are not kept are ignored.
+ *   sequence      per chromosome c the node sequences joined in id order from chromosome_start_nodes[c] up to the next
+ *                 chromosome's start node (the graph's end for the last), leaving out the allele not taken at every kept
+ *                 line.  Letters are upper-case "ACGT"[code]: an N of the reference is code 0 in the graph and comes out A.
+ *   alt nodes     slot h's alt nodes are var_nodes[v] of the kept lines v with codes[v][h] == 1, in line order.
+ * gki_haplotype_paths_create uploads one graph's plan from host arrays: h_seq uint8[n_bases]; h_var_nodes uint32[n_lines];
+ * h_kept_bits uint64[ceil(n_lines / 64)], bit v mod 64 of word v / 64 set for a kept line, the tail zero; per kept line
+ * j = 0 .. n_kept - 1 in line order its line number h_kept_line and its two allele nodes' seq_start and node_size
+ * (h_ref_start, h_ref_size, h_alt_start, h_alt_size); h_chrom_seq_start / h_chrom_first_kept int64[n_chromosomes + 1]:
+ * seq_start of chromosome c's start node and the first j of chromosome c, then n_bases and n_kept.  GKI_ERR_BAD_ARG unless
+ * the kept lines ascend, every one has its bit and no other bit is set, alt_start == ref_start + ref_size and the next kept
+ * line begins behind it: what keeps every read of the gather inside seq.
+ * gki_haplotype_spell_count / _emit spell one slot of d_alt_bits uint64[n_slots][W]: count returns *n_out letters and
+ * h_bounds int64[n_chromosomes + 1], where each chromosome begins in them and n_out; emit writes d_letters uint8[n_out]
+ * (16-byte aligned) and must follow its count call (GKI_ERR_STATE otherwise).  Offsets are 64 bits wide throughout.
+ * *count_ms / *spell_ms (may be NULL): the device time of the count pass' kernels and of the spelling kernel.
+ * gki_haplotype_alt_nodes_count / _emit list the alt nodes of all slots: count writes d_start int64[n_slots + 1] (slot h's
+ * nodes are [start[h], start[h + 1])) and returns *n_nodes = start[n_slots]; emit, given the same plane, writes d_nodes
+ * uint32[n_nodes].  Bits of the plane at and beyond n_lines are not relied on: every word is ANDed with kept_bits.
+ * gki_haplotype_paths_destroy frees the plan (NULL is allowed). */
+typedef struct gki_haplotype_paths gki_haplotype_paths;
+int gki_haplotype_paths_create(const uint8_t *h_seq, int64_t n_bases, int64_t n_lines, const uint32_t *h_var_nodes,
+                               const uint64_t *h_kept_bits, int64_t n_kept, const int64_t *h_kept_line,
+                               const int64_t *h_ref_start, const int32_t *h_ref_size, const int64_t *h_alt_start,
+                               const int32_t *h_alt_size, int64_t n_chromosomes, const int64_t *h_chrom_seq_start,
+                               const int64_t *h_chrom_first_kept, gki_haplotype_paths **plan);
+int gki_haplotype_spell_count(gki_haplotype_paths *plan, const void *d_alt_bits, int64_t n_slots, int64_t slot,
+                              int64_t *n_out, int64_t *h_bounds, float *count_ms);
+int gki_haplotype_spell_emit(gki_haplotype_paths *plan, void *d_letters, float *spell_ms);
+int gki_haplotype_alt_nodes_count(gki_haplotype_paths *plan, const void *d_alt_bits, int64_t n_slots, void *d_start,
+                                  int64_t *n_nodes, float *kernel_ms);
+int gki_haplotype_alt_nodes_emit(gki_haplotype_paths *plan, const void *d_alt_bits, int64_t n_slots, void *d_nodes,
+                                 float *kernel_ms);
+int gki_haplotype_paths_destroy(gki_haplotype_paths *plan);
+
 /* ---------------------------------------------------------------- BGZF (blocked gzip: the .gz reads files of bgzip / htslib)
  * A BGZF file is a chain of gzip members of at most 64 KiB, each with its compressed size in a 'BC' extra subfield, so
  * every member's raw DEFLATE payload, CRC-32 and ISIZE are found without inflating anything (graph_kmer_index_amd/bgzf.py
@@ -863,6 +910,9 @@ int gki_measure_random_loads(int64_t table_bytes, int64_t n_loads, double *loads
  * bytes; the caller's buffers, e.g. the output columns before a run) with nothing else in the kernel, three launches,
  * best of the last two; bytes_per_s = 24 n / time.  bench.py prints it beside the 8 TB/s spec peak. */
 int gki_measure_store_bw(void *d_hashes, void *d_nodes, void *d_ref_offsets, void *d_af32, int64_t n, double *bytes_per_s);
+/* The yardstick a streaming kernel's device time is set beside: *ms = the device time, by HIP events, of one
+ * device-to-device copy of `bytes` bytes (the buffers must not overlap). */
+int gki_measure_copy_ms(void *d_dst, const void *d_src, int64_t bytes, float *ms);
 /* Device self-test of the kernels' wave prefix sum (DPP row shifts and broadcasts, csrc/gki_common.h) against the shuffle
  * form on random and extreme inputs: *n_bad = lanes that disagree (0 on a correct build).  No reference counterpart. */
 int gki_selftest_wave_scan(int64_t *n_bad);
