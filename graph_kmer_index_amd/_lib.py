@@ -170,6 +170,12 @@ SYMBOLS = {
     "gki_haplotype_alt_nodes_count": (_I32, [_P, _P, _I64, _P, C.POINTER(_I64), C.POINTER(C.c_float)]),
     "gki_haplotype_alt_nodes_emit": (_I32, [_P, _P, _I64, _P, C.POINTER(C.c_float)]),
     "gki_haplotype_paths_destroy": (_I32, [_P]),
+    "gki_haplotype_segments_count": (_I32, [_P, _P, _I64, _I64, _I32] + [C.POINTER(_I64)] * 5 + [C.POINTER(C.c_float)]),
+    "gki_haplotype_segments_emit": (_I32, [_P, _P, _P, _P, _P, C.POINTER(C.c_float)]),
+    "gki_probe_segments_count_nodes": (_I32, [_P, _P, _I64, _P, _P, _I64, _I32, _I32, _I64, _I32, _P, _I64,
+                                              C.POINTER(_I64), C.POINTER(_I64)]),
+    "gki_node_count_model_row_start": (_I32, [_P, _I64, _I32, _P]),
+    "gki_node_count_model_accumulate": (_I32, [_P, _P, _I64, _I64, _I32, _P, _I64, _I32, _P, _P, C.POINTER(C.c_float)]),
     "gki_bgzf_inflate": (_I32, [_P, _I64, _P, _P, _P, _P, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(C.c_int)]),
     "gki_bgzf_inflate_kernel_ms": (_I32, [C.POINTER(C.c_float)]),
     "gki_last_byte_position": (_I32, [_P, _I64, _I32, C.POINTER(_I64)]),

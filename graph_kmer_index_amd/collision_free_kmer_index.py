@@ -176,6 +176,23 @@ class DeviceIndex:
             s.release(counts)
         return counts, n_kmers.value, n_hits.value
 
+    def count_nodes_from_segments(self, letters, seg_start, seg_windows, k, counts, n_nodes, strands=3, max_hits=2 ** 62,
+                                  sign=1, n_segs=None):
+        """The fused hash and probe over segments of a sequence that stays on the device (gki_probe_segments_count_nodes):
+        segment i is the seg_windows[i] windows from letters[seg_start[i]] on (int64 DeviceArrays or NumPy arrays; the
+        first n_segs of them), and every hit adds `sign` (+1 or -1) to `counts`, a uint32 DeviceArray.  Returns (k-mers
+        probed, hits)."""
+        n_kmers, n_hits = C.c_int64(0), C.c_int64(0)
+        with _lib.DeviceScope() as s:
+            d_start, d_windows = s.on_device(seg_start, np.int64), s.on_device(seg_windows, np.int64)
+            n_segs = min(d_start.n, d_windows.n) if n_segs is None else int(n_segs)
+            if n_segs > min(d_start.n, d_windows.n):
+                raise ValueError("%d segments asked for, the arrays hold %d" % (n_segs, min(d_start.n, d_windows.n)))
+            _lib.check(_lib.load().gki_probe_segments_count_nodes(
+                self.probe_table(), letters.ptr, letters.n, d_start.ptr, d_windows.ptr, n_segs, int(k), int(strands),
+                int(min(max_hits, 2 ** 62)), int(sign), counts.ptr, int(n_nodes), C.byref(n_kmers), C.byref(n_hits)))
+        return n_kmers.value, n_hits.value
+
     def __del__(self):
         try:
             if self._probe is not None:

@@ -23,7 +23,9 @@ collision_free_kmer_index.py:393-402).
     python -m graph_kmer_index_amd.command_line_interface spell_haplotype -g graph.npz -V graph.variant_to_nodes.npz \
         -m haplotypes.npz -s 0 -o haplotype0.fa
     python -m graph_kmer_index_amd.command_line_interface haplotype_node_counts -g graph.npz -V graph.variant_to_nodes.npz \
-        -m haplotypes.npz -i index.npz -k 31 -s 0,1,5 -o haplotype_counts
+        -m haplotypes.npz -i index.npz -k 31 -s 0,1,5 -o haplotype_counts [--route difference]
+    python -m graph_kmer_index_amd.command_line_interface make_node_count_model -g graph.npz -V graph.variant_to_nodes.npz \
+        -m haplotypes.npz -i index.npz -k 31 [-s 0,1,5] [-b 5] -o node_count_model
 
 `-g` takes an obgraph file when obgraph is installed, else a GraphArrays .npz (GraphArrays.to_file).  `index -t N` runs
 one process per GPU (at most N, at most the visible devices), each on its own range of critical-path numbers, and
@@ -412,14 +414,28 @@ def haplotype_node_counts(args):
     slots = [int(x) for x in args.slots.split(",") if x]
     index = CollisionFreeKmerIndex.from_file(args.kmer_index)
     with open_haplotype_paths(args) as paths:
-        counts = paths.node_counts(slots, index, args.kmer_size, args.n_nodes,
-                                   include_reverse_complement=_bool(args.include_reverse_complement))
+        route = paths.node_counts_by_difference if args.route == "difference" else paths.node_counts
+        counts = route(slots, index, args.kmer_size, args.n_nodes,
+                       include_reverse_complement=_bool(args.include_reverse_complement))
     for slot, row in zip(slots, counts):
         logging.info("slot %d: %d hits on %d nodes" % (slot, int(row.sum(dtype=np.int64)), int(np.count_nonzero(row))))
     if args.out_file_name is not None:
         out = args.out_file_name if args.out_file_name.endswith(".npy") else args.out_file_name + ".npy"
         np.save(out, counts)
         logging.info("Wrote the node counts of %d slots to %s" % (len(slots), out))
+
+
+def make_node_count_model(args):
+    """The node count model of some sampled individuals (default: all): per data line, allele and copy number a histogram
+    of the allele node's count over the individuals and the counts' sum (NodeCountModel.to_file; haplotype_paths.py)."""
+    samples = None if args.samples is None else [int(x) for x in args.samples.split(",") if x]
+    index = CollisionFreeKmerIndex.from_file(args.kmer_index)
+    with open_haplotype_paths(args) as paths:
+        model = paths.node_count_model(index, args.kmer_size, samples, args.n_bins, args.n_nodes,
+                                       include_reverse_complement=_bool(args.include_reverse_complement), route=args.route)
+    model.to_file(args.out_file_name)
+    logging.info("Wrote the node count model of %d individuals over %d data lines (%d bins) to %s"
+                 % (len(model.samples), len(model.histogram), model.n_bins, args.out_file_name))
 
 
 def _haplotype_paths_arguments(p):
@@ -597,7 +613,20 @@ def build_parser():
     p.add_argument("-o", "--out-file-name", required=False, default=None, help="np.save of uint32[slots, nodes]")
     p.add_argument("-n", "--n-nodes", required=False, type=int, default=None, help="default: the index's max node id + 1")
     p.add_argument("-r", "--include-reverse-complement", required=False, type=_bool, default=True)
+    p.add_argument("--route", required=False, choices=("whole", "difference"), default="whole",
+                   help="whole: hash and probe every k-mer of a slot; difference: only those that differ from the all-ref path")
     p.set_defaults(func=haplotype_node_counts)
+    p = sub.add_parser("make_node_count_model")
+    _haplotype_paths_arguments(p)
+    p.add_argument("-i", "--kmer-index", required=True)
+    p.add_argument("-k", "--kmer-size", required=False, type=int, default=31)
+    p.add_argument("-s", "--samples", required=False, default=None, help="comma-separated individuals; default: all")
+    p.add_argument("-b", "--n-bins", required=False, type=int, default=5, help="counts of n_bins - 1 and more share the last bin")
+    p.add_argument("-n", "--n-nodes", required=False, type=int, default=None, help="default: the index's max node id + 1")
+    p.add_argument("-r", "--include-reverse-complement", required=False, type=_bool, default=True)
+    p.add_argument("--route", required=False, choices=("whole", "difference"), default="difference")
+    p.add_argument("-o", "--out-file-name", required=True, help="the model, as NodeCountModel.to_file writes it (.npz)")
+    p.set_defaults(func=make_node_count_model)
     p = sub.add_parser("map")
     p.add_argument("-i", "--kmer-index", required=True)
     p.add_argument("-f", "--reads", required=True, help="FASTA or FASTQ, optionally .gz (gzip or BGZF)")

@@ -16,6 +16,7 @@
 //   k_hap_alt_count    per (slot, tile of 1024 plane words): the set bits of alt_bits & kept_bits
 //   (exclusive scan)   tile_before; k_hap_alt_starts picks start[h] = tile_before[h * T] out of it
 //   k_hap_alt_emit     per (slot, tile): var_nodes[64 w + b] for every set bit, behind a block prefix of the lanes' counts
+#include "gki_haplotype_plan.h"
 #include "gki_seq_gather.h"
 #include "gki_text_lines.h"
 
@@ -192,32 +193,13 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_hap_alt_emit(const uint64_t *__
 
 }  // namespace
 
-// One graph's plan: what create uploads, and what a spell count call leaves for the emit call.
-struct gki_haplotype_paths {
-    int64_t n_bases = 0, n_lines = 0, K = 0, W = 0;
-    int n_chrom = 0, device = 0;
-    DevBuf seq, kline, ref_start, ref_size, alt_start, alt_size, kept_bits, var_nodes, chrom_seq_start, chrom_first_kept;
-    DevBuf drop_len, drop_start, before, cut, bounds, tile_site, scan_tmp;      // the spell passes' own, sized once
-    int64_t scan_tmp_bytes = 0;
-    int64_t n_out = -1;                                    // of the last spell count call; -1: none since the last emit
-    DevBuf alt_tile_before;                                // int64[n_slots * T + 1] of the last alt-nodes count call
-    int64_t alt_slots = -1, alt_total = 0;
-    const void *alt_plane = nullptr;
-};
+// One graph's plan, struct gki_haplotype_paths: gki_haplotype_plan.h
 
 namespace {
 
 int upload(DevBuf &dst, const void *h_src, size_t bytes) {
     HIP_TRY(dst.alloc(bytes ? bytes : 8));
     if (bytes) HIP_TRY(hipMemcpy(dst.get(), h_src, bytes, hipMemcpyHostToDevice));
-    return GKI_OK;
-}
-
-int check_plan(const gki_haplotype_paths *p, const char *who) {
-    if (p == nullptr) return gki_set_error(GKI_ERR_BAD_ARG, "%s: plan is NULL", who);
-    int device = 0;
-    HIP_TRY(hipGetDevice(&device));
-    if (device != p->device) return gki_set_error(GKI_ERR_BAD_ARG, "%s: the plan was made on device %d", who, p->device);
     return GKI_OK;
 }
 
@@ -295,9 +277,10 @@ int gki_haplotype_spell_count(gki_haplotype_paths *plan, const void *d_alt_bits,
                               int64_t *n_out, int64_t *h_bounds, float *count_ms) {
     if (count_ms) *count_ms = 0.0f;
     if (n_out) *n_out = 0;
-    GKI_TRY(check_plan(plan, "haplotype_spell_count"));
+    GKI_TRY(gki_check_haplotype_plan(plan, "haplotype_spell_count"));
     gki_haplotype_paths &g = *plan;
     g.n_out = -1;
+    g.spelled_slot = -1;
     if (n_out == nullptr || h_bounds == nullptr || slot < 0 || slot >= n_slots || (g.W > 0 && d_alt_bits == nullptr))
         return gki_set_error(GKI_ERR_BAD_ARG, "haplotype_spell_count: slot %lld of %lld, or a pointer is NULL", (long long)slot,
                              (long long)n_slots);
@@ -333,13 +316,15 @@ int gki_haplotype_spell_count(gki_haplotype_paths *plan, const void *d_alt_bits,
     GKI_TRY(ev.stop(0, &ms_b));
     if (count_ms) *count_ms = ms_a + ms_b;
     g.n_out = total;
+    g.spelled_slot = slot;
+    g.spelled_plane = d_alt_bits;
     *n_out = total;
     return GKI_OK;
 }
 
 int gki_haplotype_spell_emit(gki_haplotype_paths *plan, void *d_letters, float *spell_ms) {
     if (spell_ms) *spell_ms = 0.0f;
-    GKI_TRY(check_plan(plan, "haplotype_spell_emit"));
+    GKI_TRY(gki_check_haplotype_plan(plan, "haplotype_spell_emit"));
     gki_haplotype_paths &g = *plan;
     if (g.n_out < 0) return gki_set_error(GKI_ERR_STATE, "haplotype_spell_emit: no spell count call came before");
     const int64_t total = g.n_out;
@@ -361,7 +346,7 @@ int gki_haplotype_alt_nodes_count(gki_haplotype_paths *plan, const void *d_alt_b
                                   int64_t *n_nodes, float *kernel_ms) {
     if (kernel_ms) *kernel_ms = 0.0f;
     if (n_nodes) *n_nodes = 0;
-    GKI_TRY(check_plan(plan, "haplotype_alt_nodes_count"));
+    GKI_TRY(gki_check_haplotype_plan(plan, "haplotype_alt_nodes_count"));
     gki_haplotype_paths &g = *plan;
     g.alt_slots = -1;
     g.alt_tile_before.reset();
@@ -400,7 +385,7 @@ int gki_haplotype_alt_nodes_count(gki_haplotype_paths *plan, const void *d_alt_b
 int gki_haplotype_alt_nodes_emit(gki_haplotype_paths *plan, const void *d_alt_bits, int64_t n_slots, void *d_nodes,
                                  float *kernel_ms) {
     if (kernel_ms) *kernel_ms = 0.0f;
-    GKI_TRY(check_plan(plan, "haplotype_alt_nodes_emit"));
+    GKI_TRY(gki_check_haplotype_plan(plan, "haplotype_alt_nodes_emit"));
     gki_haplotype_paths &g = *plan;
     if (g.alt_slots < 0) return gki_set_error(GKI_ERR_STATE, "haplotype_alt_nodes_emit: no alt-nodes count call came before");
     if (n_slots != g.alt_slots || d_alt_bits != g.alt_plane)

@@ -17,7 +17,7 @@ struct gki_probe {
     uint2 *dir = nullptr;            // [modulo]
     uint4 *rows = nullptr;           // [n]
     const uint32_t *n_kmers = nullptr;   // the index's own array (borrowed): exact length of saturated buckets
-    unsigned long long *counters = nullptr;   // [2] device: hits, k-mers probed
+    unsigned long long *counters = nullptr;   // [3] device: hits, k-mers probed, fault word of a segment pass
     uint64_t modulo = 0, bucket_begin = 0, n_buckets = 0;
     int64_t n = 0;
 };
@@ -90,15 +90,16 @@ __device__ __forceinline__ bool cand_of(const ProbeDev &t, uint64_t km, uint64_t
     return true;
 }
 
+// `add` is what a hit adds to its node's count: 1, or 2^32 - 1 where a signed pass takes hits away (uint32 wraps)
 __device__ __forceinline__ uint32_t cand_scan(const ProbeDev &t, uint4 e, int64_t max_hits, unsigned int *__restrict__ counts,
-                                              int64_t n_counts) {
+                                              int64_t n_counts, uint32_t add) {
     const uint64_t km = ((uint64_t)e.y << 32) | e.x;
     uint32_t hits = 0;
     for (int64_t j = e.z; j < (int64_t)e.z + (int64_t)e.w; j++) {
         const uint4 r = t.rows[j];
         if ((((uint64_t)r.y << 32) | r.x) != km) continue;              // :309
         if (hits == 0u && (int64_t)r.w > max_hits) break;               // :312 (frequency of the first match)
-        if ((int64_t)r.z < n_counts) atomicAdd(&counts[r.z], 1u);
+        if ((int64_t)r.z < n_counts) atomicAdd(&counts[r.z], add);
         hits++;
     }
     return hits;
@@ -106,13 +107,14 @@ __device__ __forceinline__ uint32_t cand_scan(const ProbeDev &t, uint4 e, int64_
 
 // works off the queue in groups of 64 (all of it when `all`); returns this lane's hits
 __device__ __forceinline__ uint32_t cand_drain(const ProbeDev &t, const uint4 *__restrict__ qe, int &n, bool all, int64_t max_hits,
-                                               unsigned int *__restrict__ counts, int64_t n_counts, int lane) {
+                                               unsigned int *__restrict__ counts, int64_t n_counts, int lane,
+                                               uint32_t add = 1u) {
     uint32_t hits = 0;
     __builtin_amdgcn_wave_barrier();
     while (n >= 64 || (all && n > 0)) {
         const int first = n >= 64 ? n - 64 : 0;
         const int mine = first + lane;
-        if (mine < n) hits += cand_scan(t, qe[mine], max_hits, counts, n_counts);
+        if (mine < n) hits += cand_scan(t, qe[mine], max_hits, counts, n_counts, add);
         n = first;
     }
     __builtin_amdgcn_wave_barrier();
@@ -269,10 +271,41 @@ __device__ __forceinline__ uint64_t spread32(uint64_t x) {
 // Reverse strand (read_kmers.py:23-26): the k-mers of str(Seq(read).reverse_complement()) are, window by window,
 // the reverse complements of the forward windows, with non-ACGT letters hashing as 0 on both strands
 // (Bio.Seq maps N to N): code' = acgt ? 3 - code : 0, window reversed.
-__global__ __launch_bounds__(256) void k_probe_reads(ProbeDev t, const uint8_t *__restrict__ reads,
-                                                     const int64_t *__restrict__ read_start, int64_t n_reads, int k,
-                                                     int strands, int64_t max_hits, unsigned int *__restrict__ counts,
-                                                     int64_t n_counts, unsigned long long *__restrict__ counters) {
+//
+// The walk is shared by k_probe_reads and k_probe_segments: `spans` says where span r lies in `reads`, spans.at(r, &s, &len).
+// A read is [read_start[r], read_start[r + 1]); a segment is seg_windows[r] windows from seg_start[r] on, and segments may
+// overlap one another in the letters.
+struct ReadSpans {
+    const int64_t *__restrict__ read_start;
+    __device__ __forceinline__ void at(int64_t r, int64_t *s, int64_t *len) const {
+        *s = read_start[r];
+        *len = read_start[r + 1] - *s;
+    }
+};
+
+// Whatever the arrays hold, [s, s + len) lies inside [0, n_letters): a segment that does not is cut to what does, and
+// *fault is raised for the entry to report.
+struct SegmentSpans {
+    const int64_t *__restrict__ seg_start, *__restrict__ seg_windows;
+    int64_t n_letters;
+    int k;
+    unsigned long long *__restrict__ fault;
+    __device__ __forceinline__ void at(int64_t r, int64_t *s, int64_t *len) const {
+        const int64_t a = seg_start[r], w = seg_windows[r];
+        const int64_t a_in = a < 0 ? 0 : a > n_letters ? n_letters : a;
+        const int64_t w_in = w < 0 ? 0 : w > n_letters ? n_letters : w;      // w_in + k - 1 cannot overflow
+        const int64_t want = w_in > 0 ? w_in + (k - 1) : 0, room = n_letters - a_in;
+        if (a != a_in || w != w_in || want > room) atomicOr(fault, 1ull);
+        *s = a_in;
+        *len = want < room ? want : room;
+    }
+};
+
+template <class Spans>
+__device__ __forceinline__ void probe_spans(const ProbeDev &t, const uint8_t *__restrict__ reads, const Spans &spans,
+                                            int64_t n_reads, int k, int strands, int64_t max_hits, uint32_t add,
+                                            unsigned int *__restrict__ counts, int64_t n_counts,
+                                            unsigned long long *__restrict__ counters) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -284,12 +317,12 @@ __global__ __launch_bounds__(256) void k_probe_reads(ProbeDev t, const uint8_t *
     // Letters are fetched one step ahead (the next 64 letters of this read, or the first 64 of the wave's next read)
     // so that their latency hides behind the directory loads of the current step.
     int64_t r = wave, s = 0, len = 0;
-    if (r < n_reads) { s = read_start[r]; len = read_start[r + 1] - s; }
+    if (r < n_reads) spans.at(r, &s, &len);
     unsigned ch_next = lane < len ? reads[s + lane] : 0u;
     while (r < n_reads) {
         const int64_t rn = r + n_waves;
         int64_t sn = 0, lenn = 0;
-        if (rn < n_reads) { sn = read_start[rn]; lenn = read_start[rn + 1] - sn; }
+        if (rn < n_reads) spans.at(rn, &sn, &lenn);
         if (len < k) {
             ch_next = lane < lenn ? reads[sn + lane] : 0u;
         } else {
@@ -333,16 +366,35 @@ __global__ __launch_bounds__(256) void k_probe_reads(ProbeDev t, const uint8_t *
                 if (c > 0) {                                             // wave-uniform: the queue uses ballots
                     cand_push(qe, n_c, cand_f, fw, sf, cf, lane);
                     cand_push(qe, n_c, cand_r, rc, sr, cr, lane);
-                    hits += cand_drain(t, qe, n_c, false, max_hits, counts, n_counts, lane);
+                    hits += cand_drain(t, qe, n_c, false, max_hits, counts, n_counts, lane, add);
                 }
                 C0 = N0; C1 = N1; Cm0 = Nm0; Cm1 = Nm1;
             }
         }
         r = rn; s = sn; len = lenn;
     }
-    hits += cand_drain(t, qe, n_c, true, max_hits, counts, n_counts, lane);
+    hits += cand_drain(t, qe, n_c, true, max_hits, counts, n_counts, lane, add);
     wave_add(&counters[0], hits);
     wave_add(&counters[1], probed);
+}
+
+__global__ __launch_bounds__(256) void k_probe_reads(ProbeDev t, const uint8_t *__restrict__ reads,
+                                                     const int64_t *__restrict__ read_start, int64_t n_reads, int k,
+                                                     int strands, int64_t max_hits, unsigned int *__restrict__ counts,
+                                                     int64_t n_counts, unsigned long long *__restrict__ counters) {
+    probe_spans(t, reads, ReadSpans{read_start}, n_reads, k, strands, max_hits, 1u, counts, n_counts, counters);
+}
+
+// One wave per segment of a sequence that stays where it is: the windows' letters are read in place, no
+// hash is stored, and every hit adds `add` to its node.  counters[2] is the fault word of SegmentSpans.
+__global__ __launch_bounds__(256) void k_probe_segments(ProbeDev t, const uint8_t *__restrict__ letters, int64_t n_letters,
+                                                        const int64_t *__restrict__ seg_start,
+                                                        const int64_t *__restrict__ seg_windows, int64_t n_segs, int k,
+                                                        int strands, int64_t max_hits, uint32_t add,
+                                                        unsigned int *__restrict__ counts, int64_t n_counts,
+                                                        unsigned long long *__restrict__ counters) {
+    probe_spans(t, letters, SegmentSpans{seg_start, seg_windows, n_letters, k, &counters[2]}, n_segs, k, strands, max_hits,
+                add, counts, n_counts, counters);
 }
 
 static ProbeDev dev_of(const gki_probe *p) {
@@ -368,7 +420,7 @@ static int probe_init(gki_probe *p, const gki_index_view *ix) {
     p->bucket_begin = ix->n_buckets ? ix->bucket_begin : 0; p->n_buckets = ix->n_buckets ? ix->n_buckets : ix->modulo;
     HIP_TRY(gki_dev_malloc(&p->dir, (size_t)p->n_buckets * sizeof(uint2)));
     HIP_TRY(gki_dev_malloc(&p->rows, (size_t)(ix->n > 0 ? ix->n : 1) * sizeof(uint4)));
-    HIP_TRY(gki_dev_malloc(&p->counters, 2 * sizeof(unsigned long long)));
+    HIP_TRY(gki_dev_malloc(&p->counters, 3 * sizeof(unsigned long long)));
     if (ix->n > 0)
         hipLaunchKernelGGL(k_probe_rows, dim3(stream_grid(ix->n, 256)), dim3(256), 0, 0, (const uint64_t *)ix->d_kmers,
                            (const uint32_t *)ix->d_nodes, (const uint16_t *)ix->d_frequencies, ix->n, p->rows);
@@ -425,6 +477,33 @@ int gki_probe_reads_count_nodes(gki_probe *p, const void *d_reads, const void *d
                        p->counters);
     HIP_TRY(hipGetLastError());
     return read_counters(p, n_hits, n_kmers);
+}
+
+int gki_probe_segments_count_nodes(gki_probe *p, const void *d_letters, int64_t n_letters, const void *d_seg_start,
+                                   const void *d_seg_windows, int64_t n_segs, int k, int strands, int64_t max_hits, int sign,
+                                   void *d_counts, int64_t n_counts, int64_t *n_kmers, int64_t *n_hits) {
+    if (n_hits) *n_hits = 0;
+    if (n_kmers) *n_kmers = 0;
+    if (p == nullptr) return gki_set_error(GKI_ERR_BAD_ARG, "probe_segments_count_nodes: the probe table is NULL");
+    if (k < 1 || k > GKI_MAX_K) return gki_set_error(GKI_ERR_BAD_ARG, "k must be in 1..31");
+    if (strands < 1 || strands > 3) return gki_set_error(GKI_ERR_BAD_ARG, "strands must be 1 (forward), 2 (reverse) or 3 (both)");
+    if (sign != 1 && sign != -1) return gki_set_error(GKI_ERR_BAD_ARG, "probe_segments_count_nodes: sign must be +1 or -1");
+    if (n_letters < 0 || n_segs < 0 || n_counts < 0 || (n_letters > 0 && d_letters == nullptr) || (n_counts > 0 && d_counts == nullptr) ||
+        (n_segs > 0 && (d_seg_start == nullptr || d_seg_windows == nullptr)))
+        return gki_set_error(GKI_ERR_BAD_ARG, "probe_segments_count_nodes: a size is negative or an array is NULL");
+    if (n_segs == 0) return GKI_OK;
+    HIP_TRY(hipMemsetAsync(p->counters, 0, 3 * sizeof(unsigned long long), 0));
+    int64_t blocks = ceil_div(n_segs, 4);
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    hipLaunchKernelGGL(k_probe_segments, dim3((unsigned)blocks), dim3(256), 0, 0, dev_of(p), (const uint8_t *)d_letters, n_letters,
+                       (const int64_t *)d_seg_start, (const int64_t *)d_seg_windows, n_segs, k, strands, max_hits,
+                       sign > 0 ? 1u : 0xFFFFFFFFu, (unsigned int *)d_counts, n_counts, p->counters);
+    HIP_TRY(hipGetLastError());
+    GKI_TRY(read_counters(p, n_hits, n_kmers));
+    unsigned long long fault = 0;
+    HIP_TRY(hipMemcpy(&fault, p->counters + 2, sizeof(fault), hipMemcpyDeviceToHost));
+    if (fault) return gki_set_error(GKI_ERR_BAD_ARG, "probe_segments_count_nodes: a segment reaches outside the %lld letters; it was cut", (long long)n_letters);
+    return GKI_OK;
 }
 
 int gki_probe_contains(gki_probe *p, const void *d_queries, int64_t q, void *d_flags) {

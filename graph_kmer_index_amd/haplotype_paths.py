@@ -10,6 +10,10 @@ every path and a kept line's two allele nodes lie side by side in `seq`, so a ha
 node per kept line cut out -- an output-dense gather.  `.sequence(slot)` returns a `fasta_files.DeviceReference`, so
 `linear_kmers_on_device`, `ReferenceKmerIndex` and the graph build's `records` take a haplotype where they take a reference;
 `.node_counts` composes the spelling with `linear_kmers_on_device` and `DeviceIndex.count_nodes`.
+
+`.node_counts_by_difference` gives the same rows without probing what a slot shares with the linear reference, and
+`.node_count_model` sums them per sampled individual into a `NodeCountModel` (the kernels are
+csrc/gki_haplotype_counts.hip and k_probe_segments of csrc/gki_probe.hip).
 """
 import collections
 import ctypes as C
@@ -99,6 +103,58 @@ def kmer_passes(bounds, k, chunk_kmers):
     return passes
 
 
+def whole_segments(bounds, k, windows=4096):
+    """All windows of every record [bounds[c], bounds[c + 1]) as segments of at most `windows` windows, in order: (start
+    int64[], windows int64[]).  A record shorter than k has none.  A loop over the records, not over their letters."""
+    starts, counts = [], []
+    for a, b in zip(bounds[:-1], bounds[1:]):
+        n = int(b) - int(a) - k + 1
+        if n > 0:
+            first = np.arange(int(a), int(a) + n, windows, dtype=np.int64)
+            starts.append(first)
+            counts.append(np.minimum(int(a) + n - first, windows))
+    if not starts:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    return np.concatenate(starts), np.concatenate(counts).astype(np.int64)
+
+
+class NodeCountModel:
+    """Per data line, allele (0 the ref node, 1 the var node) and number of copies of that allele an individual carries
+    (0 .. ploidy): how the node's count is spread over the sampled individuals.  `histogram` uint32[V][2][ploidy + 1][n_bins]
+    counts the individuals by min(count, n_bins - 1), `count_sum` uint64[V][2][ploidy + 1] sums their counts.  Lines that
+    are not kept are all zero.  `samples` are the individuals that went in, in the order given."""
+
+    def __init__(self, histogram, count_sum, k, ploidy, n_bins, samples):
+        self.k, self.ploidy, self.n_bins = int(k), int(ploidy), int(n_bins)
+        histogram, count_sum = np.asarray(histogram), np.asarray(count_sum)
+        per_line = 2 * (self.ploidy + 1)
+        self.histogram = np.ascontiguousarray(histogram, dtype=np.uint32).reshape(
+            histogram.size // (per_line * self.n_bins), 2, self.ploidy + 1, self.n_bins)
+        self.count_sum = np.ascontiguousarray(count_sum, dtype=np.uint64).reshape(
+            count_sum.size // per_line, 2, self.ploidy + 1)
+        self.samples = np.ascontiguousarray(samples, dtype=np.int64)
+        if len(self.histogram) != len(self.count_sum):
+            raise ValueError("the histogram has %d lines, count_sum has %d" % (len(self.histogram), len(self.count_sum)))
+
+    def mean(self):
+        """float64[V][2][ploidy + 1]: count_sum over the individuals of the entry, NaN where there is none."""
+        n = self.histogram.sum(axis=3, dtype=np.int64)
+        out = np.full(n.shape, np.nan)
+        np.divide(self.count_sum, n, out=out, where=n > 0)
+        return out
+
+    def to_file(self, file_name):
+        """np.savez with keys named after the attributes."""
+        np.savez(file_name, histogram=self.histogram, count_sum=self.count_sum, k=np.int64(self.k),
+                 ploidy=np.int64(self.ploidy), n_bins=np.int64(self.n_bins), samples=self.samples)
+
+    @classmethod
+    def from_file(cls, file_name):
+        file_name = str(file_name)
+        d = np.load(file_name if file_name.endswith(".npz") else file_name + ".npz")
+        return cls(d["histogram"], d["count_sum"], int(d["k"]), int(d["ploidy"]), int(d["n_bins"]), d["samples"])
+
+
 class HaplotypeToNodes:
     """The variant nodes every haplotype slot carries: slot h's are nodes[start[h]:start[h + 1]], in line order (`start`
     int64[H + 1], `nodes` uint32).  Valid only with the graph and variant-to-nodes it was made from; slots are numbered
@@ -145,6 +201,7 @@ class HaplotypePaths:
 
     def __init__(self, graph, variant_to_nodes, matrix):
         self._plan, self._alt_bits, self._owns_plane = None, None, False
+        self._ref_path, self._base_rows = None, {}         # the all-ref path's (letters, bounds); key -> (device index, base row)
         n_lines = len(np.asarray(variant_to_nodes.var_nodes))
         if isinstance(matrix, AltPlane):
             n_variants, self.n_slots = int(matrix.n_variants), int(matrix.n_slots)
@@ -200,30 +257,40 @@ class HaplotypePaths:
             if self._owns_plane:
                 self._alt_bits.free()
             self._alt_bits = None
+        if self._ref_path is not None:
+            self._ref_path[0].free()
+            self._ref_path = None
+        while self._base_rows:
+            self._base_rows.popitem()[1][1].free()
 
     def _open(self):
         if self._plan is None:
             raise ValueError("the HaplotypePaths is closed")
         return _lib.load()
 
-    def sequence(self, slot):
-        """Slot `slot`'s sequence as a DeviceReference: `.letters` upper-case ACGT, record c (named str(c + 1)) the
-        haplotype's chromosome c.  `.timings` holds the count pass' and the spelling kernel's device time in ms.  The
-        caller frees it.  IndexError for a slot outside 0 .. H - 1."""
+    def _spell(self, plane, n_slots, slot):
+        """Slot `slot` of `plane` spelled: (letters, which the caller frees, bounds, count ms, spell ms)."""
         lib = self._open()
-        slot = check_slot(slot, self.n_slots)
         n_out, ms_count, ms_spell = C.c_int64(0), C.c_float(0), C.c_float(0)
         bounds = np.zeros(self.n_chromosomes + 1, dtype=np.int64)
-        _lib.check(lib.gki_haplotype_spell_count(self._plan, self._alt_bits.ptr, self.n_slots, slot, C.byref(n_out),
+        _lib.check(lib.gki_haplotype_spell_count(self._plan, plane.ptr, n_slots, slot, C.byref(n_out),
                                                  _lib.hptr(bounds), C.byref(ms_count)))
         with _lib.DeviceScope() as s:
             letters = s.array(max(n_out.value, 1), np.uint8)
             letters.n = n_out.value
             _lib.check(lib.gki_haplotype_spell_emit(self._plan, letters.ptr, C.byref(ms_spell)))
             s.release(letters)
+        return letters, bounds, float(ms_count.value), float(ms_spell.value)
+
+    def sequence(self, slot):
+        """Slot `slot`'s sequence as a DeviceReference: `.letters` upper-case ACGT, record c (named str(c + 1)) the
+        haplotype's chromosome c.  `.timings` holds the count pass' and the spelling kernel's device time in ms.  The
+        caller frees it.  IndexError for a slot outside 0 .. H - 1."""
+        self._open()
+        slot = check_slot(slot, self.n_slots)
+        letters, bounds, ms_count, ms_spell = self._spell(self._alt_bits, self.n_slots, slot)
         names = [str(c + 1) for c in range(self.n_chromosomes)]
-        return DeviceReference(names, bounds, letters, list(names),
-                               {"count_kernel_ms": float(ms_count.value), "spell_kernel_ms": float(ms_spell.value)})
+        return DeviceReference(names, bounds, letters, list(names), {"count_kernel_ms": ms_count, "spell_kernel_ms": ms_spell})
 
     def alt_nodes(self, kernel_ms=None):
         """The alt nodes of all slots as a HaplotypeToNodes.  kernel_ms: a list that receives (count ms, emit ms)."""
@@ -279,6 +346,164 @@ class HaplotypePaths:
                     timings.append({"slot": slot, "letters": ref.letters.n, "spell_s": t1 - t0, "hash_s": hash_s,
                                     "probe_s": probe_s, "total_s": time.perf_counter() - t0, **ref.timings})
         return out
+
+    # ------------------------------------------------------------------ counts by difference from the all-ref path
+    def _reference_path(self):
+        """(letters, bounds) of the all-ref path -- a slot whose plane is all zero -- spelled once and kept."""
+        self._open()
+        if self._ref_path is None:
+            with _lib.DeviceScope() as s:
+                zero = s.array(max((self.n_lines + 63) // 64, 1), np.uint64)
+                zero.zero()
+                letters, bounds, _, _ = self._spell(zero, 1, 0)
+            self._ref_path = (letters, bounds)
+        return self._ref_path
+
+    def _base_row(self, index, k, n_nodes, strands):
+        """The all-ref path's node counts as a uint32 DeviceArray, made once per (index, k, n_nodes, strands) and kept.
+        The key is the index's DeviceIndex, which the entry holds on to: an index that drops its device copy and makes
+        another (remove_frequencies and the like) gets a new base row, never the stale one."""
+        self._open()
+        device_index = index._device_index()
+        key = (id(device_index), int(k), int(n_nodes), int(strands))
+        if key not in self._base_rows:
+            letters, bounds = self._reference_path()
+            start, windows = whole_segments(bounds, k)
+            with _lib.DeviceScope() as s:
+                row = zeroed_counts(s, n_nodes)
+                device_index.count_nodes_from_segments(letters, start, windows, k, row, n_nodes, strands)
+                self._base_rows[key] = (device_index, s.release(row))
+        return self._base_rows[key][1]
+
+    def reference_node_counts(self, index, k, n_nodes=None, include_reverse_complement=True):
+        """uint32[n_nodes] on the host: the node hit counts of the all-ref path, what `node_counts` gives for a slot that
+        takes no alt allele.  The path's letters and this row stay on the device until close(), for
+        `node_counts_by_difference` and `node_count_model` to start from."""
+        if n_nodes is None:
+            n_nodes = int(index.max_node_id()) + 1
+        return self._base_row(index, k, n_nodes, 3 if include_reverse_complement else 1).to_host(int(n_nodes))
+
+    def _apply_slot(self, slot, row, device_index, k, n_nodes, strands):
+        """row += counts(slot) - counts(all-ref path), by the two segment passes; returns the slot's timing dict."""
+        lib = self._open()
+        ref_letters, _ = self._reference_path()
+        with _lib.DeviceScope() as s:
+            t0 = time.perf_counter()
+            seq = s.keep(self.sequence(slot))              # leaves the slot's before / cut / bounds in the plan
+            t1 = time.perf_counter()
+            totals = [C.c_int64(0) for _ in range(5)]
+            ms_count, ms_emit = C.c_float(0), C.c_float(0)
+            _lib.check(lib.gki_haplotype_segments_count(self._plan, self._alt_bits.ptr, self.n_slots, slot, int(k),
+                                                        *[C.byref(t) for t in totals], C.byref(ms_count)))
+            n_taken, n_ref, ref_windows, n_slot, slot_windows = [t.value for t in totals]
+            ref_start, ref_n = s.array(max(n_ref, 1), np.int64), s.array(max(n_ref, 1), np.int64)
+            slot_start, slot_n = s.array(max(n_slot, 1), np.int64), s.array(max(n_slot, 1), np.int64)
+            _lib.check(lib.gki_haplotype_segments_emit(self._plan, ref_start.ptr, ref_n.ptr, slot_start.ptr, slot_n.ptr,
+                                                       C.byref(ms_emit)))
+            t2 = time.perf_counter()
+            device_index.count_nodes_from_segments(ref_letters, ref_start, ref_n, k, row, n_nodes, strands, sign=-1,
+                                                   n_segs=n_ref)
+            t3 = time.perf_counter()
+            device_index.count_nodes_from_segments(seq.letters, slot_start, slot_n, k, row, n_nodes, strands, sign=1,
+                                                   n_segs=n_slot)
+            t4 = time.perf_counter()
+            return {"slot": slot, "letters": seq.letters.n, "taken_lines": n_taken, "ref_segments": n_ref,
+                    "ref_windows": ref_windows, "slot_segments": n_slot, "slot_windows": slot_windows,
+                    "spell_s": t1 - t0, "segments_s": t2 - t1, "subtract_s": t3 - t2, "add_s": t4 - t3, "total_s": t4 - t0,
+                    "segments_kernel_ms": float(ms_count.value) + float(ms_emit.value), **seq.timings}
+
+    def segments(self, slot, k):
+        """The segments of slot `slot` read back: ((start, windows) in the all-ref path, (start, windows)
+        in the slot's sequence), int64 arrays.  For inspection and tests; the count routes keep them on the device."""
+        lib = self._open()
+        slot = check_slot(slot, self.n_slots)
+        with _lib.DeviceScope() as s:
+            s.keep(self._spell(self._alt_bits, self.n_slots, slot)[0])
+            totals = [C.c_int64(0) for _ in range(5)]
+            _lib.check(lib.gki_haplotype_segments_count(self._plan, self._alt_bits.ptr, self.n_slots, slot, int(k),
+                                                        *[C.byref(t) for t in totals], None))
+            n_ref, n_slot = totals[1].value, totals[3].value
+            arrays = [s.array(max(n, 1), np.int64) for n in (n_ref, n_ref, n_slot, n_slot)]
+            _lib.check(lib.gki_haplotype_segments_emit(self._plan, *[a.ptr for a in arrays], None))
+            out = [a.to_host(n) for a, n in zip(arrays, (n_ref, n_ref, n_slot, n_slot))]
+        return (out[0], out[1]), (out[2], out[3])
+
+    def node_counts_by_difference(self, slots, index, k, n_nodes=None, include_reverse_complement=True, timings=None):
+        """What `node_counts` returns, by another route: counts(slot) = counts(all-ref path) - counts(the all-ref path's
+        segments) + counts(the slot's segments), the segments being the windows that touch an allele the slot replaces or
+        takes.  Per slot: spell, list the segments, copy the base row, one signed probe pass over each segment list.
+        timings: a list that receives one dict per slot (seconds per stage, synchronised, and the windows probed)."""
+        self._open()
+        slots = [check_slot(h, self.n_slots) for h in slots]
+        if n_nodes is None:
+            n_nodes = int(index.max_node_id()) + 1
+        strands = 3 if include_reverse_complement else 1
+        device_index = index._device_index()
+        base = self._base_row(index, k, n_nodes, strands)
+        out = np.zeros((len(slots), int(n_nodes)), dtype=np.uint32)
+        for i, slot in enumerate(slots):
+            with _lib.DeviceScope() as s:
+                row = s.array(base.n, np.uint32)
+                _lib.check(_lib.load().gki_memcpy_d2d(row.ptr, base.ptr, base.nbytes))
+                t = self._apply_slot(slot, row, device_index, k, n_nodes, strands)
+                out[i] = row.to_host(int(n_nodes))
+                if timings is not None:
+                    timings.append(t)
+        return out
+
+    def node_count_model(self, index, k, samples=None, n_bins=5, n_nodes=None, include_reverse_complement=True,
+                         route="difference", ploidy=None, timings=None):
+        """The NodeCountModel of the individuals `samples` (default: all): sample s owns the slots s * ploidy ..
+        s * ploidy + ploidy - 1 and its row is the sum of its slots' node counts.  route "difference" starts every row from
+        ploidy x the base row and applies each slot's two segment passes; "whole" sums `node_counts` rows instead, for
+        comparison.  With an AltPlane the caller passes `ploidy`.  ValueError for n_bins < 2, IndexError for a sample
+        outside the matrix.  timings: a list that receives one dict per slot of the difference route."""
+        lib = self._open()
+        if self.ploidy is not None and ploidy is not None and int(ploidy) != self.ploidy:
+            raise ValueError("ploidy %d was given, the matrix has %d" % (int(ploidy), self.ploidy))
+        ploidy = self.ploidy if self.ploidy is not None else ploidy
+        if ploidy is None:
+            raise ValueError("an AltPlane has no ploidy: pass ploidy=")
+        ploidy = int(ploidy)
+        if not 1 <= ploidy <= 8:
+            raise ValueError("ploidy must be in 1..8")
+        if int(n_bins) < 2:
+            raise ValueError("n_bins must be at least 2")
+        if route not in ("difference", "whole"):
+            raise ValueError("route must be 'difference' or 'whole'")
+        n_samples, n_bins = self.n_slots // ploidy, int(n_bins)
+        samples = list(range(n_samples)) if samples is None else [int(x) for x in samples]
+        for x in samples:
+            if not 0 <= x < n_samples:
+                raise IndexError("sample %d is outside 0 .. %d" % (x, n_samples - 1))
+        if n_nodes is None:
+            n_nodes = int(index.max_node_id()) + 1
+        strands = 3 if include_reverse_complement else 1
+        entries = self.n_lines * 2 * (ploidy + 1)
+        with _lib.DeviceScope() as s:
+            histogram, count_sum = s.array(max(entries * n_bins, 1), np.uint32), s.array(max(entries, 1), np.uint64)
+            histogram.zero(), count_sum.zero()
+            row = s.array(max(int(n_nodes), 1), np.uint32)
+            if route == "difference":
+                device_index = index._device_index()
+                base = self._base_row(index, k, n_nodes, strands)
+            for x in samples:
+                slots = range(x * ploidy, x * ploidy + ploidy)
+                if route == "difference":
+                    _lib.check(lib.gki_node_count_model_row_start(base.ptr, int(n_nodes), ploidy, row.ptr))
+                    for slot in slots:
+                        t = self._apply_slot(slot, row, device_index, k, n_nodes, strands)
+                        if timings is not None:
+                            timings.append(t)
+                else:
+                    whole = self.node_counts(list(slots), index, k, n_nodes, include_reverse_complement)
+                    host = np.zeros(row.n, dtype=np.uint32)
+                    host[:int(n_nodes)] = whole.sum(axis=0, dtype=np.uint32)
+                    _lib.check(lib.gki_memcpy_h2d(row.ptr, _lib.hptr(host), host.nbytes))
+                _lib.check(lib.gki_node_count_model_accumulate(self._plan, self._alt_bits.ptr, self.n_slots, x * ploidy, ploidy,
+                                                               row.ptr, int(n_nodes), n_bins, histogram.ptr, count_sum.ptr,
+                                                               None))
+            return NodeCountModel(histogram.to_host(entries * n_bins), count_sum.to_host(entries), k, ploidy, n_bins, samples)
 
 
 def write_fasta(file_name, names, records, width=60):

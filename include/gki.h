@@ -875,6 +875,65 @@ int gki_haplotype_alt_nodes_emit(gki_haplotype_paths *plan, const void *d_alt_bi
                                  float *kernel_ms);
 int gki_haplotype_paths_destroy(gki_haplotype_paths *plan);
 
+/* ---------------------------------------------------------------- haplotype segments (node counts by difference from the all-ref path)
+ * A slot's node counts without probing what it shares with the linear reference.  Everything is said per
+ * sequence, in that sequence's own coordinates.  A sequence is either the all-ref path (a slot whose plane is all zero) or
+ * slot h.  Each has chromosome bounds bounds[c], as gki_haplotype_spell_count returns them.
+ *   taken lines    the taken lines t of slot h are the kept lines with alt_bits[h] & kept_bits set, in line order.  Codes 0,
+ *                  2 and 3 are not taken, as in "haplotype paths".
+ *   interval       a taken line has a half-open interval [a, b) in each sequence: in the all-ref path the position of the
+ *                  line's ref allele, in the slot's sequence the position of its alt allele.  Either may be empty, with
+ *                  a == b at the junction: an insertion's ref allele or a deletion's alt allele.
+ *   dirty windows  window start s (letters s .. s + k - 1) is dirty with respect to [a, b) exactly when s < b and
+ *                  a < s + k.  With a == b this means the window holds both a - 1 and a.
+ *   segments       each dirty window goes to the first taken line it is dirty for.  That makes the dirty windows of line t
+ *                  in chromosome c the run lo = max(a_t - k + 1, b_prev, bounds[c]) .. hi = min(b_t - 1, bounds[c + 1] - k),
+ *                  b_prev the interval end of the previous taken line, or 0 for the first.  The run is empty when hi < lo; a
+ *                  chromosome shorter than k has no runs.  A segment is (start = lo, windows = hi - lo + 1); its letters are
+ *                  [lo, hi + k).
+ *   identity       over the k-mers of both strands as asked for: counts(slot) = counts(all-ref path) - counts(segments of
+ *                  the all-ref path) + counts(segments of the slot's sequence), exact node by node.  max_hits is a rule per
+ *                  k-mer and passes through unchanged.
+ * gki_haplotype_segments_count / _emit list both sequences' segments of one slot.  The count call must follow the
+ * gki_haplotype_spell_count call of the same slot and plane (GKI_ERR_STATE otherwise; the spell emit call may lie between):
+ * it reads the before / cut / bounds that call left in the plan.  It returns the taken lines, and per sequence the segments
+ * and the windows in them; no per-line array leaves the device.  The emit call writes d_ref_seg_start / d_ref_seg_windows
+ * int64[n_ref_segs] and d_slot_seg_start / d_slot_seg_windows int64[n_slot_segs], in line order (a list of no segments may be
+ * NULL), and must follow its count call with no other slot or plane spelled between (GKI_ERR_STATE).  k is 1..31.  *kernel_ms (may be
+ * NULL): the device time of the call's kernels. */
+int gki_haplotype_segments_count(gki_haplotype_paths *plan, const void *d_alt_bits, int64_t n_slots, int64_t slot, int k,
+                                 int64_t *n_taken, int64_t *n_ref_segs, int64_t *n_ref_windows, int64_t *n_slot_segs,
+                                 int64_t *n_slot_windows, float *kernel_ms);
+int gki_haplotype_segments_emit(gki_haplotype_paths *plan, void *d_ref_seg_start, void *d_ref_seg_windows,
+                                void *d_slot_seg_start, void *d_slot_seg_windows, float *kernel_ms);
+/* gki_probe_reads_count_nodes over segments of a sequence that stays where it is: segment i is the d_seg_windows[i] windows
+ * (int64) that start at d_seg_start[i] (int64) .. in d_letters uint8[n_letters], so it reads the letters [seg_start[i],
+ * seg_start[i] + seg_windows[i] + k - 1).  Segments may overlap one another; nothing is copied and no hash is stored.  Every
+ * hit adds sign (+1 or -1) to d_counts uint32[n_counts] modulo 2^32: an intermediate wrap is harmless where the final value
+ * is not negative.  strands and max_hits as in gki_probe_reads_count_nodes; *n_kmers / *n_hits (nullable) the k-mers probed
+ * and the hits.  The kernel reads nothing outside d_letters[0, n_letters) whatever the segment arrays hold: a segment that
+ * reaches outside is cut to what lies inside, the others are counted as they are, and the call returns GKI_ERR_BAD_ARG. */
+int gki_probe_segments_count_nodes(gki_probe *p, const void *d_letters, int64_t n_letters, const void *d_seg_start,
+                                   const void *d_seg_windows, int64_t n_segs, int k, int strands, int64_t max_hits, int sign,
+                                   void *d_counts, int64_t n_counts, int64_t *n_kmers, int64_t *n_hits);
+/* ---------------------------------------------------------------- node count model
+ * What a genotyper fits on the node counts of sampled individuals: per kept line, allele (0 ref node, 1 var node) and number
+ * of copies of that allele the individual carries (0 .. ploidy), a histogram of the node's count over the individuals and
+ * the counts' sum.  d_histogram uint32[V][2][ploidy + 1][n_bins], d_count_sum uint64[V][2][ploidy + 1]; lines that are not
+ * kept are never touched.
+ * gki_node_count_model_accumulate adds one individual: d_row uint32[n_nodes] its node counts (a node at or beyond n_nodes
+ * counts 0) and the slots first_slot .. first_slot + ploidy - 1 of d_alt_bits uint64[n_slots][W] its haplotypes.  With
+ * c_alt = the number of those slots that take the line's alt allele, entry (line, 0, ploidy - c_alt) is updated with
+ * row[ref node] and entry (line, 1, c_alt) with row[var node]; an update does histogram[..][min(count, n_bins - 1)] += 1
+ * and count_sum[..] += count.  One lane per kept line, no atomics.  GKI_ERR_BAD_ARG for a ploidy outside 1..8, n_bins
+ * outside 2..65536 and slots outside the plane.
+ * gki_node_count_model_row_start writes d_row[i] = ploidy * d_base[i] (uint32[n_nodes] both, modulo 2^32): where an
+ * individual's row starts when d_base holds the all-ref path's counts and each of its slots' two segment passes follows. */
+int gki_node_count_model_row_start(const void *d_base, int64_t n_nodes, int ploidy, void *d_row);
+int gki_node_count_model_accumulate(gki_haplotype_paths *plan, const void *d_alt_bits, int64_t n_slots, int64_t first_slot,
+                                    int ploidy, const void *d_row, int64_t n_nodes, int n_bins, void *d_histogram,
+                                    void *d_count_sum, float *kernel_ms);
+
 /* ---------------------------------------------------------------- BGZF (blocked gzip: the .gz reads files of bgzip / htslib)
  * A BGZF file is a chain of gzip members of at most 64 KiB, each with its compressed size in a 'BC' extra subfield, so
  * every member's raw DEFLATE payload, CRC-32 and ISIZE are found without inflating anything (graph_kmer_index_amd/bgzf.py
