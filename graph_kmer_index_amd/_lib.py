@@ -176,6 +176,14 @@ SYMBOLS = {
                                               C.POINTER(_I64), C.POINTER(_I64)]),
     "gki_node_count_model_row_start": (_I32, [_P, _I64, _I32, _P]),
     "gki_node_count_model_accumulate": (_I32, [_P, _P, _I64, _I64, _I32, _P, _I64, _I32, _P, _P, C.POINTER(C.c_float)]),
+    "gki_genotype_fit": (_I32, [_P, _P, _P, _I64, _I32, _I32, _I64, _P, _P, C.POINTER(_U64), C.POINTER(_I64),
+                                C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    "gki_genotype_scale": (_I32, [_P, _P, _I64, _P, _I64, _I64, _P, C.POINTER(C.c_float)]),
+    "gki_genotype_call": (_I32, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _I64, _I64, _P, C.c_double, C.c_double, _P, _P, _P,
+                                 C.POINTER(C.c_float)]),
+    "gki_vcf_genotypes_count": (_I32, [_P, _I64, _P, _P, _I64, _I32, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64),
+                                       C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    "gki_vcf_genotypes_emit": (_I32, [_P, _I64, _P, _P, _I64, _I32, _P, _I64, C.POINTER(_I64), C.POINTER(C.c_float)]),
     "gki_bgzf_inflate": (_I32, [_P, _I64, _P, _P, _P, _P, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(C.c_int)]),
     "gki_bgzf_inflate_kernel_ms": (_I32, [C.POINTER(C.c_float)]),
     "gki_last_byte_position": (_I32, [_P, _I64, _I32, C.POINTER(_I64)]),

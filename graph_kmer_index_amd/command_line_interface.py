@@ -26,6 +26,8 @@ collision_free_kmer_index.py:393-402).
         -m haplotypes.npz -i index.npz -k 31 -s 0,1,5 -o haplotype_counts [--route difference]
     python -m graph_kmer_index_amd.command_line_interface make_node_count_model -g graph.npz -V graph.variant_to_nodes.npz \
         -m haplotypes.npz -i index.npz -k 31 [-s 0,1,5] [-b 5] -o node_count_model
+    python -m graph_kmer_index_amd.command_line_interface genotype -V graph.variant_to_nodes.npz -M node_count_model.npz \
+        -c node_counts.npy -v variants.vcf.gz -o sample.vcf [-s name] [--coverage X] [--error 0.01] [--pseudo-count 1] [-L loglik]
 
 `-g` takes an obgraph file when obgraph is installed, else a GraphArrays .npz (GraphArrays.to_file).  `index -t N` runs
 one process per GPU (at most N, at most the visible devices), each on its own range of critical-path numbers, and
@@ -438,6 +440,27 @@ def make_node_count_model(args):
                  % (len(model.samples), len(model.histogram), model.n_bins, args.out_file_name))
 
 
+def genotype(args):
+    """One sample's genotypes from its node counts (what `map` writes) and the node count model, as a VCF with one sample
+    column: the model fitted, the sample called and the VCF's text made on the device (genotyper.py)."""
+    from .genotyper import Genotyper, write_genotyped_vcf
+    from .haplotype_paths import NodeCountModel
+    from .unique_variant_kmers import load_variant_to_nodes
+    counts = np.load(args.counts)
+    if counts.ndim != 1:
+        raise ValueError("%s holds %d-dimensional counts: genotype takes one sample's row" % (args.counts, counts.ndim))
+    with Genotyper(NodeCountModel.from_file(args.model), load_variant_to_nodes(args.variant_to_nodes), args.error,
+                   args.pseudo_count) as genotyper:
+        ploidy = genotyper.ploidy
+        calls = genotyper.genotype(counts, args.coverage, loglik=args.loglik is not None)
+    if args.loglik is not None:
+        np.save(args.loglik if args.loglik.endswith(".npy") else args.loglik + ".npy", calls.loglik)
+    n = write_genotyped_vcf(args.vcf, args.out_file_name, calls.call, calls.gq, ploidy, args.sample_name, args.chunk_bytes,
+                            args.inflate)
+    logging.info("Wrote %d data lines (%d not called) at coverage %g to %s"
+                 % (n, int(np.count_nonzero(calls.call < 0)), calls.coverage[0], args.out_file_name))
+
+
 def _haplotype_paths_arguments(p):
     p.add_argument("-g", "--graph", required=True)
     p.add_argument("-V", "--variant_to_nodes", required=True, help="built with the graph (make_graph writes both)")
@@ -627,6 +650,22 @@ def build_parser():
     p.add_argument("--route", required=False, choices=("whole", "difference"), default="difference")
     p.add_argument("-o", "--out-file-name", required=True, help="the model, as NodeCountModel.to_file writes it (.npz)")
     p.set_defaults(func=make_node_count_model)
+    p = sub.add_parser("genotype")
+    p.add_argument("-V", "--variant_to_nodes", required=True, help="built with the graph (make_graph writes both)")
+    p.add_argument("-M", "--model", required=True, help="what make_node_count_model writes")
+    p.add_argument("-c", "--counts", required=True, help="the sample's node counts, as map writes them (.npy)")
+    p.add_argument("-v", "--vcf", required=True, help="the VCF the graph was made from, optionally .gz (BGZF or gzip)")
+    p.add_argument("-o", "--out-file-name", required=True, help="the genotyped VCF, plain text")
+    p.add_argument("-s", "--sample-name", required=False, default="sample")
+    p.add_argument("--coverage", required=False, type=float, default=None,
+                   help="the sample's coverage relative to the model's individuals; default: estimated from the counts")
+    p.add_argument("--error", required=False, type=float, default=0.01)
+    p.add_argument("--pseudo-count", required=False, type=float, default=1.0)
+    p.add_argument("-L", "--loglik", required=False, default=None, help="np.save of float64[lines, ploidy + 1]")
+    p.add_argument("--inflate", required=False, choices=("auto", "host", "device"), default="auto",
+                   help="where a .gz VCF is inflated: auto = BGZF on the device, other gzip on the host")
+    p.add_argument("--chunk-bytes", required=False, type=int, default=None)
+    p.set_defaults(func=genotype)
     p = sub.add_parser("map")
     p.add_argument("-i", "--kmer-index", required=True)
     p.add_argument("-f", "--reads", required=True, help="FASTA or FASTQ, optionally .gz (gzip or BGZF)")

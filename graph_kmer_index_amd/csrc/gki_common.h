@@ -383,6 +383,13 @@ __device__ __forceinline__ int gki_wave_incl_sum(int x) {
     return x;
 }
 __device__ __forceinline__ uint32_t gki_wave_incl_sum(uint32_t x) { return (uint32_t)gki_wave_incl_sum((int)x); }
+// *dst += the sum of v over the wave's 64 lanes, one integer atomic per wave (none when the sum is 0).  Every lane of the
+// wave must be active: a caller's loop has the same trip count for all of them.
+__device__ __forceinline__ void wave_add64(unsigned long long *dst, uint64_t v) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_down(v, s, 64);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(dst, (unsigned long long)v);
+}
 // the value lane `l` (a constant) holds, in a scalar register
 __device__ __forceinline__ int gki_lane_value(int x, int l) { return __builtin_amdgcn_readlane(x, l); }
 

@@ -68,12 +68,6 @@ __device__ __forceinline__ void seg_run(int64_t a, int64_t b, int64_t b_prev, in
     *n = h >= l ? h - l + 1 : 0;
 }
 
-__device__ __forceinline__ void wave_add64(unsigned long long *dst, uint64_t v) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_down(v, s, 64);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(dst, (unsigned long long)v);
-}
-
 // One lane per taken line r; the trip count is the same for every lane of a wave, for wave_add64.  !EMIT: has_ref[r] and
 // has_slot[r] are 1 where the line's run in that sequence is not empty, windows[0 / 1] += the runs' lengths.  EMIT: the
 // runs are written where ref_at / slot_at say.

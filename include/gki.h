@@ -933,6 +933,68 @@ int gki_node_count_model_row_start(const void *d_base, int64_t n_nodes, int ploi
 int gki_node_count_model_accumulate(gki_haplotype_paths *plan, const void *d_alt_bits, int64_t n_slots, int64_t first_slot,
                                     int ploidy, const void *d_row, int64_t n_nodes, int n_bins, void *d_histogram,
                                     void *d_count_sum, float *kernel_ms);
+/* ---------------------------------------------------------------- genotyping
+ * The node count model and one sample's node counts -> a genotype per data line.  P = the model's ploidy (1..8), V = data
+ * lines, N = the individuals the model holds; allele a is 0 for the ref node and 1 for the var node, c a copy number 0..P,
+ * g a genotype = the number of alt copies, 0..P.  Line v is kept when var_nodes[v] != 0; its nodes are ref_nodes[v] and
+ * var_nodes[v] as variant-to-nodes has them (no bubble chain is assumed); a node at or beyond n_nodes counts 0.
+ *   n[v][a][c] = the sum of histogram[v][a][c][.] over the bins, s[v][a][c] = count_sum[v][a][c].
+ * fit, once per model (gki_genotype_fit):
+ *   mean      n > 0: mu[v][a][c] = double(s) / double(n), one division.  n == 0: with c' the populated copy number (n > 0)
+ *             nearest to c, the lower at a tie, mu[v][a][c] = max(0, mu[v][a][c'] + (c - c')).  A line that is not kept: 0.
+ *   n_alt     n_alt[v][g] = n[v][1][g], the prior's counts.
+ *   total     T = the sum of s[v][a][c] over the kept lines, all a and c: exact, modulo 2^64.
+ *   faults    the lowest line at fault and its kind: 1 = an allele of a kept line has no populated entry, 2 = an allele's
+ *             n[v][a][.] do not sum to N.  (*first_bad_line = -1, *first_bad_kind = 0: none.)
+ *   No log, no sum of doubles, nothing a compiler may contract: every mean is bit-equal to NumPy's.  d_mean is
+ *   double[2 (P + 1)][V] with entry a (P + 1) + c as its row, d_n_alt uint32[P + 1][V]: entry-major, so that a wave of the
+ *   call kernel reads whole lines.  n_bins is 2..65536.
+ * scale, once per row x = uint32[n_nodes] of a batch (gki_genotype_scale): h_sums[r] = S = the sum over the kept lines of
+ *   x[ref node] + x[var node], exact.  The caller's estimate is lambda = (double(S) * double(N)) / double(T): a baseline
+ *   that takes the sample's genotypes to be spread as the population's are.
+ * call, per row and kept line (gki_genotype_call), with error e > 0, pseudo_count alpha > 0 and the row's coverage
+ *   lambda > 0, all finite:
+ *     m[a][c] = lambda * (mu[v][a][c] + e)       pi[g] = (n_alt[v][g] + alpha) / (N + (P + 1) * alpha)
+ *     x0 = x[ref node], x1 = x[var node]
+ *     L[g] = x0 * log(m[0][P - g]) - m[0][P - g] + x1 * log(m[1][g]) - m[1][g] + log(pi[g])       left to right
+ *   (the Poisson term -lgamma(x + 1) is the same for every g and is left out).
+ *     loglik[v][g] = L[g] - max L         call[v] = the lowest g at the maximum (int8)
+ *     q = 4.342944819032518 * (L[call] - the greatest L[g] of g != call);  gq[v] = 99 when q >= 99, else floor(q) (uint8)
+ *   A line that is not kept gets call -1, gq 0 and loglik all 0.  d_counts uint32[n_samples][n_nodes] (at most 65535 rows),
+ *   h_coverage double[n_samples] on the host, d_call int8[n_samples][V], d_gq uint8[n_samples][V], d_loglik
+ *   double[n_samples][V][P + 1] or NULL.  Double precision throughout; no atomics.
+ * GKI_ERR_BAD_ARG for sizes, ploidy, n_bins, e, alpha or a coverage out of range.  *kernel_ms (may be NULL): the device time
+ * of the call's kernel. */
+int gki_genotype_fit(const void *d_histogram, const void *d_count_sum, const void *d_var_nodes, int64_t n_lines, int ploidy,
+                     int n_bins, int64_t n_individuals, void *d_mean, void *d_n_alt, uint64_t *model_total,
+                     int64_t *first_bad_line, int *first_bad_kind, float *kernel_ms);
+int gki_genotype_scale(const void *d_ref_nodes, const void *d_var_nodes, int64_t n_lines, const void *d_counts,
+                       int64_t n_samples, int64_t n_nodes, uint64_t *h_sums, float *kernel_ms);
+int gki_genotype_call(const void *d_mean, const void *d_n_alt, const void *d_ref_nodes, const void *d_var_nodes,
+                      int64_t n_lines, int ploidy, int64_t n_individuals, const void *d_counts, int64_t n_samples,
+                      int64_t n_nodes, const double *h_coverage, double error, double pseudo_count, void *d_call, void *d_gq,
+                      void *d_loglik, float *kernel_ms);
+/* ---------------------------------------------------------------- genotyped VCF text
+ * One piece of whole lines of VCF text in HBM -> the data lines of a VCF with one sample column.  Lines, '\r' and data
+ * lines are those of "VCF haplotype matrix" (vcf_line; the data lines numbered in text order).  d_call int8 and d_gq uint8
+ * hold n_calls entries and sit at the piece's first data line; a piece with more data lines than n_calls is refused
+ * (GKI_ERR_BAD_ARG, *n_data_lines set).
+ *   per data line   the bytes of its first eight fields -- from the line's begin to its eighth tab, or to its end --
+ *                   followed by "\tGT:GQ\t" GT ":" GQ "\n".  GT: P alleles joined by '/', first P - call times '0', then
+ *                   call times '1'; P times '.' for call -1.  GQ: the decimal number without leading zeros; '.' for call -1.
+ *   not written     header lines, blank lines, and whatever follows field 8 (FORMAT and sample columns of the input).
+ *   faults          the lowest data line at fault (numbered from the piece's first) and its kind: 1 = fewer than eight
+ *                   fields, 2 = a call outside -1 .. P.
+ * gki_vcf_genotypes_count gives the piece's data lines, the bytes of its output and the fault.  gki_vcf_genotypes_emit
+ * writes d_out[0, *n_out_bytes) (16-byte aligned); it keeps no state and makes the count pass again.  It refuses a piece at
+ * fault and an out_capacity below the output's bytes with GKI_ERR_BAD_ARG and then writes nothing.  Offsets are 64 bits
+ * wide; a line may be of any length; a piece is at most 2^32 - 65 bytes.  ploidy is 1..8.  *kernel_ms (may be NULL): the
+ * device time of the lengths kernel and its scan, in the emit call with that of the emit kernels added. */
+int gki_vcf_genotypes_count(const void *d_text, int64_t n_bytes, const void *d_call, const void *d_gq, int64_t n_calls,
+                            int ploidy, int64_t *n_data_lines, int64_t *n_out_bytes, int64_t *first_bad_line,
+                            int *first_bad_kind, float *kernel_ms);
+int gki_vcf_genotypes_emit(const void *d_text, int64_t n_bytes, const void *d_call, const void *d_gq, int64_t n_calls,
+                           int ploidy, void *d_out, int64_t out_capacity, int64_t *n_out_bytes, float *kernel_ms);
 
 /* ---------------------------------------------------------------- BGZF (blocked gzip: the .gz reads files of bgzip / htslib)
  * A BGZF file is a chain of gzip members of at most 64 KiB, each with its compressed size in a 'BC' extra subfield, so
