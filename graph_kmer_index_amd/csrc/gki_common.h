@@ -111,17 +111,18 @@ __device__ __forceinline__ uint64_t gki_mod(const GkiMod &d, uint64_t x) {
     return r;
 }
 
-// ---------------------------------------------------------------------------------- get_frequency on the device
-// CollisionFreeKmerIndex.get_frequency with its defaults (collision_free_kmer_index.py:336-352): the first hit's frequency
-// of a k-mer plus that of its reverse complement, which the reference takes at k = 31 whatever the caller's k is.
-// Shared by gki_variant_kmers.hip and gki_sv_kmers.hip.
-// rc(x) at k = 31: digit-reverse(~x) (gki_hash.hip, kmer_hashing.py:24-28)
-__device__ __forceinline__ uint64_t gki_revcomp31(uint64_t x) {
-    uint64_t y = __brevll(~(x & ((1ull << 62) - 1ull)));
+// ---------------------------------------------------------------------------------- reverse complement of a hash
+// rc(x) = digit-reverse(~x) >> (64 - 2k) for x < 4^k (kmer_hashing.py:24-28 restated on bits; SURVEY.md 8a')
+__device__ __forceinline__ uint64_t gki_revcomp(uint64_t x, int k) {
+    uint64_t y = __brevll(~x);
     y = ((y & 0xAAAAAAAAAAAAAAAAull) >> 1) | ((y & 0x5555555555555555ull) << 1);
-    return y >> 2;
+    return y >> (64 - 2 * k);
 }
 
+// ---------------------------------------------------------------------------------- get_frequency on the device
+// CollisionFreeKmerIndex.get_frequency with its defaults (collision_free_kmer_index.py:336-352): the first hit's frequency
+// of a k-mer plus that of its reverse complement, which the reference takes at k = 31 whatever the caller's k is
+// (GkiIndexSource, gki_frequency.h).  Shared by gki_variant_kmers.hip and gki_sv_kmers.hip.
 // frequency of the first record of `q` in its bucket, 0 for a miss (collision_free_kmer_index.py:336-344)
 __device__ __forceinline__ uint32_t gki_first_hit_frequency(const int32_t *__restrict__ hashes_to_index,
                                                             const uint32_t *__restrict__ n_kmers,

@@ -20,7 +20,7 @@ struct GkiIndexSource {
     __device__ __forceinline__ uint32_t frequency(uint64_t h) const {
         return gki_first_hit_frequency(hashes_to_index, n_kmers, kmers, frequencies, n, mod, bucket_begin, n_buckets, h) +
                gki_first_hit_frequency(hashes_to_index, n_kmers, kmers, frequencies, n, mod, bucket_begin, n_buckets,
-                                       gki_revcomp31(h));
+                                       gki_revcomp(h & ((1ull << 62) - 1ull), 31));
     }
 };
 

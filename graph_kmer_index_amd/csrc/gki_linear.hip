@@ -5,20 +5,14 @@
 // each half of a segment is a SPAN (first output record, first position, strand), and the output is cut into blocks of
 // 4096 records, a wave per block, as in k_emit_interior_dense: every store covers 64 consecutive records
 // of one column, whole and line-aligned, whatever the segments' sizes.
-#include "gki_common.h"
+#include "gki_read_windows.h"
 #include <vector>
 
 namespace {
 
 constexpr int LIN_BLOCK = 4096;                  // output records of one wave-owned block: 64 groups of 64
 
-// ASCII letters -> 2-bit stream, 16 letters per lane: c/g/t (either case) are 1/2/3, every other byte is 0
-// (flat_kmers.py:134-145; the same rule as k_hash_reads).
-__device__ __forceinline__ uint32_t letter_code(uint32_t byte) {
-    const uint32_t ch = byte | 0x20u;
-    return ch == 'c' ? 1u : ch == 'g' ? 2u : ch == 't' ? 3u : 0u;
-}
-
+// ASCII letters -> 2-bit stream, 16 letters per lane, by the read side's letter rule (letter_code, gki_read_windows.h)
 __global__ __launch_bounds__(256) void k_pack_letters(const uint8_t *__restrict__ letters, int64_t n, int aligned16,
                                                       uint32_t *__restrict__ seq2_u32, int64_t n_u32) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -36,13 +30,6 @@ __global__ __launch_bounds__(256) void k_pack_letters(const uint8_t *__restrict_
         }
         seq2_u32[i] = r;
     }
-}
-
-// rc(x) = digit-reverse(~x) >> (64 - 2k), as in gki_hash.hip
-__device__ __forceinline__ uint64_t lin_revcomp(uint64_t x, int k) {
-    uint64_t y = __brevll(~x);
-    y = ((y & 0xAAAAAAAAAAAAAAAAull) >> 1) | ((y & 0x5555555555555555ull) << 1);
-    return y >> (64 - 2 * k);
 }
 
 struct LinArgs {
@@ -149,7 +136,7 @@ __global__ __launch_bounds__(256) void k_linear_emit_dense(LinArgs a, const uint
             const uint64_t hi = d == 0 ? s1 : d == 1 ? s2 : s3;
             const int sh = (rel0 & 31) * 2;
             const uint64_t h = ((lo >> sh) | ((hi << 1) << (63 - sh))) & mask;
-            const uint64_t hr = lin_revcomp(h, a.k);
+            const uint64_t hr = gki_revcomp(h, a.k);
             ph[u * 64] = rc ? hr : h;
             if (COLUMNS) {
                 pn[u * 64] = 1u;
@@ -187,7 +174,7 @@ __global__ __launch_bounds__(256) void k_linear_emit_rest(LinArgs a, const uint6
                 while (span_out[tl + 1] <= o) tl++;
                 const int64_t pos = span_pos[tl] + (o - span_out[tl]) * a.spacing;
                 uint64_t h = gki_extract(seq2, pos, a.k);
-                if (a.rc_pairs && (tl & 1)) h = lin_revcomp(h, a.k);
+                if (a.rc_pairs && (tl & 1)) h = gki_revcomp(h, a.k);
                 a.hashes[o] = h;
                 if (COLUMNS) {
                     a.nodes[o] = 1u;

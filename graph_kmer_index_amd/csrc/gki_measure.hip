@@ -1,6 +1,7 @@
 // Measurement helpers of libgki_hip.so: the box's own store ceiling for the FlatKmers column pattern (the roofline of
 // the headline kernel is the write stream, and boxes of one pool differ by a quarter), and a device-side read simulator
-// so that the read-mapping benchmark can run at BASELINE configs[4]'s 1e8 reads (their host simulation takes minutes).
+// so that the read-mapping benchmark can run at BASELINE configs[4]'s 1e8 reads (their host simulation takes minutes),
+// and the rate of random 64-byte requests that bounds a probe.
 #include "gki_common.h"
 
 namespace {
@@ -60,6 +61,26 @@ __global__ __launch_bounds__(256) void k_simulate_reads(const uint8_t *__restric
     }
 }
 
+// What bounds a probe is not bytes but 64-byte requests that miss L2.  This measures the rate the
+// device sustains right now: independent random 8-byte loads from a table of `table_bytes`, 4 in flight per lane.
+__device__ __forceinline__ uint64_t rr_mix(uint64_t x) {
+    x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
+    return x;
+}
+__global__ __launch_bounds__(256) void k_random_loads(const uint64_t *__restrict__ table, uint64_t n_entries, int64_t n_loads,
+                                                      uint64_t *__restrict__ sink) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    uint64_t acc = 0;
+    for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n_loads; i0 += stride * 4) {
+        uint64_t v[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) v[u] = table[__umul64hi(rr_mix((uint64_t)(i0 + u * stride)), n_entries)];
+#pragma unroll
+        for (int u = 0; u < 4; u++) acc ^= v[u];
+    }
+    if (acc == 0x1234567ull) sink[0] = acc;
+}
+
 }  // namespace
 
 // gki_wave_incl_sum (DPP) against the shuffle form, lane by lane, on pseudo-random and on extreme inputs
@@ -109,6 +130,27 @@ int gki_measure_copy_ms(void *d_dst, const void *d_src, int64_t bytes, float *ms
     GKI_TRY(ev.start(0));
     if (bytes > 0) HIP_TRY(hipMemcpyAsync(d_dst, d_src, (size_t)bytes, hipMemcpyDeviceToDevice, 0));
     return ev.stop(0, ms);
+}
+
+int gki_measure_random_loads(int64_t table_bytes, int64_t n_loads, double *loads_per_s) {
+    *loads_per_s = 0.0;
+    if (table_bytes < 4096 || n_loads < 1) return gki_set_error(GKI_ERR_BAD_ARG, "measure_random_loads: bad sizes");
+    float ms = 0.f;
+    // the 2 GB table is freed on every early exit too (bench.py measures with the whole 3 Gbp output resident)
+    DevBuf table, sink;
+    HIP_TRY(table.alloc((size_t)table_bytes));
+    HIP_TRY(sink.alloc(8));
+    HIP_TRY(hipMemset(table.get(), 1, (size_t)table_bytes));
+    TimerEvents ev;
+    for (int rep = 0; rep < 2; rep++) {              // the second launch is the measurement
+        GKI_TRY(ev.start(0));
+        hipLaunchKernelGGL(k_random_loads, dim3(2048), dim3(256), 0, 0, table.get<const uint64_t>(), (uint64_t)(table_bytes / 8), n_loads,
+                           sink.get<uint64_t>());
+        HIP_TRY(hipGetLastError());
+        GKI_TRY(ev.stop(0, &ms));
+    }
+    if (ms > 0.f) *loads_per_s = (double)n_loads / ((double)ms * 1e-3);
+    return GKI_OK;
 }
 
 int gki_selftest_wave_scan(int64_t *n_bad) {

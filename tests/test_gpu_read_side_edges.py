@@ -18,12 +18,12 @@ from read_side_ref import build_index_ref, contains_ref, count_nodes_ref, hash_r
 pytestmark = pytest.mark.gpu
 
 GRID_ITEMS = 2048 * 256      # csrc/gki_common.h:66-71 stream_grid: at most 256 * 8 blocks, launched with 256 threads = 524 288
-PROBE_UNROLL = 4             # csrc/gki_probe.hip:128 k_probe_kmers loads i0 + u * stride for u = 0..3
+PROBE_UNROLL = 4             # csrc/gki_probe.hip:135 k_probe_kmers loads i0 + u * stride for u = 0..3
 WAVE = 64                    # csrc/gki_common.h:12
-CAND_QUEUE = 64 + 4 * 64     # csrc/gki_probe.hip:76 CQ = 320 entries of the per-wave LDS candidate queue
-READ_WAVES = 2048 * 4        # csrc/gki_probe.hip:421-422, csrc/gki_hash.hip:149-150: at most 256 * 8 blocks of 4 waves = 8 192
-FP_SCAN_MAX = 64             # csrc/gki_probe.hip:28 longer buckets get an all-ones fingerprint set
-CNT_SAT = 0xFFFF             # csrc/gki_probe.hip:27 directory count saturates at 65 535, the length then comes from n_kmers
+CAND_QUEUE = 64 + 4 * 64     # csrc/gki_probe.hip:75 CQ = 320 entries of the per-wave LDS candidate queue
+READ_WAVES = 2048 * 4        # csrc/gki_read_windows.h:59 span_grid: at most 256 * 8 blocks of 4 waves = 8 192
+FP_SCAN_MAX = 64             # csrc/gki_probe.hip:30 longer buckets get an all-ones fingerprint set
+CNT_SAT = 0xFFFF             # csrc/gki_probe.hip:29 directory count saturates at 65 535, the length then comes from n_kmers
 SMALL_Q = 64                 # csrc/gki_index.hip:907 queries per gki_index_get_small call
 SMALL_CAP = 1024             # csrc/gki_index.hip:908 hits kept per query by k_get_small
 
@@ -114,7 +114,7 @@ def query_mix(mix, q, present, rng):
 
 @pytest.mark.parametrize("mix", ["mostly_present", "present", "absent"])
 def test_count_nodes_past_one_grid_pass_and_the_unroll(mix, wide_index):
-    """Issue items 1 and 2.  k_probe_kmers (csrc/gki_probe.hip:140-161) walks w0 in steps of stride * PROBE_UNROLL and
+    """Issue items 1 and 2.  k_probe_kmers (csrc/gki_probe.hip:147-167) walks w0 in steps of stride * PROBE_UNROLL and
     loads i0 + u * stride: with stride = GRID_ITEMS, lanes u = 1..3 are live only for q > GRID_ITEMS, all four in every
     wave only for q >= 4 * GRID_ITEMS, and the loop goes round a second time only beyond that.  q = 4 * GRID_ITEMS +
     4 * WAVE + 37 is the smallest shape with four full loads per lane, a second trip in which one wave per load still
@@ -153,9 +153,9 @@ def digits_reversed(x, k, complement):
 
 
 def test_lookup_contains_and_hash_kernels_past_one_grid_pass(wide_index):
-    """Issue item 1.  k_probe_lookup<false/true> (csrc/gki_probe.hip:175), k_lookup<false/true> (csrc/gki_index.hip:320),
-    k_probe_contains (csrc/gki_probe.hip:229), k_complement<false/true> (csrc/gki_hash.hip:26) and k_hash_windows
-    (csrc/gki_hash.hip:10) are plain grid-stride loops over GRID_ITEMS threads: any q > GRID_ITEMS takes the second
+    """Issue item 1.  k_probe_lookup<false/true> (csrc/gki_probe.hip:182), k_lookup<false/true> (csrc/gki_index.hip:320),
+    k_probe_contains (csrc/gki_probe.hip:224), k_complement<false/true> (csrc/gki_hash.hip:21) and k_hash_windows
+    (csrc/gki_hash.hip:12) are plain grid-stride loops over GRID_ITEMS threads: any q > GRID_ITEMS takes the second
     trip.  600 001 does, with a ragged last wave, and keeps the emit pass's output below two million hits."""
     dev, ref, present = wide_index
     q = 600001
@@ -186,7 +186,7 @@ FULL_WIDTH_SLICE = 4096
 
 @pytest.mark.parametrize("modulo", [1, 2, 4294967291, 452930477])
 def test_full_width_queries(modulo):
-    """Issue item 6.  bucket_of (csrc/gki_probe.hip:65-69) estimates the quotient with mulhi(kmer, floor((2^64 - 1) /
+    """Issue item 6.  bucket_of (csrc/gki_probe.hip:66-68, gki_mod csrc/gki_common.h:108-112) estimates the quotient with mulhi(kmer, floor((2^64 - 1) /
     modulo)), which can be two short, and corrects in a loop; the reference layout takes kmer % modulo
     (csrc/gki_index.hip:322, 359).  Both take any uint64, and the Python API turns negative int64 into uint64.  modulo 1
     and 2 have the largest quotients, 4 294 967 291 is the largest prime modulo a directory admits, 452 930 477 the
@@ -285,9 +285,9 @@ def boundary_reads(k, rng):
 
 @pytest.mark.parametrize("k", [1, 2, 16, 31])
 def test_reads_later_reads_of_a_wave_and_step_boundaries(k):
-    """Issue item 3.  k_probe_reads (csrc/gki_probe.hip:286-342) prefetches the next read's first 64 letters in the
-    `len < k` branch (:293-294) and in the last step of a read (:304-306); k_hash_reads (csrc/gki_hash.hip:69-72) skips
-    a short read and goes on.  Neither is reached before a wave has a second read, i.e. below READ_WAVES + 1 reads;
+    """Issue item 3.  The walk under k_probe_reads and k_hash_reads (csrc/gki_read_windows.h:90-148) prefetches the next
+    read's first 64 letters where a read has no window (:107-108) and in the last step of a read (:122-124), and goes on
+    after a short read.  Neither is reached before a wave has a second read, i.e. below READ_WAVES + 1 reads;
     (long, empty, short, long) in one wave needs 3 * READ_WAVES + 1, and five more make the last grid row ragged.  The
     lengths put n_out = len - k + 1 at 64, 65, 128 and 129 (the last step has 64, 1, 64, 1 windows) and the read's end
     at 63, 64 and 65 letters."""
@@ -330,7 +330,7 @@ def test_reads_later_reads_of_a_wave_and_step_boundaries(k):
 
 
 def test_hash_reads_past_one_grid_pass_of_reads():
-    """Issue item 1.  k_read_counts (csrc/gki_hash.hip:37) and the scan of its counts are grid-stride over GRID_ITEMS
+    """Issue item 1.  k_read_counts (csrc/gki_hash.hip:32) and the scan of its counts are grid-stride over GRID_ITEMS
     threads, one read each: 600 000 reads take the second trip.  Reads of 20..60 letters at k = 31 keep the output at a
     few million hashes, and a quarter of the reads (len < k) give none."""
     rng = np.random.default_rng(77)
@@ -348,8 +348,8 @@ def test_hash_reads_past_one_grid_pass_of_reads():
 
 # ------------------------------------------------------------------ E: directory-word boundaries
 def test_directory_word_boundaries():
-    """Issue item 5.  k_probe_dir (csrc/gki_probe.hip:43-45) scans the fingerprints of a bucket of up to FP_SCAN_MAX
-    records and gives a longer one all ones; it stores min(length, CNT_SAT), and cand_of (csrc/gki_probe.hip:89) reads
+    """Issue item 5.  k_probe_dir (csrc/gki_probe.hip:45-47) scans the fingerprints of a bucket of up to FP_SCAN_MAX
+    records and gives a longer one all ones; it stores min(length, CNT_SAT), and cand_of (csrc/gki_probe.hip:115) reads
     the length of a bucket whose stored count is CNT_SAT from n_kmers.  Buckets of 63 / 64 / 65 distinct k-mers sit on
     the first boundary, buckets of 65 534 .. 65 537 records (four k-mers each, interleaved) on the second: 65 535 is
     the one real length that reads as saturated."""
@@ -392,7 +392,7 @@ def test_directory_word_boundaries():
 @pytest.mark.parametrize("f", [1, 2, 11])
 def test_max_hits_edge(f):
     """collision_free_kmer_index.py:312 drops a k-mer whose first hit has frequency > max_hits: a k-mer of frequency f is
-    kept at max_hits = f and dropped at f - 1 (cand_scan csrc/gki_probe.hip:100, k_probe_lookup :188, k_lookup
+    kept at max_hits = f and dropped at f - 1 (cand_scan csrc/gki_probe.hip:128, k_probe_lookup :195, k_lookup
     csrc/gki_index.hip:331, k_count_nodes :366).  The k-mer has f + 2 records at f distinct ref offsets, so that the
     frequency, not the record count, decides."""
     rng = np.random.default_rng(f)
