@@ -245,12 +245,13 @@ __device__ __forceinline__ void interior_range(const FindArgs &a, int64_t n, int
 // ------------------------------------------------------------------------------------ boundary walk
 // One lane per node: depth-first over predecessor lists with an explicit stack.  Stepping onto predecessor q
 // (size s) with c context bases collected before it completes the windows of offsets o with c < k-1-o <= c+s.
-
-// The walk used by the count pass and by the emit pass keeps the TOP of the stack in registers and only
-// the levels below it in (scratch) arrays: PMC showed the first version, with the whole stack in scratch, writing
-// 1.4 GB of spills in the count pass and ~5 GB in the emit pass of the 3 Gbp graph, and every step began with a
-// dependent scratch load.  Node facts come from one aligned 32-byte NodeWalk record per visited node.
-// (LocalStack / ArenaStack / DeepArena, the storage of the levels below the top: csrc/gki_common.h)
+// The count pass sizes every node's slice of the output by this walk and the emit pass fills it, so both take it from ONE place:
+// walk_entry (a node's bounds), step_enters / step_windows (the step onto q), PathTopT (the path's first levels), LevelStackT (the suspended
+// levels).  The count pass adds the :402 check and the step budget; the emit pass the context register, the records' facts, the queue.
+// The TOP of the stack lives in registers and only the levels below it in (scratch) arrays: PMC showed the first version, with
+// the whole stack in scratch, writing 1.4 GB of spills in the count pass and ~5 GB in the emit pass of the 3 Gbp graph, and every
+// step began with a dependent scratch load.  Node facts come from one aligned 32-byte NodeWalk record per visited node.
+// (LocalStack / ArenaStack / DeepArena, the storage of the levels: csrc/gki_common.h)
 // byte offset of every per-level array inside one (level, lane) cell of the arena
 enum { DA_BELOW = 0, DA_PATH = 40, DA_LVLA = 44, DA_CT = 46, DA_CM = 47, DA_HN = 49, DA_HCUR = 53, DA_HEND = 57, DA_HD = 61,
        DA_HSZ = 65, DA_HF = 69, DA_CELL = 70 };
@@ -409,6 +410,99 @@ __device__ __forceinline__ int stored_nodes(const uint8_t *__restrict__ store, P
     return c;
 }
 
+// What the walk of end node n covers (fn: the node's flag word, 0 without nflags).
+struct WalkEntry {
+    int32_t bl;                  // bnd_len_of
+    int o_lo, o_hi, own_lo;      // the run's boundary offsets of n are [o_lo, o_hi); from own_lo on a window may lie inside n (own_window)
+    int hi, cn;                  // offsets below hi look into predecessors; cn: lossy-restart offset inside n, -1: none
+    int v0; bool nonfree0, refused;   // 1: n is a variant node; n is not free to enter; ... and the variant limit is 0: nothing admissible
+    __device__ __forceinline__ bool any() const { return o_lo < o_hi && !refused; }
+    template <bool HAS_LOSSY, bool GEN> __device__ __forceinline__ bool own_window(const FindArgs &a, int64_t n, int o) const {   // has offset o >= own_lo a window inside n, and a record?
+        return !(HAS_LOSSY && cn >= 0 && o + 1 - a.k <= cn - 1 && cn <= o) && !(GEN && a.store && !a.store[n]);
+    }
+};
+template <bool HAS_LOSSY, bool GEN>
+__device__ __forceinline__ WalkEntry walk_entry(const DevGraph &g, const FindArgs &a, const uint16_t *__restrict__ lossy, int64_t n,
+                                                const NodeWalk &wn, uint16_t fn) {
+    WalkEntry e;
+    e.bl = bnd_len_of(g, a, lossy, n, wn.size);
+    e.o_lo = (n == a.node_begin) ? (int)(a.off_begin < e.bl ? a.off_begin : e.bl) : 0;
+    e.o_hi = (n == a.node_end) ? (int)(a.off_end < e.bl ? a.off_end : e.bl) : e.bl;
+    e.own_lo = e.o_lo > a.k - 1 ? e.o_lo : a.k - 1;
+    e.v0 = GEN ? ((fn & GKI_NODE_REF) ? 0 : 1) : (wn.is_ref ? 0 : 1);
+    e.nonfree0 = GEN ? !(fn & (GKI_NODE_REF | GKI_NODE_FORCED)) : e.v0 != 0;
+    e.refused = e.nonfree0 && a.M < 1;
+    e.cn = HAS_LOSSY ? lossy_of(lossy, (int32_t)n) : -1;
+    e.hi = e.o_hi < a.k - 1 ? e.o_hi : a.k - 1;
+    if (HAS_LOSSY && e.cn >= 0 && e.cn < e.hi) e.hi = e.cn;
+    return e;
+}
+
+// LAZY: levels 1 and 2 of `path` live in registers and reach the array only through flush(), before the rare calls that
+// read it (history_ok, stored_nodes) -- a scratch store at every step of the walk sits in front of the next load (in-order
+// vmcnt).  !LAZY (all-nodes mode reads the path at every finished step): the array alone.  !KEEP: no path.  Level 0 is the end node n.
+template <bool KEEP, bool LAZY>
+struct PathTopT {
+    int32_t p1 = 0, p2 = 0;
+    template <class P> __device__ __forceinline__ void set(P &path, int L, int32_t q) { if (KEEP) { if (LAZY && L == 1) p1 = q; else if (LAZY && L == 2) p2 = q; else path[L] = q; } }
+    template <class P> __device__ __forceinline__ int32_t node_at(P &path, int L, int64_t n) const { return !LAZY ? path[L] : L == 0 ? (int32_t)n : L == 1 ? p1 : L == 2 ? p2 : path[L]; }
+    template <class P> __device__ __forceinline__ void flush(P &path) const { if (KEEP && LAZY) { path[1] = p1; path[2] = p2; } }
+};
+
+// The suspended levels: the first in registers (SNP / indel graphs never go deeper), the others in `rest` (scratch, or the
+// deep variants' arena).  `rest` is a reference and the first member, push takes a value: one aggregate with the array goes to
+// scratch as a whole, the other order or a reference cost the emit kernels six VGPRs.  pop returns by value: `L == 1 ? first :
+// rest[L - 1]` chooses between two OBJECTS, which keeps `first` addressable (general emit 2.98 -> 2.58 ms, count pass 0.57 -> 0.54 ms).
+template <class Level, class Rest>
+struct LevelStackT {
+    Rest &rest; Level first;
+    __device__ __forceinline__ void push(int L, const Level b) { if (L == 1) first = b; else rest[L - 1] = b; }
+    __device__ __forceinline__ Level pop(int L) const { Level b = first; if (L != 1) b = rest[L - 1]; return b; }
+};
+
+// The step onto predecessor q of the node at level L - 1, q becoming level L: wq / fwq its record and flag word,
+// t_cum / t_vc / t_a the top of the stack (bases collected before q, variant nodes so far, `a` of history_ok's comment),
+// [w_lo, hi) the offsets still open (w_lo = -1 only in the count pass: "the k bases before an empty node").  In two calls -- step_enters: is q
+// entered (then it is level L of the path, st holds vq / aq); step_windows: the windows q completes, whether the walk goes on behind it -- because ONE
+// call returning a `taken` flag left a join between the rule and its use in the count kernel: every result live across it, 2.6 % of the count pass.
+struct WalkStep {
+    bool deeper;         // the walk goes on into q's predecessors
+    int vq, aq;          // t_vc and t_a with q on the path
+    int from, to, lo;    // q completes the windows of offsets [from, to); lo: `from` before offset -1, which has no record, was dropped
+    int cut, new_cum;    // a lossy-restart point inside q: windows of offsets below `cut` would reach before it (INT_MIN: none); bases collected with q
+};
+template <bool GEN, class PT, class P>
+__device__ __forceinline__ bool step_enters(const FindArgs &a, int64_t n, int32_t q, const NodeWalk &wq, uint32_t fwq, int t_vc, int t_a, int L, int cap, PT &top, P &path, int *err, WalkStep &st) {
+    const uint16_t fq = (uint16_t)fwq;
+    if (GEN && (fq & GKI_NODE_DEAD)) return false;
+    if (GEN && (fq & GKI_NODE_HFS) && !(a.nflags[top.node_at(path, L - 1, n)] & GKI_NODE_FORCED)) return false;   // edge removed by a forced sibling
+    const int vq = st.vq = t_vc + (GEN ? ((fq & GKI_NODE_REF) ? 0 : 1) : (wq.is_ref ? 0 : 1));
+    const int aq = st.aq = !GEN ? 0 : t_a ? t_a : (fq & (GKI_NODE_REF | GKI_NODE_FORCED)) ? 0 : vq;
+    if (GEN ? (aq && vq - aq >= a.M) : vq > a.M) return false;          // kmer_finder.py:391-403 in order-free form
+    if (L >= cap - 1) { gki_raise(err, GKI_ERR_WINDOW_TOO_DEEP); return false; }
+    top.set(path, L, q); return true;
+}
+template <bool HAS_LOSSY, bool GEN, class PT, class P, class WC>
+__device__ __forceinline__ void step_windows(const DevGraph &g, const FindArgs &a, const WC &wc, const WalkView &wv, const NodeWalk &wq, uint32_t fwq,
+                                             int t_cum, int L, int w_lo, int hi, PT &top, P &path, int *err, const DeepArena &da, int64_t lane_global, WalkStep &st) {
+    const uint16_t fq = (uint16_t)fwq; const int k = a.k, s = wq.size, c = t_cum, vq = st.vq;
+    st.from = st.to = st.lo = 0; st.cut = INT_MIN; st.deeper = true; st.new_cum = c + s;
+    if (s == 0) return;                                  // an empty node is in the node set and adds no base
+    const int far = k - 1 - c - s;                       // with c bases before it, q completes offsets far .. k-2-c
+    int from = far < w_lo ? w_lo : far, to = k - 1 - c > hi ? hi : k - 1 - c;
+    const int cq = HAS_LOSSY ? lossy_in(fwq) : -1;
+    if (HAS_LOSSY && cq >= 0) { st.cut = far + cq; if (from < st.cut) from = st.cut; }
+    if (GEN && from < to && !(fq & (GKI_NODE_T | GKI_NODE_SIMPLE))) {      // a history before the window's first node?
+        // (fq >> 8: no history holds more variant nodes in the k bases before q -- if even that many fit under the
+        // limit, any history that enters q will do, and q is entered)
+        const bool ok = (fq & GKI_NODE_NESTED) && (vq + (int)(fq >> 8) < a.M || (top.flush(path),
+                        history_ok(WalkSrc{g.walk, g.rev_edges, g.rev_start}, wc, wv, a.nflags, k, a.M, raw(path), L, err, da, lane_global)));
+        if (!ok) to = from;
+    }
+    st.lo = from; st.to = to; st.from = (GEN && from < 0 && from < to) ? 0 : from;      // offset -1 has no record
+    st.deeper = far > w_lo && !(HAS_LOSSY && cq >= 0);
+}
+
 // The walk is a chain of dependent LDS / memory reads: its speed is the number of resident waves.  The general variant
 // needs 100 VGPRs unconstrained (4 waves per SIMD; the others 53-55 = 8) -- held to 64 it spills ~30 values around the
 // history_ok call and is still faster at every step: 1.27 / 1.11 / 0.99 / 0.95 / 0.94 ms at 4 / 5 / 6 / 7 / 8 waves on the
@@ -427,10 +521,8 @@ __global__ __launch_bounds__(64 * CNT_WPB, (GEN && !DEEP) ? 8 : 1) void k_count_
     typename StackOf<int32_t, GEN ? MAXN : 1, DEEP>::type path;   // general graphs: the node of every level (level 0 = the end node)
     bind(below, da, DA_BELOW, lane_global);
     bind(path, da, DA_PATH, lane_global);
-    LevelLo below0 = {0, 0, 0, 0, 0};  // the first suspended level stays in registers (SNP/indel graphs never go deeper)
-    // levels 1 and 2 of `path` live in registers and reach scratch only right before the rare calls that read the array
-    // (history_ok, stored_nodes): a scratch store at every step of the walk sits in front of the next load (in-order vmcnt)
-    int32_t pr1 = 0, pr2 = 0;
+    LevelStackT<LevelLo, decltype(below)> stack = {below, {0, 0, 0, 0, 0}};
+    PathTopT<GEN, true> top;
     const int k = a.k;
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -444,99 +536,54 @@ __global__ __launch_bounds__(64 * CNT_WPB, (GEN && !DEEP) ? 8 : 1) void k_count_
         const int32_t size = wn.size;
         const uint16_t fn = GEN ? (uint16_t)cached_flag(a.nflags, HAS_LOSSY ? lossy : nullptr, wc, wv, n) : (uint16_t)0;
         const bool reach_n = !(GEN && (fn & GKI_NODE_DEAD));
-        const int32_t bl = bnd_len_of(g, a, lossy, n, size);
+        const WalkEntry e = walk_entry<HAS_LOSSY, GEN>(g, a, lossy, n, wn, fn);
         uint32_t count = 0;
-        const int o_lo = (n == a.node_begin) ? (int)(a.off_begin < bl ? a.off_begin : bl) : 0;
-        const int o_hi = (n == a.node_end) ? (int)(a.off_end < bl ? a.off_end : bl) : bl;
-        const int v0 = GEN ? ((fn & GKI_NODE_REF) ? 0 : 1) : (wn.is_ref ? 0 : 1);
-        const bool nonfree0 = GEN ? !(fn & (GKI_NODE_REF | GKI_NODE_FORCED)) : v0 != 0;
         // kmer_finder.py:402: at the end of a node without exactly one linear-ref successor no reachable window may be
         // at the limit.  The windows in question end at the node's last base (oc), for an empty node "before offset 0".
         bool chk = GEN && (fn & GKI_NODE_CHECK) && reach_n && in_run(a, n);
         const int oc = size - 1;
-        if (chk && size >= k) { if (v0 >= a.M) gki_raise(err, GKI_ERR_NOT_ONE_REF_SUCC); chk = false; }
+        if (chk && size >= k) { if (e.v0 >= a.M) gki_raise(err, GKI_ERR_NOT_ONE_REF_SUCC); chk = false; }
         const bool chk_empty = chk && size == 0;
-        if (reach_n && ((bl > 0 && o_lo < o_hi) || chk_empty) && !(nonfree0 && a.M < 1)) {
-            const int cn = HAS_LOSSY ? lossy_of(lossy, (int32_t)n) : -1;
-            for (int o = o_lo > k - 1 ? o_lo : k - 1; o < o_hi; o++) {
-                if (HAS_LOSSY && cn >= 0 && o + 1 - k <= cn - 1 && cn <= o) continue;
-                if (GEN && a.store && !a.store[n]) continue;
-                count += 1;
-            }
-            int hi = o_hi < k - 1 ? o_hi : k - 1;
-            if (HAS_LOSSY && cn >= 0 && cn < hi) hi = cn;
-            const int w_lo = chk_empty ? -1 : o_lo;       // offset -1: the k bases before the node
-            if (chk_empty) hi = 0;
-            if (GEN && chk && wn.rev_cnt == 0 && v0 >= a.M) gki_raise(err, GKI_ERR_NOT_ONE_REF_SUCC);   // a root shorter than k
+        if (reach_n && ((e.bl > 0 && e.o_lo < e.o_hi) || chk_empty) && !e.refused) {
+            for (int o = e.own_lo; o < e.o_hi; o++) count += e.own_window<HAS_LOSSY, GEN>(a, n, o) ? 1 : 0;
+            const int w_lo = chk_empty ? -1 : e.o_lo;     // offset -1: the k bases before the node
+            const int hi = chk_empty ? 0 : e.hi;
+            if (GEN && chk && wn.rev_cnt == 0 && e.v0 >= a.M) gki_raise(err, GKI_ERR_NOT_ONE_REF_SUCC);   // a root shorter than k
             if (w_lo < hi) {
                 int32_t t_cur, t_end;
                 preds_begin(g, wn, n, &t_cur, &t_end);
-                int t_cum = 0, t_vc = v0, t_a = nonfree0 ? v0 : 0;
-                int L = 1;
+                int t_cum = 0, t_vc = e.v0, t_a = e.nonfree0 ? e.v0 : 0;
+                int L = 1, steps_left = STEP_BUDGET;
                 if (GEN) path[0] = (int32_t)n;
-                int steps_left = STEP_BUDGET;
                 while (L > 0) {
                     if (t_cur >= t_end) {
                         L--;
-                        if (L > 0) { LevelLo b = below0; if (L != 1) b = below[L - 1]; t_cur = b.cur; t_end = b.end; t_cum = b.cum; t_vc = b.vc; t_a = b.a; }
+                        if (L > 0) { const LevelLo b = stack.pop(L); t_cur = b.cur; t_end = b.end; t_cum = b.cum; t_vc = b.vc; t_a = b.a; }
                         continue;
                     }
                     const int32_t q = cached_preds_next(g, wc, wv, &t_cur);
                     const NodeWalk wq = cached_walk(g, wc, wv, q);
                     const uint32_t fwq = (GEN || HAS_LOSSY) ? cached_flag(GEN ? a.nflags : nullptr, HAS_LOSSY ? lossy : nullptr, wc, wv, q) : 0u;
-                    const uint16_t fq = (uint16_t)fwq;
-                    if (GEN) {
-                        if (fq & GKI_NODE_DEAD) continue;
-                        if ((fq & GKI_NODE_HFS) && !(a.nflags[L == 1 ? (int32_t)n : L == 2 ? pr1 : L == 3 ? pr2 : path[L - 1]] & GKI_NODE_FORCED)) continue;
+                    WalkStep st = {};
+                    if (!step_enters<GEN>(a, n, q, wq, fwq, t_vc, t_a, L, cap, top, path, err, st)) continue;
+                    step_windows<HAS_LOSSY, GEN>(g, a, wc, wv, wq, fwq, t_cum, L, w_lo, hi, top, path, err, da, lane_global, st);
+                    if (st.from < st.to) {
+                        uint32_t per_window = a.one_node ? 1u : (uint32_t)(L + 1);
+                        if (GEN && a.store) { top.flush(path); per_window = (uint32_t)stored_nodes(a.store, raw(path), L + 1, a.one_node != 0); }
+                        count += (uint32_t)(st.to - st.from) * per_window;
                     }
-                    const int vq = t_vc + (GEN ? ((fq & GKI_NODE_REF) ? 0 : 1) : (wq.is_ref ? 0 : 1));
-                    int aq = 0;
-                    if (!GEN) {
-                        if (vq > a.M) continue;                      // kmer_finder.py:391-403 in order-free form
-                    } else {
-                        aq = t_a ? t_a : ((fq & (GKI_NODE_REF | GKI_NODE_FORCED)) ? 0 : vq);
-                        if (aq && vq - aq >= a.M) continue;
+                    if (GEN && chk && st.vq >= a.M) {
+                        // at the limit -- a reachable window that ends at oc (a refused history leaves lo == to); a shorter one
+                        // that still decides :402, because the search restarted inside q with no history and oc's window would
+                        // reach before that point; or the graph ends before oc's window is complete and the search saw what there is
+                        if ((st.lo <= oc && oc < st.to) || (oc >= w_lo && oc < st.cut) ||
+                            (wq.size != 0 && wq.rev_cnt == 0 && st.new_cum < k - 1 - oc)) gki_raise(err, GKI_ERR_NOT_ONE_REF_SUCC);
                     }
-                    if (L >= cap - 1) { gki_raise(err, GKI_ERR_WINDOW_TOO_DEEP); continue; }
-                    if (GEN) { if (L == 1) pr1 = q; else if (L == 2) pr2 = q; else path[L] = q; }
-                    const int s = wq.size, c = t_cum;
-                    bool deeper;
-                    int new_cum;
-                    if (s == 0) {                                    // empty node: in the node set, adds no base
-                        deeper = true; new_cum = c;
-                    } else {
-                        int from = k - 1 - c - s; if (from < w_lo) from = w_lo;
-                        int to = k - 1 - c; if (to > hi) to = hi;
-                        const int cq = HAS_LOSSY ? lossy_in(fwq) : -1;
-                        if (HAS_LOSSY && cq >= 0) {
-                            const int min_ok = k - 1 - c - s + cq; if (from < min_ok) from = min_ok;
-                            // the search restarted at (q, cq) with no history: at an end position whose window would
-                            // reach before that point it holds the shorter window, which still decides :402
-                            if (GEN && chk && oc >= w_lo && oc < min_ok && vq >= a.M) gki_raise(err, GKI_ERR_NOT_ONE_REF_SUCC);
-                        }
-                        if (GEN && from < to) {
-                            bool ok = true;                          // a history before the window's first node?
-                            if (!(fq & (GKI_NODE_T | GKI_NODE_SIMPLE)))
-                                ok = (fq & GKI_NODE_NESTED) ? (vq + (int)(fq >> 8) < a.M || (path[1] = pr1, path[2] = pr2, history_ok(WalkSrc{g.walk, g.rev_edges, g.rev_start}, wc, wv, a.nflags, k, a.M, raw(path), L, err, da, lane_global))) : false;
-                            if (ok && chk && from <= oc && oc < to && vq >= a.M) gki_raise(err, GKI_ERR_NOT_ONE_REF_SUCC);
-                            if (!ok) to = from;
-                        }
-                        if (GEN && from < 0 && from < to) from = 0;      // offset -1 has no record
-                        if (from < to) {
-                            uint32_t per_window = a.one_node ? 1u : (uint32_t)(L + 1);
-                            if (GEN && a.store) { path[1] = pr1; path[2] = pr2; per_window = (uint32_t)stored_nodes(a.store, raw(path), L + 1, a.one_node != 0); }
-                            count += (uint32_t)(to - from) * per_window;
-                        }
-                        // the graph ends before the window of oc is complete (graph start): the search saw what there is
-                        if (GEN && chk && wq.rev_cnt == 0 && c + s < k - 1 - oc && vq >= a.M) gki_raise(err, GKI_ERR_NOT_ONE_REF_SUCC);
-                        deeper = (k - 1 - c - s > w_lo) && !(HAS_LOSSY && cq >= 0);
-                        new_cum = c + s;
-                    }
-                    if (deeper) {
+                    if (st.deeper) {
                         LevelLo b; b.cur = t_cur; b.end = t_end; b.cum = (uint8_t)t_cum; b.vc = (cnt_t)t_vc; b.a = (cnt_t)t_a;
-                        if (L == 1) below0 = b; else below[L - 1] = b;
+                        stack.push(L, b);
                         preds_begin(g, wq, q, &t_cur, &t_end);
-                        t_cum = new_cum; t_vc = vq; t_a = aq;
+                        t_cum = st.new_cum; t_vc = st.vq; t_a = st.aq;
                         L++;
                         // (out of budget: the walk is wound up through its ordinary exit -- a second way out of the loop
                         // cost the product kernel 13 %)
@@ -548,7 +595,7 @@ __global__ __launch_bounds__(64 * CNT_WPB, (GEN && !DEEP) ? 8 : 1) void k_count_
         uint32_t ic = 0;                              // interior offsets of this node in this run
         if (size > 0 && in_run(a, n)) {
             int64_t lo, hi2;
-            interior_range(a, n, size, bl, &lo, &hi2);
+            interior_range(a, n, size, e.bl, &lo, &hi2);
             ic = hi2 > lo ? (uint32_t)(hi2 - lo) : 0u;
         }
         bcount[n] = count;
@@ -833,14 +880,13 @@ __global__ __launch_bounds__(64 * BND_WPB, (GEN && !ALL && FMT != 1 && !DEEP) ? 
     const int cap = DEEP ? da.cap : MAXN;
     typename StackOf<LevelEmit, MAXN, DEEP>::type below;
     bind(below, da, DA_BELOW, lane_global);
-    LevelEmit below0;                  // the first suspended level stays in registers
-    below0.ctx = 0; below0.maf = 0.0; below0.cur = below0.end = below0.mn = 0; below0.cum = below0.vc = below0.evf = below0.evt = 0;
+    LevelStackT<LevelEmit, decltype(below)> stack = {below, {0, 0.0, 0, 0, 0, 0, 0, 0, 0}};
     typename StackOf<int32_t, (ALL || GEN) ? MAXN : 1, DEEP>::type path;   // all-nodes mode / general graphs: the node of every level of the walk (level 0 = the end node)
     typename StackOf<cnt_t, GEN ? MAXN : 1, DEEP>::type lvl_a;             // general graphs: `a` of the suspended levels (see history_ok)
     bind(path, da, DA_PATH, lane_global);
     bind(lvl_a, da, DA_LVLA, lane_global);
-    constexpr bool LAZY = GEN && !ALL;     // path levels 1, 2 and lvl_a[1] in registers, see k_count_boundary
-    int32_t pr1 = 0, pr2 = 0;
+    constexpr bool LAZY = GEN && !ALL;     // path levels 1, 2 (PathTopT) and lvl_a[1] in registers
+    PathTopT<ALL || GEN, LAZY> top;
     int a_l1 = 0;
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -872,33 +918,25 @@ __global__ __launch_bounds__(64 * BND_WPB, (GEN && !ALL && FMT != 1 && !DEEP) ? 
         if (n < a.n1 && bcount[n] > 0) {
             const NodeWalk wn = cached_walk(g, wc, wv, n);
             const uint16_t fn = GEN ? (uint16_t)cached_flag(a.nflags, HAS_LOSSY ? lossy : nullptr, wc, wv, n) : (uint16_t)0;
-            const int32_t bl = bnd_len_of(g, a, lossy, n, wn.size);
+            const WalkEntry e = walk_entry<HAS_LOSSY, GEN>(g, a, lossy, n, wn, fn);
             idx = rec_base[n] + *bnd_shift;
             pos0 = g.pos_base[n];
-            o_lo = (n == a.node_begin) ? (int)(a.off_begin < bl ? a.off_begin : bl) : 0;
-            const int o_hi = (n == a.node_end) ? (int)(a.off_end < bl ? a.off_end : bl) : bl;
-            const int v0 = GEN ? ((fn & GKI_NODE_REF) ? 0 : 1) : (wn.is_ref ? 0 : 1);
-            const bool nonfree0 = GEN ? !(fn & (GKI_NODE_REF | GKI_NODE_FORCED)) : v0 != 0;
-            const int cn = HAS_LOSSY ? lossy_of(lossy, (int32_t)n) : -1;
-            if (o_lo < o_hi && !(nonfree0 && a.M < 1)) {
+            o_lo = e.o_lo;
+            if (e.any()) {
                 // windows inside the node itself (lossy-restart nodes only; rare, written by the lane alone)
-                for (int o = o_lo > k - 1 ? o_lo : k - 1; o < o_hi; o++) {
-                    if (HAS_LOSSY && cn >= 0 && o + 1 - k <= cn - 1 && cn <= o) continue;
-                    if (GEN && a.store && !a.store[n]) continue;
-                    put(out, idx++, gki_extract(g.seq2, wn.seq_start + o + 1 - k, k), (int32_t)n, (int32_t)n, o, pos0 + o,
-                        FMT == 1 ? g.allele_freq[n] : (double)wn.af);
-                }
-                hi = o_hi < k - 1 ? o_hi : k - 1;
-                if (HAS_LOSSY && cn >= 0 && cn < hi) hi = cn;
+                for (int o = e.own_lo; o < e.o_hi; o++)
+                    if (e.own_window<HAS_LOSSY, GEN>(a, n, o))
+                        put(out, idx++, gki_extract(g.seq2, wn.seq_start + o + 1 - k, k), (int32_t)n, (int32_t)n, o, pos0 + o, FMT == 1 ? g.allele_freq[n] : (double)wn.af);
+                hi = e.hi;
                 if (o_lo < hi) {
                     preds_begin(g, wn, n, &t_cur, &t_end);
-                    t_cum = 0; t_vc = v0; t_evf = t_evt = 0; t_ctx = 0;
+                    t_cum = 0; t_vc = e.v0; t_evf = t_evt = 0; t_ctx = 0;
                     t_mn = (int32_t)n; t_maf = FMT == 1 ? g.allele_freq[n] : (double)wn.af;   // float32 rounding is monotonic:
                     // the minimum of the rounded values is the rounded minimum (flat layout), v2 keeps float64
                     own = gki_extract(g.seq2, wn.seq_start, hi);
                     if constexpr (EvQueue<FMT, ALL>::PACKED) { LaneC lc; lc.own = own; lc.pos0 = pos0; q.c[lane] = lc; }
                     if (ALL || GEN) path[0] = (int32_t)n;
-                    t_a = nonfree0 ? v0 : 0;
+                    t_a = e.nonfree0 ? e.v0 : 0;
                     L = 1;
                 }
             }
@@ -914,10 +952,7 @@ __global__ __launch_bounds__(64 * BND_WPB, (GEN && !ALL && FMT != 1 && !DEEP) ? 
                     if (t_evf < t_evt) { ev = true; e_from = t_evf; e_to = t_evt; e_ctx = t_ctx; e_mn = t_mn; e_maf = t_maf; e_nl = L; }
                     L--;
                     if (L > 0) {
-                        // (by value: `L == 1 ? below0 : below[L - 1]` is a choice between two OBJECTS, which keeps below0
-                        // addressable; general emit 2.98 -> 2.58 ms, all-nodes 5.91 -> 5.82 ms, count pass 0.57 -> 0.54 ms)
-                        LevelEmit b = below0;
-                        if (L != 1) b = below[L - 1];
+                        const LevelEmit b = stack.pop(L);
                         t_cur = b.cur; t_end = b.end; t_cum = b.cum; t_vc = b.vc; t_evf = b.evf; t_evt = b.evt;
                         t_ctx = b.ctx; t_mn = b.mn; t_maf = b.maf;
                         if (GEN) t_a = (LAZY && L == 1) ? a_l1 : lvl_a[L];
@@ -926,68 +961,32 @@ __global__ __launch_bounds__(64 * BND_WPB, (GEN && !ALL && FMT != 1 && !DEEP) ? 
                     const int32_t qn = cached_preds_next(g, wc, wv, &t_cur);
                     const NodeWalk wq = cached_walk(g, wc, wv, qn);
                     const uint32_t fwq = (GEN || HAS_LOSSY) ? cached_flag(GEN ? a.nflags : nullptr, HAS_LOSSY ? lossy : nullptr, wc, wv, qn) : 0u;
-                    const uint16_t fq = (uint16_t)fwq;
-                    const int vq = t_vc + (GEN ? ((fq & GKI_NODE_REF) ? 0 : 1) : (wq.is_ref ? 0 : 1));
-                    bool take;
-                    int aq = 0;
-                    if (!GEN) {
-                        take = vq <= a.M;
-                    } else {
-                        aq = t_a ? t_a : ((fq & (GKI_NODE_REF | GKI_NODE_FORCED)) ? 0 : vq);
-                        take = !(fq & GKI_NODE_DEAD) && !(aq && vq - aq >= a.M) &&
-                               !((fq & GKI_NODE_HFS) && !(a.nflags[!LAZY ? path[L - 1] : L == 1 ? (int32_t)n : L == 2 ? pr1 : L == 3 ? pr2 : path[L - 1]] & GKI_NODE_FORCED));
-                    }
-                    if (take) {
-                        if (L >= cap - 1) {
-                            gki_raise(err, GKI_ERR_WINDOW_TOO_DEEP);
-                        } else {
-                            const int s = wq.size, c = t_cum;
-                            if (LAZY) { if (L == 1) pr1 = qn; else if (L == 2) pr2 = qn; else path[L] = qn; }
-                            else if (ALL || GEN) path[L] = qn;
-                            const int32_t mn = qn < t_mn ? qn : t_mn;
-                            const double maf = fmin(t_maf, FMT == 1 ? g.allele_freq[qn] : (double)wq.af);   // np.min, kmer_finder.py:143
-                            bool deeper;
-                            int new_cum, from = 0, to = 0;
-                            uint64_t cx = t_ctx;
-                            if (s == 0) {
-                                deeper = true; new_cum = c;
-                            } else {
-                                from = k - 1 - c - s; if (from < o_lo) from = o_lo;
-                                to = k - 1 - c; if (to > hi) to = hi;
-                                const int cq = HAS_LOSSY ? lossy_in(fwq) : -1;
-                                if (HAS_LOSSY && cq >= 0) { const int min_ok = k - 1 - c - s + cq; if (from < min_ok) from = min_ok; }
-                                if (GEN && from < to && !(fq & (GKI_NODE_T | GKI_NODE_SIMPLE))) {      // a history before q?
-                                    // (fq >> 8: no history holds more variant nodes in the k bases before q -- if even
-                                    // that many fit under the limit, any history that enters q will do, and q is entered)
-                                    const bool ok = (fq & GKI_NODE_NESTED) ? (vq + (int)(fq >> 8) < a.M || (LAZY ? (void)(path[1] = pr1, path[2] = pr2) : (void)0, history_ok(WalkSrc{g.walk, g.rev_edges, g.rev_start}, wc, wv, a.nflags, k, a.M, raw(path), L, err, da, lane_global))) : false;
-                                    if (!ok) to = from;
-                                }
-                                const int tq = s < k - 1 - c ? s : k - 1 - c;
-                                cx = t_ctx | (node_tail(wq, tq) << (2 * (k - 1 - c - tq)));
-                                deeper = (k - 1 - c - s > o_lo) && !(HAS_LOSSY && cq >= 0);
-                                new_cum = c + s;
-                            }
-                            if (deeper) {
-                                LevelEmit b;
-                                b.cur = t_cur; b.end = t_end; b.cum = (uint8_t)t_cum; b.vc = (cnt_t)t_vc;
-                                b.evf = (uint8_t)t_evf; b.evt = (uint8_t)t_evt; b.ctx = t_ctx; b.mn = t_mn; b.maf = t_maf;
-                                if (L == 1) below0 = b; else below[L - 1] = b;
-                                if (GEN) { if (LAZY && L == 1) a_l1 = t_a; else lvl_a[L] = (cnt_t)t_a; t_a = aq; }
-                                preds_begin(g, wq, qn, &t_cur, &t_end);
-                                t_cum = new_cum; t_vc = vq;
-                                t_evf = from < to ? from : 0; t_evt = from < to ? to : 0;
-                                t_ctx = cx; t_mn = mn; t_maf = maf;
-                                L++;
-                            } else if (from < to) {
-                                ev = true; e_from = from; e_to = to; e_ctx = cx; e_mn = mn; e_maf = maf; e_nl = L + 1;
-                            }
-                        }
+                    WalkStep st = {};                          // a step that is refused: no windows, no descent
+                    if (step_enters<GEN>(a, n, qn, wq, fwq, t_vc, t_a, L, cap, top, path, err, st))
+                        step_windows<HAS_LOSSY, GEN>(g, a, wc, wv, wq, fwq, t_cum, L, o_lo, hi, top, path, err, da, lane_global, st);
+                    const int s = wq.size, c = t_cum;
+                    const int32_t mn = qn < t_mn ? qn : t_mn;
+                    const double maf = fmin(t_maf, FMT == 1 ? g.allele_freq[qn] : (double)wq.af);   // np.min, kmer_finder.py:143
+                    const int tq = s < k - 1 - c ? s : k - 1 - c;                 // (an empty node adds nothing)
+                    const uint64_t cx = t_ctx | (node_tail(wq, tq) << (2 * (k - 1 - c - tq)));
+                    if (st.deeper) {
+                        LevelEmit b; b.cur = t_cur; b.end = t_end; b.cum = (uint8_t)t_cum; b.vc = (cnt_t)t_vc;
+                        b.evf = (uint8_t)t_evf; b.evt = (uint8_t)t_evt; b.ctx = t_ctx; b.mn = t_mn; b.maf = t_maf;
+                        stack.push(L, b);
+                        if (GEN) { if (LAZY && L == 1) a_l1 = t_a; else lvl_a[L] = (cnt_t)t_a; t_a = st.aq; }
+                        preds_begin(g, wq, qn, &t_cur, &t_end);
+                        t_cum = st.new_cum; t_vc = st.vq;
+                        t_evf = st.from < st.to ? st.from : 0; t_evt = st.from < st.to ? st.to : 0;
+                        t_ctx = cx; t_mn = mn; t_maf = maf;
+                        L++;
+                    } else if (st.from < st.to) {
+                        ev = true; e_from = st.from; e_to = st.to; e_ctx = cx; e_mn = mn; e_maf = maf; e_nl = L + 1;
                     }
                 }
             }
             int e_nls = e_nl;                        // nodes of the window that get a record (only_store_nodes)
             if (GEN && a.store && ev) {
-                if (LAZY) { path[1] = pr1; path[2] = pr2; }
+                top.flush(path);
                 e_nls = stored_nodes(a.store, raw(path), e_nl, !ALL);
                 if (e_nls == 0) ev = false;
             }

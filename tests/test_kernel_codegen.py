@@ -102,6 +102,54 @@ def test_occupancy_footprints_of_the_walk_kernels(finder_asm):
         assert blocks_by_lds(gen["lds"]) == 4 and waves_by_regs(gen["vgpr"]) >= 4, (lossy, gen)
 
 
+# name: (VGPRs + AGPRs, LDS bytes, scratch bytes) of every product instantiation (last template argument false) as compiled at
+# the commit before the count pass and the emit pass took their walk from shared __forceinline__ helpers (walk_entry,
+# step_enters, step_windows, PathTopT, LevelStackT): the helpers must leave the kernels no larger than they were
+BOUNDARY_PARENT = {
+    "k_count_boundary<false, false, false>": (57, 4224, 580),
+    "k_count_boundary<false, true, false>": (64, 4224, 1920),
+    "k_count_boundary<true, false, false>": (53, 4224, 580),
+    "k_count_boundary<true, true, false>": (64, 4224, 1920),
+    "k_emit_boundary_one<false, 0, false, false, false>": (95, 9968, 1544),
+    "k_emit_boundary_one<false, 0, false, true, false>": (123, 9968, 2816),
+    "k_emit_boundary_one<false, 0, true, false, false>": (119, 10208, 1736),
+    "k_emit_boundary_one<false, 0, true, true, false>": (134, 10576, 2816),
+    "k_emit_boundary_one<false, 1, false, false, false>": (98, 11008, 1544),
+    "k_emit_boundary_one<false, 1, false, true, false>": (125, 11008, 2816),
+    "k_emit_boundary_one<false, 1, true, false, false>": (119, 10720, 1736),
+    "k_emit_boundary_one<false, 1, true, true, false>": (134, 11088, 2816),
+    "k_emit_boundary_one<false, 2, false, false, false>": (92, 9968, 1544),
+    "k_emit_boundary_one<false, 2, false, true, false>": (123, 9968, 2816),
+    "k_emit_boundary_one<false, 2, true, false, false>": (120, 10208, 1736),
+    "k_emit_boundary_one<false, 2, true, true, false>": (134, 10576, 2816),
+    "k_emit_boundary_one<true, 0, false, false, false>": (97, 9968, 1544),
+    "k_emit_boundary_one<true, 0, false, true, false>": (123, 9968, 2816),
+    "k_emit_boundary_one<true, 0, true, false, false>": (121, 10576, 1736),
+    "k_emit_boundary_one<true, 0, true, true, false>": (134, 10576, 2816),
+    "k_emit_boundary_one<true, 1, false, false, false>": (100, 11008, 1544),
+    "k_emit_boundary_one<true, 1, false, true, false>": (126, 11008, 2816),
+    "k_emit_boundary_one<true, 1, true, false, false>": (121, 11088, 1736),
+    "k_emit_boundary_one<true, 1, true, true, false>": (134, 11088, 2816),
+    "k_emit_boundary_one<true, 2, false, false, false>": (94, 9968, 1544),
+    "k_emit_boundary_one<true, 2, false, true, false>": (123, 9968, 2816),
+    "k_emit_boundary_one<true, 2, true, false, false>": (122, 10576, 1736),
+    "k_emit_boundary_one<true, 2, true, true, false>": (134, 10576, 2816),
+}
+
+
+def test_boundary_kernels_are_what_they_were_before_the_shared_step_rule(finder_asm):
+    r = _resources(finder_asm)
+    walk = lambda k: k.startswith("k_count_boundary<") or k.startswith("k_emit_boundary_one<")
+    # no kernel gained or lost an instantiation: every product variant with its slow path for deep windows beside it
+    assert sorted(k for k in r if walk(k) and k.endswith(", false>")) == sorted(BOUNDARY_PARENT)
+    assert sorted(k for k in r if walk(k) and k.endswith(", true>")) == sorted(k[:-len("false>")] + "true>" for k in BOUNDARY_PARENT)
+    worse = {}
+    for name, (vgpr, lds, scratch) in BOUNDARY_PARENT.items():
+        if not (r[name]["lds"] == lds and r[name]["vgpr"] <= vgpr and r[name]["scratch"] <= scratch):
+            worse[name] = ((vgpr, lds, scratch), r[name])
+    assert not worse, worse
+
+
 def test_forward_search_kernel_runs_at_full_occupancy(forward_asm):
     # the early-stop search reads everything from global memory, one lane per start position: left alone the compiler
     # builds it with 178 VGPRs (2 waves per SIMD) and it is 1.6-2.3x slower (csrc/gki_forward.hip, tools/bench_forward.py)
