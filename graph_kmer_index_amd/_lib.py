@@ -187,6 +187,9 @@ SYMBOLS = {
     "gki_bgzf_inflate": (_I32, [_P, _I64, _P, _P, _P, _P, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(C.c_int)]),
     "gki_bgzf_inflate_kernel_ms": (_I32, [C.POINTER(C.c_float)]),
     "gki_last_byte_position": (_I32, [_P, _I64, _I32, C.POINTER(_I64)]),
+    "gki_bgzf_deflate_bound": (_I32, [_I64, _I32, C.POINTER(_I64)]),
+    "gki_bgzf_deflate": (_I32, [_P, _I64, _I32, _P, _I64, C.POINTER(_I64), C.POINTER(_I64), _P]),
+    "gki_bgzf_deflate_kernel_ms": (_I32, [C.POINTER(C.c_float)]),
     "gki_measure_random_loads": (_I32, [_I64, _I64, C.POINTER(C.c_double)]),
     "gki_measure_store_bw": (_I32, [_P, _P, _P, _P, _I64, C.POINTER(C.c_double)]),
     "gki_measure_copy_ms": (_I32, [_P, _P, _I64, C.POINTER(C.c_float)]),

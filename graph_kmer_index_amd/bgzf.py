@@ -5,8 +5,14 @@ the device inflates all members of a piece side by side (gki_bgzf_inflate, csrc/
 A plain gzip file -- one member, or several without the 'BC' subfield -- is one serial DEFLATE stream per member and is
 not BGZF: `is_bgzf` says no and the reads-file route keeps it on the host (text_files.py).
 
-`inflate_on_device` is one piece's inflate; text_files.bgzf_text_pieces streams a file through it."""
+`inflate_on_device` is one piece's inflate; text_files.bgzf_text_pieces streams a file through it.
+
+The way out is the same split: `deflate_on_device` turns text that is in HBM into members there (gki_bgzf_deflate,
+csrc/gki_bgzf_deflate.hip), `BgzfWriter` cuts a stream of writes into members and writes the file, and
+`write_bgzf_on_device` converts a buffer or a plain file.  `write_bgzf` is zlib on host threads: the route of the tests
+and one of the oracles."""
 import ctypes as C
+import os
 import struct
 import zlib
 
@@ -138,6 +144,185 @@ def write_bgzf(path, data, block_size=0xff00, level=6, threads=1):
             for a in range(0, len(view), block_size):
                 f.write(one(a))
         f.write(EOF_MEMBER)
+
+
+DEFAULT_WRITE_CHUNK_BYTES = 64 << 20
+
+
+def _block_size(block_size):
+    block_size = int(block_size)
+    if not 1 <= block_size <= 0xff00:
+        raise ValueError("block_size must be in 1..0xff00")
+    return block_size
+
+
+def _device_bytes(scope, buf):
+    """`buf` as a uint8 DeviceArray: one is taken as it is, bytes-like or a NumPy uint8 array is uploaded and owned by
+    `scope`."""
+    if isinstance(buf, _lib.DeviceArray):
+        if buf.dtype.itemsize != 1:
+            raise ValueError("a device buffer of bytes is uint8")
+        return buf
+    if not isinstance(buf, np.ndarray):
+        buf = np.frombuffer(buf, dtype=np.uint8)
+    if buf.dtype.itemsize != 1:
+        raise ValueError("an array of bytes is uint8")
+    return scope.on_device(buf.reshape(-1), np.uint8)
+
+
+def deflate_on_device(buf, block_size=0xff00, n=None):
+    """The first `n` bytes of `buf` (all of it by default) as BGZF members, deflated on the device (gki_bgzf_deflate,
+    csrc/gki_bgzf_deflate.hip): (DeviceArray of uint8 holding the members back to back, their bytes).  One
+    member per `block_size` bytes, the last one shorter, no end-of-file member; no bytes give no member.  `buf`: bytes-like,
+    a NumPy uint8 array or a uint8 DeviceArray.  The caller owns the DeviceArray, which is as large as the bound, not as the
+    members."""
+    block_size = _block_size(block_size)
+    if n is not None and int(n) < 0:
+        raise ValueError("n must be >= 0")
+    _lib.require_device()
+    with _lib.DeviceScope() as s:
+        d_in = _device_bytes(s, buf)
+        n = d_in.n if n is None else int(n)
+        if n > d_in.n:
+            raise ValueError("n is %d, the buffer holds %d bytes" % (n, d_in.n))
+        bound, n_out, n_members = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _lib.check(_lib.load().gki_bgzf_deflate_bound(n, block_size, C.byref(bound)))
+        out = s.array(bound.value, np.uint8)
+        _lib.check(_lib.load().gki_bgzf_deflate(d_in.ptr, n, block_size, out.ptr, bound.value, C.byref(n_out), C.byref(n_members),
+                                                None))
+        return s.release(out), n_out.value
+
+
+class BgzfWriter:
+    """A BGZF file written from text that is on the device: `write_device(d_array, n)` and `write(bytes_like)` add text,
+    `close()` writes what is left and the end-of-file member.  Members are cut every `block_size` bytes of ALL the text
+    written so far -- what is left below `block_size` after a write stays on the device and goes in front of the next -- so
+    the file depends on the concatenated text and `block_size` only, not on how the text was cut into writes.  Only
+    compressed bytes cross to the host.  A context manager: an exception inside the `with` block removes the file.
+    `bytes_in`, `bytes_out` and `kernel_ms` count what went through."""
+
+    def __init__(self, path, block_size=0xff00):
+        self.block_size = _block_size(block_size)
+        _lib.require_device()
+        self.path, self.bytes_in, self.bytes_out, self.kernel_ms = path, 0, 0, 0.0
+        self._scope = _lib.DeviceScope()
+        self._rest = self._scope.array(self.block_size, np.uint8)      # the text below block_size that is not written yet
+        self._rest_n = 0
+        try:
+            self._file = open(path, "wb")
+        except BaseException:
+            self._scope.__exit__(None, None, None)
+            raise
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        else:
+            self.abandon()
+        return False
+
+    def _deflate(self, d_array, n):
+        out, n_out = deflate_on_device(d_array, self.block_size, n)
+        try:
+            ms = C.c_float(0)
+            _lib.check(_lib.load().gki_bgzf_deflate_kernel_ms(C.byref(ms)))
+            self.kernel_ms += ms.value
+            out.to_host(n_out).tofile(self._file)
+            self.bytes_out += n_out
+        finally:
+            out.free()
+
+    def write_device(self, d_array, n=None):
+        """Adds the first `n` bytes (all by default) of a uint8 DeviceArray, which is the caller's again on return."""
+        if self._file is None:
+            raise ValueError("the writer is closed")
+        if not isinstance(d_array, _lib.DeviceArray) or d_array.dtype.itemsize != 1:
+            raise ValueError("write_device takes a uint8 DeviceArray")
+        n = d_array.n if n is None else int(n)
+        if not 0 <= n <= d_array.n:
+            raise ValueError("n is %d, the buffer holds %d bytes" % (n, d_array.n))
+        copy, at = _lib.load().gki_memcpy_d2d, 0
+        self.bytes_in += n
+        if self._rest_n:                                     # fill the member that is begun, and write it when it is whole
+            at = min(n, self.block_size - self._rest_n)
+            _lib.check(copy(C.c_void_p(self._rest.ptr.value + self._rest_n), d_array.ptr, at))
+            self._rest_n += at
+            if self._rest_n < self.block_size:
+                return
+            self._deflate(self._rest, self.block_size)
+            self._rest_n = 0
+        whole = (n - at) // self.block_size * self.block_size
+        if whole:
+            self._deflate(d_array.view(at, whole), whole)
+        left = n - at - whole
+        if left:
+            _lib.check(copy(self._rest.ptr, C.c_void_p(d_array.ptr.value + at + whole), left))
+            self._rest_n = left
+
+    def write(self, data):
+        """Adds bytes-like or NumPy uint8 host data (uploaded for the call)."""
+        if self._file is None:
+            raise ValueError("the writer is closed")
+        view = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+        if view.size == 0:
+            return
+        with _lib.DeviceScope() as s:
+            self.write_device(_device_bytes(s, view))
+
+    def close(self):
+        """Writes the text that is left and the end-of-file member; closing twice is closing once."""
+        if self._file is None:
+            return
+        try:
+            if self._rest_n:
+                self._deflate(self._rest, self._rest_n)
+                self._rest_n = 0
+            self._file.write(EOF_MEMBER)
+            self.bytes_out += len(EOF_MEMBER)
+        except BaseException:
+            self.abandon()
+            raise
+        self._file.close()
+        self._file = None
+        self._scope.__exit__(None, None, None)
+
+    def abandon(self):
+        """Closes and removes the file and frees the device buffers."""
+        if self._file is not None:
+            self._file.close()
+            self._file = None
+            self._scope.__exit__(None, None, None)
+        if os.path.exists(self.path):
+            os.remove(self.path)
+
+
+def write_bgzf_on_device(path, data, block_size=0xff00, chunk_bytes=DEFAULT_WRITE_CHUNK_BYTES):
+    """Writes a BGZF file deflated on the device: `data` is the text (bytes-like, a NumPy uint8 array or a uint8
+    DeviceArray) or the name of a plain file, which is streamed in reads of `chunk_bytes`.  The file is that of one
+    `BgzfWriter` given all the text, whatever `chunk_bytes`.  Returns the bytes written.  `write_bgzf` is the host route."""
+    block_size, chunk_bytes = _block_size(block_size), int(chunk_bytes)
+    if chunk_bytes < 1:
+        raise ValueError("chunk_bytes must be positive")
+    if isinstance(data, (str, os.PathLike)) and not os.path.isfile(data):
+        raise FileNotFoundError("no file %s" % data)
+    with BgzfWriter(path, block_size) as writer:
+        if isinstance(data, (str, os.PathLike)):
+            with open(data, "rb") as f:
+                while True:
+                    piece = f.read(chunk_bytes)
+                    if not piece:
+                        break
+                    writer.write(piece)
+        elif isinstance(data, _lib.DeviceArray):
+            writer.write_device(data)
+        else:
+            view = memoryview(data).cast("B")
+            for a in range(0, len(view), chunk_bytes):
+                writer.write(view[a:a + chunk_bytes])
+    return writer.bytes_out
 
 
 def inflate_on_device(buf, members, prefix=0):

@@ -27,7 +27,9 @@ collision_free_kmer_index.py:393-402).
     python -m graph_kmer_index_amd.command_line_interface make_node_count_model -g graph.npz -V graph.variant_to_nodes.npz \
         -m haplotypes.npz -i index.npz -k 31 [-s 0,1,5] [-b 5] -o node_count_model
     python -m graph_kmer_index_amd.command_line_interface genotype -V graph.variant_to_nodes.npz -M node_count_model.npz \
-        -c node_counts.npy -v variants.vcf.gz -o sample.vcf [-s name] [--coverage X] [--error 0.01] [--pseudo-count 1] [-L loglik]
+        -c node_counts.npy -v variants.vcf.gz -o sample.vcf [-s name] [--coverage X] [--error 0.01] [--pseudo-count 1] [-L loglik] \
+        [--compress none|bgzf|auto]
+    python -m graph_kmer_index_amd.command_line_interface bgzf -i reads.fq -o reads.fq.gz [--block-size 65280] [--chunk-bytes N]
 
 `-g` takes an obgraph file when obgraph is installed, else a GraphArrays .npz (GraphArrays.to_file).  `index -t N` runs
 one process per GPU (at most N, at most the visible devices), each on its own range of critical-path numbers, and
@@ -456,9 +458,24 @@ def genotype(args):
     if args.loglik is not None:
         np.save(args.loglik if args.loglik.endswith(".npy") else args.loglik + ".npy", calls.loglik)
     n = write_genotyped_vcf(args.vcf, args.out_file_name, calls.call, calls.gq, ploidy, args.sample_name, args.chunk_bytes,
-                            args.inflate)
+                            args.inflate, compress=output_compression(args.compress, args.out_file_name))
     logging.info("Wrote %d data lines (%d not called) at coverage %g to %s"
                  % (n, int(np.count_nonzero(calls.call < 0)), calls.coverage[0], args.out_file_name))
+
+
+def output_compression(compress, out_file_name):
+    """`--compress`: none and bgzf are themselves, auto is bgzf for a name that ends in .gz."""
+    if compress == "auto":
+        return "bgzf" if str(out_file_name).endswith(".gz") else "none"
+    return compress
+
+
+def bgzf_command(args):
+    """A plain file -> a BGZF file deflated on the device (bgzf.write_bgzf_on_device): the conversion the `--inflate device`
+    routes ask for, without a host `bgzip` run."""
+    from .bgzf import write_bgzf_on_device
+    n = write_bgzf_on_device(args.out_file_name, args.in_file_name, args.block_size, args.chunk_bytes)
+    logging.info("Wrote %d bytes of BGZF to %s" % (n, args.out_file_name))
 
 
 def _haplotype_paths_arguments(p):
@@ -655,7 +672,7 @@ def build_parser():
     p.add_argument("-M", "--model", required=True, help="what make_node_count_model writes")
     p.add_argument("-c", "--counts", required=True, help="the sample's node counts, as map writes them (.npy)")
     p.add_argument("-v", "--vcf", required=True, help="the VCF the graph was made from, optionally .gz (BGZF or gzip)")
-    p.add_argument("-o", "--out-file-name", required=True, help="the genotyped VCF, plain text")
+    p.add_argument("-o", "--out-file-name", required=True, help="the genotyped VCF: plain text, or BGZF as --compress says")
     p.add_argument("-s", "--sample-name", required=False, default="sample")
     p.add_argument("--coverage", required=False, type=float, default=None,
                    help="the sample's coverage relative to the model's individuals; default: estimated from the counts")
@@ -665,7 +682,15 @@ def build_parser():
     p.add_argument("--inflate", required=False, choices=("auto", "host", "device"), default="auto",
                    help="where a .gz VCF is inflated: auto = BGZF on the device, other gzip on the host")
     p.add_argument("--chunk-bytes", required=False, type=int, default=None)
+    p.add_argument("--compress", required=False, choices=("none", "bgzf", "auto"), default="none",
+                   help="bgzf = the VCF leaves as BGZF, deflated on the device; auto = bgzf when -o ends in .gz")
     p.set_defaults(func=genotype)
+    p = sub.add_parser("bgzf")
+    p.add_argument("-i", "--in-file-name", required=True, help="a plain file: FASTA, FASTQ, VCF, any text")
+    p.add_argument("-o", "--out-file-name", required=True, help="the BGZF file (.gz)")
+    p.add_argument("--block-size", required=False, type=int, default=0xff00, help="input bytes per member, 1..65280")
+    p.add_argument("--chunk-bytes", required=False, type=int, default=64 << 20, help="bytes per read of the input")
+    p.set_defaults(func=bgzf_command)
     p = sub.add_parser("map")
     p.add_argument("-i", "--kmer-index", required=True)
     p.add_argument("-f", "--reads", required=True, help="FASTA or FASTQ, optionally .gz (gzip or BGZF)")

@@ -15,6 +15,7 @@ import os
 import numpy as np
 
 from . import _lib
+from .bgzf import BgzfWriter
 from .text_files import DEFAULT_CHUNK_BYTES, open_reads_file, owned_pieces
 
 FIT_FAULTS = {1: "an allele has no populated entry", 2: "an allele's entries do not hold the model's individuals"}
@@ -229,12 +230,16 @@ def genotyped_lines_on_device(scope, text, n_bytes, d_call, d_gq, first, n_calls
 
 
 def write_genotyped_vcf(vcf_file_name, out_file_name, call, gq, ploidy, sample_name="sample",
-                        chunk_bytes=DEFAULT_CHUNK_BYTES, inflate="auto", timings=None):
-    """Write `out_file_name`, plain text: the header (`header_text`) and, per data line of `vcf_file_name` (.vcf, or
-    .vcf.gz as BGZF or gzip), its first eight fields with GT:GQ of `call` int8[V] and `gq` uint8[V].  The input is streamed
-    in pieces of about `chunk_bytes`; each piece's lines are made on the device and written.  ValueError when the file's
-    data lines are not V, for a data line of fewer than eight fields and for a call outside -1 .. ploidy; the output file
-    is then removed.  Returns the data lines written."""
+                        chunk_bytes=DEFAULT_CHUNK_BYTES, inflate="auto", timings=None, compress="none"):
+    """Write `out_file_name`: the header (`header_text`) and, per data line of `vcf_file_name` (.vcf, or .vcf.gz as BGZF or
+    gzip), its first eight fields with GT:GQ of `call` int8[V] and `gq` uint8[V].  The input is streamed in pieces of about
+    `chunk_bytes`; each piece's lines are made on the device and written.  `compress`: "none" writes plain text; "bgzf"
+    sends the header and each piece's lines through a `bgzf.BgzfWriter`, so the lines are deflated where they were made
+    and only compressed bytes are copied to the host -- the file inflates to the plain one's bytes, whatever `chunk_bytes`.
+    ValueError when the file's data lines are not V, for a data line of fewer than eight fields and for a call outside
+    -1 .. ploidy; the output file is then removed.  Returns the data lines written."""
+    if compress not in ("none", "bgzf"):
+        raise ValueError("compress must be 'none' or 'bgzf', not %r" % (compress,))
     call = np.ascontiguousarray(call, dtype=np.int8).reshape(-1)
     gq = np.ascontiguousarray(gq, dtype=np.uint8).reshape(-1)
     if len(call) != len(gq):
@@ -244,7 +249,7 @@ def write_genotyped_vcf(vcf_file_name, out_file_name, call, gq, ploidy, sample_n
     V, done = len(call), 0
     header = header_text(vcf_file_name, sample_name)
     try:
-        with _lib.DeviceScope() as s, open(out_file_name, "wb") as out:
+        with _lib.DeviceScope() as s, (BgzfWriter(out_file_name) if compress == "bgzf" else open(out_file_name, "wb")) as out:
             d_call = s.on_device(call if V else np.zeros(1, np.int8), np.int8)
             d_gq = s.on_device(gq if V else np.zeros(1, np.uint8), np.uint8)
             out.write(header)
@@ -252,11 +257,16 @@ def write_genotyped_vcf(vcf_file_name, out_file_name, call, gq, ploidy, sample_n
                 with _lib.DeviceScope() as piece:
                     lines, n_out, n_data = genotyped_lines_on_device(piece, text, n_bytes, d_call, d_gq, done, V, int(ploidy),
                                                                      timings)
-                    if n_out:
+                    if n_out and compress == "bgzf":
+                        out.write_device(lines, n_out)
+                    elif n_out:
                         lines.to_host(n_out).tofile(out)
                     done += n_data
             if done != V:
                 raise ValueError("%s has %d data lines, there are %d calls" % (vcf_file_name, done, V))
+            if compress == "bgzf" and timings is not None:
+                out.close()                                  # the last member's time too
+                timings["deflate_ms"] = timings.get("deflate_ms", 0.0) + out.kernel_ms
     except BaseException:
         if os.path.exists(out_file_name):
             os.remove(out_file_name)

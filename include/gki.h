@@ -1023,6 +1023,24 @@ int gki_bgzf_inflate(const void *d_in, int64_t n_in, const void *d_payload_start
 int gki_bgzf_inflate_kernel_ms(float *ms);
 int gki_last_byte_position(const void *d_bytes, int64_t n_bytes, int value, int64_t *position);
 
+/* ---------------------------------------------------------------- BGZF deflate (the way out: text in HBM to a .gz file's bytes)
+ * gki_bgzf_deflate compresses the n_in bytes of d_in into complete BGZF members, packed back to back in d_out: one member
+ * per block_size (1..0xff00) input bytes, the last one shorter, each with the 18-byte header of bgzip (MTIME 0, XFL 0,
+ * OS 255, 'BC' with BSIZE), a raw DEFLATE payload, CRC-32 and ISIZE.  No end-of-file member is written: that is the
+ * writer's.  A payload is one final block: LZ77 matches with dynamic Huffman codes from the member's own counts, or a stored
+ * block when that is not smaller, so a member is at most its input + 31 bytes.  The bytes are a function of the input and
+ * block_size alone (csrc/gki_deflate_core.h; a host program built from that header writes the same bytes).
+ *   *n_out: the bytes written; *n_members: ceil(n_in / block_size); d_member_end (may be NULL): int64[n_members] in HBM,
+ *   where each member ends in d_out.  n_in == 0 writes nothing and gives 0 and 0.
+ *   GKI_ERR_BAD_ARG, with nothing written, for a block_size outside 1..0xff00, a negative size, a NULL buffer with a
+ *   positive size, or an out_capacity below gki_bgzf_deflate_bound's *bytes = n_in + 31 * n_members.
+ * gki_bgzf_deflate_kernel_ms: the device time of the calling thread's last gki_bgzf_deflate, by events around its launches
+ * (the deflate kernel, the scan of the members' sizes, the pack); 0 when that call launched nothing. */
+int gki_bgzf_deflate_bound(int64_t n_in, int block_size, int64_t *bytes);
+int gki_bgzf_deflate(const void *d_in, int64_t n_in, int block_size, void *d_out, int64_t out_capacity, int64_t *n_out,
+                     int64_t *n_members, void *d_member_end);
+int gki_bgzf_deflate_kernel_ms(float *ms);
+
 /* Measurement aid: independent random 8-byte loads per second the device sustains from a table of table_bytes (every
  * load that misses L2 is one 64-byte request -- the unit the probe kernels are bound by, not bytes).  Runs n_loads loads
  * twice and reports the second launch.  bench.py reports the read-side rate as a fraction of this. */
