@@ -4,8 +4,7 @@
 // A window of a slot's sequence that touches no alt allele the slot takes occurs in the all-ref path too, so only the
 // windows around the taken lines are probed: those of the all-ref path are taken away, those of the slot's sequence added
 // (k_probe_segments, gki_probe.hip).  This file lists them.  With the kept lines j = 0 .. K - 1 and a spell count call of the
-// slot behind us (its before / cut / bounds are the plan's):
-//   (scan of alt_size), k_seg_ref_bounds   once per plan: before and bounds of the all-ref path, which drops every alt
+// slot behind us (the plan's slot_path is its path; ref_path, the all-ref path, is built once per plan by the same builder):
 //   k_seg_taken_flags  one lane per kept line: does the slot take its alt allele
 //   (exclusive scan)   rank[j]; k_seg_taken_emit compacts: taken[rank[j]] = j
 //   k_seg_runs<false>  one lane per taken line: its run of dirty windows in either sequence; 1 or 0 segments each, and the
@@ -21,24 +20,12 @@ namespace {
 
 constexpr int SEG_BLOCK = 256;
 
-// bounds[c] of the all-ref path, c = 0 .. n_chrom, as k_hap_cuts forms a slot's
-__global__ __launch_bounds__(SEG_BLOCK) void k_seg_ref_bounds(int n_chrom, const int64_t *__restrict__ chrom_seq_start,
-                                                              const int64_t *__restrict__ chrom_first_kept,
-                                                              const int64_t *__restrict__ ref_before,
-                                                              int64_t *__restrict__ ref_bounds) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c <= n_chrom; c += stride)
-        ref_bounds[c] = chrom_seq_start[c] - ref_before[chrom_first_kept[c]];
-}
-
 __global__ __launch_bounds__(SEG_BLOCK) void k_seg_taken_flags(int64_t K, const int64_t *__restrict__ kline,
                                                                const uint64_t *__restrict__ slot_bits,
                                                                uint32_t *__restrict__ flag) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < K; j += stride) {
-        const int64_t line = kline[j];
-        flag[j] = (uint32_t)((slot_bits[line >> 6] >> (line & 63)) & 1ull);
-    }
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < K; j += stride)
+        flag[j] = hap_alt_bit(slot_bits, kline[j]);
 }
 
 __global__ __launch_bounds__(SEG_BLOCK) void k_seg_taken_emit(int64_t K, const uint32_t *__restrict__ flag,
@@ -48,11 +35,18 @@ __global__ __launch_bounds__(SEG_BLOCK) void k_seg_taken_emit(int64_t K, const u
         if (flag[j]) taken[rank[j]] = j;
 }
 
+// A path as k_seg_runs sees it at a taken line j: `size` is that of the allele the path keeps there.  It begins at cut[j],
+// or, with in_front, ends there.  The slot's path drops the ref allele of a taken line and its alt allele stands at the
+// cut.  The all-ref path drops the alt allele, cut[j] = alt_start[j] - before[j], and create holds alt_start[j] ==
+// ref_start[j] + ref_size[j]: its ref allele lies in front of the cut, at ref_start[j] - before[j].
+struct SegView {
+    const int64_t *cut, *bounds;
+    const int32_t *size;
+    bool in_front;
+};
+
 struct SegPlan {
-    const int64_t *ref_start;
-    const int32_t *ref_size, *alt_size;
-    const int64_t *ref_before, *ref_bounds;                // the all-ref path
-    const int64_t *cut, *bounds;                           // the slot's sequence
+    SegView ref, slot;                                     // the all-ref path, the slot's path
     const int64_t *chrom_first_kept;
     int n_chrom, k;
 };
@@ -66,6 +60,18 @@ __device__ __forceinline__ void seg_run(int64_t a, int64_t b, int64_t b_prev, in
     if (h > c_hi - k) h = c_hi - k;
     *lo = l;
     *n = h >= l ? h - l + 1 : 0;
+}
+
+// where the allele that path v keeps at taken line j ends
+__device__ __forceinline__ int64_t seg_allele_end(const SegView &v, int64_t j) {
+    return v.in_front ? v.cut[j] : v.cut[j] + v.size[j];
+}
+
+// the run of taken line j in path v, jp the taken line before it (-1: none), c its chromosome
+__device__ __forceinline__ void seg_line_run(const SegView &v, int64_t j, int64_t jp, int64_t c, int k, int64_t *lo,
+                                             int64_t *n) {
+    const int64_t b = seg_allele_end(v, j);
+    seg_run(b - v.size[j], b, jp < 0 ? 0 : seg_allele_end(v, jp), v.bounds[c], v.bounds[c + 1], k, lo, n);
 }
 
 // One lane per taken line r; the trip count is the same for every lane of a wave, for wave_add64.  !EMIT: has_ref[r] and
@@ -89,27 +95,19 @@ __global__ __launch_bounds__(SEG_BLOCK) void k_seg_runs(SegPlan p, int64_t n_tak
         int64_t c = first_site_after(p.chrom_first_kept, 0, (int64_t)p.n_chrom + 1, j) - 1;
         c = c < 0 ? 0 : c >= p.n_chrom ? p.n_chrom - 1 : c;
         int64_t lo, n;
-        {                                                  // the all-ref path: the line's ref allele
-            const int64_t a = p.ref_start[j] - p.ref_before[j];
-            const int64_t b_prev = jp >= 0 ? p.ref_start[jp] - p.ref_before[jp] + p.ref_size[jp] : 0;
-            seg_run(a, a + p.ref_size[j], b_prev, p.ref_bounds[c], p.ref_bounds[c + 1], p.k, &lo, &n);
-            if (EMIT) {
-                if (n > 0) { const int64_t o = ref_at[r]; ref_seg_start[o] = lo; ref_seg_windows[o] = n; }
-            } else {
-                has_ref[r] = n > 0;
-                w_ref += (uint64_t)n;
-            }
+        seg_line_run(p.ref, j, jp, c, p.k, &lo, &n);       // the all-ref path: the line's ref allele
+        if (EMIT) {
+            if (n > 0) { const int64_t o = ref_at[r]; ref_seg_start[o] = lo; ref_seg_windows[o] = n; }
+        } else {
+            has_ref[r] = n > 0;
+            w_ref += (uint64_t)n;
         }
-        {                                                  // the slot's sequence: the line's alt allele, at its cut
-            const int64_t a = p.cut[j];
-            const int64_t b_prev = jp >= 0 ? p.cut[jp] + p.alt_size[jp] : 0;
-            seg_run(a, a + p.alt_size[j], b_prev, p.bounds[c], p.bounds[c + 1], p.k, &lo, &n);
-            if (EMIT) {
-                if (n > 0) { const int64_t o = slot_at[r]; slot_seg_start[o] = lo; slot_seg_windows[o] = n; }
-            } else {
-                has_slot[r] = n > 0;
-                w_slot += (uint64_t)n;
-            }
+        seg_line_run(p.slot, j, jp, c, p.k, &lo, &n);      // the slot's sequence: the line's alt allele
+        if (EMIT) {
+            if (n > 0) { const int64_t o = slot_at[r]; slot_seg_start[o] = lo; slot_seg_windows[o] = n; }
+        } else {
+            has_slot[r] = n > 0;
+            w_slot += (uint64_t)n;
         }
     }
     if (!EMIT) {
@@ -138,7 +136,7 @@ __global__ __launch_bounds__(SEG_BLOCK) void k_model_accumulate(int64_t K, const
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < K; j += stride) {
         const int64_t line = kline[j];
         int c_alt = 0;
-        for (int i = 0; i < ploidy; i++) c_alt += (int)((alt_bits[(first_slot + i) * W + (line >> 6)] >> (line & 63)) & 1ull);
+        for (int i = 0; i < ploidy; i++) c_alt += (int)hap_alt_bit(alt_bits + (first_slot + i) * W, line);
         const int64_t var = var_nodes[line], ref = var - 1;               // a bubble: the two allele nodes side by side
         const uint32_t count[2] = {ref < n_nodes ? row[ref] : 0u, var < n_nodes ? row[var] : 0u};
         const int copies[2] = {ploidy - c_alt, c_alt};
@@ -152,56 +150,30 @@ __global__ __launch_bounds__(SEG_BLOCK) void k_model_accumulate(int64_t K, const
     }
 }
 
-// before and bounds of the all-ref path, once per plan
-int ensure_ref_path(gki_haplotype_paths &g) {
-    if (g.has_ref_path) return GKI_OK;
-    const int64_t K = g.K;
-    DevBuf before, bounds, tmp;
-    HIP_TRY(before.alloc((size_t)(K + 1) * 8));
-    HIP_TRY(bounds.alloc((size_t)(g.n_chrom + 1) * 8));
-    HIP_TRY(hipMemsetAsync(before.get(), 0, (size_t)(K + 1) * 8, 0));      // K == 0: before = [0], no scan runs
-    if (K > 0) {
-        const int64_t tmp_bytes = gki_scan_tmp_bytes(K);
-        HIP_TRY(tmp.alloc((size_t)tmp_bytes));
-        GKI_TRY(gki_scan_i32_to_i64(g.alt_size.get<const int32_t>(), K, before.get<int64_t>(), tmp.get(), tmp_bytes, 0));
-    }
-    hipLaunchKernelGGL(k_seg_ref_bounds, dim3(stream_grid(g.n_chrom + 1, SEG_BLOCK)), dim3(SEG_BLOCK), 0, 0, g.n_chrom,
-                       g.chrom_seq_start.get<const int64_t>(), g.chrom_first_kept.get<const int64_t>(),
-                       before.get<const int64_t>(), bounds.get<int64_t>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(0));
-    g.ref_before.swap(before);
-    g.ref_bounds.swap(bounds);
-    g.has_ref_path = true;
-    return GKI_OK;
+SegView seg_view_of(const HapPath &path, const DevBuf &size, bool in_front) {
+    return {path.cut.get<const int64_t>(), path.bounds.get<const int64_t>(), size.get<const int32_t>(), in_front};
 }
 
 SegPlan seg_plan_of(const gki_haplotype_paths &g, int k) {
-    SegPlan p;
-    p.ref_start = g.ref_start.get<const int64_t>();
-    p.ref_size = g.ref_size.get<const int32_t>();
-    p.alt_size = g.alt_size.get<const int32_t>();
-    p.ref_before = g.ref_before.get<const int64_t>();
-    p.ref_bounds = g.ref_bounds.get<const int64_t>();
-    p.cut = g.cut.get<const int64_t>();
-    p.bounds = g.bounds.get<const int64_t>();
-    p.chrom_first_kept = g.chrom_first_kept.get<const int64_t>();
-    p.n_chrom = g.n_chrom;
-    p.k = k;
-    return p;
+    return {seg_view_of(g.ref_path, g.ref_size, true), seg_view_of(g.slot_path, g.alt_size, false),
+            g.chrom_first_kept.get<const int64_t>(), g.n_chrom, k};
 }
 
 // what a segments count call leaves in the plan goes back unless the call succeeds
 void drop_segments(gki_haplotype_paths &g) {
-    g.seg_taken.reset();
-    g.seg_ref_at.reset();
-    g.seg_slot_at.reset();
-    g.seg_n_taken = -1;
+    g.seg.taken.reset();
+    g.seg.ref_at.reset();
+    g.seg.slot_at.reset();
+    g.seg.of = HapKey();
 }
 
 int segments_count(gki_haplotype_paths &g, const void *d_alt_bits, int64_t slot, int k, int64_t *totals, float *kernel_ms) {
-    GKI_TRY(ensure_ref_path(g));
     const int64_t K = g.K;
+    if (g.ref_path.of != HapKey::all_ref()) {              // once per plan; the null stream puts it in front of k_seg_runs
+        HIP_TRY(g.ref_path.alloc(K, g.n_chrom));
+        GKI_TRY(gki_haplotype_build_path(g, nullptr, g.ref_path));
+        g.ref_path.of = HapKey::all_ref();
+    }
     int64_t n_taken = 0;
     TimerEvents ev;
     float ms = 0.0f;
@@ -222,10 +194,10 @@ int segments_count(gki_haplotype_paths &g, const void *d_alt_bits, int64_t slot,
         if (n_taken < 0 || n_taken > K)
             return gki_set_error(GKI_ERR_BAD_ARG, "haplotype_segments_count: %lld taken lines of %lld (internal)", (long long)n_taken, (long long)K);
         if (n_taken > 0) {
-            HIP_TRY(g.seg_taken.alloc((size_t)n_taken * 8));
+            HIP_TRY(g.seg.taken.alloc((size_t)n_taken * 8));
             GKI_TRY(ev.start(0));
             hipLaunchKernelGGL(k_seg_taken_emit, dim3(stream_grid(K, SEG_BLOCK)), dim3(SEG_BLOCK), 0, 0, K,
-                               flag.get<const uint32_t>(), rank.get<const int64_t>(), g.seg_taken.get<int64_t>());
+                               flag.get<const uint32_t>(), rank.get<const int64_t>(), g.seg.taken.get<int64_t>());
             HIP_TRY(hipGetLastError());
             GKI_TRY(ev.stop(0, &ms));
             if (kernel_ms) *kernel_ms += ms;
@@ -239,22 +211,22 @@ int segments_count(gki_haplotype_paths &g, const void *d_alt_bits, int64_t slot,
         HIP_TRY(has_slot.alloc((size_t)n_taken * 4));
         HIP_TRY(windows.alloc(16));
         HIP_TRY(tmp.alloc((size_t)tmp_bytes));
-        HIP_TRY(g.seg_ref_at.alloc((size_t)(n_taken + 1) * 8));
-        HIP_TRY(g.seg_slot_at.alloc((size_t)(n_taken + 1) * 8));
+        HIP_TRY(g.seg.ref_at.alloc((size_t)(n_taken + 1) * 8));
+        HIP_TRY(g.seg.slot_at.alloc((size_t)(n_taken + 1) * 8));
         HIP_TRY(hipMemsetAsync(windows.get(), 0, 16, 0));
         GKI_TRY(ev.start(0));
         hipLaunchKernelGGL(k_seg_runs<false>, dim3(stream_grid(n_taken, SEG_BLOCK)), dim3(SEG_BLOCK), 0, 0, seg_plan_of(g, k),
-                           n_taken, g.seg_taken.get<const int64_t>(), has_ref.get<uint32_t>(), has_slot.get<uint32_t>(),
+                           n_taken, g.seg.taken.get<const int64_t>(), has_ref.get<uint32_t>(), has_slot.get<uint32_t>(),
                            windows.get<unsigned long long>(), (const int64_t *)nullptr, (const int64_t *)nullptr,
                            (int64_t *)nullptr, (int64_t *)nullptr, (int64_t *)nullptr, (int64_t *)nullptr);
         HIP_TRY(hipGetLastError());
-        GKI_TRY(gki_scan_u32_to_i64(has_ref.get<const uint32_t>(), n_taken, g.seg_ref_at.get<int64_t>(), tmp.get(), tmp_bytes, 0));
-        GKI_TRY(gki_scan_u32_to_i64(has_slot.get<const uint32_t>(), n_taken, g.seg_slot_at.get<int64_t>(), tmp.get(), tmp_bytes, 0));
+        GKI_TRY(gki_scan_u32_to_i64(has_ref.get<const uint32_t>(), n_taken, g.seg.ref_at.get<int64_t>(), tmp.get(), tmp_bytes, 0));
+        GKI_TRY(gki_scan_u32_to_i64(has_slot.get<const uint32_t>(), n_taken, g.seg.slot_at.get<int64_t>(), tmp.get(), tmp_bytes, 0));
         GKI_TRY(ev.stop(0, &ms));
         if (kernel_ms) *kernel_ms += ms;
         unsigned long long w[2] = {0, 0};
-        HIP_TRY(hipMemcpy(&totals[1], g.seg_ref_at.get<const int64_t>() + n_taken, 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(&totals[3], g.seg_slot_at.get<const int64_t>() + n_taken, 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&totals[1], g.seg.ref_at.get<const int64_t>() + n_taken, 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&totals[3], g.seg.slot_at.get<const int64_t>() + n_taken, 8, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(w, windows.get(), 16, hipMemcpyDeviceToHost));
         totals[2] = (int64_t)w[0];
         totals[4] = (int64_t)w[1];
@@ -281,18 +253,14 @@ int gki_haplotype_segments_count(gki_haplotype_paths *plan, const void *d_alt_bi
     if (slot < 0 || slot >= n_slots || (g.W > 0 && d_alt_bits == nullptr))
         return gki_set_error(GKI_ERR_BAD_ARG, "haplotype_segments_count: slot %lld of %lld, or the plane is NULL", (long long)slot,
                              (long long)n_slots);
-    if (g.spelled_slot != slot || g.spelled_plane != d_alt_bits)
+    if (g.slot_path.of != HapKey{slot, d_alt_bits})
         return gki_set_error(GKI_ERR_STATE, "haplotype_segments_count: the last spell count call was not of slot %lld of this plane",
                              (long long)slot);
     int64_t totals[5] = {0, 0, 0, 0, 0};
     const int rc = segments_count(g, d_alt_bits, slot, k, totals, kernel_ms);
     if (rc != GKI_OK) { drop_segments(g); return rc; }
-    g.seg_n_taken = totals[0];
-    g.seg_n_ref = totals[1];
-    g.seg_n_slot = totals[3];
-    g.seg_k = k;
-    g.seg_slot = slot;
-    g.seg_plane = d_alt_bits;
+    g.seg.n_taken = totals[0]; g.seg.n_ref = totals[1]; g.seg.n_slot = totals[3]; g.seg.k = k;
+    g.seg.of = g.slot_path.of;
     for (int i = 0; i < 5; i++) *outs[i] = totals[i];
     return GKI_OK;
 }
@@ -302,22 +270,23 @@ int gki_haplotype_segments_emit(gki_haplotype_paths *plan, void *d_ref_seg_start
     if (kernel_ms) *kernel_ms = 0.0f;
     GKI_TRY(gki_check_haplotype_plan(plan, "haplotype_segments_emit"));
     gki_haplotype_paths &g = *plan;
-    if (g.seg_n_taken < 0) return gki_set_error(GKI_ERR_STATE, "haplotype_segments_emit: no segments count call came before");
+    if (g.seg.of == HapKey()) return gki_set_error(GKI_ERR_STATE, "haplotype_segments_emit: no segments count call came before");
     DevBuf taken, ref_at, slot_at;                         // the plan's go back to the pool when the call returns
-    taken.swap(g.seg_taken);
-    ref_at.swap(g.seg_ref_at);
-    slot_at.swap(g.seg_slot_at);
-    const int64_t n_taken = g.seg_n_taken;
-    g.seg_n_taken = -1;
-    if (g.spelled_slot != g.seg_slot || g.spelled_plane != g.seg_plane)
+    taken.swap(g.seg.taken);
+    ref_at.swap(g.seg.ref_at);
+    slot_at.swap(g.seg.slot_at);
+    const int64_t n_taken = g.seg.n_taken;
+    const HapKey of = g.seg.of;
+    g.seg.of = HapKey();
+    if (g.slot_path.of != of)
         return gki_set_error(GKI_ERR_STATE, "haplotype_segments_emit: another slot or plane was spelled since the count call");
-    if (n_taken == 0 || (g.seg_n_ref == 0 && g.seg_n_slot == 0)) return GKI_OK;
-    if ((g.seg_n_ref > 0 && (d_ref_seg_start == nullptr || d_ref_seg_windows == nullptr)) ||
-        (g.seg_n_slot > 0 && (d_slot_seg_start == nullptr || d_slot_seg_windows == nullptr)))
+    if (n_taken == 0 || (g.seg.n_ref == 0 && g.seg.n_slot == 0)) return GKI_OK;
+    if ((g.seg.n_ref > 0 && (d_ref_seg_start == nullptr || d_ref_seg_windows == nullptr)) ||
+        (g.seg.n_slot > 0 && (d_slot_seg_start == nullptr || d_slot_seg_windows == nullptr)))
         return gki_set_error(GKI_ERR_BAD_ARG, "haplotype_segments_emit: an output is NULL");
     TimerEvents ev;
     GKI_TRY(ev.start(0));
-    hipLaunchKernelGGL(k_seg_runs<true>, dim3(stream_grid(n_taken, SEG_BLOCK)), dim3(SEG_BLOCK), 0, 0, seg_plan_of(g, g.seg_k),
+    hipLaunchKernelGGL(k_seg_runs<true>, dim3(stream_grid(n_taken, SEG_BLOCK)), dim3(SEG_BLOCK), 0, 0, seg_plan_of(g, g.seg.k),
                        n_taken, taken.get<const int64_t>(), (uint32_t *)nullptr, (uint32_t *)nullptr,
                        (unsigned long long *)nullptr, ref_at.get<const int64_t>(), slot_at.get<const int64_t>(),
                        (int64_t *)d_ref_seg_start, (int64_t *)d_ref_seg_windows, (int64_t *)d_slot_seg_start,

@@ -26,7 +26,8 @@ constexpr int HAP_TILE = PARSE_BLOCK * 16;                 // 4096 output letter
 constexpr int HAP_LANE_WORDS = 4;                          // plane words per lane in the alt-node kernels
 constexpr int HAP_WORD_TILE = PARSE_BLOCK * HAP_LANE_WORDS; // 1024 plane words per workgroup
 
-// the allele kept line j does not take: the ref allele when the slot's alt bit of its line is set, else the alt allele
+// the allele kept line j does not take: the ref allele when the slot's alt bit of its line is set, else the alt allele; a
+// NULL bit row has no bit set (the same for every lane)
 __global__ __launch_bounds__(PARSE_BLOCK) void k_hap_drops(int64_t K, const int64_t *__restrict__ kline,
                                                            const int64_t *__restrict__ ref_start,
                                                            const int32_t *__restrict__ ref_size,
@@ -36,8 +37,7 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_hap_drops(int64_t K, const int6
                                                            int32_t *__restrict__ drop_len, int64_t *__restrict__ drop_start) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < K; j += stride) {
-        const int64_t line = kline[j];
-        const bool alt = (slot_bits[line >> 6] >> (line & 63)) & 1ull;
+        const bool alt = slot_bits != nullptr && hap_alt_bit(slot_bits, kline[j]);
         drop_len[j] = alt ? ref_size[j] : alt_size[j];
         drop_start[j] = alt ? ref_start[j] : alt_start[j];
     }
@@ -191,12 +191,6 @@ __global__ __launch_bounds__(PARSE_BLOCK) void k_hap_alt_emit(const uint64_t *__
     }
 }
 
-}  // namespace
-
-// One graph's plan, struct gki_haplotype_paths: gki_haplotype_plan.h
-
-namespace {
-
 int upload(DevBuf &dst, const void *h_src, size_t bytes) {
     HIP_TRY(dst.alloc(bytes ? bytes : 8));
     if (bytes) HIP_TRY(hipMemcpy(dst.get(), h_src, bytes, hipMemcpyHostToDevice));
@@ -204,6 +198,27 @@ int upload(DevBuf &dst, const void *h_src, size_t bytes) {
 }
 
 }  // namespace
+
+int gki_haplotype_build_path(gki_haplotype_paths &g, const uint64_t *slot_bits, HapPath &path) {
+    const int64_t K = g.K;
+    path.of = HapKey();
+    if (K > 0) {
+        hipLaunchKernelGGL(k_hap_drops, dim3(stream_grid(K, PARSE_BLOCK)), dim3(PARSE_BLOCK), 0, 0, K,
+                           g.kline.get<const int64_t>(), g.ref_start.get<const int64_t>(), g.ref_size.get<const int32_t>(),
+                           g.alt_start.get<const int64_t>(), g.alt_size.get<const int32_t>(), slot_bits,
+                           g.drop_len.get<int32_t>(), g.drop_start.get<int64_t>());
+        HIP_TRY(hipGetLastError());
+        GKI_TRY(gki_scan_i32_to_i64(g.drop_len.get<const int32_t>(), K, path.before.get<int64_t>(), g.scan_tmp.get(),
+                                    g.scan_tmp_bytes, 0));
+    } else
+        HIP_TRY(hipMemsetAsync(path.before.get(), 0, 8, 0));              // no kept line: before = [0], no scan runs
+    hipLaunchKernelGGL(k_hap_cuts, dim3(stream_grid(K + g.n_chrom + 1, PARSE_BLOCK)), dim3(PARSE_BLOCK), 0, 0, K,
+                       g.drop_start.get<const int64_t>(), path.before.get<const int64_t>(), path.cut.get<int64_t>(),
+                       g.chrom_seq_start.get<const int64_t>(), g.chrom_first_kept.get<const int64_t>(), g.n_chrom,
+                       path.bounds.get<int64_t>());
+    HIP_TRY(hipGetLastError());
+    return GKI_OK;
+}
 
 extern "C" {
 
@@ -262,12 +277,9 @@ int gki_haplotype_paths_create(const uint8_t *h_seq, int64_t n_bases, int64_t n_
     g.scan_tmp_bytes = gki_scan_tmp_bytes(K > 0 ? K : 1);
     HIP_TRY(g.drop_len.alloc((size_t)(K + 1) * 4));
     HIP_TRY(g.drop_start.alloc((size_t)(K + 1) * 8));
-    HIP_TRY(g.before.alloc((size_t)(K + 1) * 8));
-    HIP_TRY(g.cut.alloc((size_t)(K + 1) * 8));
-    HIP_TRY(g.bounds.alloc((size_t)(C + 1) * 8));
-    HIP_TRY(g.tile_site.alloc((size_t)(ceil_div(n_bases, HAP_TILE) + 1) * 8));
     HIP_TRY(g.scan_tmp.alloc((size_t)g.scan_tmp_bytes));
-    HIP_TRY(hipMemset(g.before.get(), 0, (size_t)(K + 1) * 8));          // K == 0: before = [0], no scan runs
+    HIP_TRY(g.slot_path.alloc(K, g.n_chrom));
+    HIP_TRY(g.tile_site.alloc((size_t)(ceil_div(n_bases, HAP_TILE) + 1) * 8));
     *plan_out = raw;
     guard.p = nullptr;
     return GKI_OK;
@@ -280,30 +292,17 @@ int gki_haplotype_spell_count(gki_haplotype_paths *plan, const void *d_alt_bits,
     GKI_TRY(gki_check_haplotype_plan(plan, "haplotype_spell_count"));
     gki_haplotype_paths &g = *plan;
     g.n_out = -1;
-    g.spelled_slot = -1;
+    g.slot_path.of = HapKey();
     if (n_out == nullptr || h_bounds == nullptr || slot < 0 || slot >= n_slots || (g.W > 0 && d_alt_bits == nullptr))
         return gki_set_error(GKI_ERR_BAD_ARG, "haplotype_spell_count: slot %lld of %lld, or a pointer is NULL", (long long)slot,
                              (long long)n_slots);
-    const int64_t K = g.K;
+    HapPath &path = g.slot_path;
     TimerEvents ev;
     float ms_a = 0.0f, ms_b = 0.0f;
     GKI_TRY(ev.start(0));
-    if (K > 0) {
-        hipLaunchKernelGGL(k_hap_drops, dim3(stream_grid(K, PARSE_BLOCK)), dim3(PARSE_BLOCK), 0, 0, K,
-                           g.kline.get<const int64_t>(), g.ref_start.get<const int64_t>(), g.ref_size.get<const int32_t>(),
-                           g.alt_start.get<const int64_t>(), g.alt_size.get<const int32_t>(),
-                           (const uint64_t *)d_alt_bits + slot * g.W, g.drop_len.get<int32_t>(), g.drop_start.get<int64_t>());
-        HIP_TRY(hipGetLastError());
-        GKI_TRY(gki_scan_i32_to_i64(g.drop_len.get<const int32_t>(), K, g.before.get<int64_t>(), g.scan_tmp.get(),
-                                    g.scan_tmp_bytes, 0));
-    }
-    hipLaunchKernelGGL(k_hap_cuts, dim3(stream_grid(K + g.n_chrom + 1, PARSE_BLOCK)), dim3(PARSE_BLOCK), 0, 0, K,
-                       g.drop_start.get<const int64_t>(), g.before.get<const int64_t>(), g.cut.get<int64_t>(),
-                       g.chrom_seq_start.get<const int64_t>(), g.chrom_first_kept.get<const int64_t>(), g.n_chrom,
-                       g.bounds.get<int64_t>());
-    HIP_TRY(hipGetLastError());
+    GKI_TRY(gki_haplotype_build_path(g, (const uint64_t *)d_alt_bits + slot * g.W, path));
     GKI_TRY(ev.stop(0, &ms_a));
-    HIP_TRY(hipMemcpy(h_bounds, g.bounds.get(), (size_t)(g.n_chrom + 1) * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_bounds, path.bounds.get(), (size_t)(g.n_chrom + 1) * 8, hipMemcpyDeviceToHost));
     const int64_t total = h_bounds[g.n_chrom];
     if (total < 0 || total > g.n_bases)
         return gki_set_error(GKI_ERR_BAD_ARG, "haplotype_spell_count: %lld letters out of %lld (internal)", (long long)total,
@@ -311,13 +310,12 @@ int gki_haplotype_spell_count(gki_haplotype_paths *plan, const void *d_alt_bits,
     const int64_t n_tiles = ceil_div(total, HAP_TILE);
     GKI_TRY(ev.start(0));
     hipLaunchKernelGGL(k_hap_tile_sites, dim3(stream_grid(n_tiles + 1, PARSE_BLOCK)), dim3(PARSE_BLOCK), 0, 0,
-                       g.cut.get<const int64_t>(), K, n_tiles, g.tile_site.get<int64_t>());
+                       path.cut.get<const int64_t>(), g.K, n_tiles, g.tile_site.get<int64_t>());
     HIP_TRY(hipGetLastError());
     GKI_TRY(ev.stop(0, &ms_b));
     if (count_ms) *count_ms = ms_a + ms_b;
     g.n_out = total;
-    g.spelled_slot = slot;
-    g.spelled_plane = d_alt_bits;
+    path.of = {slot, d_alt_bits};
     *n_out = total;
     return GKI_OK;
 }
@@ -336,7 +334,8 @@ int gki_haplotype_spell_emit(gki_haplotype_paths *plan, void *d_letters, float *
     TimerEvents ev;
     GKI_TRY(ev.start(0));
     hipLaunchKernelGGL(k_hap_spell, dim3((unsigned)(n_tiles < 256 * 8 ? n_tiles : 256 * 8)), dim3(PARSE_BLOCK), 0, 0,
-                       g.seq.get<const uint8_t>(), g.K, g.cut.get<const int64_t>(), g.before.get<const int64_t>(),
+                       g.seq.get<const uint8_t>(), g.K, g.slot_path.cut.get<const int64_t>(),
+                       g.slot_path.before.get<const int64_t>(),
                        g.tile_site.get<const int64_t>(), total, (uint8_t *)d_letters);
     HIP_TRY(hipGetLastError());
     return ev.stop(0, spell_ms);
@@ -348,8 +347,8 @@ int gki_haplotype_alt_nodes_count(gki_haplotype_paths *plan, const void *d_alt_b
     if (n_nodes) *n_nodes = 0;
     GKI_TRY(gki_check_haplotype_plan(plan, "haplotype_alt_nodes_count"));
     gki_haplotype_paths &g = *plan;
-    g.alt_slots = -1;
-    g.alt_tile_before.reset();
+    g.alt.of = HapKey();
+    g.alt.tile_before.reset();
     if (n_nodes == nullptr || d_start == nullptr || n_slots < 0 || (n_slots > 0 && g.W > 0 && d_alt_bits == nullptr))
         return gki_set_error(GKI_ERR_BAD_ARG, "haplotype_alt_nodes_count: n_slots %lld, or a pointer is NULL", (long long)n_slots);
     const int64_t T = ceil_div(g.W, HAP_WORD_TILE), n_tiles = n_slots * T;
@@ -357,8 +356,8 @@ int gki_haplotype_alt_nodes_count(gki_haplotype_paths *plan, const void *d_alt_b
         return gki_set_error(GKI_ERR_BAD_ARG, "haplotype_alt_nodes_count: %lld slots are too many", (long long)n_slots);
     DevBuf tile_cnt, tmp;
     const int64_t tmp_bytes = gki_scan_tmp_bytes(n_tiles > 0 ? n_tiles : 1);
-    HIP_TRY(g.alt_tile_before.alloc((size_t)(n_tiles + 1) * 8));
-    HIP_TRY(hipMemset(g.alt_tile_before.get(), 0, 8));     // no tile: [0]
+    HIP_TRY(g.alt.tile_before.alloc((size_t)(n_tiles + 1) * 8));
+    HIP_TRY(hipMemset(g.alt.tile_before.get(), 0, 8));     // no tile: [0]
     HIP_TRY(tile_cnt.alloc((size_t)(n_tiles + 1) * 4));
     HIP_TRY(tmp.alloc((size_t)tmp_bytes));
     TimerEvents ev;
@@ -368,17 +367,16 @@ int gki_haplotype_alt_nodes_count(gki_haplotype_paths *plan, const void *d_alt_b
                            (const uint64_t *)d_alt_bits, g.kept_bits.get<const uint64_t>(), g.W, T, n_slots,
                            tile_cnt.get<uint32_t>());
         HIP_TRY(hipGetLastError());
-        GKI_TRY(gki_scan_u32_to_i64(tile_cnt.get<const uint32_t>(), n_tiles, g.alt_tile_before.get<int64_t>(), tmp.get(),
+        GKI_TRY(gki_scan_u32_to_i64(tile_cnt.get<const uint32_t>(), n_tiles, g.alt.tile_before.get<int64_t>(), tmp.get(),
                                     tmp_bytes, 0));
     }
     hipLaunchKernelGGL(k_hap_alt_starts, dim3(stream_grid(n_slots + 1, PARSE_BLOCK)), dim3(PARSE_BLOCK), 0, 0,
-                       g.alt_tile_before.get<const int64_t>(), T, n_slots, (int64_t *)d_start);
+                       g.alt.tile_before.get<const int64_t>(), T, n_slots, (int64_t *)d_start);
     HIP_TRY(hipGetLastError());
     GKI_TRY(ev.stop(0, kernel_ms));
-    HIP_TRY(hipMemcpy(&g.alt_total, g.alt_tile_before.get<const int64_t>() + n_tiles, 8, hipMemcpyDeviceToHost));
-    g.alt_slots = n_slots;
-    g.alt_plane = d_alt_bits;
-    *n_nodes = g.alt_total;
+    HIP_TRY(hipMemcpy(&g.alt.total, g.alt.tile_before.get<const int64_t>() + n_tiles, 8, hipMemcpyDeviceToHost));
+    g.alt.of = {n_slots, d_alt_bits};
+    *n_nodes = g.alt.total;
     return GKI_OK;
 }
 
@@ -387,13 +385,13 @@ int gki_haplotype_alt_nodes_emit(gki_haplotype_paths *plan, const void *d_alt_bi
     if (kernel_ms) *kernel_ms = 0.0f;
     GKI_TRY(gki_check_haplotype_plan(plan, "haplotype_alt_nodes_emit"));
     gki_haplotype_paths &g = *plan;
-    if (g.alt_slots < 0) return gki_set_error(GKI_ERR_STATE, "haplotype_alt_nodes_emit: no alt-nodes count call came before");
-    if (n_slots != g.alt_slots || d_alt_bits != g.alt_plane)
+    if (g.alt.of == HapKey()) return gki_set_error(GKI_ERR_STATE, "haplotype_alt_nodes_emit: no alt-nodes count call came before");
+    if (g.alt.of != HapKey{n_slots, d_alt_bits})
         return gki_set_error(GKI_ERR_STATE, "haplotype_alt_nodes_emit: the count call was given another plane");
     DevBuf tile_before;                                    // the plan's goes back to the pool when the call returns
-    tile_before.swap(g.alt_tile_before);
-    g.alt_slots = -1;
-    if (g.alt_total == 0) return GKI_OK;
+    tile_before.swap(g.alt.tile_before);
+    g.alt.of = HapKey();
+    if (g.alt.total == 0) return GKI_OK;
     if (d_nodes == nullptr) return gki_set_error(GKI_ERR_BAD_ARG, "haplotype_alt_nodes_emit: the output is NULL");
     const int64_t T = ceil_div(g.W, HAP_WORD_TILE), n_tiles = n_slots * T;
     TimerEvents ev;

@@ -82,6 +82,16 @@ def check_slot(slot, n_slots):
     return int(slot)
 
 
+def nodes_of_index(index, n_nodes):
+    """The `n_nodes` default of the count routes: the index's highest node + 1."""
+    return int(index.max_node_id()) + 1 if n_nodes is None else n_nodes
+
+
+def strands_of(include_reverse_complement):
+    """The `strands` of the segment probe: 3 both strands, 1 forward only."""
+    return 3 if include_reverse_complement else 1
+
+
 def kmer_passes(bounds, k, chunk_kmers):
     """The k-mers of every record [bounds[c], bounds[c + 1]) as passes of (seg_first, seg_count) lists, each pass of at
     most `chunk_kmers` k-mers: no k-mer crosses a record's end, a record shorter than k has none, and a pass may end
@@ -268,6 +278,11 @@ class HaplotypePaths:
             raise ValueError("the HaplotypePaths is closed")
         return _lib.load()
 
+    def _slots(self, slots):
+        """`slots` as ints on an open plan; IndexError for one outside 0 .. H - 1."""
+        self._open()
+        return [check_slot(h, self.n_slots) for h in slots]
+
     def _spell(self, plane, n_slots, slot):
         """Slot `slot` of `plane` spelled: (letters, which the caller frees, bounds, count ms, spell ms)."""
         lib = self._open()
@@ -286,8 +301,7 @@ class HaplotypePaths:
         """Slot `slot`'s sequence as a DeviceReference: `.letters` upper-case ACGT, record c (named str(c + 1)) the
         haplotype's chromosome c.  `.timings` holds the count pass' and the spelling kernel's device time in ms.  The
         caller frees it.  IndexError for a slot outside 0 .. H - 1."""
-        self._open()
-        slot = check_slot(slot, self.n_slots)
+        slot, = self._slots([slot])
         letters, bounds, ms_count, ms_spell = self._spell(self._alt_bits, self.n_slots, slot)
         names = [str(c + 1) for c in range(self.n_chromosomes)]
         return DeviceReference(names, bounds, letters, list(names), {"count_kernel_ms": ms_count, "spell_kernel_ms": ms_spell})
@@ -316,10 +330,7 @@ class HaplotypePaths:
         `chunk_kmers` k-mers through `linear_kmers_on_device` and `DeviceIndex.count_nodes`.
         timings: a list that receives one dict per slot (seconds per stage, synchronised)."""
         from .snp_kmer_finder import linear_kmers_on_device
-        self._open()
-        slots = [check_slot(h, self.n_slots) for h in slots]
-        if n_nodes is None:
-            n_nodes = int(index.max_node_id()) + 1
+        slots, n_nodes = self._slots(slots), nodes_of_index(index, n_nodes)
         device_index = index._device_index()
         out = np.zeros((len(slots), int(n_nodes)), dtype=np.uint32)
         for i, slot in enumerate(slots):
@@ -379,28 +390,31 @@ class HaplotypePaths:
         """uint32[n_nodes] on the host: the node hit counts of the all-ref path, what `node_counts` gives for a slot that
         takes no alt allele.  The path's letters and this row stay on the device until close(), for
         `node_counts_by_difference` and `node_count_model` to start from."""
-        if n_nodes is None:
-            n_nodes = int(index.max_node_id()) + 1
-        return self._base_row(index, k, n_nodes, 3 if include_reverse_complement else 1).to_host(int(n_nodes))
+        n_nodes = nodes_of_index(index, n_nodes)
+        return self._base_row(index, k, n_nodes, strands_of(include_reverse_complement)).to_host(int(n_nodes))
+
+    def _list_segments(self, s, slot, k):
+        """Slot `slot` spelled, which leaves its path in the plan, and its segments listed, all owned by `s`: (the sequence,
+        [ref start, ref windows, slot start, slot windows], the five totals, kernel ms, the host clock at the three stages)."""
+        lib = self._open()
+        t0 = time.perf_counter()
+        seq = s.keep(self.sequence(slot))
+        t1 = time.perf_counter()
+        totals = [C.c_int64(0) for _ in range(5)]
+        ms_count, ms_emit = C.c_float(0), C.c_float(0)
+        _lib.check(lib.gki_haplotype_segments_count(self._plan, self._alt_bits.ptr, self.n_slots, slot, int(k),
+                                                    *[C.byref(t) for t in totals], C.byref(ms_count)))
+        totals = [t.value for t in totals]
+        arrays = [s.array(max(n, 1), np.int64) for n in (totals[1], totals[1], totals[3], totals[3])]
+        _lib.check(lib.gki_haplotype_segments_emit(self._plan, *[a.ptr for a in arrays], C.byref(ms_emit)))
+        return seq, arrays, totals, float(ms_count.value) + float(ms_emit.value), (t0, t1, time.perf_counter())
 
     def _apply_slot(self, slot, row, device_index, k, n_nodes, strands):
         """row += counts(slot) - counts(all-ref path), by the two segment passes; returns the slot's timing dict."""
-        lib = self._open()
         ref_letters, _ = self._reference_path()
         with _lib.DeviceScope() as s:
-            t0 = time.perf_counter()
-            seq = s.keep(self.sequence(slot))              # leaves the slot's before / cut / bounds in the plan
-            t1 = time.perf_counter()
-            totals = [C.c_int64(0) for _ in range(5)]
-            ms_count, ms_emit = C.c_float(0), C.c_float(0)
-            _lib.check(lib.gki_haplotype_segments_count(self._plan, self._alt_bits.ptr, self.n_slots, slot, int(k),
-                                                        *[C.byref(t) for t in totals], C.byref(ms_count)))
-            n_taken, n_ref, ref_windows, n_slot, slot_windows = [t.value for t in totals]
-            ref_start, ref_n = s.array(max(n_ref, 1), np.int64), s.array(max(n_ref, 1), np.int64)
-            slot_start, slot_n = s.array(max(n_slot, 1), np.int64), s.array(max(n_slot, 1), np.int64)
-            _lib.check(lib.gki_haplotype_segments_emit(self._plan, ref_start.ptr, ref_n.ptr, slot_start.ptr, slot_n.ptr,
-                                                       C.byref(ms_emit)))
-            t2 = time.perf_counter()
+            seq, (ref_start, ref_n, slot_start, slot_n), totals, kernel_ms, (t0, t1, t2) = self._list_segments(s, slot, k)
+            n_taken, n_ref, ref_windows, n_slot, slot_windows = totals
             device_index.count_nodes_from_segments(ref_letters, ref_start, ref_n, k, row, n_nodes, strands, sign=-1,
                                                    n_segs=n_ref)
             t3 = time.perf_counter()
@@ -410,22 +424,14 @@ class HaplotypePaths:
             return {"slot": slot, "letters": seq.letters.n, "taken_lines": n_taken, "ref_segments": n_ref,
                     "ref_windows": ref_windows, "slot_segments": n_slot, "slot_windows": slot_windows,
                     "spell_s": t1 - t0, "segments_s": t2 - t1, "subtract_s": t3 - t2, "add_s": t4 - t3, "total_s": t4 - t0,
-                    "segments_kernel_ms": float(ms_count.value) + float(ms_emit.value), **seq.timings}
+                    "segments_kernel_ms": kernel_ms, **seq.timings}
 
     def segments(self, slot, k):
         """The segments of slot `slot` read back: ((start, windows) in the all-ref path, (start, windows)
         in the slot's sequence), int64 arrays.  For inspection and tests; the count routes keep them on the device."""
-        lib = self._open()
-        slot = check_slot(slot, self.n_slots)
         with _lib.DeviceScope() as s:
-            s.keep(self._spell(self._alt_bits, self.n_slots, slot)[0])
-            totals = [C.c_int64(0) for _ in range(5)]
-            _lib.check(lib.gki_haplotype_segments_count(self._plan, self._alt_bits.ptr, self.n_slots, slot, int(k),
-                                                        *[C.byref(t) for t in totals], None))
-            n_ref, n_slot = totals[1].value, totals[3].value
-            arrays = [s.array(max(n, 1), np.int64) for n in (n_ref, n_ref, n_slot, n_slot)]
-            _lib.check(lib.gki_haplotype_segments_emit(self._plan, *[a.ptr for a in arrays], None))
-            out = [a.to_host(n) for a, n in zip(arrays, (n_ref, n_ref, n_slot, n_slot))]
+            _, arrays, totals, _, _ = self._list_segments(s, slot, k)
+            out = [a.to_host(n) for a, n in zip(arrays, (totals[1], totals[1], totals[3], totals[3]))]
         return (out[0], out[1]), (out[2], out[3])
 
     def node_counts_by_difference(self, slots, index, k, n_nodes=None, include_reverse_complement=True, timings=None):
@@ -433,11 +439,7 @@ class HaplotypePaths:
         segments) + counts(the slot's segments), the segments being the windows that touch an allele the slot replaces or
         takes.  Per slot: spell, list the segments, copy the base row, one signed probe pass over each segment list.
         timings: a list that receives one dict per slot (seconds per stage, synchronised, and the windows probed)."""
-        self._open()
-        slots = [check_slot(h, self.n_slots) for h in slots]
-        if n_nodes is None:
-            n_nodes = int(index.max_node_id()) + 1
-        strands = 3 if include_reverse_complement else 1
+        slots, n_nodes, strands = self._slots(slots), nodes_of_index(index, n_nodes), strands_of(include_reverse_complement)
         device_index = index._device_index()
         base = self._base_row(index, k, n_nodes, strands)
         out = np.zeros((len(slots), int(n_nodes)), dtype=np.uint32)
@@ -476,9 +478,7 @@ class HaplotypePaths:
         for x in samples:
             if not 0 <= x < n_samples:
                 raise IndexError("sample %d is outside 0 .. %d" % (x, n_samples - 1))
-        if n_nodes is None:
-            n_nodes = int(index.max_node_id()) + 1
-        strands = 3 if include_reverse_complement else 1
+        n_nodes, strands = nodes_of_index(index, n_nodes), strands_of(include_reverse_complement)
         entries = self.n_lines * 2 * (ploidy + 1)
         with _lib.DeviceScope() as s:
             histogram, count_sum = s.array(max(entries * n_bins, 1), np.uint32), s.array(max(entries, 1), np.uint64)

@@ -7,9 +7,12 @@ import functools
 import numpy as np
 import pytest
 
+import spec_graph_build
 import spec_haplotype_count_model as spec
 import spec_haplotype_paths
+from graph_build_cases import random_reference, vcf
 from haplotype_count_model_cases import CASE_NAMES, KS, case, model_case
+from haplotype_path_cases import graph_of
 from graph_kmer_index_amd import CollisionFreeKmerIndex, DenseKmerFinder, _lib
 from graph_kmer_index_amd.haplotype_paths import AltPlane, HaplotypePaths, NodeCountModel
 from graph_kmer_index_amd.unique_variant_kmers import VariantToNodesArrays
@@ -94,6 +97,76 @@ def test_counts_by_difference_equal_the_whole_route_and_the_spec(name, k):
         # n_nodes left out: the index's highest node + 1; reverse complements are the default
         assert np.array_equal(paths.node_counts_by_difference([1], index, k)[0],
                               spec_counts(name, 1, k, True)[:int(index.max_node_id()) + 1])
+
+
+def assert_segments(got, want, where):
+    for which in (0, 1):
+        for g, w in zip(got[which], want[which]):
+            assert g.dtype == np.int64 and np.array_equal(g, w), (where, which)
+
+
+@pytest.mark.parametrize("k", KS)
+@pytest.mark.parametrize("name", ["indels", "lines_63", "lines_64", "lines_65", "lines_129", "short_chromosome_4"])
+def test_a_plans_first_segments_call_is_of_a_slot_that_takes_every_alt_allele(name, k):
+    """The all-ref path is built inside the plan's first segments call, behind the slot's own path and through the same
+    scratch.  The test above starts every plan with slot 0, whose path IS the all-ref path; here it differs at every line."""
+    c = case(name)
+    assert c.codes[:, 1].all() and not c.codes[:, 0].any()
+    with paths_of(c) as paths:
+        first = paths.segments(1, k)
+        assert_segments(first, spec_segments(c, 1, k), (name, k, "first"))
+        for slot in (2, 1, 0):
+            got = paths.segments(slot, k)
+            assert_segments(got, spec_segments(c, slot, k), (name, k, slot))
+            if slot == 1:
+                assert_segments(got, first, (name, k, "again"))
+
+
+@pytest.mark.parametrize("k", KS)
+@pytest.mark.parametrize("name", ["indels", "merge_edges"])
+def test_paths_do_not_leak_into_one_another(name, k):
+    import ctypes as C
+    c = case(name)
+    index, n_nodes, lib = index_of(name, k), c.graph.n_nodes, _lib.load()
+    with paths_of(c) as paths, _lib.DeviceScope() as s:
+        totals = [C.c_int64(0) for _ in range(5)]
+        args = [C.byref(t) for t in totals] + [None]
+        s.keep(paths.sequence(1))
+        # the all-ref letters are spelled as slot 0 of a zeroed plane: another slot between the two calls, as sequence(2) is
+        base = paths.reference_node_counts(index, k, n_nodes)
+        assert np.array_equal(base, spec_counts(name, 0, k, True))
+        assert lib.gki_haplotype_segments_count(paths._plan, paths._alt_bits.ptr, paths.n_slots, 1, k, *args) == 5   # GKI_ERR_STATE
+        got = paths.node_counts_by_difference([1, 2, 1], index, k, n_nodes)
+        assert np.array_equal(got[0], got[2])
+        for row, slot in zip(got, (1, 2, 1)):
+            assert np.array_equal(row, spec_counts(name, slot, k, True)), (name, k, slot)
+
+
+def test_a_chain_without_a_kept_line():
+    """Two chromosomes and a VCF with no data line: no path drops anything, no line is taken, the model has no entry."""
+    k, ploidy, n_bins = 5, 2, 3
+    reference = {"a": random_reference(40, 71), "b": random_reference(33, 72)}
+    build = spec_graph_build.build(reference, vcf([]))
+    graph, codes = graph_of(build), np.zeros((0, 4), np.uint8)
+    assert len(build.var_nodes) == 0 and len(graph.chromosome_start_nodes) == 2
+    finder = DenseKmerFinder(graph, k, max_variant_nodes=4)
+    finder.find()
+    index = CollisionFreeKmerIndex.from_flat_kmers(finder.get_flat_kmers(v="1"), modulo=MODULO)
+    starts = [graph.chromosome_start_nodes[x] for x in sorted(graph.chromosome_start_nodes)]
+    want = spec_haplotype_paths.node_counts(spec_haplotype_paths.spell(graph, build.ref_nodes, build.var_nodes, codes, 0, starts),
+                                            index, k, graph.n_nodes, True)
+    assert want.any()
+    matrix = HaplotypeMatrix(codes, np.ones(0, np.uint8), 4 // ploidy, ploidy)
+    with HaplotypePaths(graph, VariantToNodesArrays(build.ref_nodes, build.var_nodes), matrix) as paths:
+        for pair in paths.segments(0, k):
+            for a in pair:
+                assert a.dtype == np.int64 and a.shape == (0,)
+        base = paths.reference_node_counts(index, k, graph.n_nodes)
+        assert np.array_equal(base, paths.node_counts([0], index, k, graph.n_nodes)[0]) and np.array_equal(base, want)
+        assert np.array_equal(paths.node_counts_by_difference([3], index, k, graph.n_nodes)[0], want)
+        m = paths.node_count_model(index, k, None, n_bins, graph.n_nodes)
+        assert m.histogram.shape == (0, 2, ploidy + 1, n_bins) and m.count_sum.shape == (0, 2, ploidy + 1)
+        assert m.samples.tolist() == [0, 1]
 
 
 @pytest.mark.parametrize("k", KS)

@@ -7,9 +7,8 @@ from codegen_asm import _bodies, _metadata, _of, asm_of, needs_hipcc
 
 pytestmark = needs_hipcc
 # kernel -> (VGPRs, LDS bytes): exactly what the build this was written against gives, upper bounds from then on
-FOOTPRINT = {"k_seg_ref_bounds": (10, 0), "k_seg_taken_flags": (10, 0), "k_seg_taken_emit": (8, 0),
-             "k_seg_runsILb0EE": (33, 0), "k_seg_runsILb1EE": (25, 0), "k_model_row_start": (16, 0),
-             "k_model_accumulate": (23, 0)}
+FOOTPRINT = {"k_seg_taken_flags": (10, 0), "k_seg_taken_emit": (8, 0), "k_seg_runsILb0EE": (33, 0),
+             "k_seg_runsILb1EE": (25, 0), "k_model_row_start": (16, 0), "k_model_accumulate": (23, 0)}
 # the two span walks share one body: a candidate queue of 4 waves x 320 entries of 16 bytes
 PROBE_FOOTPRINT = {"k_probe_reads": (53, 20480), "k_probe_segments": (55, 20480)}
 asm = asm_of("gki_haplotype_counts")
