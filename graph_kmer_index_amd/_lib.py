@@ -184,6 +184,11 @@ SYMBOLS = {
     "gki_vcf_genotypes_count": (_I32, [_P, _I64, _P, _P, _I64, _I32, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64),
                                        C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "gki_vcf_genotypes_emit": (_I32, [_P, _I64, _P, _P, _I64, _I32, _P, _I64, C.POINTER(_I64), C.POINTER(C.c_float)]),
+    "gki_vcf_cohort_count": (_I32, [_P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I32, C.POINTER(_I64), C.POINTER(_I64),
+                                    C.POINTER(_I64), C.POINTER(C.c_int), _P, _I64, C.POINTER(C.c_float)]),
+    "gki_vcf_cohort_emit": (_I32, [_P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I32, _I64, _I64, _P, _I64, C.POINTER(_I64),
+                                   C.POINTER(C.c_float)]),
+    "gki_vcf_cohort_kernel_ms": (_I32, [C.POINTER(C.c_float)] * 3),
     "gki_bgzf_inflate": (_I32, [_P, _I64, _P, _P, _P, _P, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(C.c_int)]),
     "gki_bgzf_inflate_kernel_ms": (_I32, [C.POINTER(C.c_float)]),
     "gki_last_byte_position": (_I32, [_P, _I64, _I32, C.POINTER(_I64)]),

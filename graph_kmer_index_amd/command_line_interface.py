@@ -29,6 +29,9 @@ collision_free_kmer_index.py:393-402).
     python -m graph_kmer_index_amd.command_line_interface genotype -V graph.variant_to_nodes.npz -M node_count_model.npz \
         -c node_counts.npy -v variants.vcf.gz -o sample.vcf [-s name] [--coverage X] [--error 0.01] [--pseudo-count 1] [-L loglik] \
         [--compress none|bgzf|auto]
+    python -m graph_kmer_index_amd.command_line_interface genotype -V graph.variant_to_nodes.npz -M node_count_model.npz \
+        -c cohort_counts.npy | -c a.npy,b.npy,c.npy -v variants.vcf.gz -o cohort.vcf [-s a,b,c] [--coverage X | X,Y,Z] \
+        [--batch-bytes N]
     python -m graph_kmer_index_amd.command_line_interface bgzf -i reads.fq -o reads.fq.gz [--block-size 65280] [--chunk-bytes N]
 
 `-g` takes an obgraph file when obgraph is installed, else a GraphArrays .npz (GraphArrays.to_file).  `index -t N` runs
@@ -443,14 +446,27 @@ def make_node_count_model(args):
 
 
 def genotype(args):
-    """One sample's genotypes from its node counts (what `map` writes) and the node count model, as a VCF with one sample
-    column: the model fitted, the sample called and the VCF's text made on the device (genotyper.py)."""
+    """Genotypes from node counts (what `map` writes) and the node count model, as a VCF: the model fitted once, the rows
+    called and the VCF's text made on the device (genotyper.py).  One-dimensional counts are one sample and one sample
+    column; two-dimensional counts, or a comma-separated list of one-dimensional files, are a cohort: one VCF with a column
+    per row, the rows called in batches of at most --batch-bytes of counts."""
     from .genotyper import Genotyper, write_genotyped_vcf
     from .haplotype_paths import NodeCountModel
     from .unique_variant_kmers import load_variant_to_nodes
-    counts = np.load(args.counts)
+    if "," in args.counts:
+        rows = [np.load(name) for name in args.counts.split(",")]
+        if any(r.ndim != 1 for r in rows) or len({len(r) for r in rows}) != 1:
+            raise ValueError("%s: a list of counts files holds one-dimensional rows of one length" % args.counts)
+        counts = np.stack(rows)
+    else:
+        counts = np.load(args.counts)
+    if counts.ndim == 2:
+        return genotype_cohort(args, counts)
     if counts.ndim != 1:
-        raise ValueError("%s holds %d-dimensional counts: genotype takes one sample's row" % (args.counts, counts.ndim))
+        raise ValueError("%s holds %d-dimensional counts: genotype takes one sample's row or a batch of rows"
+                         % (args.counts, counts.ndim))
+    if isinstance(args.coverage, tuple):
+        raise ValueError("--coverage takes one number for one sample's row")
     with Genotyper(NodeCountModel.from_file(args.model), load_variant_to_nodes(args.variant_to_nodes), args.error,
                    args.pseudo_count) as genotyper:
         ploidy = genotyper.ploidy
@@ -461,6 +477,54 @@ def genotype(args):
                             args.inflate, compress=output_compression(args.compress, args.out_file_name))
     logging.info("Wrote %d data lines (%d not called) at coverage %g to %s"
                  % (n, int(np.count_nonzero(calls.call < 0)), calls.coverage[0], args.out_file_name))
+
+
+def genotype_cohort(args, counts):
+    """`genotype` for counts uint32[S][n_nodes]: every row called with the one fitted model, in batches whose counts hold at
+    most --batch-bytes (a row's calls do not depend on its batch), and one VCF with S sample columns written."""
+    from .genotyper import Genotyper, check_sample_names, write_cohort_vcf
+    from .haplotype_paths import NodeCountModel
+    from .unique_variant_kmers import load_variant_to_nodes
+    n_samples, n_nodes = counts.shape
+    if n_samples < 1:
+        raise ValueError("%s holds no row" % args.counts)
+    if n_samples > 1 and args.sample_name == "sample":     # the option's default
+        names = ["sample_%d" % (i + 1) for i in range(n_samples)]
+    else:
+        names = check_sample_names(args.sample_name.split(","))
+    if len(names) != n_samples:
+        raise ValueError("%d sample names for %d rows of counts" % (len(names), n_samples))
+    coverage = None
+    if args.coverage is not None:
+        coverage = np.array(args.coverage if isinstance(args.coverage, tuple) else [args.coverage], dtype=np.float64)
+        if len(coverage) not in (1, n_samples):
+            raise ValueError("--coverage takes one number or one per row: %d for %d rows" % (len(coverage), n_samples))
+        coverage = np.ascontiguousarray(np.broadcast_to(coverage, (n_samples,)))
+    if args.batch_bytes < 1:
+        raise ValueError("--batch-bytes must be positive")
+    rows_per_batch = int(min(65535, max(1, args.batch_bytes // max(4 * n_nodes, 1))))
+    parts = []
+    with Genotyper(NodeCountModel.from_file(args.model), load_variant_to_nodes(args.variant_to_nodes), args.error,
+                   args.pseudo_count) as genotyper:
+        ploidy = genotyper.ploidy
+        for at in range(0, n_samples, rows_per_batch):
+            to = min(n_samples, at + rows_per_batch)
+            parts.append(genotyper.genotype(counts[at:to], None if coverage is None else coverage[at:to],
+                                            loglik=args.loglik is not None))
+    call, gq = np.concatenate([p.call for p in parts]), np.concatenate([p.gq for p in parts])
+    if args.loglik is not None:
+        np.save(args.loglik if args.loglik.endswith(".npy") else args.loglik + ".npy", np.concatenate([p.loglik for p in parts]))
+    n = write_cohort_vcf(args.vcf, args.out_file_name, call, gq, ploidy, names, args.chunk_bytes, args.inflate,
+                         compress=output_compression(args.compress, args.out_file_name))
+    lam = np.concatenate([p.coverage for p in parts])
+    logging.info("Wrote %d data lines with %d sample columns (%d calls not made) at coverages %g .. %g to %s"
+                 % (n, n_samples, int(np.count_nonzero(call < 0)), lam.min(), lam.max(), args.out_file_name))
+
+
+def _coverage(text):
+    """`--coverage`: one number as a float, comma-separated numbers as a tuple of floats."""
+    values = tuple(float(x) for x in text.split(","))
+    return values[0] if len(values) == 1 else values
 
 
 def output_compression(compress, out_file_name):
@@ -670,15 +734,22 @@ def build_parser():
     p = sub.add_parser("genotype")
     p.add_argument("-V", "--variant_to_nodes", required=True, help="built with the graph (make_graph writes both)")
     p.add_argument("-M", "--model", required=True, help="what make_node_count_model writes")
-    p.add_argument("-c", "--counts", required=True, help="the sample's node counts, as map writes them (.npy)")
+    p.add_argument("-c", "--counts", required=True,
+                   help="node counts as map writes them (.npy): one sample's row; or a cohort, as a two-dimensional .npy "
+                        "or a comma-separated list of one-dimensional files, for one VCF with a column per row")
     p.add_argument("-v", "--vcf", required=True, help="the VCF the graph was made from, optionally .gz (BGZF or gzip)")
     p.add_argument("-o", "--out-file-name", required=True, help="the genotyped VCF: plain text, or BGZF as --compress says")
-    p.add_argument("-s", "--sample-name", required=False, default="sample")
-    p.add_argument("--coverage", required=False, type=float, default=None,
-                   help="the sample's coverage relative to the model's individuals; default: estimated from the counts")
+    p.add_argument("-s", "--sample-name", required=False, default="sample",
+                   help="the sample's name, for a cohort comma-separated names; the default is sample_1 .. sample_S for a "
+                        "cohort of more than one row")
+    p.add_argument("--coverage", required=False, type=_coverage, default=None,
+                   help="the sample's coverage relative to the model's individuals, for a cohort one number or one per row, "
+                        "comma-separated; default: estimated from the counts")
+    p.add_argument("--batch-bytes", required=False, type=int, default=1 << 30,
+                   help="a cohort's rows are called in batches whose counts hold at most this many bytes")
     p.add_argument("--error", required=False, type=float, default=0.01)
     p.add_argument("--pseudo-count", required=False, type=float, default=1.0)
-    p.add_argument("-L", "--loglik", required=False, default=None, help="np.save of float64[lines, ploidy + 1]")
+    p.add_argument("-L", "--loglik", required=False, default=None, help="np.save of float64[lines, ploidy + 1], for a cohort [rows, lines, ploidy + 1]")
     p.add_argument("--inflate", required=False, choices=("auto", "host", "device"), default="auto",
                    help="where a .gz VCF is inflated: auto = BGZF on the device, other gzip on the host")
     p.add_argument("--chunk-bytes", required=False, type=int, default=None)

@@ -6,7 +6,9 @@ counts.  `Genotyper(model, variant_to_nodes)` uploads the model, fits it and kee
 `.genotype(counts)` estimates the sample's coverage and calls every kept line; `write_genotyped_vcf` copies the first eight
 fields of the input VCF's data lines and appends GT:GQ, the text made on the device piece by piece.  The rules are stated
 in include/gki.h ("genotyping", "genotyped VCF text") and DESIGN.md 4.21; the kernels are csrc/gki_genotype.hip and
-csrc/gki_vcf_write.hip.  This is this package's own model, not KAGE's.
+csrc/gki_vcf_write.hip.  A cohort -- the batch `.genotype` returns for counts with a leading axis of samples -- leaves as
+one VCF with a column per sample through `write_cohort_vcf` ("genotyped cohort VCF text", DESIGN.md 4.23,
+csrc/gki_vcf_cohort.hip).  This is this package's own model, not KAGE's.
 """
 import ctypes as C
 import math
@@ -262,6 +264,122 @@ def write_genotyped_vcf(vcf_file_name, out_file_name, call, gq, ploidy, sample_n
                     elif n_out:
                         lines.to_host(n_out).tofile(out)
                     done += n_data
+            if done != V:
+                raise ValueError("%s has %d data lines, there are %d calls" % (vcf_file_name, done, V))
+            if compress == "bgzf" and timings is not None:
+                out.close()                                  # the last member's time too
+                timings["deflate_ms"] = timings.get("deflate_ms", 0.0) + out.kernel_ms
+    except BaseException:
+        if os.path.exists(out_file_name):
+            os.remove(out_file_name)
+        raise
+    return done
+
+
+# ------------------------------------------------------------------------------------------------ a cohort
+
+def check_sample_names(sample_names):
+    """The names as a list of str.  ValueError unless they are non-empty, unique and free of tabs, spaces and line ends."""
+    names = [str(n) for n in sample_names]
+    for n in names:
+        if not n or any(c in n for c in "\t \n\r"):
+            raise ValueError("sample name %r: a name is not empty and holds no tab, space or line end" % (n,))
+    if len(set(names)) != len(names):
+        raise ValueError("the sample names are not unique")
+    return names
+
+
+def cohort_header_text(vcf_file_name, sample_names):
+    """`header_text` with the #CHROM line carrying all the names, in order."""
+    return header_text(vcf_file_name, "\t".join(check_sample_names(sample_names)))
+
+
+def cohort_lines_on_device(text, n_bytes, d_call, d_gq, n_samples, row_stride, first, ploidy, max_out_bytes=1 << 30,
+                           timings=None):
+    """The genotyped data lines of one piece of text with `n_samples` sample columns, made on the device (include/gki.h,
+    "genotyped cohort VCF text").  `d_call` int8 and `d_gq` uint8 are [n_samples][row_stride] as the call kernel writes
+    them; the piece's first data line is entry `first` of every row.  A generator: yields (uint8 DeviceArray, bytes of it,
+    data lines in it) for consecutive ranges of the piece's data lines, each of at most `max_out_bytes` bytes unless one
+    line alone has more; a range's array lives until the next one is asked for.  A piece without data lines yields
+    nothing.  ValueError for a line at fault, named by its number in the file, and for a piece with more data lines than
+    there are calls left."""
+    lib = _lib.load()
+    left = row_stride - first
+    batch = (text.ptr, n_bytes, d_call.ptr, d_gq.ptr, row_stride, first, n_samples, left, ploidy)
+    n_data, n_out, line, kind, ms = C.c_int64(0), C.c_int64(0), C.c_int64(-1), C.c_int(0), C.c_float(0)
+    with _lib.DeviceScope() as piece:
+        try:
+            _lib.check(lib.gki_vcf_cohort_count(*batch, C.byref(n_data), C.byref(n_out), C.byref(line), C.byref(kind), None, 0,
+                                                C.byref(ms)))
+        except _lib.GkiError:
+            if n_data.value > left:
+                raise ValueError("the VCF has more than the %d data lines there are calls for" % row_stride) from None
+            raise
+        _add_ms(timings, "lengths_ms", ms)
+        if kind.value:
+            raise ValueError("data line %d: %s" % (first + line.value, TEXT_FAULTS[kind.value]))
+        V = n_data.value
+        cuts = [0, V]
+        if n_out.value > max(int(max_out_bytes), 1):         # cut where the line starts say, at least a line a range
+            d_start = piece.array(V + 1, np.int64)
+            _lib.check(lib.gki_vcf_cohort_count(*batch, C.byref(n_data), C.byref(n_out), C.byref(line), C.byref(kind),
+                                                d_start.ptr, V + 1, C.byref(ms)))
+            _add_ms(timings, "lengths_ms", ms)
+            start = d_start.to_host(V + 1)
+            cuts = [0]
+            while cuts[-1] < V:
+                fit = int(np.searchsorted(start, start[cuts[-1]] + int(max_out_bytes), side="right")) - 1
+                cuts.append(min(V, max(fit, cuts[-1] + 1)))
+    for line_from, line_to in zip(cuts[:-1], cuts[1:]):
+        if line_to == line_from:
+            continue
+        with _lib.DeviceScope() as part:
+            capacity = n_out.value if len(cuts) == 2 else int(start[line_to] - start[line_from])
+            out, written = part.array(capacity, np.uint8), C.c_int64(0)
+            _lib.check(lib.gki_vcf_cohort_emit(*batch, line_from, line_to, out.ptr, out.n, C.byref(written), C.byref(ms)))
+            _add_ms(timings, "emit_call_ms", ms)
+            yield out, written.value, line_to - line_from
+
+
+def write_cohort_vcf(vcf_file_name, out_file_name, call, gq, ploidy, sample_names, chunk_bytes=None, inflate="auto",
+                     compress="none", max_out_bytes=1 << 30, timings=None):
+    """Write `out_file_name`: the header (`cohort_header_text`) and, per data line of `vcf_file_name` (.vcf, or .vcf.gz as
+    BGZF or gzip), its first eight fields, GT:GQ and one column per sample s of `call` int8[S][V] and `gq` uint8[S][V]
+    (a quality above 99 is written as 99).  The batch is uploaded once, as it is; the input is streamed in pieces of
+    about `chunk_bytes` (default: text_files' own, divided by the number of 64-column groups so that a piece's tables stay
+    small), each piece's lines are made on the device in ranges of at most `max_out_bytes` output bytes (a line alone may
+    have more) and written, or with `compress` "bgzf" sent through a `bgzf.BgzfWriter` where they were made.  The file's
+    bytes depend on the input's text and the calls alone.  ValueError as `write_genotyped_vcf`, and when the names do not
+    match the rows or break `check_sample_names`' rule; the output file is then removed.  Returns the data lines written."""
+    if compress not in ("none", "bgzf"):
+        raise ValueError("compress must be 'none' or 'bgzf', not %r" % (compress,))
+    call, gq = np.ascontiguousarray(call, dtype=np.int8), np.ascontiguousarray(gq, dtype=np.uint8)
+    if call.ndim != 2 or call.shape != gq.shape:
+        raise ValueError("call is int8[S][V] and gq uint8[S][V], not %r and %r" % (call.shape, gq.shape))
+    S, V = call.shape
+    names = check_sample_names(sample_names)
+    if len(names) != S or S < 1:
+        raise ValueError("%d sample names for %d rows of calls (at least one)" % (len(names), S))
+    if not 1 <= int(ploidy) <= 8:
+        raise ValueError("ploidy must be in 1..8")
+    if int(max_out_bytes) < 1:
+        raise ValueError("max_out_bytes must be positive")
+    if chunk_bytes is None:
+        chunk_bytes = max(1 << 20, DEFAULT_CHUNK_BYTES // ((S + 63) // 64))
+    header, done = cohort_header_text(vcf_file_name, names), 0
+    try:
+        with _lib.DeviceScope() as s, (BgzfWriter(out_file_name) if compress == "bgzf" else open(out_file_name, "wb")) as out:
+            d_call = s.on_device(call.reshape(-1) if V else np.zeros(1, np.int8), np.int8)
+            d_gq = s.on_device(gq.reshape(-1) if V else np.zeros(1, np.uint8), np.uint8)
+            out.write(header)
+            for text, n_bytes in owned_pieces(vcf_file_name, chunk_bytes, inflate):
+                for lines, n_out, n_lines in cohort_lines_on_device(text, n_bytes, d_call, d_gq, S, V, done, int(ploidy),
+                                                                    max_out_bytes, timings):
+                    if compress == "bgzf":
+                        out.write_device(lines, n_out)
+                    else:
+                        lines.to_host(n_out).tofile(out)
+                    done += n_lines
             if done != V:
                 raise ValueError("%s has %d data lines, there are %d calls" % (vcf_file_name, done, V))
             if compress == "bgzf" and timings is not None:

@@ -995,6 +995,40 @@ int gki_vcf_genotypes_count(const void *d_text, int64_t n_bytes, const void *d_c
                             int *first_bad_kind, float *kernel_ms);
 int gki_vcf_genotypes_emit(const void *d_text, int64_t n_bytes, const void *d_call, const void *d_gq, int64_t n_calls,
                            int ploidy, void *d_out, int64_t out_capacity, int64_t *n_out_bytes, float *kernel_ms);
+/* ---------------------------------------------------------------- genotyped cohort VCF text
+ * One piece of whole lines of VCF text in HBM -> the data lines of a VCF with S = n_samples sample columns.  Lines, data
+ * lines, what is not written and P = ploidy (1..8) are those of "genotyped VCF text".
+ *   per data line   the bytes of its first eight fields, then "\tGT:GQ", then for every sample s = 0 .. S - 1 in order
+ *                   "\t" GT ":" GQ, then "\n".  GT and GQ as in "genotyped VCF text"; a gq above 99 is written as 99.  With
+ *                   S = 1 and gq <= 99 the output is byte for byte that of gki_vcf_genotypes_emit.
+ *   column width    a column has 2P + 2 + w bytes, w = 1 when call >= 0 and gq >= 10 (a wide column), w = 0 otherwise: so
+ *                   column s of a line begins (2P + 2) s + (the number of wide columns below s) bytes behind "\tGT:GQ".
+ *                   The emit kernel finds a byte's column from this identity, with a bit mask of the line's wide columns
+ *                   and a running count per 64 columns, and walks no columns.
+ *   faults          the lowest data line at fault (numbered from the piece's first) and its kind: 1 = fewer than eight
+ *                   fields, 2 = a call outside -1 .. P in any sample's column (the line is named, not the sample).
+ * d_call int8 and d_gq uint8 are the call kernel's own [S][row_stride] (gki_genotype_call with V = row_stride); the piece's
+ * first data line is entry `first` of every row and n_calls entries are left there (first + n_calls <= row_stride): nothing
+ * is transposed or copied by the caller.  A piece with more data lines than n_calls is refused (GKI_ERR_BAD_ARG,
+ * *n_data_lines set).  n_samples is 1 .. 2^20; 0 is GKI_ERR_BAD_ARG.
+ * gki_vcf_cohort_count gives the piece's data lines, the bytes of its output and the fault; d_line_start (may be NULL):
+ * int64[line_start_capacity >= data lines + 1] in HBM, where each data line's output begins, from 0, and the total.
+ * gki_vcf_cohort_emit writes the data lines [line_from, line_to) of the piece to d_out[0, *n_out_bytes) (16-byte aligned),
+ * so that a caller bounds one call's output by the line starts; it keeps no state and makes the count pass again.  It
+ * refuses a piece at fault (wherever the line), a range beyond the piece's data lines and an out_capacity below the range's
+ * bytes with GKI_ERR_BAD_ARG and then writes nothing.  Offsets are 64 bits wide; a line's columns may be longer than any
+ * tile; the piece's bytes + 7 + (2P + 3) S stay below 2^32 - 64.  *kernel_ms (may be NULL): the device time of the pack
+ * pass, the lengths kernel and the scan, in the emit call with that of the emit kernels added.
+ * gki_vcf_cohort_kernel_ms: those times of the calling thread's last call apart -- the pack pass, the lengths kernel with
+ * the scan, the tile search with the emit kernel (0 for what that call did not launch), for tools/bench_genotype_cohort.py. */
+int gki_vcf_cohort_count(const void *d_text, int64_t n_bytes, const void *d_call, const void *d_gq, int64_t row_stride,
+                         int64_t first, int64_t n_samples, int64_t n_calls, int ploidy, int64_t *n_data_lines,
+                         int64_t *n_out_bytes, int64_t *first_bad_line, int *first_bad_kind, void *d_line_start,
+                         int64_t line_start_capacity, float *kernel_ms);
+int gki_vcf_cohort_emit(const void *d_text, int64_t n_bytes, const void *d_call, const void *d_gq, int64_t row_stride,
+                        int64_t first, int64_t n_samples, int64_t n_calls, int ploidy, int64_t line_from, int64_t line_to,
+                        void *d_out, int64_t out_capacity, int64_t *n_out_bytes, float *kernel_ms);
+int gki_vcf_cohort_kernel_ms(float *pack_ms, float *lengths_ms, float *emit_ms);
 
 /* ---------------------------------------------------------------- BGZF (blocked gzip: the .gz reads files of bgzip / htslib)
  * A BGZF file is a chain of gzip members of at most 64 KiB, each with its compressed size in a 'BC' extra subfield, so
